@@ -6,10 +6,16 @@ edit-ratio on the 256x256 DDPM (LSUN-Church) U-Net, fp32, synthetic activations,
 random-init weights.  Workload at N=1: BASELINE.json configs[1] -- one sparse
 (SIGE) forward of the DDPM-256 U-Net at a 1.2 % square edit.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
 
 `python bench.py --gpus N` launches its own N ranks (torch.distributed.run, one process per GPU, RCCL);
 under a torchrun environment it joins it.
+
+A plain run does only what the headline figure needs: set-up, W warm-up replays, the K timed steps, the outputs of the
+last timed step (--dump-outputs DIR: DIR/output.npy, float32) and the result line.  Everything else described below
+(dense baseline, per-kernel accounting and rooflines, the edit-ratio / f16 / f16x3 sweeps, mask-change latencies,
+stacked edits, GauGAN, the SD transformer, the CPU baseline and the parity against the reference's CPU path) runs
+only with --full.
 
 A "step" = one sparse U-Net forward per GPU (each rank edits its own region of the shared original image).
 N = 1: the timed region is K hipGraph replays of that forward.  N > 1: the timed region is one JOB -- the
@@ -18,7 +24,7 @@ activation cache of the original image, computed by rank 0, is distributed to th
 forwards -- so `value` counts the distribution inside the job; the steady-state rate (cache already resident)
 and the cache-per-step rate are reported next to it (`multi_gpu`).  Barrier + synchronize on both sides, max over ranks.
 
-One JSON line on rank 0, with `roofline` (dominant hot-path kernel, HIP events on the launch stream, rotating
+One JSON line on rank 0, with (--full) `roofline` (dominant hot-path kernel, HIP events on the launch stream, rotating
 buffers), `roofline_gather` / `roofline_scatter_gather` / `roofline_hbm` + the `data_movement` table (the HBM-bound
 kernels, standalone), `parity_max_abs` (the benchmarked artefact's outputs against the reference's CPU path on the
 same weights / inputs / masks, per edit ratio) and `cpu_baseline` (the reference's own sige/cpu backend --
@@ -344,6 +350,23 @@ def edit_mask(ratio, rank=0):
     return square_mask(ratio, top=100 - 6 * rank, left=90 + 6 * rank)
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(directory, arrays, rank=0):
+    """--dump-outputs: every array as <directory>/<name>.npy, float32, NCHW (rank r > 0: <name>_rank<r>.npy).  Weights, inputs
+    and masks are seeded, so two builds run with the same arguments can be compared output for output."""
+    import numpy as np
+
+    host = {name: a.detach().float().contiguous().cpu().numpy() for name, a in arrays.items()}
+    total = sum(v.nbytes for v in host.values())
+    if total > DUMP_LIMIT_BYTES:
+        raise ValueError("--dump-outputs: %d bytes, more than the %d allowed" % (total, DUMP_LIMIT_BYTES))
+    os.makedirs(directory, exist_ok=True)
+    for name, v in host.items():
+        np.save(os.path.join(directory, name + ("_rank%d" % rank if rank else "") + ".npy"), v)
+
+
 # ---------------------------------------------------------------- cpu baseline --
 CPU_THREADS_CAP = 32
 CPU_THREADS_CAP_REASON = ("OpenMP over all 256 hardware threads of the GPU box is slower than 16-32 threads on loops this small "
@@ -519,7 +542,7 @@ def main_sd(args, world, rank, dev):
     with torch.no_grad():
         model.set_mode("full")
         dense_ms = None
-        if rank == 0:
+        if rank == 0 and args.full:
             dense_ms, _, gd = _replay_ms(lambda: run(x1), k=10, warm=2)
             del gd
         run(x0 if rank == 0 else torch.zeros_like(x0))
@@ -547,7 +570,7 @@ def main_sd(args, world, rank, dev):
         from sige_amd.workloads import sd_transformer as _sdt
 
         routing, kernels_sd, roof_sd = {}, None, None
-        if rank == 0 and world == 1:
+        if rank == 0 and args.full and world == 1:
             keep_flags = (_sdt.NATIVE_ATTENTION, _sdt.NATIVE_LINEAR, _sdt.BATCHED_QKV)
             ref_out = None
             for tag, att, lin, form, bq in (("reference_chain", False, False, 0, False), ("native_attention", True, False, 0, True),
@@ -618,12 +641,15 @@ def main_sd(args, world, rank, dev):
 
         dt_steady, _ = job(False)
         dt, dist_s = job(True) if world > 1 else (dt_steady, 0.0)
+        if args.dump_outputs:  # (the graph's output buffer still holds the last timed step)
+            dump_outputs(args.dump_outputs, {"output": out}, rank)
         assert torch.isfinite(out).all()
-        g.replay()
-        torch.cuda.synchronize()
-        gpu_sparse = out.float().cpu()
+        if args.full:
+            g.replay()
+            torch.cuda.synchronize()
+            gpu_sparse = out.float().cpu()
     parity = None
-    if rank == 0 and args.cpu_seconds > 0:
+    if rank == 0 and args.full and args.cpu_seconds > 0:
         # configs[3] AT ITS OWN SIZE against the reference's CPU path: the same 860 M-parameter U-Net (same seed), latent,
         # context and masks on the host cores, native ops from oracle/_ref (the reference's compiled sige/cpu) or the C
         # restatement, convs = torch CPU; one full + one sparse forward, outside every timed region
@@ -675,11 +701,14 @@ def main_sd(args, world, rank, dev):
                                        % (n_params / 1e6, world, "; the timed job = distribute the original's cache from rank 0 (%s) + %d "
                                           "sparse forwards per rank" % (method, args.steps) if world > 1 else ""),
                            "edit_ratio": 0.15, "batch_per_gpu": 2, "parallelism": "dp%d" % world},
-                "forward_ms": round(ms_steady, 4), "dense_forward_ms": round(dense_ms, 3), "speedup_vs_dense": round(dense_ms / ms_steady, 2),
-                "hip_kernel_launches_per_forward": launches, "cache_bytes": int(flat.numel() * 4), "cached_tensors": n_cached,
-                "active_token_ratio_64": round(float(masks[(64, 64)].float().mean()), 4),
-                "native_attention": bool(_sdt.NATIVE_ATTENTION), "native_linear": bool(_sdt.NATIVE_LINEAR), "batched_qkv": bool(_sdt.BATCHED_QKV),
-                "tuned_token_gemms": bool(tuned_gemms)}
+                "forward_ms": round(ms_steady, 4)}
+        if dense_ms is not None:
+            line.update(dense_forward_ms=round(dense_ms, 3), speedup_vs_dense=round(dense_ms / ms_steady, 2))
+        line.update({
+            "hip_kernel_launches_per_forward": launches, "cache_bytes": int(flat.numel() * 4), "cached_tensors": n_cached,
+            "active_token_ratio_64": round(float(masks[(64, 64)].float().mean()), 4),
+            "native_attention": bool(_sdt.NATIVE_ATTENTION), "native_linear": bool(_sdt.NATIVE_LINEAR), "batched_qkv": bool(_sdt.BATCHED_QKV),
+            "tuned_token_gemms": bool(tuned_gemms)})
         if routing:
             line["attention_routing"] = routing
         if roof_sd is not None:
@@ -715,7 +744,8 @@ def settle():
 
 
 def self_launch(args):
-    """`python bench.py --gpus N` without a torchrun environment: re-exec under torch.distributed.run, one rank per GPU."""
+    """`python bench.py --gpus N` without a torchrun environment: run under torch.distributed.run, one rank per GPU, in a child
+    process (this one has initialised the GPU already), and exit with its status."""
     if args.gpus <= 1 or "WORLD_SIZE" in os.environ:
         return
     n_vis = torch.cuda.device_count()
@@ -732,7 +762,9 @@ def self_launch(args):
     env.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")  # dmabuf IPC only on this host driver (RCCL needs it)
     env.setdefault("OMP_NUM_THREADS", "8")
     sys.stdout.flush()
-    os.execvpe(cmd[0], cmd, env)
+    import subprocess
+
+    raise SystemExit(subprocess.call(cmd, env=env))
 
 
 def source_hash():
@@ -767,6 +799,13 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--warmup", type=int, default=20)
+    ap.add_argument("--full", action="store_true",
+                    help="also run every section besides the headline timing: dense baseline, per-kernel accounting and rooflines, "
+                         "sweeps, other precisions, mask-change latencies, stacked edits, GauGAN / SD transformer, CPU baseline and "
+                         "parity (the options below that tune those sections apply only with --full)")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps, write the output of the last timed step as DIR/output.npy (float32, NCHW; "
+                         "rank r > 0: output_rank<r>.npy)")
     ap.add_argument("--ratio", type=float, default=0.012, help="edit ratio of the headline workload")
     ap.add_argument("--sweep", default="0.012,0.05,0.15", help="edit ratios for the sweep section ('' = skip)")
     ap.add_argument("--cpu-seconds", type=float, default=12.0, help="budget of the cpu_baseline timing (0 = skip the CPU leg)")
@@ -819,6 +858,8 @@ def main():
         ap.error("--cache-dtype f16 goes with --dtype f16 (an fp16-rounded cache does not keep the fp32 path's 1e-3)")
     if args.wire_dtype == "f16" and args.dtype != "f16":
         ap.error("--wire-dtype f16 goes with --dtype f16 (an fp16-rounded cache does not keep the fp32 path's 1e-3)")
+    if args.dump_calls and not args.full:
+        ap.error("--dump-calls goes with --full (the per-call table comes from the per-kernel accounting)")
 
     if not torch.cuda.is_available():
         raise SystemExit("bench.py needs an MI355X (no CPU path; see DESIGN.md)")
@@ -884,7 +925,7 @@ def main():
     with torch.no_grad():
         # ---- dense baseline: the stock U-Net forward on the same GPU (rank 0) ------
         dense_ms = None
-        if rank == 0:
+        if rank == 0 and args.full:
             model.set_mode("full")
             model.set_plain_dense(True)
             mask, x1 = edited(args.ratio)
@@ -973,13 +1014,15 @@ def main():
         x1 = prepare(args.ratio)
         model(x1, t)  # packs weights, builds tile tables, registers the activated twins
         model(x1, t)  # builds the twins' persistent buffers (library launches since round 4: not part of a steady-state forward)
-        tracer.log = []
-        n0, p0 = hip.launch_count(), hip.conv_pairs_fused()
-        model(x1, t)
-        launches_per_forward = hip.launch_count() - n0  # kernels libsige_hip.so launched for one sparse forward
-        pairs_per_forward = hip.conv_pairs_fused() - p0  # (shortcut, conv1) pairs that shared a launch
-        trace, tracer.log = tracer.log, None
-        e_ms = eager_ms(model, x1, t, 20)
+        trace, e_ms = None, None
+        if args.full:
+            tracer.log = []
+            n0, p0 = hip.launch_count(), hip.conv_pairs_fused()
+            model(x1, t)
+            launches_per_forward = hip.launch_count() - n0  # kernels libsige_hip.so launched for one sparse forward
+            pairs_per_forward = hip.conv_pairs_fused() - p0  # (shortcut, conv1) pairs that shared a launch
+            trace, tracer.log = tracer.log, None
+            e_ms = eager_ms(model, x1, t, 20)
         g, out = capture(model, x1, t)
         settle()
         for _ in range(args.warmup):
@@ -1019,12 +1062,15 @@ def main():
             dt, dist_s = dt_steady, 0.0
         ms_per_step = dt * 1e3 / args.steps
         ms_steady = dt_steady * 1e3 / args.steps
-        g.replay()
-        torch.cuda.synchronize()
+        if args.dump_outputs:  # (the graph's output buffer still holds the last timed step)
+            dump_outputs(args.dump_outputs, {"output": out}, rank)
         assert torch.isfinite(out).all()
-        gpu_out[args.ratio] = out.float().cpu()
+        if args.full:
+            g.replay()
+            torch.cuda.synchronize()
+            gpu_out[args.ratio] = out.float().cpu()
 
-        if rank == 0:
+        if rank == 0 and args.full:
             # ---- per-kernel accounting of the hot path (warm, in-situ tensors) ----
             fam, per_cfg, kernels, conv_tflops, hot_us = kernel_families(trace)
             if args.dump_calls:  # the per-call-shape table behind `kernels` (which layers are furthest from the matrix rate)
@@ -1081,7 +1127,7 @@ def main():
         del trace
 
         # ---- the same forward with the reference's out-of-place Scatter semantics (a fresh tensor per call) ----
-        if rank == 0 and inplace:
+        if rank == 0 and inplace and args.full:
             model.set_scatter_inplace(False)
             model(x1, t)
             g2, out2 = capture(model, x1, t)
@@ -1095,7 +1141,7 @@ def main():
 
         # ---- edit-ratio sweep (rank 0 only, short) -----------------------------------
         sweep = []
-        if rank == 0 and args.sweep and world == 1:  # (at N > 1 the other ranks would idle in the final barrier)
+        if rank == 0 and args.full and args.sweep and world == 1:  # (at N > 1 the other ranks would idle in the final barrier)
             for r in [float(v) for v in args.sweep.split(",")]:
                 xs = prepare(r)
                 model(xs, t)
@@ -1121,7 +1167,7 @@ def main():
         # ---- the tile conv v3 (csrc/conv_tile3.hpp): routed by the library from sige_amd.hip.TILE3_MIN_BLOCKS = 512 v3 workgroups on
         #      (decided in C per launch); the same forward with the router off, at the edit ratios where launches reach the threshold ----
         tile3 = None
-        if rank == 0 and world == 1 and args.dtype == "f32" and args.layout == "nhwc" and args.sweep and not args.no_extras:
+        if rank == 0 and args.full and world == 1 and args.dtype == "f32" and args.layout == "nhwc" and args.sweep and not args.no_extras:
             rows3 = []
             keep3 = hip.TILE3_MIN_BLOCKS
             try:
@@ -1151,7 +1197,7 @@ def main():
         # ---- f16 compute (BASELINE.json configs[4]): the same forward with fp16 operands on the fp16 matrix cores ----
         f16 = None
         gpu_out_f16 = {}
-        if rank == 0 and world == 1 and args.dtype == "f32" and args.f16_sweep and args.layout == "nhwc":
+        if rank == 0 and args.full and world == 1 and args.dtype == "f32" and args.f16_sweep and args.layout == "nhwc":
             rows = []
             for r in [float(v) for v in args.f16_sweep.split(",")]:
                 model.set_compute_dtype("f16", edit_ratio=r)  # (the model's precision policy depends on the edited area)
@@ -1204,7 +1250,7 @@ def main():
         # ---- split fp16 operands ("f16x3"): fp32-level results on the fp16 matrix cores -- dense remainder + the full pass ----
         x3 = None
         gpu_out_x3 = {}
-        if rank == 0 and world == 1 and args.dtype == "f32" and args.x3_sweep and args.layout == "nhwc":
+        if rank == 0 and args.full and world == 1 and args.dtype == "f32" and args.x3_sweep and args.layout == "nhwc":
             model.set_compute_dtype("f16x3")
             rows = []
             kern_x3 = None
@@ -1271,7 +1317,7 @@ def main():
 
         # ---- a new edit arrives (mask change), and one cache per denoising step (cache_id) ----
         dyn = None
-        if rank == 0 and world == 1 and not args.no_dynamic and args.layout == "nhwc":
+        if rank == 0 and args.full and world == 1 and not args.no_dynamic and args.layout == "nhwc":
             import statistics
 
             model.set_compute_dtype(args.dtype)
@@ -1456,7 +1502,7 @@ def main():
 
     # ---- stacked edits ("throughput mode"): E edits of ONE original, each with its own mask, through one set of launches ----
     batched = None
-    if rank == 0 and world == 1 and not args.no_dynamic and args.layout == "nhwc" and args.batched_edits:
+    if rank == 0 and args.full and world == 1 and not args.no_dynamic and args.layout == "nhwc" and args.batched_edits:
         from sige_amd import stacked
         from sige_amd.nn import dense as _dense
 
@@ -1595,7 +1641,7 @@ def main():
                 pass
 
     extras = {}
-    if rank == 0 and world == 1 and not args.no_extras and args.layout == "nhwc":
+    if rank == 0 and args.full and world == 1 and not args.no_extras and args.layout == "nhwc":
         for key, fn in (("gaugan", lambda: gaugan_section(dev, cpu_parity=args.cpu_seconds > 0)), ("sd_transformer", lambda: sd_transformer_section(dev))):
             try:
                 extras[key] = fn()
@@ -1608,7 +1654,7 @@ def main():
     if rank == 0:
         cpu = None
         parity = None
-        if args.cpu_seconds > 0:
+        if args.full and args.cpu_seconds > 0:
             # the benchmarked artefact (this layout, in-place buffers, hipGraph replay) against the reference's CPU path on
             # the SAME weights / image / noise / masks: max |gpu - cpu| per edit ratio, outside every timed region
             ratios = sorted(set(gpu_out) | set(gpu_out_f16) | set(gpu_out_x3))
@@ -1647,12 +1693,12 @@ def main():
             "rccl_ranks": dist.get_world_size() if world > 1 else 1, "backend": args.backend if world > 1 else None,
             "devices": [torch.cuda.get_device_name(i) for i in range(min(world, torch.cuda.device_count()))],
             "forward_ms": round(ms_steady, 4),
-            "forward_ms_eager": round(e_ms, 3),
-            "dense_forward_ms": round(dense_ms, 3),
-            "speedup_vs_dense": round(dense_ms / ms_steady, 2),
-            "cache_bytes": int(flat.numel() * flat.element_size()), "cache_dtype": args.cache_dtype, "cached_tensors": n_cached,
-            "sweep": sweep,
         }
+        if args.full:
+            line.update(forward_ms_eager=round(e_ms, 3), dense_forward_ms=round(dense_ms, 3), speedup_vs_dense=round(dense_ms / ms_steady, 2))
+        line.update(cache_bytes=int(flat.numel() * flat.element_size()), cache_dtype=args.cache_dtype, cached_tensors=n_cached)
+        if args.full:
+            line["sweep"] = sweep
         if world > 1:
             step_s = dt_steady / args.steps
             line["multi_gpu"] = dict(
@@ -1677,12 +1723,13 @@ def main():
         # the >= 6x target of north_star is quoted against the stock dense forward (MIOpen: SURVEY.md 8d); the same forward on this
         # library's own dense-layer kernels is faster than MIOpen, so both ratios are printed
         fp = (x3 or {}).get("full_pass_ms") or {}
-        line["speedup_vs_dense_detail"] = {
-            "vs_miopen": round(dense_ms / ms_steady, 2),
-            "vs_library_full_pass_f32_exact": round(fp["library_f32_exact"] / ms_steady, 2) if fp.get("library_f32_exact") else None,
-            "vs_library_full_pass_f16x3": round(fp["library_f16x3"] / ms_steady, 2) if fp.get("library_f16x3") else None,
-            "note": "dense forward of the same U-Net on the same GPU / this sparse forward: MIOpen fp32 (best of NCHW / NHWC; the "
-                    "contract of SURVEY.md 8d), the library's own exact-fp32 full pass, the library's full pass on split fp16 operands"}
+        if dense_ms is not None:
+            line["speedup_vs_dense_detail"] = {
+                "vs_miopen": round(dense_ms / ms_steady, 2),
+                "vs_library_full_pass_f32_exact": round(fp["library_f32_exact"] / ms_steady, 2) if fp.get("library_f32_exact") else None,
+                "vs_library_full_pass_f16x3": round(fp["library_f16x3"] / ms_steady, 2) if fp.get("library_f16x3") else None,
+                "note": "dense forward of the same U-Net on the same GPU / this sparse forward: MIOpen fp32 (best of NCHW / NHWC; the "
+                        "contract of SURVEY.md 8d), the library's own exact-fp32 full pass, the library's full pass on split fp16 operands"}
         if parity is not None:
             line["parity_max_abs"] = parity
             if args.dtype == "f16":

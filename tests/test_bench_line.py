@@ -181,3 +181,37 @@ def test_cpu_baseline_names_its_model_on_both_branches(monkeypatch):
         runtime.unregister_backend("cpu")
     assert float((outs_ref[r] - quirk).abs().max()) < 2e-4
     assert float((outs_ref[r] - outs_repo[r]).abs().max()) > 1e-3  # (the quirk is real: the two maths differ)
+
+
+# ---- --dump-outputs / --full ----------------------------------------------------------------------------------------------------
+def test_dump_outputs_writes_float32_arrays(tmp_path):
+    """bench.py --dump-outputs: one float32 .npy per output in logical NCHW order (also from a channels-last tensor), a suffix per
+    rank > 0, and nothing at all past the 64 MB limit."""
+    import numpy as np
+    import torch
+
+    import bench
+
+    x = torch.randn(2, 3, 4, 5, dtype=torch.float64).contiguous(memory_format=torch.channels_last)
+    bench.dump_outputs(str(tmp_path / "d"), {"output": x})
+    bench.dump_outputs(str(tmp_path / "d"), {"output": x}, rank=2)
+    a = np.load(tmp_path / "d" / "output.npy")
+    assert a.dtype == np.float32 and a.shape == (2, 3, 4, 5) and a.flags["C_CONTIGUOUS"]
+    assert np.array_equal(a, x.float().numpy())
+    assert np.array_equal(np.load(tmp_path / "d" / "output_rank2.npy"), a)
+    with pytest.raises(ValueError):
+        bench.dump_outputs(str(tmp_path / "big"), {"output": torch.zeros(bench.DUMP_LIMIT_BYTES // 4 + 1)})
+    assert not (tmp_path / "big").exists()
+
+
+def test_bench_cli_has_full_and_dump_outputs():
+    """A plain run times the headline only; every other section is behind --full, and --dump-calls needs it."""
+    import subprocess
+    import sys
+
+    p = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--help"], capture_output=True, text=True, timeout=300)
+    assert p.returncode == 0, p.stderr[-2000:]
+    assert "--full" in p.stdout and "--dump-outputs" in p.stdout
+    p = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--dump-calls", "x.json"], capture_output=True, text=True,
+                       timeout=300)
+    assert p.returncode == 2 and "--dump-calls goes with --full" in p.stderr
