@@ -895,3 +895,84 @@ def test_gaugan_stacked_mode_refuses_off_the_gpu():
     model.cfg.fused = False
     with pytest.raises(RuntimeError, match="stacked edits"):
         model(seg)
+
+
+# ---- tests/util.poisoned: the helper tests/test_gpu_poison.py runs every kernel under ----------------------------------------
+@pytest.mark.parametrize("value", [float("nan"), 1e30])
+def test_poisoned_fills_every_fresh_floating_point_allocation(value):
+    def poison(t):
+        if value != value:
+            return bool(torch.isnan(t).all())
+        return bool((t == min(value, torch.finfo(t.dtype).max)).all())  # (fp16 cannot hold 1e30: its largest finite value)
+
+    base = torch.randn(6, 5)
+    with util.poisoned(value) as p:
+        fresh = {
+            "empty": torch.empty(3, 4),
+            "empty_like": torch.empty_like(base),
+            "new_empty": base.new_empty(7),
+            "channels_last": torch.empty(2, 3, 5, 4, memory_format=torch.channels_last),
+            "empty_like_cl": torch.empty_like(torch.randn(2, 3, 5, 4).contiguous(memory_format=torch.channels_last)),
+            "fp16": torch.empty(9, dtype=torch.float16),
+            "bf16": torch.empty(9, dtype=torch.bfloat16),
+            "empty_strided": torch.empty_strided((3, 2), (1, 3)),
+            "new_empty_strided": base.new_empty_strided((2, 2), (2, 1)),
+        }
+        buf = torch.empty(40)
+        sliced = buf[8:20].view(3, 4)  # (a slice of a fresh buffer: the storage is poisoned, not only the view)
+    assert fresh["channels_last"].is_contiguous(memory_format=torch.channels_last)
+    assert fresh["empty_like_cl"].is_contiguous(memory_format=torch.channels_last)
+    for name, t in fresh.items():
+        assert poison(t), name
+    assert poison(buf) and poison(sliced)
+    assert p.n == len(fresh) + 1
+
+
+def test_poisoned_leaves_integers_and_written_tensors_alone():
+    src = torch.randn(4, 5)
+    with util.poisoned() as p:
+        i32 = torch.empty(1000, dtype=torch.int32)
+        u8 = torch.empty(1000, dtype=torch.uint8)
+        b = torch.empty(10, dtype=torch.bool)
+        zeros = torch.zeros(4, 5)
+        ones = torch.ones(3, dtype=torch.float16)
+        full = torch.full((2, 2), 3.0)
+        cl = src.clone()
+        cp = src.to(torch.float16)
+        r = torch.randn(8)
+        s = src * 2 + 1
+    assert p.n == 0  # (integer / bool allocations are not counted: they were not touched)
+    assert i32.dtype == torch.int32 and u8.dtype == torch.uint8 and b.dtype == torch.bool
+    assert torch.equal(zeros, torch.zeros(4, 5)) and torch.equal(ones, torch.ones(3, dtype=torch.float16))
+    assert torch.equal(full, torch.full((2, 2), 3.0))
+    assert torch.equal(cl, src) and torch.equal(cp, src.half()) and torch.equal(s, src * 2 + 1)
+    assert bool(torch.isfinite(r).all())
+
+
+def test_poisoned_restores_plain_allocation_on_exit_and_on_error():
+    p = util.poisoned()
+    with pytest.raises(RuntimeError, match="boom"):
+        with p:
+            torch.empty(3)
+            raise RuntimeError("boom")
+    assert p.n == 1
+    n = p.n
+    torch.empty(5)
+    torch.empty_like(torch.randn(3))
+    assert p.n == n  # (the mode is off: nothing more is counted)
+    from torch.utils._python_dispatch import _get_current_dispatch_mode
+
+    assert _get_current_dispatch_mode() is None
+
+
+def test_assert_finite_names_the_first_non_finite_element():
+    util.assert_finite(torch.randn(3, 4), "ok")
+    t = torch.zeros(2, 3, 4)
+    t[1, 2, 3] = float("inf")
+    t[1, 0, 1] = float("nan")
+    with pytest.raises(AssertionError, match=r"out: 2 non-finite of 24, first at \(1, 0, 1\)"):
+        util.assert_finite(t, "out")
+    cl = torch.zeros(1, 2, 3, 3).contiguous(memory_format=torch.channels_last)
+    cl[0, 1, 2, 0] = float("nan")
+    with pytest.raises(AssertionError, match=r"first at \(0, 1, 2, 0\)"):
+        util.assert_finite(cl, "cl")

@@ -156,3 +156,62 @@ def record_margin(test, what, value, tol):
         except OSError:  # (a read-only scratch directory must not fail a parity test)
             pass
     return float(value)
+
+
+# ---- poisoned allocations: what a kernel leaves unwritten, or reads from memory nobody wrote, must show ----------------------
+class poisoned:
+    """Inside `with poisoned(value) as p:` every floating-point tensor that aten.empty / empty_like / new_empty / empty_strided /
+    new_empty_strided returns (any device, any memory format; fp64 / fp32 / fp16 / bf16) is filled with `value` before anyone
+    sees it, so an output a kernel never stores to, or a workspace it reads before writing, carries NaN (or a huge finite value,
+    for the reads a NaN slips through: max, ReLU, `x > tol`).  torch.empty hands back freed blocks of the same size, which in a
+    test often still hold the right answer; poisoning is what makes a missed store visible.  Integer and bool tensors (index
+    lists, tables, maps) are left alone on purpose: an out-of-range index turns an over-read into an out-of-bounds address; they
+    are compared bit-exactly instead.  Inside a CUDA graph capture the fill is captured too, so every replay re-poisons.
+    A finite value beyond a narrow type's range becomes that type's largest finite value.  `p.n` counts the tensors poisoned.  (Not torch.utils.deterministic.fill_uninitialized_memory: that fills integers with
+    INT_MAX and, through use_deterministic_algorithms, changes algorithm choice everywhere.)"""
+
+    def __init__(self, value=float("nan")):
+        self.value = float(value)
+        self.n = 0
+        self._mode = None
+
+    def __enter__(self):
+        from torch.utils._python_dispatch import TorchDispatchMode
+
+        aten = torch.ops.aten
+        empties = {aten.empty.memory_format, aten.empty_like.default, aten.new_empty.default, aten.empty_strided.default,
+                   aten.new_empty_strided.default}
+        owner = self
+
+        class _Poison(TorchDispatchMode):
+            def __torch_dispatch__(self, func, types, args=(), kwargs=None):
+                out = func(*args, **(kwargs or {}))
+                if (func in empties and isinstance(out, torch.Tensor) and out.is_floating_point()
+                        and out.device.type != "meta" and out.numel() > 0):
+                    v = owner.value
+                    if abs(v) != float("inf") and abs(v) > torch.finfo(out.dtype).max:  # (1e30 in an fp16 buffer: its largest finite)
+                        v = torch.finfo(out.dtype).max if v > 0 else -torch.finfo(out.dtype).max
+                    out.fill_(v)
+                    owner.n += 1
+                return out
+
+        self._mode = _Poison()
+        self._mode.__enter__()
+        return self
+
+    def __exit__(self, *exc):
+        mode, self._mode = self._mode, None
+        mode.__exit__(*exc)
+        return False
+
+
+def assert_finite(t, what):
+    """`t` holds no NaN / Inf; else name the first non-finite element (multi-index into t's logical shape) and its value."""
+    ok = torch.isfinite(t)
+    if bool(ok.all()):
+        return
+    flat = (~ok).reshape(-1).nonzero()
+    first = int(flat[0])
+    index = tuple(int(i) for i in np.unravel_index(first, tuple(t.shape)))
+    raise AssertionError("%s: %d non-finite of %d, first at %s = %r" % (what, int(flat.numel()), t.numel(), index,
+                                                                        float(t.reshape(-1)[first])))
