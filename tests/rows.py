@@ -16,7 +16,10 @@ ROW_TESTS = {
     "a7 scatter_gather + map": ["test_gpu_parity.py::test_golden_cases", "test_gpu_round3.py::test_scatter_gather_row_form_bit_exact"],
     "a8 module / model wrappers": ["test_gpu_parity.py::test_ddpm_unet_gpu_vs_oracle_backend", "test_gpu_parity.py::test_example_py_on_gpu",
                                    "test_gpu_parity.py::test_example_golden_output_on_gpu",
-                                   "test_gpu_round2.py::test_benchmarked_forward_vs_oracle_at_full_size"],
+                                   "test_gpu_round2.py::test_benchmarked_forward_vs_oracle_at_full_size",
+                                   "test_gpu_masks.py::test_one_model_through_every_mask_vs_oracle",
+                                   "test_gpu_masks.py::test_launch_plan_follows_every_mask_vs_oracle",
+                                   "test_gpu_masks.py::test_stacked_zoo_vs_cpu_oracle"],
     "a9 cached affine producer": ["test_gpu_parity.py::test_group_norm_affine_vs_torch", "test_gpu_channels_last.py::test_group_norm_affine_cl"],
     "f1 dense remainder": ["test_gpu_parity.py::test_dense_fused_conv_vs_torch", "test_gpu_parity.py::test_attention_vs_torch",
                            "test_gpu_round2.py::test_benchmarked_forward_vs_oracle_at_full_size"],
