@@ -681,6 +681,18 @@ int sige_hip_attention_f32(const float *qkv, int B, int C, int HW, float scale, 
 /* channels-last form: qkv [B,HW,3C] -> out [B,HW,C]; C % 64 == 0 */
 int sige_hip_attention_nhwc_f32(const float *qkv, int B, int C, int HW, float scale, float *workspace,
                                 float *out, void *stream);
+/* ... with the epilogue of the 1x1 proj_out conv that follows the attention in the U-Net, for a caller that has folded that
+ * conv's matrix into the value projection (softmax rows sum to 1: W_p (P v) + b_p = P (W_p W_v x + W_p b_v) + b_p):
+ *   out = (attention + bias[c]) + residual;   twin_k = SiLU(twin_k_shift[c] + twin_k_scale[c] * out)
+ * -- separately rounded fp32 ops in that order, the twins as in the full-tensor conv entry points.  bias / twin scale / shift
+ * [C]; residual / twins [B,HW,C]; each optional (NULL), all NULL = sige_hip_attention_nhwc_f32 bit for bit.  The same two
+ * launches, workspace and supported shapes (SIGE_HIP_EUNSUPPORTED otherwise); SIGE_HIP_EINVAL for a twin without its scale and
+ * shift, or an optional pointer that is not 16-byte aligned. */
+int sige_hip_attention_residual_nhwc_f32(const float *qkv, int B, int C, int HW, float scale, float *workspace,
+                                         const float *bias, const float *residual,
+                                         float *twin0, const float *twin0_scale, const float *twin0_shift,
+                                         float *twin1, const float *twin1_scale, const float *twin1_shift,
+                                         float *out, void *stream);
 /* the same in ONE launch (round 4): workgroup = 16 queries x 64 keys, exact fp32 MFMA scores, the 64-key slices of a query
  * block combined by the last one to finish (flash-decoding split; the tickets of the conv kernels' K-split finish) -- no score
  * tensor in HBM, 6 launches fewer per DDPM forward.  C in {64, 128, 256, 512}, HW % 16 == 0, HW <= 1024; `workspace` holds the

@@ -91,6 +91,12 @@ def build_tuning(force: bool = False, verbose: bool = True) -> str:
     library that exports sige_hip_tuning_set / _get (include/sige_hip.h).  tools/, the bench sections that compare kernel
     forms and the tests that force a form load it (sige_amd.hip.tuning_build())."""
     build(force=force, verbose=verbose)
+    if not force and os.path.isfile(TUNING_LIB):
+        # (a tree that carries the libraries without their objects: current if nothing it was made from is newer)
+        t = os.path.getmtime(TUNING_LIB)
+        deps = [os.path.join(CSRC, f) for f in os.listdir(CSRC)] + [os.path.join(REPO, "include", "sige_hip.h"), LIB]
+        if all(os.path.getmtime(d) <= t for d in deps):
+            return TUNING_LIB
     tdir = os.path.join(LIB_DIR, "tuning")
     os.makedirs(tdir, exist_ok=True)
     headers = _headers()

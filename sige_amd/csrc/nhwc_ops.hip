@@ -297,10 +297,21 @@ __global__ __launch_bounds__(kT) void attn_scores_nhwc_kernel(const float *__res
     S[((size_t)b * HW + i0 + qi) * HW + j0 + kj] = v * scale;
 }
 
+// Optional epilogue of attn_apply_nhwc_kernel<true> (sige_hip_attention_residual_nhwc_f32): what the 1x1 proj_out launch behind
+// the attention did besides its matrix product, once that product is folded into the value projection --
+// out = (P v + bias[c]) + residual, twin_k = SiLU(tshift_k[c] + tscale_k[c] * out).  Every pointer may be null.
+struct AttnEpilogue {
+    const float *bias, *residual;  // [C], [B,HW,C]
+    float *twin0, *twin1;          // [B,HW,C]
+    const float *tscale0, *tshift0, *tscale1, *tshift1;  // [C]
+};
+
 // out[i][c] = sum_j softmax_j(S[i][.])[j] v[j][c]:  A[m = query][k = key] = P (LDS), B[k = key][n = channel] = v (global,
 // 64-byte coalesced per lane group).  Workgroup = 16 queries x 64 channels (one 16x16 tile per wave).
+// EPI: the epilogue above (`e` is not read without it: that instance is the kernel as it was).
+template <bool EPI>
 __global__ __launch_bounds__(kT) void attn_apply_nhwc_kernel(const float *__restrict__ qkv, const float *__restrict__ S,
-                                                            int C, int HW, float *__restrict__ out) {
+                                                            int C, int HW, float *__restrict__ out, AttnEpilogue e) {
     extern __shared__ __attribute__((aligned(16))) float P[];  // [16][HW + 4]
     const int PS = HW + 4;
     const int b = blockIdx.z;
@@ -321,6 +332,21 @@ __global__ __launch_bounds__(kT) void attn_apply_nhwc_kernel(const float *__rest
         (unsigned)min((size_t)0x7fffffff, ((size_t)HW * 3 * C - 2 * C) * sizeof(float)), 0x00020000);
     const int v_lane = ((cok ? c : 0) + kq * (int)rs) * (int)sizeof(float);
     const int v_step = 4 * (int)rs * (int)sizeof(float);  // bytes between key steps
+    // the epilogue's operands: a lane's channel is fixed, so bias and twin affine are five scalars; its four residual values (one per
+    // query row of its accumulators) are requested with the score rows and are in flight during the softmax and the K loop
+    // (branch-free: a null operand reads qkv at the same offsets -- inside it, B*HW*C <= B*HW*3C -- and is dropped by a select)
+    float e_bias = 0.f, e_s0 = 0.f, e_t0 = 0.f, e_s1 = 0.f, e_t1 = 0.f, e_res[4] = {0.f, 0.f, 0.f, 0.f};
+    auto load_epilogue = [&]() {
+        if constexpr (EPI) {
+            const int cc = cok ? c : 0;
+            e_bias = (e.bias ? e.bias : qkv)[cc];
+            e_s0 = (e.twin0 ? e.tscale0 : qkv)[cc]; e_t0 = (e.twin0 ? e.tshift0 : qkv)[cc];
+            e_s1 = (e.twin1 ? e.tscale1 : qkv)[cc]; e_t1 = (e.twin1 ? e.tshift1 : qkv)[cc];
+            const float *rp = (e.residual ? e.residual : qkv) + ((size_t)b * HW + i0 + 4 * kq) * C + cc;
+#pragma unroll
+            for (int r = 0; r < 4; ++r) e_res[r] = rp[(size_t)r * C];
+        }
+    };
     float bv[64];
     auto load_values = [&](int j0) {
         const int nk = min(256, HW - j0) / 4;  // k-steps in this block (HW % 16 == 0)
@@ -341,6 +367,7 @@ __global__ __launch_bounds__(kT) void attn_apply_nhwc_kernel(const float *__rest
                 const float4 q4 = ld4(srow + min(j, HW - 4));  // (branch-free: a group past the row reads its last four, masked below)
                 t[u] = j < HW ? q4 : make_float4(-INFINITY, -INFINITY, -INFINITY, -INFINITY);
             }
+            load_epilogue();
             load_values(0);
             float m = -INFINITY;
 #pragma unroll
@@ -365,6 +392,7 @@ __global__ __launch_bounds__(kT) void attn_apply_nhwc_kernel(const float *__rest
                 }
             }
         } else {
+            load_epilogue();
             load_values(0);
             float m = -INFINITY;
             for (int j = l16 * 4; j < HW; j += 64) {
@@ -408,7 +436,18 @@ __global__ __launch_bounds__(kT) void attn_apply_nhwc_kernel(const float *__rest
     // D[row = query 4*kq + r][col = channel n]
     if (cok) {
 #pragma unroll
-        for (int r = 0; r < 4; ++r) out[((size_t)b * HW + i0 + 4 * kq + r) * C + c] = acc0[r] + acc1[r];
+        for (int r = 0; r < 4; ++r) {
+            const size_t at = ((size_t)b * HW + i0 + 4 * kq + r) * C + c;
+            float s = acc0[r] + acc1[r];
+            if constexpr (EPI) {
+                // bias, residual, twins: separately rounded ops in the order of the conv epilogues (conv_mfma.hpp: emit)
+                if (e.bias) s += e_bias;
+                if (e.residual) s += e_res[r];
+                if (e.twin0) { float t = e_s0 * s; t = e_t0 + t; e.twin0[at] = swish(t); }
+                if (e.twin1) { float t = e_s1 * s; t = e_t1 + t; e.twin1[at] = swish(t); }
+            }
+            out[at] = s;
+        }
     }
 }
 
@@ -731,6 +770,32 @@ extern "C" int sige_hip_attention_nhwc_f32(const float *qkv, int B, int C, int H
     if (lds > 64 * 1024 || (size_t)HW * 3 * C * sizeof(float) >= 0x7fffffffu) return SIGE_HIP_EUNSUPPORTED;  // (32-bit value offsets)
     hipStream_t st = as_stream(stream);
     attn_scores_nhwc_kernel<<<dim3(HW / 16, HW / 16, B), kT, 0, st>>>(qkv, C, HW, scale, workspace);
-    attn_apply_nhwc_kernel<<<dim3(ceil_div(C, 64), HW / 16, B), kT, lds, st>>>(qkv, workspace, C, HW, out);
+    attn_apply_nhwc_kernel<false><<<dim3(ceil_div(C, 64), HW / 16, B), kT, lds, st>>>(qkv, workspace, C, HW, out, AttnEpilogue{});
+    return launch_status(2);
+}
+
+extern "C" int sige_hip_attention_residual_nhwc_f32(const float *qkv, int B, int C, int HW, float scale, float *workspace,
+                                                    const float *bias, const float *residual,
+                                                    float *twin0, const float *twin0_scale, const float *twin0_shift,
+                                                    float *twin1, const float *twin1_scale, const float *twin1_shift,
+                                                    float *out, void *stream) {
+    SIGE_PLAN_HOOK(sige_hip_attention_residual_nhwc_f32, qkv, B, C, HW, scale, workspace, bias, residual, twin0, twin0_scale, twin0_shift, twin1, twin1_scale, twin1_shift, out, stream);
+    if (B <= 0 || C <= 0 || HW <= 0) return SIGE_HIP_EINVAL;
+    if (!qkv || !workspace || !out) return SIGE_HIP_EINVAL;
+    if ((twin0 && !(twin0_scale && twin0_shift)) || (twin1 && !(twin1_scale && twin1_shift))) return SIGE_HIP_EINVAL;
+    if (!al16(bias) || !al16(residual) || !al16(twin0) || !al16(twin0_scale) || !al16(twin0_shift) || !al16(twin1) ||
+        !al16(twin1_scale) || !al16(twin1_shift))
+        return SIGE_HIP_EINVAL;
+    // (shapes: exactly those of sige_hip_attention_nhwc_f32 -- the same scores launch, the same workspace)
+    if (HW % 16 || C % 64 || B > 65535 || !al16(qkv) || !al16(workspace)) return SIGE_HIP_EUNSUPPORTED;
+    const size_t lds = (size_t)16 * (HW + 4) * sizeof(float);
+    if (lds > 64 * 1024 || (size_t)HW * 3 * C * sizeof(float) >= 0x7fffffffu) return SIGE_HIP_EUNSUPPORTED;
+    AttnEpilogue e{};
+    e.bias = bias; e.residual = residual;
+    e.twin0 = twin0; e.tscale0 = twin0_scale; e.tshift0 = twin0_shift;
+    e.twin1 = twin1; e.tscale1 = twin1_scale; e.tshift1 = twin1_shift;
+    hipStream_t st = as_stream(stream);
+    attn_scores_nhwc_kernel<<<dim3(HW / 16, HW / 16, B), kT, 0, st>>>(qkv, C, HW, scale, workspace);
+    attn_apply_nhwc_kernel<true><<<dim3(ceil_div(C, 64), HW / 16, B), kT, lds, st>>>(qkv, workspace, C, HW, out, e);
     return launch_status(2);
 }

@@ -132,6 +132,7 @@ _SIGNATURES = {
     "sige_hip_conv3x3_small_cin_tiles_nhwc_f32": (
         _c_int, [_c_vp] + [ctypes.c_int64] * 4 + [_c_int] * 4 + [_c_vp, _c_vp, _c_int, _c_vp, _c_int, _c_int, _c_int, _c_vp, _c_vp]),
     "sige_hip_attention_nhwc_f32": (_c_int, [_c_vp, _c_int, _c_int, _c_int, ctypes.c_float, _c_vp, _c_vp, _c_vp]),
+    "sige_hip_attention_residual_nhwc_f32": (_c_int, [_c_vp, _c_int, _c_int, _c_int, ctypes.c_float, _c_vp] + [_c_vp] * 10),
     "sige_hip_attention_fused_workspace": (_c_sz, [_c_int] * 3),
     "sige_hip_attention_fused_nhwc_f32": (_c_int, [_c_vp, _c_int, _c_int, _c_int, ctypes.c_float, _c_vp, _c_vp, _c_vp]),
     # split fp16 operands (tile kernels)
@@ -2057,6 +2058,34 @@ def attention_cl(qkv: torch.Tensor, scale: float):
         return None
     _check(status, "attention_cl")
     return out
+
+
+def attention_residual_cl(qkv: torch.Tensor, scale: float, bias: Optional[torch.Tensor] = None,
+                          residual: Optional[torch.Tensor] = None, twins: Optional[dict] = None):
+    """attention_cl with the epilogue of the 1x1 conv that follows it, for a caller that has folded that conv's matrix into the
+    value projection (include/sige_hip.h: sige_hip_attention_residual_nhwc_f32): out = (attention + bias[c]) + residual, and per
+    entry of `twins` = {key: (scale [C], shift [C])} (at most two are served) SiLU(shift + scale * out).  Two launches, as
+    attention_cl.  Returns (out, {key: twin}) -- or None if the shape is unsupported."""
+    qkv = _req_cl(qkv, "qkv")
+    B, C3, H, W = qkv.shape
+    C, HW = C3 // 3, H * W
+    out = _empty_cl((B, C, H, W), qkv.device)
+    bias_keep = _vec(bias, "bias")
+    if bias_keep is not None and bias_keep.numel() != C:
+        raise RuntimeError("attention_residual_cl: bias needs one entry per channel")
+    if residual is not None:
+        residual = _req_cl(residual, "residual")
+        if tuple(residual.shape) != tuple(out.shape):
+            raise RuntimeError("attention_residual_cl: residual must be shaped like the output")
+    tw = [(key, _empty_cl((B, C, H, W), qkv.device), sc, sh) for key, (sc, sh) in list((twins or {}).items())[:2]]
+    targs, twin_keep = _twin_args([(b, sc, sh) for _, b, sc, sh in tw] or None, out, C, "attention_residual_cl")
+    ws = torch.empty(B * HW * HW, dtype=torch.float32, device=qkv.device)
+    status = lib().sige_hip_attention_residual_nhwc_f32(qkv.data_ptr(), B, C, HW, float(scale), ws.data_ptr(), _p(bias_keep),
+                                                        _p(residual), *targs, out.data_ptr(), _stream(qkv))
+    if status == UNSUPPORTED:
+        return None
+    _check(status, "attention_residual_cl")
+    return out, {key: b for key, b, _, _ in tw}
 
 
 def attention_tokens(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, heads: int, scale: float) -> Optional[torch.Tensor]:

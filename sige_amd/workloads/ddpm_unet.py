@@ -105,6 +105,31 @@ def _as4(v: torch.Tensor) -> torch.Tensor:
     return v.reshape(1, -1, 1, 1)
 
 
+# Dense attention blocks in sparse mode: run proj_out inside the value projection (AttnBlock.folded_proj) and its bias, residual
+# and twins in the epilogue of the attention's second kernel -- three launches per block instead of four.
+# False: the chain as it was, qkv conv -> attention -> proj_out conv (A/B runs, tests).
+FOLD_ATTN_PROJ = True
+
+
+def fold_proj_into_qkv(w_qkv: torch.Tensor, b_qkv: Optional[torch.Tensor], w_p: torch.Tensor, b_p: Optional[torch.Tensor]):
+    """proj_out folded into the value rows of a single-head attention block's qkv conv.  The softmax rows P sum to 1, so
+
+        W_p (P v) + b_p = P (W_p W_v x + W_p b_v) + b_p = P (W_vp x) + b'     W_vp = W_p W_v,  b' = W_p b_v + b_p
+
+    Returns (weight [3C,C,1,1] = cat(W_q, W_k, W_vp), bias [3C] = cat(b_q, b_k, 0), b' [C]) in the dtype of `w_qkv`; the
+    products are formed in fp64 and rounded once."""
+    C = w_p.shape[0]
+    wq = w_qkv.detach().reshape(3 * C, C)
+    wp = w_p.detach().reshape(C, C).double()
+    bq = torch.zeros(3 * C, dtype=wq.dtype, device=wq.device) if b_qkv is None else b_qkv.detach()
+    w = torch.cat([wq[:2 * C], (wp @ wq[2 * C:].double()).to(wq.dtype)]).reshape(3 * C, C, 1, 1)
+    b = torch.cat([bq[:2 * C], torch.zeros_like(bq[2 * C:])])
+    bp = wp @ bq[2 * C:].double()
+    if b_p is not None:
+        bp = bp + b_p.detach().double()
+    return w.contiguous(), b, bp.to(wq.dtype)
+
+
 class _TwinProducer:
     """Mixin of the modules whose output is written by a full-tensor conv epilogue and can therefore carry activated twins
     for the conv1 of a consumer (cfg.conv1_twins).  `_twin_scatter()`: the Scatter module that owns the persistent in-place
@@ -417,9 +442,6 @@ class AttnBlock(SIGEModule, _TwinProducer):
         self.affine = {}
         self.plain = False
 
-    def clear_cache(self):
-        self.affine = {}
-
     def forward(self, x: torch.Tensor) -> torch.Tensor:
         if self.mode == "full" and self.plain:
             h = self.norm(x)
@@ -475,7 +497,62 @@ class AttnBlock(SIGEModule, _TwinProducer):
     def _twins_ok(self) -> bool:
         return not self.sparse  # (the tiled form ends in a plain Scatter with a residual: not wired for twins)
 
+    def clear_cache(self):
+        self.affine = {}
+        self.__dict__.pop("_fold", None)
+
+    def folded_proj(self):
+        """(conv, b'): the qkv conv with proj_out folded into its value rows (fold_proj_into_qkv) as a derived nn.Conv2d that the
+        dense-layer launches pack like any other, and the bias left for the attention's epilogue.  Neither is a Parameter, a
+        buffer or a submodule -- the state dict keeps the reference's keys.  Rebuilt when a parameter of `qkv` / `proj_out` has
+        been replaced, moved or edited in place (address, version counter, shape, device, dtype: what the packed-weight caches
+        key on, sige_amd/nn/base.py), and after clear_cache() -- an edit through `.data` moves no version counter."""
+        params = (self.qkv.weight, self.qkv.bias, self.proj_out.weight, self.proj_out.bias)
+        key = tuple(None if p is None else (p.data_ptr(), p._version, tuple(p.shape), p.device, p.dtype) for p in params)
+        key += (getattr(self.qkv, "compute_dtype", "f32"),)
+        entry = self.__dict__.get("_fold")
+        if entry is None or entry[0] != key:
+            w, b, bp = fold_proj_into_qkv(*params)
+            conv = nn.Conv2d(self.ch, 3 * self.ch, 1, 1, 0, device="meta")
+            conv.weight, conv.bias = nn.Parameter(w, requires_grad=False), nn.Parameter(b, requires_grad=False)
+            conv.compute_dtype = key[-1]
+            entry = (key, conv, bp)
+            self.__dict__["_fold"] = entry  # (not through nn.Module.__setattr__: that would register the conv as a submodule)
+        return entry[1], entry[2]
+
+    def _fold_ok(self, x) -> bool:
+        # where hip.attention_residual_cl runs, and in exact fp32 only ("f16" / "f16x3" layers keep the chain their sweeps pin)
+        if not (FOLD_ATTN_PROJ and x.is_cuda and x.dtype == torch.float32):
+            return False
+        if getattr(self.qkv, "compute_dtype", "f32") != "f32" or getattr(self.proj_out, "compute_dtype", "f32") != "f32":
+            return False
+        from .. import hip
+
+        return hip.is_cl(x) and not hip.FUSED_ATTENTION
+
     def _dense_sparse(self, x, s, t):
+        refused = self.__dict__.setdefault("_fold_refused", set())  # (shapes the attention kernels do not take: asked once)
+        if tuple(x.shape) not in refused and self._fold_ok(x):
+            from .. import hip
+
+            conv, bp = self.folded_proj()
+            qkv = fused_conv2d(conv, x, s, t, "identity")
+            if hip.is_cl(qkv):
+                E = self.edit_batch if qkv.shape[0] == 1 else 1
+                if E > 1:
+                    # stacked edits: the tall image is E images -- tokens attend within their own image (the same bytes seen as
+                    # batch E, residual and twins alike)
+                    from ..stacked import tall, untall
+
+                    res = hip.attention_residual_cl(untall(qkv, E), self.ch ** -0.5, bp, residual=untall(x, E), twins=self._my_twins())
+                    if res is not None:
+                        res = (tall(res[0]), {k: tall(v) for k, v in res[1].items()})
+                else:
+                    res = hip.attention_residual_cl(qkv, self.ch ** -0.5, bp, residual=x, twins=self._my_twins())
+                if res is not None:
+                    res[0]._sige_twins = res[1]
+                    return self._produced(res[0])
+            refused.add(tuple(x.shape))
         qkv = fused_conv2d(self.qkv, x, s, t, "identity")
         return self._produced(fused_conv2d(self.proj_out, self._attention(qkv), residual=x, twins=self._my_twins()))
 
