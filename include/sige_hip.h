@@ -693,6 +693,19 @@ int sige_hip_attention_residual_nhwc_f32(const float *qkv, int B, int C, int HW,
                                          float *twin0, const float *twin0_scale, const float *twin0_shift,
                                          float *twin1, const float *twin1_scale, const float *twin1_shift,
                                          float *out, void *stream);
+/* ... with the key projection folded away as well.  With x_n = s*x + t the block's normalised input, q = W_q x_n + b_q and
+ * k = W_k x_n + b_k, every term of q_i . k_j that does not depend on the key j cancels in the softmax over j, so
+ *   softmax_j(scale q_i . k_j) = softmax_j(scale q''_i . x_j),   q'' = s * ((W_k^T W_q) x_n + W_k^T b_q)
+ * and the keys are the block input itself.  qv [B,HW,2C] = (q | v') on the channel axis, keys [B,HW,C] (16-byte aligned).
+ * qscale [qscaleB, C] (qscaleB 1 or B; 16-byte aligned) or NULL: the factor s, applied to the query channels as the score kernel
+ * loads them (q'' = qscale * q) -- read from the caller's own tensor at every launch, so a caller whose cached scale is rewritten
+ * in place keeps no copy of it; NULL: qv holds q'' already.  SIGE_HIP_EINVAL for another qscaleB or a misaligned qscale;
+ * everything else -- epilogue, launches, workspace, supported shapes, error codes -- as sige_hip_attention_residual_nhwc_f32. */
+int sige_hip_attention_residual_qv_nhwc_f32(const float *qv, const float *keys, const float *qscale, int qscaleB,
+                                            int B, int C, int HW, float scale, float *workspace, const float *bias, const float *residual,
+                                            float *twin0, const float *twin0_scale, const float *twin0_shift,
+                                            float *twin1, const float *twin1_scale, const float *twin1_shift,
+                                            float *out, void *stream);
 /* the same in ONE launch (round 4): workgroup = 16 queries x 64 keys, exact fp32 MFMA scores, the 64-key slices of a query
  * block combined by the last one to finish (flash-decoding split; the tickets of the conv kernels' K-split finish) -- no score
  * tensor in HBM, 6 launches fewer per DDPM forward.  C in {64, 128, 256, 512}, HW % 16 == 0, HW <= 1024; `workspace` holds the

@@ -257,29 +257,41 @@ static int grid_for(long units) {
 // ---------------------------------------------------------------- attention ----
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
-// qkv [B,HW,3C] (q | k | v on the channel axis).  S[i][j] = scale * sum_c q[i][c] k[j][c]
-__global__ __launch_bounds__(kT) void attn_scores_nhwc_kernel(const float *__restrict__ qkv, int C, int HW, float scale,
-                                                             float *__restrict__ S) {
+// q [B,HW,.] with row stride sq, k [B,HW,.] with row stride sk (floats; C channels of each row are read).
+// S[i][j] = scale * sum_c q[i][c] k[j][c].  qkv [B,HW,3C] (q | k | v on the channel axis): q = qkv, k = qkv + C, sq = sk = 3C;
+// the key-folded form (sige_hip_attention_residual_qv_nhwc_f32): q = qv, sq = 2C, k = the block input itself, sk = C.
+// QS: every query channel is multiplied by qs[b * qs_sb + c] as it is loaded (the cached GroupNorm scale of the key fold, read from
+// the cache's own tensor: no copy of it exists that could go stale); without it the kernel is the one it was.
+template <bool QS>
+__global__ __launch_bounds__(kT) void attn_scores_nhwc_kernel(const float *__restrict__ q, int sq, const float *__restrict__ k,
+                                                             int sk, int C, int HW, float scale, float *__restrict__ S,
+                                                             const float *__restrict__ qs, int qs_sb) {
     __shared__ float red[4][16][20];
     const int b = blockIdx.z;
     const int i0 = blockIdx.y * 16, j0 = blockIdx.x * 16;
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
     const int kq = lane >> 4, n = lane & 15;
-    const int C3 = 3 * C, cw = C / 4;  // wave w: channels [w*cw, (w+1)*cw), lane group kq: 4 consecutive channels per step of 16
-    const float *qa = qkv + ((size_t)b * HW + i0 + n) * C3 + wave * cw + kq * 4;       // A[m = query][k]
-    const float *kb = qkv + ((size_t)b * HW + j0 + n) * C3 + C + wave * cw + kq * 4;   // B[k][n = key]
+    const int cw = C / 4;  // wave w: channels [w*cw, (w+1)*cw), lane group kq: 4 consecutive channels per step of 16
+    const float *qa = q + ((size_t)b * HW + i0 + n) * sq + wave * cw + kq * 4;   // A[m = query][k]
+    const float *kb = k + ((size_t)b * HW + j0 + n) * sk + wave * cw + kq * 4;   // B[k][n = key]
+    const float *qsp = QS ? qs + (size_t)b * qs_sb + wave * cw + kq * 4 : nullptr;
     f32x4 acc0 = {0.f, 0.f, 0.f, 0.f}, acc1 = {0.f, 0.f, 0.f, 0.f};
     // each 16-byte load feeds 4 MFMA k-steps; the k order (kq*4 + e within a block of 16 channels)
     // is the same for A and B, which is all the contraction needs
     // (8 steps = 16 loads in flight per lane: a loop that loads as it goes pays the memory latency every step)
     for (int s0 = 0; s0 < cw; s0 += 128) {
-        float4 a4[8], b4[8];
+        float4 a4[8], b4[8], s4[8];
 #pragma unroll
         for (int u = 0; u < 8; ++u) {
             const int s = s0 + 16 * u;
             const bool ok = s < cw;  // (steps past the end contribute exact zeros)
             a4[u] = ok ? ld4(qa + s) : make_float4(0.f, 0.f, 0.f, 0.f);
             b4[u] = ok ? ld4(kb + s) : make_float4(0.f, 0.f, 0.f, 0.f);
+            if constexpr (QS) s4[u] = ok ? ld4(qsp + s) : make_float4(0.f, 0.f, 0.f, 0.f);
+        }
+        if constexpr (QS) {
+#pragma unroll
+            for (int u = 0; u < 8; ++u) { a4[u].x *= s4[u].x; a4[u].y *= s4[u].y; a4[u].z *= s4[u].z; a4[u].w *= s4[u].w; }
         }
 #pragma unroll
         for (int u = 0; u < 8; ++u) {
@@ -308,10 +320,13 @@ struct AttnEpilogue {
 
 // out[i][c] = sum_j softmax_j(S[i][.])[j] v[j][c]:  A[m = query][k = key] = P (LDS), B[k = key][n = channel] = v (global,
 // 64-byte coalesced per lane group).  Workgroup = 16 queries x 64 channels (one 16x16 tile per wave).
+// v [B,HW,.] with row stride sv floats (qkv: v = qkv + 2C, sv = 3C; qv: v = qv + C, sv = 2C); `base` = the start of the tensor
+// v lies in, at least B*HW*C floats long (what a null epilogue operand reads instead).
 // EPI: the epilogue above (`e` is not read without it: that instance is the kernel as it was).
 template <bool EPI>
-__global__ __launch_bounds__(kT) void attn_apply_nhwc_kernel(const float *__restrict__ qkv, const float *__restrict__ S,
-                                                            int C, int HW, float *__restrict__ out, AttnEpilogue e) {
+__global__ __launch_bounds__(kT) void attn_apply_nhwc_kernel(const float *__restrict__ v, int sv, const float *__restrict__ base,
+                                                            const float *__restrict__ S, int C, int HW, float *__restrict__ out,
+                                                            AttnEpilogue e) {
     extern __shared__ __attribute__((aligned(16))) float P[];  // [16][HW + 4]
     const int PS = HW + 4;
     const int b = blockIdx.z;
@@ -320,29 +335,30 @@ __global__ __launch_bounds__(kT) void attn_apply_nhwc_kernel(const float *__rest
     const int kq = lane >> 4, n = lane & 15;
     const int c = c0 + wave * 16 + n;
     const bool cok = c < C;
-    const size_t rs = (size_t)3 * C;
+    const size_t rs = (size_t)sv;
     // 256 keys per block: all 64 value loads of a block are issued before the first MFMA needs one (a loop that
     // loads one step ahead pays the memory latency every step: 16 x ~0.6 us for 256 tokens); the first block's
     // are issued before the softmax, which does not depend on them
-    // (one buffer descriptor over this batch's qkv rows from the value columns on, ONE 32-bit offset register per lane, the key step
+    // (one buffer descriptor over this batch's rows from the value columns on, ONE 32-bit offset register per lane, the key step
     //  as a scalar offset: the 64 loads of a block are 64 instructions, not 64 x ten of 64-bit address arithmetic -- 1 us of issue
     //  in front of everything else, round 6)
     const __amdgpu_buffer_rsrc_t r_v = __builtin_amdgcn_make_buffer_rsrc(
-        const_cast<float *>(qkv + (size_t)b * HW * 3 * C + 2 * C), 0,
-        (unsigned)min((size_t)0x7fffffff, ((size_t)HW * 3 * C - 2 * C) * sizeof(float)), 0x00020000);
+        const_cast<float *>(v + (size_t)b * HW * rs), 0,
+        (unsigned)min((size_t)0x7fffffff, ((size_t)(HW - 1) * rs + C) * sizeof(float)), 0x00020000);
     const int v_lane = ((cok ? c : 0) + kq * (int)rs) * (int)sizeof(float);
     const int v_step = 4 * (int)rs * (int)sizeof(float);  // bytes between key steps
     // the epilogue's operands: a lane's channel is fixed, so bias and twin affine are five scalars; its four residual values (one per
     // query row of its accumulators) are requested with the score rows and are in flight during the softmax and the K loop
-    // (branch-free: a null operand reads qkv at the same offsets -- inside it, B*HW*C <= B*HW*3C -- and is dropped by a select)
+    // (branch-free: a null operand reads `base` at the same offsets -- inside it, B*HW*C <= B*HW*2C <= B*HW*3C -- and is dropped by
+    //  a select)
     float e_bias = 0.f, e_s0 = 0.f, e_t0 = 0.f, e_s1 = 0.f, e_t1 = 0.f, e_res[4] = {0.f, 0.f, 0.f, 0.f};
     auto load_epilogue = [&]() {
         if constexpr (EPI) {
             const int cc = cok ? c : 0;
-            e_bias = (e.bias ? e.bias : qkv)[cc];
-            e_s0 = (e.twin0 ? e.tscale0 : qkv)[cc]; e_t0 = (e.twin0 ? e.tshift0 : qkv)[cc];
-            e_s1 = (e.twin1 ? e.tscale1 : qkv)[cc]; e_t1 = (e.twin1 ? e.tshift1 : qkv)[cc];
-            const float *rp = (e.residual ? e.residual : qkv) + ((size_t)b * HW + i0 + 4 * kq) * C + cc;
+            e_bias = (e.bias ? e.bias : base)[cc];
+            e_s0 = (e.twin0 ? e.tscale0 : base)[cc]; e_t0 = (e.twin0 ? e.tshift0 : base)[cc];
+            e_s1 = (e.twin1 ? e.tscale1 : base)[cc]; e_t1 = (e.twin1 ? e.tshift1 : base)[cc];
+            const float *rp = (e.residual ? e.residual : base) + ((size_t)b * HW + i0 + 4 * kq) * C + cc;
 #pragma unroll
             for (int r = 0; r < 4; ++r) e_res[r] = rp[(size_t)r * C];
         }
@@ -769,8 +785,34 @@ extern "C" int sige_hip_attention_nhwc_f32(const float *qkv, int B, int C, int H
     const size_t lds = (size_t)16 * (HW + 4) * sizeof(float);
     if (lds > 64 * 1024 || (size_t)HW * 3 * C * sizeof(float) >= 0x7fffffffu) return SIGE_HIP_EUNSUPPORTED;  // (32-bit value offsets)
     hipStream_t st = as_stream(stream);
-    attn_scores_nhwc_kernel<<<dim3(HW / 16, HW / 16, B), kT, 0, st>>>(qkv, C, HW, scale, workspace);
-    attn_apply_nhwc_kernel<false><<<dim3(ceil_div(C, 64), HW / 16, B), kT, lds, st>>>(qkv, workspace, C, HW, out, AttnEpilogue{});
+    attn_scores_nhwc_kernel<false><<<dim3(HW / 16, HW / 16, B), kT, 0, st>>>(qkv, 3 * C, qkv + C, 3 * C, C, HW, scale, workspace, nullptr, 0);
+    attn_apply_nhwc_kernel<false><<<dim3(ceil_div(C, 64), HW / 16, B), kT, lds, st>>>(qkv + 2 * C, 3 * C, qkv, workspace, C, HW, out, AttnEpilogue{});
+    return launch_status(2);
+}
+
+// the two entries with the proj_out epilogue: q / k / v rows with their strides, `base` as in attn_apply_nhwc_kernel
+static int attention_residual_impl(const float *q, int sq, const float *k, int sk, const float *v, int sv, const float *base,
+                                   const float *qs, int qs_sb, int B, int C, int HW, float scale, float *workspace, const float *bias, const float *residual,
+                                   float *twin0, const float *twin0_scale, const float *twin0_shift,
+                                   float *twin1, const float *twin1_scale, const float *twin1_shift, float *out, void *stream) {
+    if (B <= 0 || C <= 0 || HW <= 0) return SIGE_HIP_EINVAL;
+    if (!base || !k || !workspace || !out) return SIGE_HIP_EINVAL;
+    if ((twin0 && !(twin0_scale && twin0_shift)) || (twin1 && !(twin1_scale && twin1_shift))) return SIGE_HIP_EINVAL;
+    if (!al16(bias) || !al16(residual) || !al16(twin0) || !al16(twin0_scale) || !al16(twin0_shift) || !al16(twin1) ||
+        !al16(twin1_scale) || !al16(twin1_shift))
+        return SIGE_HIP_EINVAL;
+    // (shapes: exactly those of sige_hip_attention_nhwc_f32 -- the same scores launch, the same workspace)
+    if (HW % 16 || C % 64 || B > 65535 || !al16(base) || !al16(k) || !al16(workspace)) return SIGE_HIP_EUNSUPPORTED;
+    const size_t lds = (size_t)16 * (HW + 4) * sizeof(float);
+    if (lds > 64 * 1024 || (size_t)HW * 3 * C * sizeof(float) >= 0x7fffffffu) return SIGE_HIP_EUNSUPPORTED;
+    AttnEpilogue e{};
+    e.bias = bias; e.residual = residual;
+    e.twin0 = twin0; e.tscale0 = twin0_scale; e.tshift0 = twin0_shift;
+    e.twin1 = twin1; e.tscale1 = twin1_scale; e.tshift1 = twin1_shift;
+    hipStream_t st = as_stream(stream);
+    if (qs) attn_scores_nhwc_kernel<true><<<dim3(HW / 16, HW / 16, B), kT, 0, st>>>(q, sq, k, sk, C, HW, scale, workspace, qs, qs_sb);
+    else attn_scores_nhwc_kernel<false><<<dim3(HW / 16, HW / 16, B), kT, 0, st>>>(q, sq, k, sk, C, HW, scale, workspace, nullptr, 0);
+    attn_apply_nhwc_kernel<true><<<dim3(ceil_div(C, 64), HW / 16, B), kT, lds, st>>>(v, sv, base, workspace, C, HW, out, e);
     return launch_status(2);
 }
 
@@ -780,22 +822,20 @@ extern "C" int sige_hip_attention_residual_nhwc_f32(const float *qkv, int B, int
                                                     float *twin1, const float *twin1_scale, const float *twin1_shift,
                                                     float *out, void *stream) {
     SIGE_PLAN_HOOK(sige_hip_attention_residual_nhwc_f32, qkv, B, C, HW, scale, workspace, bias, residual, twin0, twin0_scale, twin0_shift, twin1, twin1_scale, twin1_shift, out, stream);
-    if (B <= 0 || C <= 0 || HW <= 0) return SIGE_HIP_EINVAL;
-    if (!qkv || !workspace || !out) return SIGE_HIP_EINVAL;
-    if ((twin0 && !(twin0_scale && twin0_shift)) || (twin1 && !(twin1_scale && twin1_shift))) return SIGE_HIP_EINVAL;
-    if (!al16(bias) || !al16(residual) || !al16(twin0) || !al16(twin0_scale) || !al16(twin0_shift) || !al16(twin1) ||
-        !al16(twin1_scale) || !al16(twin1_shift))
-        return SIGE_HIP_EINVAL;
-    // (shapes: exactly those of sige_hip_attention_nhwc_f32 -- the same scores launch, the same workspace)
-    if (HW % 16 || C % 64 || B > 65535 || !al16(qkv) || !al16(workspace)) return SIGE_HIP_EUNSUPPORTED;
-    const size_t lds = (size_t)16 * (HW + 4) * sizeof(float);
-    if (lds > 64 * 1024 || (size_t)HW * 3 * C * sizeof(float) >= 0x7fffffffu) return SIGE_HIP_EUNSUPPORTED;
-    AttnEpilogue e{};
-    e.bias = bias; e.residual = residual;
-    e.twin0 = twin0; e.tscale0 = twin0_scale; e.tshift0 = twin0_shift;
-    e.twin1 = twin1; e.tscale1 = twin1_scale; e.tshift1 = twin1_shift;
-    hipStream_t st = as_stream(stream);
-    attn_scores_nhwc_kernel<<<dim3(HW / 16, HW / 16, B), kT, 0, st>>>(qkv, C, HW, scale, workspace);
-    attn_apply_nhwc_kernel<true><<<dim3(ceil_div(C, 64), HW / 16, B), kT, lds, st>>>(qkv, workspace, C, HW, out, e);
-    return launch_status(2);
+    if (!qkv) return SIGE_HIP_EINVAL;
+    return attention_residual_impl(qkv, 3 * C, qkv + C, 3 * C, qkv + 2 * C, 3 * C, qkv, nullptr, 0, B, C, HW, scale, workspace, bias, residual,
+                                   twin0, twin0_scale, twin0_shift, twin1, twin1_scale, twin1_shift, out, stream);
+}
+
+// key-folded form: qv [B,HW,2C] = (q'' | v'), the keys are the block input [B,HW,C] itself (include/sige_hip.h)
+extern "C" int sige_hip_attention_residual_qv_nhwc_f32(const float *qv, const float *keys, const float *qscale, int qscaleB,
+                                                       int B, int C, int HW, float scale, float *workspace, const float *bias, const float *residual,
+                                                       float *twin0, const float *twin0_scale, const float *twin0_shift,
+                                                       float *twin1, const float *twin1_scale, const float *twin1_shift,
+                                                       float *out, void *stream) {
+    SIGE_PLAN_HOOK(sige_hip_attention_residual_qv_nhwc_f32, qv, keys, qscale, qscaleB, B, C, HW, scale, workspace, bias, residual, twin0, twin0_scale, twin0_shift, twin1, twin1_scale, twin1_shift, out, stream);
+    if (!qv || !keys) return SIGE_HIP_EINVAL;
+    if (qscale && ((qscaleB != 1 && qscaleB != B) || !al16(qscale))) return SIGE_HIP_EINVAL;
+    return attention_residual_impl(qv, 2 * C, keys, C, qv + C, 2 * C, qv, qscale, qscale && qscaleB > 1 ? C : 0, B, C, HW, scale, workspace, bias, residual,
+                                   twin0, twin0_scale, twin0_shift, twin1, twin1_scale, twin1_shift, out, stream);
 }

@@ -133,6 +133,7 @@ _SIGNATURES = {
         _c_int, [_c_vp] + [ctypes.c_int64] * 4 + [_c_int] * 4 + [_c_vp, _c_vp, _c_int, _c_vp, _c_int, _c_int, _c_int, _c_vp, _c_vp]),
     "sige_hip_attention_nhwc_f32": (_c_int, [_c_vp, _c_int, _c_int, _c_int, ctypes.c_float, _c_vp, _c_vp, _c_vp]),
     "sige_hip_attention_residual_nhwc_f32": (_c_int, [_c_vp, _c_int, _c_int, _c_int, ctypes.c_float, _c_vp] + [_c_vp] * 10),
+    "sige_hip_attention_residual_qv_nhwc_f32": (_c_int, [_c_vp, _c_vp, _c_vp, _c_int, _c_int, _c_int, _c_int, ctypes.c_float, _c_vp] + [_c_vp] * 10),
     "sige_hip_attention_fused_workspace": (_c_sz, [_c_int] * 3),
     "sige_hip_attention_fused_nhwc_f32": (_c_int, [_c_vp, _c_int, _c_int, _c_int, ctypes.c_float, _c_vp, _c_vp, _c_vp]),
     # split fp16 operands (tile kernels)
@@ -2085,6 +2086,40 @@ def attention_residual_cl(qkv: torch.Tensor, scale: float, bias: Optional[torch.
     if status == UNSUPPORTED:
         return None
     _check(status, "attention_residual_cl")
+    return out, {key: b for key, b, _, _ in tw}
+
+
+def attention_residual_qv_cl(qv: torch.Tensor, keys: torch.Tensor, scale: float, bias: Optional[torch.Tensor] = None,
+                             residual: Optional[torch.Tensor] = None, twins: Optional[dict] = None,
+                             qscale: Optional[torch.Tensor] = None):
+    """attention_residual_cl for a caller that has folded the key projection away as well (include/sige_hip.h:
+    sige_hip_attention_residual_qv_nhwc_f32): `qv` [B,2C,H,W] = (q | v') channels-last, `keys` [B,C,H,W] channels-last -- the
+    block input itself; `qscale` [1|B,C,1,1]: the factor s of q'' = s * q, multiplied in as the score kernel loads the queries --
+    read at every launch from the tensor given (the cached affine itself: nothing here copies it).  Returns (out, {key: twin}) -- or None if the shape is unsupported."""
+    qv, keys = _req_cl(qv, "qv"), _req_cl(keys, "keys")
+    B, C2, H, W = qv.shape
+    C, HW = C2 // 2, H * W
+    if C2 != 2 * C or tuple(keys.shape) != (B, C, H, W):
+        raise RuntimeError("attention_residual_qv_cl: qv must be [B,2C,H,W] and keys [B,C,H,W]")
+    out = _empty_cl((B, C, H, W), qv.device)
+    bias_keep = _vec(bias, "bias")
+    if bias_keep is not None and bias_keep.numel() != C:
+        raise RuntimeError("attention_residual_qv_cl: bias needs one entry per channel")
+    if residual is not None:
+        residual = _req_cl(residual, "residual")
+        if tuple(residual.shape) != tuple(out.shape):
+            raise RuntimeError("attention_residual_qv_cl: residual must be shaped like the output")
+    tw = [(key, _empty_cl((B, C, H, W), qv.device), sc, sh) for key, (sc, sh) in list((twins or {}).items())[:2]]
+    targs, twin_keep = _twin_args([(b, sc, sh) for _, b, sc, sh in tw] or None, out, C, "attention_residual_qv_cl")
+    (qa, q_keep) = _cvec(qscale, "qscale")
+    if q_keep is not None and (qa[2] != C or qa[1] not in (1, B)):
+        raise RuntimeError("attention_residual_qv_cl: qscale must be [1|B, C, 1, 1]")
+    ws = torch.empty(B * HW * HW, dtype=torch.float32, device=qv.device)
+    status = lib().sige_hip_attention_residual_qv_nhwc_f32(qv.data_ptr(), keys.data_ptr(), qa[0], qa[1], B, C, HW, float(scale), ws.data_ptr(),
+                                                           _p(bias_keep), _p(residual), *targs, out.data_ptr(), _stream(qv))
+    if status == UNSUPPORTED:
+        return None
+    _check(status, "attention_residual_qv_cl")
     return out, {key: b for key, b, _, _ in tw}
 
 

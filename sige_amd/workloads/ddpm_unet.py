@@ -130,6 +130,32 @@ def fold_proj_into_qkv(w_qkv: torch.Tensor, b_qkv: Optional[torch.Tensor], w_p: 
     return w.contiguous(), b, bp.to(wq.dtype)
 
 
+# ... and the key projection as well (fold_keys_into_query, AttnBlock.folded_qv): the qkv conv becomes C -> 2C with outputs
+# (M x_n + m | v') and the keys are the block input itself.  Active where FOLD_ATTN_PROJ is; False: the C -> 3C conv
+# of 5.9 (A/B runs, tests).
+FOLD_ATTN_QK = True
+
+
+def fold_keys_into_query(w_qkv: torch.Tensor, b_qkv: Optional[torch.Tensor]):
+    """The key projection of a single-head attention block folded into its query projection.  With x_n = s*x + t the
+    normalised input, q = W_q x_n + b_q and k = W_k x_n + b_k, a term of q_i . k_j that does not depend on the key j cancels
+    in the softmax over j:
+
+        q_i . k_j          = (W_k^T q_i) . x_n,j + q_i . b_k              (second term constant in j)
+        (W_k^T q_i) . x_n,j = (s * W_k^T q_i) . x_j + (W_k^T q_i) . t      (second term constant in j)
+
+        softmax_j(scale q_i . k_j) = softmax_j(scale q''_i . x_j),   q'' = s * (M x_n + m),   M = W_k^T W_q,  m = W_k^T b_q
+
+    Returns (M [C,C], m [C]) in the dtype of `w_qkv`; the products are formed in fp64 and rounded once.  The factor s is the
+    cached GroupNorm scale: not a weight, so it stays with the caller (the conv's out-affine, or the score kernel's query scale)."""
+    C = w_qkv.shape[0] // 3
+    wq = w_qkv.detach().reshape(3 * C, C)
+    wk_t = wq[C:2 * C].double().t()
+    M = wk_t @ wq[:C].double()
+    m = torch.zeros(C, dtype=torch.float64, device=wq.device) if b_qkv is None else wk_t @ b_qkv.detach()[:C].double()
+    return M.to(wq.dtype).contiguous(), m.to(wq.dtype)
+
+
 class _TwinProducer:
     """Mixin of the modules whose output is written by a full-tensor conv epilogue and can therefore carry activated twins
     for the conv1 of a consumer (cfg.conv1_twins).  `_twin_scatter()`: the Scatter module that owns the persistent in-place
@@ -500,6 +526,8 @@ class AttnBlock(SIGEModule, _TwinProducer):
     def clear_cache(self):
         self.affine = {}
         self.__dict__.pop("_fold", None)
+        self.__dict__.pop("_fold_qv", None)
+        self.__dict__.pop("_qv_oaffine", None)
 
     def folded_proj(self):
         """(conv, b'): the qkv conv with proj_out folded into its value rows (fold_proj_into_qkv) as a derived nn.Conv2d that the
@@ -520,6 +548,49 @@ class AttnBlock(SIGEModule, _TwinProducer):
             self.__dict__["_fold"] = entry  # (not through nn.Module.__setattr__: that would register the conv as a submodule)
         return entry[1], entry[2]
 
+    def folded_qv(self):
+        """(conv, b'): the C -> 2C conv with outputs (M x_n + m | v') -- the key projection folded into the query rows
+        (fold_keys_into_query) next to the value rows of folded_proj(), bias (m | 0).  Derived, keyed and rebuilt exactly as
+        folded_proj(); the factor s of q'' is not in it: the caller applies it (the conv's out-affine, or the score kernel's qscale)."""
+        conv3, bp = self.folded_proj()
+        key = self.__dict__["_fold"][0]
+        entry = self.__dict__.get("_fold_qv")
+        if entry is None or entry[0] != key or entry[3] is not conv3:
+            C = self.ch
+            M, m = fold_keys_into_query(self.qkv.weight, self.qkv.bias)
+            conv = nn.Conv2d(C, 2 * C, 1, 1, 0, device="meta")
+            w = torch.cat([M.reshape(C, C, 1, 1), conv3.weight.detach()[2 * C:]]).contiguous()
+            conv.weight = nn.Parameter(w, requires_grad=False)
+            conv.bias = nn.Parameter(torch.cat([m, torch.zeros_like(m)]), requires_grad=False)
+            conv.compute_dtype = key[-1]
+            entry = (key, conv, bp, conv3)
+            self.__dict__["_fold_qv"] = entry
+        return entry[1], entry[2]
+
+    def _qv_out_affine(self, s):
+        """Out-affine of the key-folded conv for a cache with one affine: scale (s | 1), shift 0, identity.  (s | 1) is a COPY of the
+        cached scale, kept per cache id at a fixed address (launch plans and captured graphs replay pointers; no per-forward
+        temporaries).  It is rebuilt when the cached affine is another tensor, and re-copied IN PLACE by rebuild_derived_caches()
+        when the cache was rewritten behind the module's back (parallel.refresh_derived)."""
+        src = self.affine[self.cache_id][0]
+        kept = self.__dict__.setdefault("_qv_oaffine", {})
+        entry = kept.get(self.cache_id)
+        if entry is None or entry[0] is not src or entry[1] != self.quirk:
+            sv = s.reshape(-1)
+            entry = (src, self.quirk, torch.cat([sv, torch.ones_like(sv)]), torch.zeros(2 * sv.numel(), dtype=s.dtype, device=s.device))
+            kept[self.cache_id] = entry
+        return entry[2], entry[3], "identity"
+
+    def rebuild_derived_caches(self):
+        # (parallel.refresh_derived: the cached affines were overwritten in place -- the kept (s | 1) vectors follow, at their addresses)
+        for cid, (src, quirk, vec, _) in list(self.__dict__.get("_qv_oaffine", {}).items()):
+            cur = self.affine.get(cid)
+            if cur is None or cur[0] is not src:
+                del self.__dict__["_qv_oaffine"][cid]  # (re-pointed: rebuilt at the next forward)
+                continue
+            sv = src.reshape(-1)
+            vec[:sv.numel()].copy_(sv[:1].expand_as(sv) if quirk else sv)
+
     def _fold_ok(self, x) -> bool:
         # where hip.attention_residual_cl runs, and in exact fp32 only ("f16" / "f16x3" layers keep the chain their sweeps pin)
         if not (FOLD_ATTN_PROJ and x.is_cuda and x.dtype == torch.float32):
@@ -535,6 +606,27 @@ class AttnBlock(SIGEModule, _TwinProducer):
         if tuple(x.shape) not in refused and self._fold_ok(x):
             from .. import hip
 
+            if FOLD_ATTN_QK:
+                # the factor s of q'': one affine for the whole batch -> the conv's out-affine (s | 1) (measured 3 us per forward
+                # faster than the score kernel's query scale); one affine per image -> the score kernel reads it
+                conv, bp = self.folded_qv()
+                one = s.shape[0] == 1
+                qv = fused_conv2d(conv, x, s, t, "identity", out_affine=self._qv_out_affine(s) if one else None)
+                qs = None if one else s
+                if hip.is_cl(qv):
+                    E = self.edit_batch if qv.shape[0] == 1 else 1
+                    if E > 1:  # (stacked edits, as below: queries, values, keys, residual and twins per image)
+                        from ..stacked import tall, untall
+
+                        res = hip.attention_residual_qv_cl(untall(qv, E), untall(x, E), self.ch ** -0.5, bp, residual=untall(x, E),
+                                                           twins=self._my_twins(), qscale=qs)
+                        if res is not None:
+                            res = (tall(res[0]), {k: tall(v) for k, v in res[1].items()})
+                    else:
+                        res = hip.attention_residual_qv_cl(qv, x, self.ch ** -0.5, bp, residual=x, twins=self._my_twins(), qscale=qs)
+                    if res is not None:
+                        res[0]._sige_twins = res[1]
+                        return self._produced(res[0])
             conv, bp = self.folded_proj()
             qkv = fused_conv2d(conv, x, s, t, "identity")
             if hip.is_cl(qkv):
