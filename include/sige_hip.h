@@ -217,6 +217,21 @@ int sige_hip_reduce_mask_i32(const uint8_t *mask, int H, int W, int bH, int bW,
                              int strideH, int strideW, int padH, int padW,
                              int32_t *indices, int capacity, int32_t *count, void *stream);
 
+/* ---- demand regions of a dense stage in front of a tiled consumer (not in the reference) ----
+ * A dense [Hp,Wp] stage whose output is read ONLY through the (bH x bW) windows of a Gather needs it on N0 = the pixels under
+ * those windows; `indices` / `*count` (device int32, at most `capacity` rows used) are the consumer's reduce_mask list over
+ * its [inH,inW] input, which is the stage's output itself (upsample2x = 0) or its nearest x2 upsampling (1: inH = 2 Hp).  The
+ * 3x3 conv k layers before the output is needed on N0 dilated k times by one pixel (3x3 box, clamped to the image).  For
+ * k = 0 .. depth-1 the launch writes the (tileH x tileW) output cells that intersect that set, row-major, as index lists in
+ * reduce_mask form: lists[k] = cell origin - (padH, padW) (the 3x3 geometry), lists[depth + k] = cell origin (the 1x1
+ * geometry), each int32 [cells,2] with cells = sige_hip_demand_tiles_capacity(...), and counts[k] (device int32) = how many.
+ * One workgroup, no host synchronisation; Hp*Wp <= 16384 and cells <= 4096, SIGE_HIP_EUNSUPPORTED beyond (and with stacked
+ * edits). */
+int sige_hip_demand_tiles_capacity(int Hp, int Wp, int tileH, int tileW);
+int sige_hip_demand_tiles_i32(const int32_t *indices, const int32_t *count, int capacity, int bH, int bW,
+                              int inH, int inW, int upsample2x, int Hp, int Wp, int tileH, int tileW,
+                              int padH, int padW, int depth, int32_t *lists, int32_t *counts, void *stream);
+
 /* ---- stacked-block convolution : replaces the F.conv2d call of
  * SIGEConv2d.forward in sparse mode (sige/nn/base.py:88-89) ----------------
  * x [T,Cin,R,S] (*) w [Cout,Cin/groups,kH,kW] + bias -> out [T,Cout,Ro,So],

@@ -131,9 +131,98 @@ __global__ __launch_bounds__(kMPThreads) void mask_pyramid_kernel(
     }
 }
 
+// ---- demand regions: which output cells of a DENSE producer stage does a tiled consumer read? ----------------------------
+// A dense stage whose only consumer is a Gather reads its output through that Gather's windows alone.  N0 = the producer
+// pixels under the windows (consumer pixel (y, x) reads producer pixel (y >> up, x >> up): the fused nearest x2 upsampling);
+// the conv `k` 3x3 layers before the stage's output is needed on N0 (+) k = N0 dilated k times by one pixel (3x3 box, clamped to
+// the image).  One workgroup walks the consumer's index list (count read from DEVICE memory: no host round trip in front of
+// it), keeps the pixel set in LDS and, per depth, compacts the (oH x oW) cells that intersect it in row-major order.
+constexpr int kDTThreads = 1024, kDTMaxPix = 16384, kDTMaxCells = 4096;
+
+__global__ __launch_bounds__(kDTThreads) void demand_tiles_kernel(
+        const int32_t *__restrict__ idx, const int32_t *__restrict__ count, int capacity, int bH, int bW, int inH, int inW, int up,
+        int Hp, int Wp, int oH, int oW, int padH, int padW, int depth, int32_t *__restrict__ lists, int32_t *__restrict__ counts) {
+    __shared__ uint8_t s_map[2][kDTMaxPix];
+    __shared__ uint8_t s_flag[kDTMaxCells];
+    const int tid = threadIdx.x;
+    const int npix = Hp * Wp, gh = (Hp + oH - 1) / oH, gw = (Wp + oW - 1) / oW, ncell = gh * gw;
+    for (int p = tid; p < npix; p += kDTThreads) s_map[0][p] = 0;
+    __syncthreads();
+    int n = *count;
+    n = n < 0 ? 0 : (n > capacity ? capacity : n);
+    const int bpix = bH * bW;
+    for (long i = tid; i < (long)n * bpix; i += kDTThreads) {
+        const int t = (int)(i / bpix), r = (int)(i % bpix);
+        const int y = idx[2 * t] + r / bW, x = idx[2 * t + 1] + r % bW;
+        if (y < 0 || y >= inH || x < 0 || x >= inW) continue;  // (the window's zero fill reads nothing)
+        const int py = y >> up, px = x >> up;
+        if (py < Hp && px < Wp) s_map[0][py * Wp + px] = 1;
+    }
+    __syncthreads();
+    int cur = 0;
+    for (int k = 0; k < depth; ++k) {
+        const uint8_t *m = s_map[cur];
+        for (int c = tid; c < ncell; c += kDTThreads) {
+            const int y0 = (c / gw) * oH, x0 = (c % gw) * oW;
+            const int y1 = y0 + oH < Hp ? y0 + oH : Hp, x1 = x0 + oW < Wp ? x0 + oW : Wp;
+            uint8_t any = 0;
+            for (int y = y0; y < y1; ++y)
+                for (int x = x0; x < x1; ++x) any |= m[y * Wp + x];
+            s_flag[c] = any;
+        }
+        __syncthreads();
+        int32_t *main_list = lists + (size_t)k * ncell * 2, *flat_list = lists + ((size_t)depth + k) * ncell * 2;
+        for (int c = tid; c < ncell; c += kDTThreads) {
+            if (!s_flag[c] && c != ncell - 1) continue;
+            int rank = 0;
+            for (int j = 0; j < c; ++j) rank += s_flag[j];
+            if (s_flag[c]) {
+                const int y0 = (c / gw) * oH, x0 = (c % gw) * oW;
+                main_list[2 * rank] = y0 - padH; main_list[2 * rank + 1] = x0 - padW;
+                flat_list[2 * rank] = y0; flat_list[2 * rank + 1] = x0;
+            }
+            if (c == ncell - 1) counts[k] = rank + s_flag[c];
+        }
+        if (k + 1 < depth) {
+            uint8_t *d = s_map[cur ^ 1];
+            for (int p = tid; p < npix; p += kDTThreads) {
+                const int y = p / Wp, x = p % Wp;
+                uint8_t any = 0;
+                for (int yy = (y > 0 ? y - 1 : 0); yy <= (y + 1 < Hp ? y + 1 : Hp - 1); ++yy)
+                    for (int xx = (x > 0 ? x - 1 : 0); xx <= (x + 1 < Wp ? x + 1 : Wp - 1); ++xx) any |= m[yy * Wp + xx];
+                d[p] = any;
+            }
+        }
+        __syncthreads();
+        cur ^= 1;
+    }
+}
+
 }  // namespace sige
 
 using namespace sige;
+
+extern "C" int sige_hip_demand_tiles_capacity(int Hp, int Wp, int tileH, int tileW) {
+    if (Hp <= 0 || Wp <= 0 || tileH <= 0 || tileW <= 0) return SIGE_HIP_EINVAL;
+    return ((Hp + tileH - 1) / tileH) * ((Wp + tileW - 1) / tileW);
+}
+
+extern "C" int sige_hip_demand_tiles_i32(const int32_t *indices, const int32_t *count, int capacity, int bH, int bW,
+                                         int inH, int inW, int upsample2x, int Hp, int Wp, int tileH, int tileW,
+                                         int padH, int padW, int depth, int32_t *lists, int32_t *counts, void *stream) {
+    SIGE_PLAN_HOOK(sige_hip_demand_tiles_i32, indices, count, capacity, bH, bW, inH, inW, upsample2x, Hp, Wp, tileH, tileW, padH, padW, depth, lists, counts, stream);
+    if (capacity < 0 || bH <= 0 || bW <= 0 || inH <= 0 || inW <= 0 || Hp <= 0 || Wp <= 0 || tileH <= 0 || tileW <= 0 ||
+        padH < 0 || padW < 0 || depth <= 0)
+        return SIGE_HIP_EINVAL;
+    if (!count || !lists || !counts || (capacity > 0 && !indices)) return SIGE_HIP_EINVAL;
+    const int up = upsample2x ? 1 : 0;
+    if (inH != (Hp << up) || inW != (Wp << up)) return SIGE_HIP_EINVAL;
+    if (stacked_shift(Hp) != 0) return SIGE_HIP_EUNSUPPORTED;  // (stacked edits: the dense stages run every tile)
+    if ((long)Hp * Wp > kDTMaxPix || sige_hip_demand_tiles_capacity(Hp, Wp, tileH, tileW) > kDTMaxCells) return SIGE_HIP_EUNSUPPORTED;
+    demand_tiles_kernel<<<1, kDTThreads, 0, as_stream(stream)>>>(indices, count, capacity, bH, bW, inH, inW, up, Hp, Wp, tileH, tileW,
+                                                                padH, padW, depth, lists, counts);
+    return launch_status();
+}
 
 extern "C" int sige_hip_difference_mask_u8(const float *a, const float *b, int C, int H, int W,
                                            int64_t strideC, int64_t strideH, int64_t strideW, float eps,

@@ -58,6 +58,8 @@ _SIGNATURES = {
     "sige_hip_mask_pyramid_u8": (_c_int, [_c_vp] + [_c_int] * 6 + [ctypes.c_float] * 2 + [_c_vp, _c_sz, _c_vp, _c_vp]),
     "sige_hip_reduce_mask_capacity": (_c_int, [_c_int] * 6),
     "sige_hip_reduce_mask_i32": (_c_int, [_c_vp] + [_c_int] * 8 + [_c_vp, _c_int, _c_vp, _c_vp]),
+    "sige_hip_demand_tiles_capacity": (_c_int, [_c_int] * 4),
+    "sige_hip_demand_tiles_i32": (_c_int, [_c_vp, _c_vp] + [_c_int] * 13 + [_c_vp, _c_vp, _c_vp]),
     "sige_hip_block_conv_packed_size": (_c_sz, [_c_int] * 9),
     "sige_hip_block_conv_packed_size_f16c": (_c_sz, [_c_int] * 9),
     "sige_hip_block_conv_pack_f16c": (_c_int, [_c_vp] + [_c_int] * 4 + [_c_vp, _c_vp]),
@@ -684,13 +686,30 @@ def reduce_mask(mask: torch.Tensor, block_size, stride, padding) -> torch.Tensor
     return buf[:n].clone()
 
 
-def reduce_mask_batch(requests) -> list:
+class DemandTiles:
+    """Index lists of a dense stage's demand regions (include/sige_hip.h: sige_hip_demand_tiles_i32): `main[k]` / `flat[k]` =
+    the cells the conv k 3x3 layers before the stage's output has to compute, as origins of the 3x3 geometry (cell - pad) and of
+    the 1x1 geometry (cell); `cells` = how many cells the producer resolution has (a list of that length is every tile)."""
+
+    def __init__(self, main, flat, cells: int):
+        self.main, self.flat, self.cells = list(main), list(flat), int(cells)
+
+    @property
+    def counts(self):
+        return [int(t.shape[0]) for t in self.main]
+
+
+def reduce_mask_batch(requests, demands=None):
     """`reduce_mask` for many (mask [H,W], block, stride, padding) requests with ONE device -> host read for all
-    their counts (SIGEModel.set_masks: one request per distinct tile geometry and resolution of the network)."""
+    their counts (SIGEModel.set_masks: one request per distinct tile geometry and resolution of the network).
+    `demands`: [(i, in_res, upsample2x, producer_res, out_tile, pad, depth)] -- the demand regions of a dense stage read only
+    through the windows of request i (one more launch each, fed by that request's list and DEVICE-side count; their counts
+    ride on the same read).  Returns the index lists, and with `demands` given (lists, [DemandTiles])."""
     if not requests:
-        return []
+        return [] if demands is None else ([], [])
     dev = requests[0][0].device
-    counts = torch.empty(len(requests), dtype=torch.int32, device=dev)
+    n_req = len(requests)
+    counts = torch.empty(n_req + sum(d[6] for d in demands or ()), dtype=torch.int32, device=dev)
     bufs = []
     for i, (mask, block, stride, padding) in enumerate(requests):
         if mask.dim() != 2 or not mask.is_cuda or mask.device != dev:
@@ -703,23 +722,49 @@ def reduce_mask_batch(requests) -> list:
         _check(lib().sige_hip_reduce_mask_i32(m.data_ptr(), H, W, block[0], block[1], stride[0], stride[1],
                                               padding[0], padding[1], buf.data_ptr(), cap,
                                               counts.data_ptr() + 4 * i, _stream(m)), "reduce_mask")
-        bufs.append((buf, m))
+        bufs.append((buf, m, cap))
+    dbufs, at = [], n_req
+    for (i, in_res, up, prod_res, out_tile, pad, depth) in demands or ():
+        buf, m, cap = bufs[i]
+        block = requests[i][1]
+        cells = lib().sige_hip_demand_tiles_capacity(prod_res[0], prod_res[1], out_tile[0], out_tile[1])
+        if cells <= 0:
+            raise RuntimeError("sige_amd.hip.reduce_mask_batch: bad demand-region geometry")
+        lists = torch.empty((2, depth, cells, 2), dtype=torch.int32, device=dev)
+        _check(lib().sige_hip_demand_tiles_i32(buf.data_ptr(), counts.data_ptr() + 4 * i, cap, block[0], block[1], in_res[0], in_res[1],
+                                               int(bool(up)), prod_res[0], prod_res[1], out_tile[0], out_tile[1], pad[0], pad[1],
+                                               depth, lists.data_ptr(), counts.data_ptr() + 4 * at, _stream(m)), "demand_tiles")
+        dbufs.append((lists, at, depth, cells))
+        at += depth
     rec = plan_recorder()
     if rec is not None:
         # the plan replays these compaction launches under later masks: their outputs ARE the index lists (persistent, sized
         # for every candidate tile), and the count read-back is a recorded step that sets one slot per list
-        first = rec.new_slots(len(requests))
-        _check(lib().sige_hip_plan_record_readback(rec.handle, counts.data_ptr(), first, len(requests)), "plan_record_readback")
+        first = rec.new_slots(counts.numel())
+        _check(lib().sige_hip_plan_record_readback(rec.handle, counts.data_ptr(), first, counts.numel()), "plan_record_readback")
         ns = counts.cpu().tolist()
         out = []
-        for i, ((buf, m), n) in enumerate(zip(bufs, ns)):
+        for i, ((buf, m, _), n) in enumerate(zip(bufs, ns)):
             rec.bind_index_list(buf, first + i, n)
             rec.keep.extend((buf, m))
             out.append(buf[:n])
+        dout = []
+        for lists, at, depth, cells in dbufs:
+            for g in range(2):  # (the two geometries of one depth share a count, hence a slot)
+                for k in range(depth):
+                    rec.bind_index_list(lists[g, k], first + at + k, ns[at + k])
+            rec.keep.append(lists)
+            dout.append(DemandTiles([lists[0, k, :ns[at + k]] for k in range(depth)],
+                                    [lists[1, k, :ns[at + k]] for k in range(depth)], cells))
         rec.keep.append(counts)
-        return out
+        return out if demands is None else (out, dout)
     ns = counts.cpu().tolist()  # the one synchronisation of the mask -> index pipeline
-    return [buf[:n].clone() for (buf, _), n in zip(bufs, ns)]
+    out = [buf[:n].clone() for (buf, _, _), n in zip(bufs, ns)]
+    if demands is None:
+        return out
+    dout = [DemandTiles([lists[0, k, :ns[at + k]] for k in range(depth)], [lists[1, k, :ns[at + k]] for k in range(depth)], cells)
+            for lists, at, depth, cells in dbufs]
+    return out, dout
 
 
 def difference_mask(tensor1: torch.Tensor, tensor2: torch.Tensor, eps: float) -> torch.Tensor:

@@ -276,11 +276,39 @@ class SIGEModel(nn.Module):
                 if mask is not None and mask.is_cuda and mask.dim() == 2 and key not in cache and key not in keys:
                     keys.append(key)
                     reqs.append((mask, m.block_size, m.block_stride, m.offset))
+        # demand regions (dense stages read only through a Gather's windows): one more launch per stage behind the compactions,
+        # their counts on the same device -> host read, the lists memoised per mask next to the index lists
+        self._demand_lists = {}
+        demands = []
+        for name, g, up, prod_res, depth in self._demand_requests(masks):
+            key = g.index_key(tuple(g.input_res))
+            if key in keys:
+                demands.append((name, ("demand_tiles", *key[1:], int(up), *prod_res, *g.out_tile, *g.offset, depth),
+                                (keys.index(key), tuple(g.input_res), up, tuple(prod_res), tuple(g.out_tile), tuple(g.offset), depth)))
         if reqs:
             from .. import hip
 
-            for key, idx in zip(keys, hip.reduce_mask_batch(reqs)):
+            lists, regions = hip.reduce_mask_batch(reqs, [d[2] for d in demands])
+            for key, idx in zip(keys, lists):
                 cache[key] = idx
+            for (name, key, _), region in zip(demands, regions):
+                cache[key] = region
+                self._demand_lists[name] = region
+
+    def _demand_requests(self, masks):
+        """[(name, consumer Gather, upsample2x, producer resolution, depth)]: the dense stages of this network whose output is
+        read only through that Gather's windows and that can run on their demand regions (hip.DemandTiles, kept in
+        `self._demand_lists[name]` after set_masks).  None by default."""
+        return []
+
+    def adopt_index_lists(self, view_of):
+        """(LaunchPlan.bind_mask) `view_of(list)` = the plan's view of a persistent index list under the new mask, or None."""
+        for region in getattr(self, "_demand_lists", {}).values():
+            for lists in (region.main, region.flat):
+                for k, t in enumerate(lists):
+                    v = view_of(t)
+                    if v is not None:
+                        lists[k] = v
 
     def set_mode(self, mode: str):
         self.mode = mode

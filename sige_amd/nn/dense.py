@@ -218,16 +218,22 @@ def fused_conv2d(conv: nn.Conv2d, x: torch.Tensor, scale: Optional[torch.Tensor]
                  shift: Optional[torch.Tensor] = None, activation_name: str = "identity",
                  x2: Optional[torch.Tensor] = None, residual: Optional[torch.Tensor] = None,
                  pad_bottom_right: bool = False, out_affine: Optional[tuple] = None,
-                 twins: Optional[dict] = None) -> torch.Tensor:
+                 twins: Optional[dict] = None, tiles: Optional[torch.Tensor] = None,
+                 out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """conv(act(cat(x, x2) * scale + shift)) + residual.  scale/shift: [1|B, C, 1, 1].
     `pad_bottom_right`: the DDPM downsample's (0,1,0,1) zero padding (stride-2 convs).
     `out_affine` = (scale, shift, activation) of the CONSUMER, applied to the result in the kernel's
     epilogue (one launch, once per element): act(out * scale + shift).
     `twins` = {key: (scale [Cout], shift [Cout])} (at most two): where the launch can, it also writes
     SiLU(scale * result + shift) -- the activated input of a consumer's conv1 -- and returns them as
-    `out._sige_twins[key]` (scatter.tag_twins); a consumer that finds no entry activates for itself."""
+    `out._sige_twins[key]` (scatter.tag_twins); a consumer that finds no entry activates for itself.
+    `tiles` = an index list in this conv's tile geometry (hip.DemandTiles: `main` for a 3x3, `flat` for a 1x1) with `out` a
+    persistent channels-last buffer (demand_buffer): the conv is evaluated on those output cells only, in place -- `out` and the
+    twins (persistent too, one set per conv) keep whatever they held outside the list, which nobody may read; ignored where the
+    channels-last tile launch does not apply."""
     made = {}
-    out = _fused_conv2d(conv, x, scale, shift, activation_name, x2, residual, pad_bottom_right, out_affine, twins, made)
+    out = _fused_conv2d(conv, x, scale, shift, activation_name, x2, residual, pad_bottom_right, out_affine, twins, made,
+                        tiles, out)
     if isinstance(out, tuple):  # (tensor, epilogue still to apply)
         out, (os_, oh_, oact) = out
         out = _act(out * os_.reshape(1, -1, 1, 1) + oh_.reshape(1, -1, 1, 1), oact)
@@ -240,11 +246,50 @@ def fused_conv2d(conv: nn.Conv2d, x: torch.Tensor, scale: Optional[torch.Tensor]
     return out
 
 
-def _fused_conv2d(conv, x, scale, shift, activation_name, x2, residual, pad_bottom_right, out_affine, twins=None, made=None):
+def demand_buffer(conv: nn.Conv2d, name, shape, device) -> torch.Tensor:
+    """Persistent, zero-initialised, channels-last [B,C,H,W] buffer `name` of `conv` for launches over a partial tile list
+    (fused_conv2d(tiles=..., out=...)): written on the listed cells only -- everything else is stale and must stay unread."""
+    bufs = conv.__dict__.setdefault("_sige_demand_bufs", {})
+    buf = bufs.get(name)
+    if buf is None or tuple(buf.shape) != tuple(shape) or buf.device != device:
+        buf = torch.zeros(tuple(shape), dtype=torch.float32, device=device).contiguous(memory_format=torch.channels_last)
+        bufs[name] = buf
+    return buf
+
+
+def _demand_twin_buffers(conv: nn.Conv2d, keys, shape, device):
+    """One persistent twin buffer per registered consumer key (registrations of an affine that is gone are dropped)."""
+    bufs = conv.__dict__.setdefault("_sige_demand_bufs", {})
+    for name in [n for n in bufs if isinstance(n, tuple) and n[0] == "twin" and n[1] not in keys]:
+        del bufs[name]
+    return [demand_buffer(conv, ("twin", k), shape, device) for k in keys]
+
+
+def _fused_conv2d(conv, x, scale, shift, activation_name, x2, residual, pad_bottom_right, out_affine, twins=None, made=None,
+                  tiles=None, out_buf=None):
     if x.is_cuda and x.dtype == torch.float32 and fusable(conv):
         from .. import hip
 
         block, out_tile, offset = _GEOMETRY[(tuple(conv.kernel_size), tuple(conv.stride), tuple(conv.padding))]
+        partial = (tiles is not None and out_buf is not None and not pad_bottom_right and conv.stride[0] == 1 and hip.is_cl(x)
+                   and (x2 is None or (hip.is_cl(x2) and hip.cat_fusable(x.shape[0], x.shape[1], conv.kernel_size)))
+                   and hip.cl_supported(x.shape[1], 0 if x2 is None else x2.shape[1], conv.out_channels))
+        if partial:
+            # the tile kernel over a partial list, into the persistent buffers: the dispatcher sizes output block, channel
+            # blocks and workgroup order from the tile count, as for a SIGE layer of that size (csrc/block_conv.hip plan_conv)
+            B, _, H, W = x.shape
+            keys = list(twins)[:2] if twins and out_affine is None else []
+            tbufs = _demand_twin_buffers(conv, keys, (B, conv.out_channels, H, W), x.device)
+            tw = [(k, b, *twins[k]) for k, b in zip(keys, tbufs)]
+            out = hip.gather_conv_cl(x, x2, block, tiles, scale, shift, activation_name, _packed(conv, block), conv.bias,
+                                     conv.out_channels, conv.kernel_size, conv.stride,
+                                     full=dict(offset=offset, out_res=(H, W), residual=residual), out_affine=out_affine,
+                                     out=out_buf, twins=[(b, sc, sh) for _, b, sc, sh in tw] or None)
+            if out is None:
+                raise RuntimeError("fused_conv2d: no tile kernel for this conv over a partial tile list")
+            if made is not None:
+                made.update({k: b for k, b, _, _ in tw})
+            return out
         if not pad_bottom_right:
             out = _wide_conv(conv, x, x2, scale, shift, activation_name, residual, out_affine, twins, made)
             if out is not None:

@@ -224,6 +224,9 @@ class LaunchPlan:
                 v = views.get(hip.base_ptr(m.active_indices))
                 if v is not None:
                     m.active_indices = v
+        adopt = getattr(self.model, "adopt_index_lists", None)
+        if adopt is not None:  # (index lists the model keeps outside its Gather modules: demand regions)
+            adopt(lambda t: views.get(hip.base_ptr(t)))
 
     def run(self) -> torch.Tensor:
         """The sparse forward under the bound mask, issued from C on the current stream.  Returns the output tensor (the same

@@ -145,3 +145,50 @@ def downsample_mask(
         if h < min_h and w < min_w:
             return pyramid
         level = F.interpolate(level, (h, w), mode="bilinear", align_corners=False)
+
+
+def demand_tiles(
+    active_indices: torch.Tensor,
+    block_size: IntPair,
+    in_res: IntPair,
+    upsample2x: bool,
+    producer_res: IntPair,
+    out_tile: IntPair = 4,
+    padding: IntPair = 1,
+    depth: int = 1,
+):
+    """Host restatement of libsige_hip.so's demand-region lists (include/sige_hip.h: sige_hip_demand_tiles_i32).
+
+    A dense [Hp,Wp] stage read ONLY through the `block_size` windows of a Gather (`active_indices` over its `in_res` input: the
+    stage's output, or its nearest x2 upsampling with `upsample2x`) is needed on N0 = the pixels under those windows, and
+    its 3x3 conv k layers before the output on N0 dilated k times by one pixel (3x3 box, clamped to the image).  Returns
+    (main, flat): for k = 0 .. depth-1 the `out_tile` cells that intersect that set, row-major, int32 [n,2], as origins
+    cell - padding (the 3x3 geometry) and cell (the 1x1 geometry)."""
+    (bh, bw), (ih, iw), (hp, wp) = _pair(block_size), _pair(in_res), _pair(producer_res)
+    (oh, ow), (ph, pw) = _pair(out_tile), _pair(padding)
+    up = 1 if upsample2x else 0
+    if (ih, iw) != (hp << up, wp << up):
+        raise ValueError("demand_tiles: in_res must be producer_res (times 2 with upsample2x)")
+    need = torch.zeros((hp, wp), dtype=torch.bool)
+    for y0, x0 in active_indices.cpu().tolist():
+        ys, xs = max(y0, 0), max(x0, 0)
+        ye, xe = min(y0 + bh, ih), min(x0 + bw, iw)
+        if ys < ye and xs < xe:
+            need[ys >> up:((ye - 1) >> up) + 1, xs >> up:((xe - 1) >> up) + 1] = True
+    gh, gw = -(-hp // oh), -(-wp // ow)
+    main, flat = [], []
+    for k in range(depth):
+        padded = torch.zeros((gh * oh, gw * ow), dtype=torch.bool)
+        padded[:hp, :wp] = need
+        cells = torch.nonzero(padded.reshape(gh, oh, gw, ow).any(dim=3).any(dim=1))
+        origin = torch.stack((cells[:, 0] * oh, cells[:, 1] * ow), dim=1).to(torch.int32)
+        flat.append(origin.contiguous())
+        main.append((origin - torch.tensor([ph, pw], dtype=torch.int32)).contiguous())
+        if k + 1 < depth:
+            grown = need.clone()
+            for dy in (-1, 0, 1):
+                for dx in (-1, 0, 1):
+                    src = need[max(-dy, 0):hp - max(dy, 0), max(-dx, 0):wp - max(dx, 0)]
+                    grown[max(dy, 0):hp - max(-dy, 0), max(dx, 0):wp - max(-dx, 0)] |= src
+            need = grown
+    return main, flat

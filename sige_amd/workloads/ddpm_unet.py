@@ -27,7 +27,7 @@ from torch.nn import functional as F
 
 from ..nn import Gather, Scatter, ScatterGather, ScatterWithBlockResidual, SIGEConv2d, SIGEModel, SIGEModule, paired_convs
 from ..nn.deferred import lazy_cat
-from ..nn.dense import fast_full_pass, full_conv2d, fused_conv2d, group_norm_affine, input_conv2d
+from ..nn.dense import demand_buffer, fast_full_pass, full_conv2d, fused_conv2d, group_norm_affine, input_conv2d
 
 
 @dataclass
@@ -315,9 +315,11 @@ class ResBlock(SIGEModule, _TwinProducer):
         """Context for [shortcut conv, conv1] of a sparse-mode block: on the GPU the two share one launch."""
         return paired_convs(t, enabled=self.pair and self.cin != self.cout and self.mode == "sparse")
 
-    def forward(self, x, temb: Optional[torch.Tensor]) -> torch.Tensor:
+    def forward(self, x, temb: Optional[torch.Tensor], demand=None) -> torch.Tensor:
         """`x` may be a pair (h, skip): the up path's torch.cat, which the dense
-        sparse-mode blocks fold into their convs' two-pointer input."""
+        sparse-mode blocks fold into their convs' two-pointer input.
+        `demand` = (hip.DemandTiles, depth of this block's conv2) for a dense block of a stage that runs on its demand regions
+        (DDPMSparseUNet.DENSE_ON_DEMAND): conv2 and the shortcut compute the cells of that depth, conv1 those one deeper."""
         pair = x if isinstance(x, (tuple, list)) else None
         if self.mode == "full":
             if pair and not self.plain and self._fast_full() and pair[0].is_cuda:
@@ -325,7 +327,7 @@ class ResBlock(SIGEModule, _TwinProducer):
             return self._full(torch.cat(pair, dim=1) if pair else x, temb)
         if self.mode in ("sparse", "profile"):
             if pair and not self.sparse_main and self.mode == "sparse":
-                return self._sparse_dense(pair[0], pair[1])
+                return self._sparse_dense(pair[0], pair[1], demand)
             if pair and self.mode == "sparse" and self.cin != self.cout:
                 return self._sparse(lazy_cat(pair[0], pair[1]))  # consumed by the block's two Gathers only
             return self._sparse(torch.cat(pair, dim=1) if pair else x)
@@ -421,7 +423,23 @@ class ResBlock(SIGEModule, _TwinProducer):
             return self.scatter.forward_fused(self.conv2, self.scatter_gather(h, s2, t2), skip)
         return self.scatter(self.conv2(self.scatter_gather(h, s2, t2)), skip)
 
-    def _sparse_dense(self, x, x2):
+    def _demand_args(self, conv, demand, deeper: int, x) -> dict:
+        """fused_conv2d's `tiles` / `out` for `conv` of a block that runs on its demand regions ({}: the all-tiles call).
+        Outside a launch plan a list that holds every cell takes the all-tiles call, so a large edit runs exactly the launches
+        it always ran; a plan follows any later mask and therefore always takes the list."""
+        if demand is None:
+            return {}
+        from .. import hip
+
+        region, depth = demand
+        lists = region.flat if tuple(conv.kernel_size) == (1, 1) else region.main
+        tiles = lists[depth + deeper]
+        if tiles.shape[0] == region.cells and hip.plan_recorder() is None:
+            return {}
+        shape = (x.shape[0], conv.out_channels, x.shape[2], x.shape[3])
+        return dict(tiles=tiles, out=demand_buffer(conv, "out", shape, x.device))
+
+    def _sparse_dense(self, x, x2, demand=None):
         """Dense block on the cached affine: 2-3 fused launches (shortcut 1x1, conv1, conv2+skip)."""
         s1, t1, s2, t2 = self.affine[self.cache_id]
         join = lambda: None  # noqa: E731
@@ -431,14 +449,18 @@ class ResBlock(SIGEModule, _TwinProducer):
                 if self.cin == self.cout:
                     skip = x if x2 is None else torch.cat([x, x2], dim=1)
                 else:
-                    skip, join = self._shortcut_async(lambda: fused_conv2d(self.nin_shortcut, x, x2=x2), x)
+                    # (the shortcut is needed where conv2 adds it: on conv2's cells)
+                    skip, join = self._shortcut_async(lambda: fused_conv2d(self.nin_shortcut, x, x2=x2,
+                                                                           **self._demand_args(self.nin_shortcut, demand, 0, x)), x)
                 if tw is not None:  # the producers wrote SiLU(s1 * x + t1): conv1 stages raw values
                     h = fused_conv2d(self.conv1, tw[0], None, None, "identity", x2=(tw[1] if len(tw) > 1 else None),
-                                     out_affine=(s2, t2, "swish"))
+                                     out_affine=(s2, t2, "swish"), **self._demand_args(self.conv1, demand, 1, x))
                 else:
-                    h = fused_conv2d(self.conv1, x, s1, t1, "swish", x2=x2, out_affine=(s2, t2, "swish"))
+                    h = fused_conv2d(self.conv1, x, s1, t1, "swish", x2=x2, out_affine=(s2, t2, "swish"),
+                                     **self._demand_args(self.conv1, demand, 1, x))
             join()
-            return self._produced(fused_conv2d(self.conv2, h, residual=skip, twins=self._my_twins()))
+            return self._produced(fused_conv2d(self.conv2, h, residual=skip, twins=self._my_twins(),
+                                               **self._demand_args(self.conv2, demand, 0, x)))
         if self.cin == self.cout:
             skip = x if x2 is None else torch.cat([x, x2], dim=1)
         else:
@@ -834,6 +856,68 @@ class DDPMSparseUNet(SIGEModel):
                 return input_conv2d(self.conv_in, x, tiles=(g0.active_indices, tuple(g0.block_size)), out=buf)
         return input_conv2d(self.conv_in, x)
 
+    # ---- a dense up level in front of a tiled Upsample, on the cells that Upsample reads (DESIGN.md 5.11) ---------------------------
+    # `Upsample` is always a SIGE layer; where its gather fuses the upsampling, a sparse pass reads the half-resolution output of
+    # the level below it ONLY through that gather's 6x6 windows, and backwards through the level's 3x3 convs the needed region
+    # grows by one pixel per conv.  A level that is dense, has no attention (keys and values need every pixel) and feeds nothing
+    # else therefore computes, conv by conv, only the 4x4 cells that intersect its region (hip.DemandTiles: built on the device
+    # behind the index compactions of set_masks).  The outputs and twins of its convs are persistent buffers; outside the cells
+    # of the current mask they are stale and unread.  False: every tile, as before (A/B runs, tests).
+    DENSE_ON_DEMAND = True
+
+    def _demand_stages(self):
+        """[(name, stage)]: the up levels that can run on their demand regions whatever the mask -- dense, no attention, output
+        to a tiled Upsample only, and wider than the region of the level's first conv can grow (2 pixels per ResBlock on each
+        side of a window: a level no wider than that is covered by any edit -- the 8x8 level of DDPM-256)."""
+        out = []
+        for lvl, stage in enumerate(self.up):
+            up = getattr(stage, "upsample", None)
+            if up is None or len(stage.attn) or up.gather.input_res is None:
+                continue
+            if any(b.sparse_main or not b.preactivate or b.overlap for b in stage.block):
+                continue
+            if min(up.gather.input_res) // 2 <= 4 * len(stage.block):
+                continue
+            out.append(("up.%d" % lvl, stage))
+        return out
+
+    def _demand_requests(self, masks):
+        if not self.DENSE_ON_DEMAND or self.edit_batch != 1:
+            return []
+        reqs = []
+        for name, stage in self._demand_stages():
+            g = stage.upsample.gather
+            res = tuple(g.input_res)
+            mask = masks.get(res)
+            if mask is None or not mask.is_cuda or mask.dim() != 2 or res[0] % 2 or res[1] % 2 or tuple(g.model_stride) != (1, 1):
+                continue
+            reqs.append((name, g, True, (res[0] // 2, res[1] // 2), 2 * len(stage.block)))
+        if reqs:
+            from .. import hip
+
+            if hip.get_edit_batch() != 1:  # (sige_amd.stacked.set_masks: masks E images tall -- stacked edits run every tile)
+                return []
+        return reqs
+
+    def _stage_demand(self, lvl: int, stage, h):
+        """The demand regions the dense level `stage` runs on in this forward, or None (every tile): sparse mode, channels-last
+        fp32 tensors on the GPU, one edit, exact-fp32 convs, and the Upsample above it reading `h`-like tensors through its
+        fused gather."""
+        if not (self.DENSE_ON_DEMAND and self.mode == "sparse" and self.edit_batch == 1 and isinstance(h, torch.Tensor) and h.is_cuda):
+            return None
+        region = getattr(self, "_demand_lists", {}).get("up.%d" % lvl)
+        if region is None or h.shape[0] != 1:
+            return None
+        from .. import hip
+
+        convs = [c for b in stage.block for c in (b.conv1, b.conv2, getattr(b, "nin_shortcut", None)) if c is not None]
+        if not hip.is_cl(h) or any(getattr(c, "compute_dtype", "f32") != "f32" for c in convs):
+            return None
+        g = stage.upsample.gather
+        if not g.fuses_upsample(h) or tuple(g.input_res) != (2 * h.shape[2], 2 * h.shape[3]):
+            return None
+        return region
+
     def forward(self, x: torch.Tensor, t: torch.Tensor) -> torch.Tensor:
         assert x.shape[2] == x.shape[3] == self.resolution
         temb = self._temb(t)
@@ -873,8 +957,12 @@ class DDPMSparseUNet(SIGEModel):
 
         for lvl in reversed(range(self.num_levels)):
             stage = self.up[lvl]
+            region = self._stage_demand(lvl, stage, h)
             for i, block in enumerate(stage.block):
-                h = block((h, hs.pop()), nxt())
+                if region is not None:  # (conv2 of block i is 2 * (blocks after it) convs in front of the level's output)
+                    h = block((h, hs.pop()), nxt(), demand=(region, 2 * (len(stage.block) - 1 - i)))
+                else:
+                    h = block((h, hs.pop()), nxt())
                 if len(stage.attn):
                     h = stage.attn[i](h)
             if lvl != 0:
