@@ -85,7 +85,8 @@ enum {
     SIGE_HIP_TUNE_TILE3_F16_TPW4_MIN = 11,  /* tile conv v3, fp16 operands: 4 tiles per workgroup from this many 2-tile workgroups on (-1 = library; 0 never) */
     SIGE_HIP_TUNE_TILE3_F16_PAIR_MIN = 12,  /* tile conv v3, fp16 operands: a conv1 whose 1x1 shortcut is held for the pair kernel goes to v3 anyway (the shortcut launched on its own) from this many workgroups on (-1 = library; 0 never) */
     SIGE_HIP_TUNE_TILE3_F16_SPARSE_MIN = 13, /* tile conv v3, fp16 operands: launches over a SPARSE tile list (fewer tiles than 4x4 cells) go to v3 from this many workgroups on, below the general threshold (-1 = library; 0 = no separate rule) */
-    SIGE_HIP_TUNE_COUNT = 14
+    SIGE_HIP_TUNE_TOKEN_LINEAR_FORM = 14,    /* token_linear: 1 = 16 tokens per workgroup | 2 = 64 (0 = automatic, by grid fill) */
+    SIGE_HIP_TUNE_COUNT = 15
 };
 #ifdef SIGE_HIP_TUNING
 int sige_hip_tuning_set(int key, int value); /* SIGE_HIP_EINVAL for an unknown key or a value outside the key's range */
@@ -593,6 +594,26 @@ int sige_hip_add_layer_norm_tokens_f32(const float *x, const float *delta, const
                                        const float *beta, int64_t T, int C, float eps, float *sum_out, float *out, void *stream);
 int sige_hip_geglu_tokens_f32(const float *x, int64_t T, int D, float *out, void *stream);
 int sige_hip_add_bias_tokens_f32(const float *x, const float *delta, const float *bias, int64_t T, int C, float *out, void *stream);
+
+/* ---- token linear of the same transformer blocks (csrc/token_linear.hip): out[M,N] = epilogue(prologue(x)[M,K] . W^T) for tokens x
+ * [M,K] row-major fp32 and W = nn.Linear.weight [N,K], exact fp32 products on the f32 MFMA, fixed summation order (no atomics).
+ *   packed_size  floats of the packed weights, 0 = unsupported (N % 16, K % 16; geglu: N = 2 D with D % 32 == 0).  Host only.
+ *   supported    1 if token_linear_f32 takes the shape: layer_norm needs K <= 2048; parts in 1..3, (N / parts) % 64 == 0 and no geglu
+ *                when parts > 1; tensors below 2 GiB.  Host only.
+ *   pack         W [N,K] -> packed (one launch; re-pack after every weight update).  geglu: the rows of W are [value D | gate D].
+ *   token_linear prologue: ln_gamma != NULL -> a = (x - mean_r) * rstd_r * gamma[k] + beta[k] (statistics over K, two-pass, eps as
+ *                nn.LayerNorm's); epilogue: acc + bias[n] (bias may be NULL), then
+ *                  geglu     out0[m,d] = (acc[m,d] + bias[d]) * gelu(acc[m,D+d] + bias[D+d]), out0 [M,D] (F.gelu's erf form)
+ *                  residual  out0 = residual + (...), residual shaped like out0 (parts == 1 only)
+ *                  parts     column group p of N / parts columns goes to its own contiguous [M, N/parts] tensor out<p>
+ *                            (q | k | v over stacked weights); unused out pointers may be NULL.
+ *                M == 0 returns OK without a launch.  All pointers 16-byte aligned. */
+size_t sige_hip_token_linear_packed_size(int N, int K, int geglu);
+int sige_hip_token_linear_supported(int64_t M, int N, int K, int layer_norm, int geglu, int parts);
+int sige_hip_token_linear_pack(const float *w, int N, int K, int geglu, float *packed, void *stream);
+int sige_hip_token_linear_f32(const float *x, int64_t M, int K, const float *ln_gamma, const float *ln_beta, float ln_eps,
+                              const float *packed, const float *bias, int N, int geglu, const float *residual, int parts,
+                              float *out0, float *out1, float *out2, void *stream);
 
 /* ---- 3x3 / padding-1 conv with <= 4 output channels over a full channels-last tensor
  * (the U-Net's conv_out after norm_out + SiLU, sige_fused_unet.py:430-434, which the

@@ -11,9 +11,9 @@
 namespace sige {
 std::atomic<int> g_tuning[SIGE_HIP_TUNE_COUNT] = {{kTuningDefaults[0]}, {kTuningDefaults[1]}, {kTuningDefaults[2]}, {kTuningDefaults[3]},
                                                   {kTuningDefaults[4]}, {kTuningDefaults[5]}, {kTuningDefaults[6]}, {kTuningDefaults[7]},
-                                                  {kTuningDefaults[8]}, {kTuningDefaults[9]}, {kTuningDefaults[10]}, {kTuningDefaults[11]}, {kTuningDefaults[12]}, {kTuningDefaults[13]}};
+                                                  {kTuningDefaults[8]}, {kTuningDefaults[9]}, {kTuningDefaults[10]}, {kTuningDefaults[11]}, {kTuningDefaults[12]}, {kTuningDefaults[13]}, {kTuningDefaults[14]}};
 }
-static_assert(SIGE_HIP_TUNE_COUNT == 14, "g_tuning's initialiser lists every key");
+static_assert(SIGE_HIP_TUNE_COUNT == 15, "g_tuning's initialiser lists every key");
 
 extern "C" int sige_hip_tuning_set(int key, int value) {
     bool ok = false;
@@ -32,6 +32,7 @@ extern "C" int sige_hip_tuning_set(int key, int value) {
         case SIGE_HIP_TUNE_SMALL_COUT_SCALAR: ok = value == 0 || value == 1; break;
         case SIGE_HIP_TUNE_WIDE_KSPLIT: ok = value >= 0 && value <= 16; break;  // (conv_wide.hpp: kWideMaxSplit)
         case SIGE_HIP_TUNE_ATTENTION_FORM: ok = value >= 0 && value <= 2; break;
+        case SIGE_HIP_TUNE_TOKEN_LINEAR_FORM: ok = value >= 0 && value <= 2; break;
         default: return SIGE_HIP_EINVAL;
     }
     if (!ok) return SIGE_HIP_EINVAL;

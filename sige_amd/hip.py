@@ -210,6 +210,11 @@ _SIGNATURES = {
     "sige_hip_add_layer_norm_tokens_f32": (_c_int, [_c_vp] * 5 + [ctypes.c_int64, _c_int, ctypes.c_float, _c_vp, _c_vp, _c_vp]),
     "sige_hip_geglu_tokens_f32": (_c_int, [_c_vp, ctypes.c_int64, _c_int, _c_vp, _c_vp]),
     "sige_hip_add_bias_tokens_f32": (_c_int, [_c_vp, _c_vp, _c_vp, ctypes.c_int64, _c_int, _c_vp, _c_vp]),
+    "sige_hip_token_linear_packed_size": (_c_sz, [_c_int] * 3),
+    "sige_hip_token_linear_supported": (_c_int, [ctypes.c_int64] + [_c_int] * 5),
+    "sige_hip_token_linear_pack": (_c_int, [_c_vp, _c_int, _c_int, _c_int, _c_vp, _c_vp]),
+    "sige_hip_token_linear_f32": (_c_int, [_c_vp, ctypes.c_int64, _c_int, _c_vp, _c_vp, ctypes.c_float, _c_vp, _c_vp, _c_int, _c_int, _c_vp, _c_int]
+                                  + [_c_vp] * 4),
     "sige_hip_set_edit_batch": (_c_int, [_c_int]),
     "sige_hip_get_edit_batch": (_c_int, []),
     # launch plans (csrc/plan.hip; host side: sige_amd/plan.py)
@@ -241,7 +246,7 @@ _TUNING_SIGNATURES = {
 TUNING_LIB_PATH = os.path.join(_PKG, "lib", "libsige_hip_tuning.so")
 # include/sige_hip.h: SIGE_HIP_TUNE_*
 TUNE = {"conv_tile_mt": 0, "conv_tile_nb": 1, "conv_waves": 2, "conv_large_grid_nb1": 3, "conv_ksplit": 4, "conv_ksplit_second_pass": 5,
-        "gather_one_tile_rows": 6, "scatter_gather_form": 7, "small_cout_scalar": 8, "wide_ksplit": 9, "attention_form": 10, "tile3_f16_tpw4_min": 11, "tile3_f16_pair_min": 12, "tile3_f16_sparse_min": 13}
+        "gather_one_tile_rows": 6, "scatter_gather_form": 7, "small_cout_scalar": 8, "wide_ksplit": 9, "attention_form": 10, "tile3_f16_tpw4_min": 11, "tile3_f16_pair_min": 12, "tile3_f16_sparse_min": 13, "token_linear_form": 14}
 
 
 # how many guarded entry-point calls had to switch HIP's current device to the tensor's ("switched") and how many found it current
@@ -1894,6 +1899,64 @@ def add_bias_tokens(x, delta, bias):
     _check(lib().sige_hip_add_bias_tokens_f32(x.data_ptr(), delta.data_ptr(), _p(bias), x.shape[0] * x.shape[1], x.shape[2], out.data_ptr(),
                                               _stream(x)), "add_bias_tokens")
     return out
+
+
+# ---- token linear of the SD transformer blocks (csrc/token_linear.hip) --------------------------------------------------------------
+def token_linear_pack(weight, geglu: bool = False) -> Optional[torch.Tensor]:
+    """nn.Linear.weight [N,K] (or a list of them, stacked along N: q | k | v) in the token linear's packed order; None if the shape
+    is unsupported (include/sige_hip.h: sige_hip_token_linear_packed_size).  `geglu`: the rows are [value D | gate D]."""
+    ws = list(weight) if isinstance(weight, (list, tuple)) else [weight]
+    ws = [w.detach() for w in ws]
+    w = ws[0] if len(ws) == 1 else torch.cat(ws, dim=0)
+    if not (w.is_cuda and w.dtype == torch.float32 and w.dim() == 2):
+        return None
+    N, K = w.shape
+    size = lib().sige_hip_token_linear_packed_size(N, K, int(geglu))
+    if not size:
+        return None
+    w = w if w.is_contiguous() else w.contiguous()
+    packed = torch.empty(size, dtype=torch.float32, device=w.device)
+    status = lib().sige_hip_token_linear_pack(w.data_ptr(), N, K, int(geglu), packed.data_ptr(), _stream(w))
+    if status == UNSUPPORTED:
+        return None
+    _check(status, "token_linear_pack")
+    return packed
+
+
+def token_linear(x: torch.Tensor, packed: torch.Tensor, N: int, bias=None, norm: Optional[torch.nn.LayerNorm] = None, residual=None,
+                 geglu: bool = False, parts: int = 1):
+    """epilogue(LayerNorm?(x) @ W^T) in ONE launch for tokens x [..., K] and W [N,K] packed by token_linear_pack: `norm` = the
+    LayerNorm applied to x on the way in; `bias` [N]; `geglu`: value * gelu(gate) -> [..., N/2]; `residual` (shaped like the output) is
+    added; `parts` > 1: a tuple of that many [..., N/parts] tensors (q, k, v).  None if unsupported (the caller runs its other path)."""
+    if not (x.is_cuda and x.dtype == torch.float32 and x.dim() >= 2 and packed is not None):
+        return None
+    K = x.shape[-1]
+    M = x.numel() // K if K else 0
+    if not lib().sige_hip_token_linear_supported(M, N, K, int(norm is not None), int(geglu), parts) or (parts > 1 and residual is not None):
+        return None
+    if packed.numel() != lib().sige_hip_token_linear_packed_size(N, K, int(geglu)):
+        raise RuntimeError("sige_amd.hip.token_linear: `packed` does not belong to a [%d, %d] weight" % (N, K))
+    x = x if x.is_contiguous() else x.contiguous()
+    No = N // 2 if geglu else N // parts
+    outs = [torch.empty((*x.shape[:-1], No), dtype=torch.float32, device=x.device) for _ in range(parts)]
+    if residual is not None:
+        if tuple(residual.shape) != tuple(outs[0].shape) or residual.dtype != torch.float32:
+            return None
+        residual = residual if residual.is_contiguous() else residual.contiguous()
+    if bias is not None:
+        bias = bias.detach()
+        bias = bias if bias.is_contiguous() else bias.contiguous()
+    g = e = None
+    if norm is not None:
+        g, e = norm.weight.detach(), norm.bias.detach()
+    status = lib().sige_hip_token_linear_f32(x.data_ptr(), M, K, _p(g), _p(e), float(norm.eps) if norm is not None else 0.0,
+                                             packed.data_ptr(), _p(bias), N, int(geglu), _p(residual), parts,
+                                             outs[0].data_ptr(), _p(outs[1] if parts > 1 else None), _p(outs[2] if parts > 2 else None),
+                                             _stream(x))
+    if status == UNSUPPORTED:
+        return None
+    _check(status, "token_linear")
+    return outs[0] if parts == 1 else tuple(outs)
 
 
 # ---- GauGAN helpers (csrc/spade_ops.hip): the sparse forward of the SPADE generator without a torch kernel ----------------------

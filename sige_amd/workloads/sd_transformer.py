@@ -44,10 +44,16 @@ from ..nn import Gather, Scatter, SIGEConv2d, SIGEModule
 #                     lane, and the elementwise kernels divided 64-bit indices by run-time values -- and with both fixed it is
 #                     FASTER and on: 10.08 vs 10.24 ms (tools/sd_fused_tokens_ab.py, profiles/r6ac_sd_fused_tokens.json; the
 #                     round-5 kernels in the same run: 10.46 vs 10.27)
+#   TOKEN_LINEAR      the six token linears of a sparse-mode block on the library's own token GEMM (csrc/token_linear.hip) with what
+#                     FUSED_TOKENS launches between them folded in: LayerNorm in the prologue of the q | k | v, the cross-attention's q
+#                     and the GEGLU projection; bias + residual in the epilogue of the three output projections; GEGLU in the
+#                     projection's epilogue -- six library launches instead of six GEMM-library calls plus five helpers, no aten GEMM
+#                     left in the block, no dependence on a tuning table.  Off by default: DESIGN.md 5.12 has the measurements.
 NATIVE_ATTENTION = True
 NATIVE_LINEAR = False
 BATCHED_QKV = True
 FUSED_TOKENS = True
+TOKEN_LINEAR = False
 
 
 def linear(lin: nn.Linear, x: torch.Tensor) -> torch.Tensor:
@@ -167,6 +173,63 @@ class TransformerBlock(SIGEModule):
         return (FUSED_TOKENS and NATIVE_ATTENTION and not NATIVE_LINEAR and x.is_cuda and x.dtype == torch.float32 and x.dim() == 3
                 and x.shape[2] % 4 == 0 and x.shape[2] <= 2048 and x.is_contiguous())
 
+    def _token_linear_packs(self, x):
+        """The packed weights of the block's six token linears (csrc/token_linear.hip), cached on the modules as plain attributes
+        under the key linear() uses -- an in-place weight update re-packs --; None if the library refuses one of the six shapes (or
+        the cross-attention has no cached K / V): the block then takes the other path as a whole."""
+        from .. import hip
+
+        a1, a2, ff = self.attn1, self.attn2, self.ff
+        if a2.cached_k is None or a2.cached_v is None or a1.to_k.in_features != a1.to_q.in_features:
+            return None
+        m, c = x.shape[0] * x.shape[1], x.shape[2]
+        L = hip.lib()
+        # (owner, weights, LayerNorm, GEGLU, parts)
+        spec = ((a1, (a1.to_q, a1.to_k, a1.to_v), True, False, 3), (a1.to_out[0], (a1.to_out[0],), False, False, 1),
+                (a2.to_q, (a2.to_q,), True, False, 1), (a2.to_out[0], (a2.to_out[0],), False, False, 1),
+                (ff.net[0].proj, (ff.net[0].proj,), True, True, 1), (ff.net[2], (ff.net[2],), False, False, 1))
+        packs = []
+        for owner, lins, ln, geglu, parts in spec:
+            n, k = sum(l.out_features for l in lins), lins[0].in_features
+            if not L.sige_hip_token_linear_supported(m, n, k, int(ln), int(geglu), parts):
+                return None
+            key = tuple((l.weight.data_ptr(), l.weight._version, tuple(l.weight.shape), l.weight.device) for l in lins)
+            if getattr(owner, "_sige_tl_key", None) != key:
+                owner._sige_tl_packed = hip.token_linear_pack([l.weight for l in lins], geglu)
+                owner._sige_tl_key = key
+            if owner._sige_tl_packed is None:
+                return None
+            packs.append((owner._sige_tl_packed, n))
+        return packs
+
+    def _forward_token_linear(self, x, packs, kv_scatter):
+        """The sparse-mode block with TOKEN_LINEAR: [LayerNorm -> q | k | v], K / V scatter, attention, [out-projection + bias + x],
+        [LayerNorm -> q], attention on the cached text K / V, [out-projection + bias + x1], [LayerNorm -> GEGLU projection -> GEGLU],
+        [second feed-forward layer + bias + x2] -- every bracket one launch.  Same operations as forward()."""
+        from .. import hip
+
+        a1, a2, ff = self.attn1, self.attn2, self.ff
+        (p_qkv, n_qkv), (p_o1, n_o1), (p_q2, n_q2), (p_o2, n_o2), (p_f0, n_f0), (p_f2, n_f2) = packs
+        sk, sv, (hh, ww) = kv_scatter
+        as_tiles = lambda t: t.reshape(-1, 4, 4, t.shape[2]).permute(0, 3, 1, 2)  # noqa: E731
+        as_tokens = lambda t: t.permute(0, 2, 3, 1).reshape(t.shape[0], hh * ww, t.shape[1])  # noqa: E731
+
+        def need(t, what):  # (the shapes were accepted by sige_hip_token_linear_supported: a refusal here is an error, not a detour)
+            if t is None:
+                raise RuntimeError("TOKEN_LINEAR: the library refused %s" % what)
+            return t
+
+        q_t, k_t, v_t = need(hip.token_linear(x, p_qkv, n_qkv, norm=self.norm1, parts=3), "the q | k | v projection")
+        k = sk(as_tiles(k_t))
+        v = sv(as_tiles(v_t))
+        o = need(hip.attention_tokens(q_t, as_tokens(k), as_tokens(v), a1.heads, a1.scale), "the self-attention")
+        x1 = need(hip.token_linear(o, p_o1, n_o1, bias=a1.to_out[0].bias, residual=x), "attn1.to_out")
+        q2 = need(hip.token_linear(x1, p_q2, n_q2, norm=self.norm2), "attn2.to_q")
+        o = need(hip.attention_tokens(q2, a2.cached_k, a2.cached_v, a2.heads, a2.scale), "the cross-attention")
+        x2 = need(hip.token_linear(o, p_o2, n_o2, bias=a2.to_out[0].bias, residual=x1), "attn2.to_out")
+        h = need(hip.token_linear(x2, p_f0, n_f0, bias=ff.net[0].proj.bias, norm=self.norm3, geglu=True), "the GEGLU projection")
+        return need(hip.token_linear(h, p_f2, n_f2, bias=ff.net[2].bias, residual=x2), "ff.net.2")
+
     def _forward_fused(self, x, full_x, context, kv_scatter):
         """The sparse-mode block with the token helpers of csrc/token_ops.hip: per block LayerNorm, [q | k | v GEMM, K / V scatter,
         attention], out-projection GEMM, add + bias + LayerNorm, q GEMM, [attention], out-projection GEMM, add + bias + LayerNorm,
@@ -194,6 +257,9 @@ class TransformerBlock(SIGEModule):
         """x: query tokens [B,n,C]; full_x: all tokens [B,HW,C] (None: x itself); kv_scatter: (scatter_k, scatter_v, hw)
         -- Scatter modules of the enclosing transformer for the sparse K / V refresh, or None for the reference's form."""
         if kv_scatter is not None and self.mode == "sparse" and self._fused_ok(x):
+            packs = self._token_linear_packs(x) if TOKEN_LINEAR else None
+            if packs is not None:
+                return self._forward_token_linear(x, packs, kv_scatter)
             return self._forward_fused(x, full_x, context, kv_scatter)
         a1 = self.attn1
         xn = self.norm1(x)
