@@ -11,7 +11,7 @@
  * Conventions
  *   - plain C: device pointers + sizes, no torch types.  All tensors are dense,
  *     contiguous, fp32 (the reference is fp32-only: sige/nn/base.py:15), NCHW like the
- *     reference's -- except in the entry points named *_nhwc_*, which take the same
+ *     reference's -- except in the entry points named *_nhwc*, which take the same
  *     tensors channels-last ([B,H,W,C], tiles [T,R,S,C]; same arithmetic);
  *     index tensors are int32 [N,2] = (h, w) tile origins in the INPUT
  *     coordinates of the paired conv (sige/utils.py:30-37).
@@ -38,7 +38,7 @@
 extern "C" {
 #endif
 
-#define SIGE_HIP_VERSION 309 /* 0.3.9: round 6 -- tile conv v3 on fp16 operands (configs[4]), write-through epilogue stores */
+#define SIGE_HIP_VERSION 310 /* 0.3.10: one entry point per channels-last tile conv, `compute` / cache storage / v3 weights as arguments */
 
 enum {
     SIGE_HIP_OK = 0,
@@ -274,7 +274,7 @@ int sige_hip_spade_modulate_nhwc_f32(
         int B, int C, int H, int W, int bH, int bW, const int32_t *active_indices, int N,
         int leaky, float slope, float *out, void *stream);
 
-/* ---- f16 compute ("_f16c"): the same stacked-block convs on the fp16 matrix cores ---------
+/* ---- f16 compute (compute = 1): the same stacked-block convs on the fp16 matrix cores ---------
  * (v_mfma_f32_32x32x16_f16 / v_mfma_f32_16x16x32_f16, 16x the rate of the f32-input forms).
  * Tensors stay fp32 in HBM (x, y, residual, out, bias, scale / shift): the staging path
  * finishes a value in fp32 (cached GroupNorm affine + SiLU), rounds it to fp16 (RNE) into LDS;
@@ -283,47 +283,12 @@ int sige_hip_spade_modulate_nhwc_f32(
  * (sige/nn/base.py:15,55-63): BASELINE.json configs[4]; parity vs the fp32 oracle is quoted at
  * 2e-2 abs.  Channels-last entry points only; geometries: 3x3/s1 on 6x6 and
  * 1x1 on 4x4 (packed_size_f16c returns 0 for the stride-2 geometry: pack that conv for fp32).
- * `packed` sizes are in 4-byte units as for the fp32 forms; arguments as the _f32 functions
- * of the same name (declared further down).                                              */
+ * `packed` sizes are in 4-byte units as for the fp32 forms; the convs themselves are the
+ * channels-last entry points further down, called with compute = 1.                      */
 size_t sige_hip_block_conv_packed_size_f16c(int Cout, int Cin, int kH, int kW, int R, int S,
                                             int strideH, int strideW, int groups);
 int sige_hip_block_conv_pack_f16c(const float *w, int Cout, int Cin, int kH, int kW,
                                   float *packed, void *stream);
-int sige_hip_block_conv_nhwc_f16c(const float *x, int T, int Cin, int R, int S,
-                                  const float *packed, const float *bias, int Cout, int kH, int kW,
-                                  int strideH, int strideW, float *out, void *stream);
-int sige_hip_gather_conv_nhwc_f16c(const float *x, const float *x2, int B, int C1, int C2, int H, int W,
-                                   int bH, int bW, const int32_t *active_indices, int N,
-                                   const float *scale, int scaleB, int scaleC,
-                                   const float *shift, int shiftB, int shiftC,
-                                   int activation,
-                                   const float *packed, const float *bias, int Cout, int kH, int kW,
-                                   int strideH, int strideW,
-                                   int to_full, int offsetH, int offsetW, const float *residual, int Ho, int Wo,
-                                   float *workspace, size_t workspace_floats,
-                                   const float *out_scale, const float *out_shift, int out_activation,
-                                   int upsample2x,
-                                   float *twin0, const float *twin0_scale, const float *twin0_shift,
-                                   float *twin1, const float *twin1_scale, const float *twin1_shift,
-                                   float *out, void *stream);
-int sige_hip_scatter_gather_conv_nhwc_f16c(const float *x, const float *y, int B, int Cin, int H, int W,
-                                           int Rx, int Sx, int bH, int bW,
-                                           const int32_t *active_indices, int N, const int32_t *scatter_map,
-                                           const float *scale, int scaleB, int scaleC,
-                                           const float *shift, int shiftB, int shiftC,
-                                           int activation,
-                                           const float *packed, const float *bias, int Cout, int kH, int kW,
-                                           int strideH, int strideW, float *out, void *stream);
-int sige_hip_scatter_gather_conv_scatter_nhwc_f16c(
-        const float *x, const float *y, int B, int Cin, int H, int W, int Rx, int Sx, int bH, int bW,
-        const int32_t *active_indices, int N, const int32_t *scatter_map,
-        const float *scale, int scaleB, int scaleC, const float *shift, int shiftB, int shiftC, int activation,
-        const float *packed, const float *bias, int Cout, int kH, int kW,
-        int offsetH, int offsetW, const float *residual,
-        const float *x1, const int32_t *table1, int gH1, int gW1, int N1, int R1, int S1,
-        float *twin0, const float *twin0_scale, const float *twin0_shift,
-        float *twin1, const float *twin1_scale, const float *twin1_shift,
-        float *out, void *stream);
 
 /* Horizontal fusion of the two independent convs at the head of a residual block.  After pair_begin() the next
  * channels-last fp32 1x1 gather -> conv launch with raw staging (the block's shortcut) is HELD: the call returns
@@ -394,28 +359,48 @@ int sige_hip_gather_conv_nchw_f32(const float *x, const float *x2, int B, int C1
  * 24-byte segments per channel; with the channels contiguous every staging load is a
  * coalesced 16 bytes per lane.  Requirements: channel counts
  * multiples of 4, 16-byte aligned pointers; scale/shift [1|B, 1|C] as above.
- *   sige_hip_block_conv_nhwc_f32            x [T,R,S,Cin]              -> out [T,Ro,So,Cout]
- *   sige_hip_gather_conv_nhwc_f32           x [B,H,W,C1] (+ x2 [1,H,W,C2]: a fused cat)
+ * One entry point per operation; arithmetic, cache storage and routing are arguments:
+ *   `compute`   0 exact fp32 | 1 fp16 operands | 2 split fp16 operands -- the arithmetic, and with it which of
+ *               sige_hip_block_conv_pack_f32 / _f16c / _f16x3 made `packed`; anything else: SIGE_HIP_EINVAL
+ *   `y_f16`, `residual_f16`   the cached tensor `y` / the cached shortcut tensor `residual` (const void *) holds halves --
+ *               the fp16-STORED caches described further down -- instead of floats; independent of `compute`
+ *   `packed_tile3`, `min_blocks`   the same weights in the tile conv v3 layout and the routing threshold (below)
+ *   sige_hip_block_conv_nhwc            x [T,R,S,Cin]              -> out [T,Ro,So,Cout]
+ *   sige_hip_gather_conv_nhwc           x [B,H,W,C1] (+ x2 [1,H,W,C2]: a fused cat)
  *        to_full = 0 -> out [B*N,Ro,So,Cout];  to_full = 1 -> out [B,Ho,Wo,Cout] written at
  *        (offset+idx)/stride, clipped, + residual [B,Ho,Wo,Cout] (dense layers)
- *   sige_hip_scatter_gather_conv_nhwc_f32   x [B*N,Rx,Sx,Cin] tiles, y [B,H,W,Cin] -> out [B*N,Ro,So,Cout] */
-int sige_hip_block_conv_nhwc_f32(const float *x, int T, int Cin, int R, int S,
-                                 const float *packed, const float *bias, int Cout, int kH, int kW,
-                                 int strideH, int strideW, float *out, void *stream);
-int sige_hip_gather_conv_nhwc_f32(const float *x, const float *x2, int B, int C1, int C2, int H, int W,
-                                  int bH, int bW, const int32_t *active_indices, int N,
-                                  const float *scale, int scaleB, int scaleC,
-                                  const float *shift, int shiftB, int shiftC,
-                                  int activation,
-                                  const float *packed, const float *bias, int Cout, int kH, int kW,
-                                  int strideH, int strideW,
-                                  int to_full, int offsetH, int offsetW, const float *residual, int Ho, int Wo,
-                                  float *workspace, size_t workspace_floats,
-                                  const float *out_scale, const float *out_shift, int out_activation,
-                                  int upsample2x,
-                                  float *twin0, const float *twin0_scale, const float *twin0_shift,
-                                  float *twin1, const float *twin1_scale, const float *twin1_shift,
-                                  float *out, void *stream);
+ *   sige_hip_scatter_gather_conv_nhwc   x [B*N,Rx,Sx,Cin] tiles, y [B,H,W,Cin] -> out [B*N,Ro,So,Cout]; y_f16: 3x3 / stride 1 only */
+int sige_hip_block_conv_nhwc(int compute, const float *x, int T, int Cin, int R, int S,
+                             const float *packed, const float *bias, int Cout, int kH, int kW,
+                             int strideH, int strideW, float *out, void *stream);
+/* ... over the tiles of an index list, T = B * N: `count_key` is that list's pointer (not read); a launch plan looks N up under
+ * it, so a conv over a tile SLAB follows a new mask like the gather-type entry points do (a plan that records the plain entry
+ * point above only replays under the tile counts it was recorded with). */
+int sige_hip_block_conv_nhwc_keyed(int compute, const float *x, const int32_t *count_key, int B, int N, int Cin, int R, int S,
+                                   const float *packed, const float *bias, int Cout, int kH, int kW,
+                                   int strideH, int strideW, float *out, void *stream);
+/* Routing: `packed_tile3` (may be NULL) = the weights in the tile conv v3 layout -- sige_hip_wide_conv_pack(prec = 2) for compute 0,
+ * (prec = 0) for compute 1.  A launch whose v3 grid (tile pairs x 64-channel output blocks) has >= min_blocks workgroups -- and
+ * that is not about to share its launch with a held 1x1 shortcut (sige_hip_conv_pair_begin) -- runs on the v3 kernel (below);
+ * every other launch on the stacked-block kernels.  The decision is taken HERE, from N, so that a launch plan (which replays the
+ * recorded entry point with the new mask's count) routes like the module-level forward under that mask: the two stay
+ * bit-identical.  min_blocks <= 0 or packed_tile3 == NULL: never; compute 2 ignores both, and so does compute 0 over an
+ * fp16-stored `y` / `residual` (the exact-fp32 v3 kernel reads fp32 caches only). */
+int sige_hip_gather_conv_nhwc(int compute, const float *x, const float *x2, int B, int C1, int C2, int H, int W,
+                              int bH, int bW, const int32_t *active_indices, int N,
+                              const float *scale, int scaleB, int scaleC,
+                              const float *shift, int shiftB, int shiftC,
+                              int activation,
+                              const float *packed, const float *bias, int Cout, int kH, int kW,
+                              int strideH, int strideW,
+                              int to_full, int offsetH, int offsetW, const float *residual, int Ho, int Wo,
+                              float *workspace, size_t workspace_floats,
+                              const float *out_scale, const float *out_shift, int out_activation,
+                              int upsample2x,
+                              float *twin0, const float *twin0_scale, const float *twin0_shift,
+                              float *twin1, const float *twin1_scale, const float *twin1_shift,
+                              const float *packed_tile3, int min_blocks,
+                              float *out, void *stream);
 /* `out_scale` / `out_shift` ([Cout], optional): epilogue out = act(out_scale * (conv + bias + residual) + out_shift)
  * -- the CONSUMER's cached GroupNorm affine + SiLU applied by the producer, once per element; the consumer then
  * gathers with no affine (e.g. conv1 -> conv2 of a ResBlock, sige_fused_unet.py:112-125).
@@ -427,14 +412,14 @@ int sige_hip_gather_conv_nhwc_f32(const float *x, const float *x2, int B, int C1
  * launch adds them in a fixed order with bias / residual (deterministic; no atomics).
  * sige_hip_conv_ksplit_hint: how many copies such a call would use (1 = no split). */
 int sige_hip_conv_ksplit_hint(int T, int Cin, int Cout, int kH, int kW, int strideH, int strideW);
-int sige_hip_scatter_gather_conv_nhwc_f32(const float *x, const float *y, int B, int Cin, int H, int W,
-                                          int Rx, int Sx, int bH, int bW,
-                                          const int32_t *active_indices, int N, const int32_t *scatter_map,
-                                          const float *scale, int scaleB, int scaleC,
-                                          const float *shift, int shiftB, int shiftC,
-                                          int activation,
-                                          const float *packed, const float *bias, int Cout, int kH, int kW,
-                                          int strideH, int strideW, float *out, void *stream);
+int sige_hip_scatter_gather_conv_nhwc(int compute, const float *x, const void *y, int y_f16, int B, int Cin, int H, int W,
+                                      int Rx, int Sx, int bH, int bW,
+                                      const int32_t *active_indices, int N, const int32_t *scatter_map,
+                                      const float *scale, int scaleB, int scaleC,
+                                      const float *shift, int shiftB, int shiftC,
+                                      int activation,
+                                      const float *packed, const float *bias, int Cout, int kH, int kW,
+                                      int strideH, int strideW, float *out, void *stream);
 
 /* conv2 -> Scatter / ScatterWithBlockResidual fused (in-place scatter mode): the scatter_gather-fed 3x3 conv writes
  * out[b, (offset+idx)/1 + r, ..., :] = conv + bias + residual  straight into `out` [B,H,W,Cout], a buffer that already
@@ -442,15 +427,16 @@ int sige_hip_scatter_gather_conv_nhwc_f32(const float *x, const float *y, int B,
  * tensor y1 and out += x1 - y1 wherever a shortcut tile (table1 over R1 x S1 cells, tiles x1 [B*N1,R1,S1,Cout]) covers
  * the pixel (scatter.cpp:41-68).  The shortcut tiles must lie inside the main tiles (true for index lists that
  * reduce_mask derives from one mask: a 4x4 block hit by the mask is inside an active 6x6 window). */
-int sige_hip_scatter_gather_conv_scatter_nhwc_f32(
-        const float *x, const float *y, int B, int Cin, int H, int W, int Rx, int Sx, int bH, int bW,
+int sige_hip_scatter_gather_conv_scatter_nhwc(
+        int compute, const float *x, const void *y, int y_f16, int B, int Cin, int H, int W, int Rx, int Sx, int bH, int bW,
         const int32_t *active_indices, int N, const int32_t *scatter_map,
         const float *scale, int scaleB, int scaleC, const float *shift, int shiftB, int shiftC, int activation,
         const float *packed, const float *bias, int Cout, int kH, int kW,
-        int offsetH, int offsetW, const float *residual,
+        int offsetH, int offsetW, const void *residual, int residual_f16,
         const float *x1, const int32_t *table1, int gH1, int gW1, int N1, int R1, int S1,
         float *twin0, const float *twin0_scale, const float *twin0_shift,
         float *twin1, const float *twin1_scale, const float *twin1_shift,
+        const float *packed_tile3, int min_blocks,
         float *out, void *stream);
 
 /* ---- channels-last forms of gather / scatter_gather / scatter ------------------
@@ -489,67 +475,22 @@ int sige_hip_scatter_with_block_residual_nhwc_f32(
 
 /* ---- tile conv v3 (csrc/conv_tile3.hpp): the 3x3 / stride-1 stacked-block conv over 6x6 tiles with the dense-layer kernel's
  * K loop -- wave-private stages (no workgroup barrier per channel chunk), 64 output channels per workgroup -- for grids that
- * fill the chip (large edits, stacked edits); exact fp32 (v_mfma_f32_32x32x2_f32).  Replaces, on those grids, what
- * sige_hip_gather_conv_nhwc_f32 (source 1) and sige_hip_scatter_gather_conv[_scatter]_nhwc_f32 (source 2) do:
+ * fill the chip (large edits, stacked edits).  What sige_hip_gather_conv_nhwc (source 1) and
+ * sige_hip_scatter_gather_conv_scatter_nhwc (source 2) route to on those grids, and the kernel's own entry point:
  *   source 1: tiles of x [B,H>>up,W>>up,C1] (+ x2 [.., C2]: a fused torch.cat) at active_indices, zero padded, optional cached
  *             affine [affineB in {1,B}, C1+C2] + SiLU;   source 2: x = conv tiles [B*N,Rx,Sx,C1], x2 = the cached tensor
  *             [B,H,W,C1] through scatter_map (raw);
  *   to_full 0: out = tiles [B*N,4,4,Cout];  1: straight into out [B,Ho,Wo,Cout] at offset + origin, clipped, + residual, with x1 /
  *             table1: + (x1 - residual) where a shortcut tile covers the pixel (ScatterWithBlockResidual), twins, out-affine.
- * `packed` = sige_hip_wide_conv_pack(prec = 2) of the [Cout, C1+C2, 3, 3] weight; C1, C2, Cout multiples of 64. */
+ * compute 0: exact fp32 (v_mfma_f32_32x32x2_f32), `packed` = sige_hip_wide_conv_pack(prec = 2) of the [Cout, C1+C2, 3, 3] weight,
+ *   fp32-stored tensors only (y_f16 / residual_f16 != 0: SIGE_HIP_EUNSUPPORTED);
+ * compute 1 (round 6; BASELINE.json configs[4]): fp16 operands, `packed` = sige_hip_wide_conv_pack(prec = 0); activations fp32 in
+ *   HBM, rounded to fp16 (RNE) in the staging path, products exact, accumulation fp32 (v_mfma_f32_32x32x16_f16).  y_f16: the cached
+ *   tensor of source 2 (x2) holds halves; residual_f16: `residual` holds halves -- the fp16-stored caches;
+ * compute 2: SIGE_HIP_EUNSUPPORTED (no split-fp16 form).  C1, C2, Cout multiples of 64. */
 int sige_hip_tile_conv3_supported(int C1, int C2, int Cout);
-int sige_hip_tile_conv3_nhwc_f32(
-        int source, const float *x, const float *x2, int B, int C1, int C2, int H, int W, int upsample2x,
-        const int32_t *active_indices, int N, const int32_t *scatter_map, int Rx, int Sx,
-        const float *scale, const float *shift, int affineB, int activation,
-        const float *packed, const float *bias, int Cout,
-        int to_full, int offsetH, int offsetW, int Ho, int Wo, const float *residual,
-        const float *x1, const int32_t *table1, int gH1, int gW1, int N1, int R1, int S1,
-        const float *out_scale, const float *out_shift, int out_activation,
-        float *twin0, const float *twin_scale0, const float *twin_shift0,
-        float *twin1, const float *twin_scale1, const float *twin_shift1,
-        float *out, void *stream);
-
-/* ... and the two entry points the sparse forward actually calls: sige_hip_gather_conv_nhwc_f32 / sige_hip_scatter_gather_conv_scatter_nhwc_f32
- * with the weights in the v3 layout (`packed_tile3`, may be NULL) and a threshold beside them.  A launch whose v3 grid (tile pairs x
- * 64-channel output blocks) has >= min_blocks workgroups -- and that is not about to share its launch with a held 1x1 shortcut
- * (sige_hip_conv_pair_begin) -- runs on the v3 kernel; every other launch exactly as the plain entry point.  The decision is
- * taken HERE, from N, so that a launch plan (which replays the recorded entry point with the new mask's count) routes like the
- * module-level forward under that mask: the two stay bit-identical.  min_blocks <= 0 or packed_tile3 == NULL: never. */
-int sige_hip_gather_conv_nhwc_v3_f32(const float *x, const float *x2, int B, int C1, int C2, int H, int W,
-                                     int bH, int bW, const int32_t *active_indices, int N,
-                                     const float *scale, int scaleB, int scaleC,
-                                     const float *shift, int shiftB, int shiftC,
-                                     int activation,
-                                     const float *packed, const float *bias, int Cout, int kH, int kW,
-                                     int strideH, int strideW,
-                                     int to_full, int offsetH, int offsetW, const float *residual, int Ho, int Wo,
-                                     float *workspace, size_t workspace_floats,
-                                     const float *out_scale, const float *out_shift, int out_activation,
-                                     int upsample2x,
-                                     float *twin0, const float *twin0_scale, const float *twin0_shift,
-                                     float *twin1, const float *twin1_scale, const float *twin1_shift,
-                                     const float *packed_tile3, int min_blocks,
-                                     float *out, void *stream);
-int sige_hip_scatter_gather_conv_scatter_nhwc_v3_f32(
-        const float *x, const float *y, int B, int Cin, int H, int W, int Rx, int Sx, int bH, int bW,
-        const int32_t *active_indices, int N, const int32_t *scatter_map,
-        const float *scale, int scaleB, int scaleC, const float *shift, int shiftB, int shiftC, int activation,
-        const float *packed, const float *bias, int Cout, int kH, int kW,
-        int offsetH, int offsetW, const float *residual,
-        const float *x1, const int32_t *table1, int gH1, int gW1, int N1, int R1, int S1,
-        float *twin0, const float *twin0_scale, const float *twin0_shift,
-        float *twin1, const float *twin1_scale, const float *twin1_shift,
-        const float *packed_tile3, int min_blocks,
-        float *out, void *stream);
-
-/* ... and the fp16-operand form of the three (round 6; BASELINE.json configs[4]): `packed` / `packed_tile3` =
- * sige_hip_wide_conv_pack(prec = 0) of the weight; activations fp32 in HBM, rounded to fp16 (RNE) in the staging path, products exact
- * in fp32, accumulation fp32 (v_mfma_f32_32x32x16_f16).  y_f16: the cached tensor of source 2 (x2 / y) holds halves; residual_f16:
- * `residual` holds halves -- the fp16-stored caches of the _c16 entry points.  The two routing entry points replace
- * sige_hip_gather_conv_nhwc_f16c and sige_hip_scatter_gather_conv_scatter_nhwc_f16c / _c16(compute = 1). */
-int sige_hip_tile_conv3_nhwc_f16c(
-        int source, const float *x, const void *x2, int y_f16, int B, int C1, int C2, int H, int W, int upsample2x,
+int sige_hip_tile_conv3_nhwc(
+        int compute, int source, const float *x, const void *x2, int y_f16, int B, int C1, int C2, int H, int W, int upsample2x,
         const int32_t *active_indices, int N, const int32_t *scatter_map, int Rx, int Sx,
         const float *scale, const float *shift, int affineB, int activation,
         const float *packed, const float *bias, int Cout,
@@ -558,32 +499,6 @@ int sige_hip_tile_conv3_nhwc_f16c(
         const float *out_scale, const float *out_shift, int out_activation,
         float *twin0, const float *twin_scale0, const float *twin_shift0,
         float *twin1, const float *twin_scale1, const float *twin_shift1,
-        float *out, void *stream);
-int sige_hip_gather_conv_nhwc_v3_f16c(const float *x, const float *x2, int B, int C1, int C2, int H, int W,
-                                      int bH, int bW, const int32_t *active_indices, int N,
-                                      const float *scale, int scaleB, int scaleC,
-                                      const float *shift, int shiftB, int shiftC,
-                                      int activation,
-                                      const float *packed, const float *bias, int Cout, int kH, int kW,
-                                      int strideH, int strideW,
-                                      int to_full, int offsetH, int offsetW, const float *residual, int Ho, int Wo,
-                                      float *workspace, size_t workspace_floats,
-                                      const float *out_scale, const float *out_shift, int out_activation,
-                                      int upsample2x,
-                                      float *twin0, const float *twin0_scale, const float *twin0_shift,
-                                      float *twin1, const float *twin1_scale, const float *twin1_shift,
-                                      const float *packed_tile3, int min_blocks,
-                                      float *out, void *stream);
-int sige_hip_scatter_gather_conv_scatter_nhwc_v3_f16c(
-        const float *x, const void *y, int y_f16, int B, int Cin, int H, int W, int Rx, int Sx, int bH, int bW,
-        const int32_t *active_indices, int N, const int32_t *scatter_map,
-        const float *scale, int scaleB, int scaleC, const float *shift, int shiftB, int shiftC, int activation,
-        const float *packed, const float *bias, int Cout, int kH, int kW,
-        int offsetH, int offsetW, const void *residual, int residual_f16,
-        const float *x1, const int32_t *table1, int gH1, int gW1, int N1, int R1, int S1,
-        float *twin0, const float *twin0_scale, const float *twin0_shift,
-        float *twin1, const float *twin1_scale, const float *twin1_shift,
-        const float *packed_tile3, int min_blocks,
         float *out, void *stream);
 
 /* ---- token-matrix helpers of Stable Diffusion's spatial transformer (csrc/token_ops.hip; sige_attention.py:86-185): tokens [T,C]
@@ -751,57 +666,17 @@ size_t sige_hip_attention_fused_workspace(int B, int C, int HW);
 int sige_hip_attention_fused_nhwc_f32(const float *qkv, int B, int C, int HW, float scale, float *workspace,
                                       float *out, void *stream);
 
-/* ---- split fp16 operands ("_f16x3"): fp32-level results from the fp16 matrix cores -------------------
- * The same entry points once more: every fp32 operand (staged activation after the cached affine + SiLU, weight) is
+/* ---- split fp16 operands (compute = 2): fp32-level results from the fp16 matrix cores -------------------
+ * The channels-last entry points with compute = 2: every fp32 operand (staged activation after the cached affine + SiLU, weight) is
  * carried as an fp16 pair hi = fp16(v), lo = fp16(v - hi); hi*hi + lo*hi + hi*lo accumulate in fp32 (22-bit operands;
  * the dropped lo*lo term is 2^-22 relative).  Results are inside the fp32 path's 1e-3 (measured ~1e-6 relative against an
  * fp64 conv) at a third of the fp16 matrix rate = 5.3x the f32-input rate.  sige_hip_block_conv_pack_f16x3 scales the
  * weights by a power of two chosen on the device (max |w| * 2^S in [2^13, 2^14): lo parts stay normal fp16 numbers) and
- * stores 2^-S behind the packed data; no host synchronisation.  Geometries and arguments as the _f16c functions.  */
+ * stores 2^-S behind the packed data; no host synchronisation.  Geometries as for compute = 1.  */
 size_t sige_hip_block_conv_packed_size_f16x3(int Cout, int Cin, int kH, int kW, int R, int S,
                                             int strideH, int strideW, int groups);
 int sige_hip_block_conv_pack_f16x3(const float *w, int Cout, int Cin, int kH, int kW,
                                   float *packed, void *stream);
-int sige_hip_block_conv_nhwc_f16x3(const float *x, int T, int Cin, int R, int S,
-                                  const float *packed, const float *bias, int Cout, int kH, int kW,
-                                  int strideH, int strideW, float *out, void *stream);
-/* ... over the tiles of an index list, T = B * N: `count_key` is that list's pointer (not read); a launch plan looks N up under
- * it, so a conv over a tile SLAB follows a new mask like the gather-type entry points do.  compute: 0 fp32 | 1 f16c | 2 f16x3. */
-int sige_hip_block_conv_nhwc_keyed(int compute, const float *x, const int32_t *count_key, int B, int N, int Cin, int R, int S,
-                                   const float *packed, const float *bias, int Cout, int kH, int kW,
-                                   int strideH, int strideW, float *out, void *stream);
-int sige_hip_gather_conv_nhwc_f16x3(const float *x, const float *x2, int B, int C1, int C2, int H, int W,
-                                   int bH, int bW, const int32_t *active_indices, int N,
-                                   const float *scale, int scaleB, int scaleC,
-                                   const float *shift, int shiftB, int shiftC,
-                                   int activation,
-                                   const float *packed, const float *bias, int Cout, int kH, int kW,
-                                   int strideH, int strideW,
-                                   int to_full, int offsetH, int offsetW, const float *residual, int Ho, int Wo,
-                                   float *workspace, size_t workspace_floats,
-                                   const float *out_scale, const float *out_shift, int out_activation,
-                                   int upsample2x,
-                                   float *twin0, const float *twin0_scale, const float *twin0_shift,
-                                   float *twin1, const float *twin1_scale, const float *twin1_shift,
-                                   float *out, void *stream);
-int sige_hip_scatter_gather_conv_nhwc_f16x3(const float *x, const float *y, int B, int Cin, int H, int W,
-                                           int Rx, int Sx, int bH, int bW,
-                                           const int32_t *active_indices, int N, const int32_t *scatter_map,
-                                           const float *scale, int scaleB, int scaleC,
-                                           const float *shift, int shiftB, int shiftC,
-                                           int activation,
-                                           const float *packed, const float *bias, int Cout, int kH, int kW,
-                                           int strideH, int strideW, float *out, void *stream);
-int sige_hip_scatter_gather_conv_scatter_nhwc_f16x3(
-        const float *x, const float *y, int B, int Cin, int H, int W, int Rx, int Sx, int bH, int bW,
-        const int32_t *active_indices, int N, const int32_t *scatter_map,
-        const float *scale, int scaleB, int scaleC, const float *shift, int shiftB, int shiftC, int activation,
-        const float *packed, const float *bias, int Cout, int kH, int kW,
-        int offsetH, int offsetW, const float *residual,
-        const float *x1, const int32_t *table1, int gH1, int gW1, int N1, int R1, int S1,
-        float *twin0, const float *twin0_scale, const float *twin0_shift,
-        float *twin1, const float *twin1_scale, const float *twin1_shift,
-        float *out, void *stream);
 
 /* ---- dense layers on the fp16 matrix cores ("wide" conv: 8x8 pixels x 64 output channels per workgroup) -------
  * The layers a SIGE network runs DENSELY -- below `sparse_resolution_threshold` in the sparse pass
@@ -871,11 +746,11 @@ int sige_hip_attention_tokens_f32(const float *q, const float *k, const float *v
  *   scatter_with_block_residual_nhwc_f16  y0 and y1
  *   affine_act_nhwc_f16                   x; out fp16 (out_f16 != 0: the activated copy) or fp32 (a persistent twin)
  *   convert_f16_f32 / convert_f32_f16     n elements, n % 4 == 0 (persistent-output refresh / storing a full-pass output)
- *   scatter_gather_conv_nhwc_c16, scatter_gather_conv_scatter_nhwc_c16
- *                                         the fused scatter_gather -> conv (-> scatter) launches with `y` fp16 and, in the
- *                                         second, `residual` fp16 when residual_f16 != 0 (a fused ScatterWithBlockResidual's
- *                                         cached shortcut); `compute`: 0 exact fp32 | 1 fp16 operands | 2 split fp16
- *                                         operands = the packing of `packed`.  3x3 / stride 1 only.                   */
+ *   scatter_gather_conv_nhwc, scatter_gather_conv_scatter_nhwc
+ *                                         (declared above) the fused scatter_gather -> conv (-> scatter) launches read `y`
+ *                                         as fp16 when y_f16 != 0 and, in the second, `residual` when residual_f16 != 0 (a
+ *                                         fused ScatterWithBlockResidual's cached shortcut), under every `compute`.
+ *                                         3x3 / stride 1 only.                                                          */
 int sige_hip_gather_nhwc_f16(const void *x, int B, int C, int H, int W, int bH, int bW,
                              const int32_t *active_indices, int N,
                              const float *scale, int scaleB, int scaleC,
@@ -902,24 +777,6 @@ int sige_hip_affine_act_nhwc_f16(const void *x, int B, int C, int H, int W, cons
                                  int affineB, int activation, void *out, int out_f16, void *stream);
 int sige_hip_convert_f16_f32(const void *src, float *dst, size_t n, void *stream);
 int sige_hip_convert_f32_f16(const float *src, void *dst, size_t n, void *stream);
-int sige_hip_scatter_gather_conv_nhwc_c16(int compute, const float *x, const void *y, int B, int Cin, int H, int W,
-                                          int Rx, int Sx, int bH, int bW,
-                                          const int32_t *active_indices, int N, const int32_t *scatter_map,
-                                          const float *scale, int scaleB, int scaleC,
-                                          const float *shift, int shiftB, int shiftC,
-                                          int activation,
-                                          const float *packed, const float *bias, int Cout, int kH, int kW,
-                                          int strideH, int strideW, float *out, void *stream);
-int sige_hip_scatter_gather_conv_scatter_nhwc_c16(
-        int compute, const float *x, const void *y, int B, int Cin, int H, int W, int Rx, int Sx, int bH, int bW,
-        const int32_t *active_indices, int N, const int32_t *scatter_map,
-        const float *scale, int scaleB, int scaleC, const float *shift, int shiftB, int shiftC, int activation,
-        const float *packed, const float *bias, int Cout, int kH, int kW,
-        int offsetH, int offsetW, const void *residual, int residual_f16,
-        const float *x1, const int32_t *table1, int gH1, int gW1, int N1, int R1, int S1,
-        float *twin0, const float *twin0_scale, const float *twin0_shift,
-        float *twin1, const float *twin1_scale, const float *twin1_shift,
-        float *out, void *stream);
 
 /* ---- stacked edits ("throughput mode"; not in the reference, whose batch shares ONE mask: sige/cpu/gather.cpp:17-21) ----
  * E edited versions of one original image, each with ITS OWN mask, processed by one set of launches: every activation

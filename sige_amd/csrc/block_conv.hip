@@ -9,7 +9,7 @@
 #include <mutex>
 
 #include "conv_mfma.hpp"
-#include "conv_tile3.hpp"  // (tile_conv3_launch: the routing entry points at the end of this file)
+#include "conv_tile3.hpp"  // (tile_conv3_launch: the routing in sige_hip_gather_conv_nhwc / sige_hip_scatter_gather_conv_scatter_nhwc)
 
 namespace sige {
 
@@ -939,6 +939,14 @@ extern "C" int sige_hip_conv_ksplit_hint(int T, int Cin, int Cout, int kH, int k
     return 8;  // (the launch decides the actual factor, at most 8)
 }
 
+// `compute` selects the arithmetic of a channels-last tile conv, i.e. which packing `packed` has: 0 exact fp32 | 1 fp16 operands |
+// 2 split fp16 operands; anything else is SIGE_HIP_EINVAL.  The one place where it becomes the implementations' PREC.
+#define SIGE_BY_COMPUTE(compute, impl, ...)         \
+    ((compute) == 0   ? impl<0>(__VA_ARGS__)        \
+     : (compute) == 1 ? impl<1>(__VA_ARGS__)        \
+     : (compute) == 2 ? impl<2>(__VA_ARGS__)        \
+                      : SIGE_HIP_EINVAL)
+
 template <int PREC>
 static int block_conv_nhwc_impl(const float *x, int T, int Cin, int R, int S,
                                 const float *packed, const float *bias, int Cout, int kH, int kW,
@@ -954,25 +962,11 @@ static int block_conv_nhwc_impl(const float *x, int T, int Cin, int R, int S,
     return launch_conv<SRC_TILES, DST_TILES, LAYOUT_NHWC, PREC>(a, 0, kH, kW, R, S, strideH, strideW, as_stream(stream));
 }
 
-extern "C" int sige_hip_block_conv_nhwc_f32(const float *x, int T, int Cin, int R, int S,
-                                            const float *packed, const float *bias, int Cout, int kH, int kW,
-                                            int strideH, int strideW, float *out, void *stream) {
-    SIGE_PLAN_HOOK_FIXED(sige_hip_block_conv_nhwc_f32, x, T, Cin, R, S, packed, bias, Cout, kH, kW, strideH, strideW, out, stream);
-    return block_conv_nhwc_impl<0>(x, T, Cin, R, S, packed, bias, Cout, kH, kW, strideH, strideW, out, stream);
-}
-
-extern "C" int sige_hip_block_conv_nhwc_f16c(const float *x, int T, int Cin, int R, int S,
-                                             const float *packed, const float *bias, int Cout, int kH, int kW,
-                                             int strideH, int strideW, float *out, void *stream) {
-    SIGE_PLAN_HOOK_FIXED(sige_hip_block_conv_nhwc_f16c, x, T, Cin, R, S, packed, bias, Cout, kH, kW, strideH, strideW, out, stream);
-    return block_conv_nhwc_impl<1>(x, T, Cin, R, S, packed, bias, Cout, kH, kW, strideH, strideW, out, stream);
-}
-
-extern "C" int sige_hip_block_conv_nhwc_f16x3(const float *x, int T, int Cin, int R, int S,
-                                              const float *packed, const float *bias, int Cout, int kH, int kW,
-                                              int strideH, int strideW, float *out, void *stream) {
-    SIGE_PLAN_HOOK_FIXED(sige_hip_block_conv_nhwc_f16x3, x, T, Cin, R, S, packed, bias, Cout, kH, kW, strideH, strideW, out, stream);
-    return block_conv_nhwc_impl<2>(x, T, Cin, R, S, packed, bias, Cout, kH, kW, strideH, strideW, out, stream);
+extern "C" int sige_hip_block_conv_nhwc(int compute, const float *x, int T, int Cin, int R, int S,
+                                        const float *packed, const float *bias, int Cout, int kH, int kW,
+                                        int strideH, int strideW, float *out, void *stream) {
+    SIGE_PLAN_HOOK_FIXED(sige_hip_block_conv_nhwc, compute, x, T, Cin, R, S, packed, bias, Cout, kH, kW, strideH, strideW, out, stream);
+    return SIGE_BY_COMPUTE(compute, block_conv_nhwc_impl, x, T, Cin, R, S, packed, bias, Cout, kH, kW, strideH, strideW, out, stream);
 }
 
 // ... over the tiles of an index list: T = B * N.  `count_key` is the index list the N tiles belong to; it is not read -- a launch
@@ -984,10 +978,7 @@ extern "C" int sige_hip_block_conv_nhwc_keyed(int compute, const float *x, const
     SIGE_PLAN_HOOK_N(sige_hip_block_conv_nhwc_keyed, (sige::CountOf<2, 4>), compute, x, count_key, B, N, Cin, R, S, packed, bias, Cout, kH, kW, strideH, strideW, out, stream);
     if (B < 0 || N < 0 || !count_key || (long)B * N > 0x7fffffffL) return SIGE_HIP_EINVAL;
     const int T = B * N;
-    if (compute == 0) return block_conv_nhwc_impl<0>(x, T, Cin, R, S, packed, bias, Cout, kH, kW, strideH, strideW, out, stream);
-    if (compute == 1) return block_conv_nhwc_impl<1>(x, T, Cin, R, S, packed, bias, Cout, kH, kW, strideH, strideW, out, stream);
-    if (compute == 2) return block_conv_nhwc_impl<2>(x, T, Cin, R, S, packed, bias, Cout, kH, kW, strideH, strideW, out, stream);
-    return SIGE_HIP_EINVAL;
+    return SIGE_BY_COMPUTE(compute, block_conv_nhwc_impl, x, T, Cin, R, S, packed, bias, Cout, kH, kW, strideH, strideW, out, stream);
 }
 
 template <int PREC>
@@ -1053,287 +1044,13 @@ static int gather_conv_nhwc_impl(const float *x, const float *x2, int B, int C1,
     return launch_conv<SRC_GATHER, DST_TILES, LAYOUT_NHWC, PREC>(a, mode, kH, kW, bH, bW, strideH, strideW, as_stream(stream));
 }
 
-#define SIGE_GATHER_CONV_ARGS x, x2, B, C1, C2, H, W, bH, bW, active_indices, N, scale, scaleB, scaleC, shift, shiftB, shiftC, \
-    activation, packed, bias, Cout, kH, kW, strideH, strideW, to_full, offsetH, offsetW, residual, Ho, Wo, workspace,          \
-    workspace_floats, out_scale, out_shift, out_activation, upsample2x, twin0, twin0_scale, twin0_shift, twin1, twin1_scale, \
-    twin1_shift, out, stream
-extern "C" int sige_hip_gather_conv_nhwc_f32(const float *x, const float *x2, int B, int C1, int C2, int H, int W,
-                                             int bH, int bW, const int32_t *active_indices, int N,
-                                             const float *scale, int scaleB, int scaleC,
-                                             const float *shift, int shiftB, int shiftC,
-                                             int activation,
-                                             const float *packed, const float *bias, int Cout, int kH, int kW,
-                                             int strideH, int strideW,
-                                             int to_full, int offsetH, int offsetW, const float *residual, int Ho, int Wo,
-                                             float *workspace, size_t workspace_floats,
-                                             const float *out_scale, const float *out_shift, int out_activation,
-                                             int upsample2x,
-                                             float *twin0, const float *twin0_scale, const float *twin0_shift,
-                                             float *twin1, const float *twin1_scale, const float *twin1_shift,
-                                             float *out, void *stream) {
-    SIGE_PLAN_HOOK_N(sige_hip_gather_conv_nhwc_f32, (sige::CountOf<9, 10>), x, x2, B, C1, C2, H, W, bH, bW, active_indices, N, scale, scaleB, scaleC, shift, shiftB, shiftC, activation, packed, bias, Cout, kH, kW, strideH, strideW, to_full, offsetH, offsetW, residual, Ho, Wo, workspace, workspace_floats, out_scale, out_shift, out_activation, upsample2x, twin0, twin0_scale, twin0_shift, twin1, twin1_scale, twin1_shift, out, stream);
-    return gather_conv_nhwc_impl<0>(SIGE_GATHER_CONV_ARGS);
-}
-extern "C" int sige_hip_gather_conv_nhwc_f16c(const float *x, const float *x2, int B, int C1, int C2, int H, int W,
-                                             int bH, int bW, const int32_t *active_indices, int N,
-                                             const float *scale, int scaleB, int scaleC,
-                                             const float *shift, int shiftB, int shiftC,
-                                             int activation,
-                                             const float *packed, const float *bias, int Cout, int kH, int kW,
-                                             int strideH, int strideW,
-                                             int to_full, int offsetH, int offsetW, const float *residual, int Ho, int Wo,
-                                             float *workspace, size_t workspace_floats,
-                                             const float *out_scale, const float *out_shift, int out_activation,
-                                             int upsample2x,
-                                             float *twin0, const float *twin0_scale, const float *twin0_shift,
-                                             float *twin1, const float *twin1_scale, const float *twin1_shift,
-                                             float *out, void *stream) {
-    SIGE_PLAN_HOOK_N(sige_hip_gather_conv_nhwc_f16c, (sige::CountOf<9, 10>), x, x2, B, C1, C2, H, W, bH, bW, active_indices, N, scale, scaleB, scaleC, shift, shiftB, shiftC, activation, packed, bias, Cout, kH, kW, strideH, strideW, to_full, offsetH, offsetW, residual, Ho, Wo, workspace, workspace_floats, out_scale, out_shift, out_activation, upsample2x, twin0, twin0_scale, twin0_shift, twin1, twin1_scale, twin1_shift, out, stream);
-    return gather_conv_nhwc_impl<1>(SIGE_GATHER_CONV_ARGS);
-}
-extern "C" int sige_hip_gather_conv_nhwc_f16x3(const float *x, const float *x2, int B, int C1, int C2, int H, int W,
-                                             int bH, int bW, const int32_t *active_indices, int N,
-                                             const float *scale, int scaleB, int scaleC,
-                                             const float *shift, int shiftB, int shiftC,
-                                             int activation,
-                                             const float *packed, const float *bias, int Cout, int kH, int kW,
-                                             int strideH, int strideW,
-                                             int to_full, int offsetH, int offsetW, const float *residual, int Ho, int Wo,
-                                             float *workspace, size_t workspace_floats,
-                                             const float *out_scale, const float *out_shift, int out_activation,
-                                             int upsample2x,
-                                             float *twin0, const float *twin0_scale, const float *twin0_shift,
-                                             float *twin1, const float *twin1_scale, const float *twin1_shift,
-                                             float *out, void *stream) {
-    SIGE_PLAN_HOOK_N(sige_hip_gather_conv_nhwc_f16x3, (sige::CountOf<9, 10>), x, x2, B, C1, C2, H, W, bH, bW, active_indices, N, scale, scaleB, scaleC, shift, shiftB, shiftC, activation, packed, bias, Cout, kH, kW, strideH, strideW, to_full, offsetH, offsetW, residual, Ho, Wo, workspace, workspace_floats, out_scale, out_shift, out_activation, upsample2x, twin0, twin0_scale, twin0_shift, twin1, twin1_scale, twin1_shift, out, stream);
-    return gather_conv_nhwc_impl<2>(SIGE_GATHER_CONV_ARGS);
-}
-
-template <int PREC>
-static int scatter_gather_conv_nhwc_impl(const float *x, const float *y, int B, int Cin, int H, int W,
-                                                     int Rx, int Sx, int bH, int bW,
-                                                     const int32_t *active_indices, int N, const int32_t *scatter_map,
-                                                     const float *scale, int scaleB, int scaleC,
-                                                     const float *shift, int shiftB, int shiftC,
-                                                     int activation,
-                                                     const float *packed, const float *bias, int Cout, int kH, int kW,
-                                                     int strideH, int strideW, float *out, void *stream, int y_f16 = 0) {
-    if (B < 0 || Cin <= 0 || Cout <= 0 || H <= 0 || W <= 0 || N < 0 || Rx <= 0 || Sx <= 0) return SIGE_HIP_EINVAL;
-    if (activation != SIGE_HIP_ACT_IDENTITY && activation != SIGE_HIP_ACT_SWISH) return SIGE_HIP_EUNSUPPORTED;
-    if ((long)B * Cin * H * W >= (1L << 29) || (long)B * N * Cin * Rx * Sx >= (1L << 29)) return SIGE_HIP_EUNSUPPORTED;
-    if ((long)B * N == 0) return SIGE_HIP_OK;
-    if (!x || !y || !packed || !out || !active_indices || !scatter_map) return SIGE_HIP_EINVAL;
-    if (!nhwc_ok(Cin, Cin, Cout, x, y, out, bias) || (reinterpret_cast<uintptr_t>(packed) & 15)) return SIGE_HIP_EUNSUPPORTED;
-    if (y_f16 && (kH != 3 || kW != 3 || strideH != 1 || strideW != 1)) return SIGE_HIP_EUNSUPPORTED;
-    ConvArgs a{};
-    a.y_f16 = y_f16 ? 1 : 0;
-    a.x = x; a.y = y; a.idx = active_indices; a.map = scatter_map; a.packed = packed; a.bias = bias; a.out = out;
-    a.T = B * N; a.Cin = Cin; a.Cout = Cout; a.B = B; a.N = N; a.H = H; a.W = W;
-    a.hp_shift = stacked_shift(H);  // (stacked edits: sige_hip_set_edit_batch)
-    if (a.hp_shift < 0 || (a.hp_shift && B != 1)) return SIGE_HIP_EUNSUPPORTED;
-    a.RxSx = Rx * Sx; a.Sx = Sx;
-    a.scale = scale; a.shift = shift;
-    const int mode = staging_mode(scale, scaleB, scaleC, shift, shiftB, shiftC, activation, B, Cin, &a.aff_sb, &a.aff_sc);
-    if (mode < 0) return SIGE_HIP_EUNSUPPORTED;
-    return launch_conv<SRC_SCATTER_GATHER, DST_TILES, LAYOUT_NHWC, PREC>(a, mode, kH, kW, bH, bW, strideH, strideW, as_stream(stream));
-}
-
-#define SIGE_SG_CONV_ARGS x, y, B, Cin, H, W, Rx, Sx, bH, bW, active_indices, N, scatter_map, scale, scaleB, scaleC, shift, shiftB, \
-    shiftC, activation, packed, bias, Cout, kH, kW, strideH, strideW, out, stream
-extern "C" int sige_hip_scatter_gather_conv_nhwc_f32(const float *x, const float *y, int B, int Cin, int H, int W,
-                                                     int Rx, int Sx, int bH, int bW,
-                                                     const int32_t *active_indices, int N, const int32_t *scatter_map,
-                                                     const float *scale, int scaleB, int scaleC,
-                                                     const float *shift, int shiftB, int shiftC,
-                                                     int activation,
-                                                     const float *packed, const float *bias, int Cout, int kH, int kW,
-                                                     int strideH, int strideW, float *out, void *stream) {
-    SIGE_PLAN_HOOK_N(sige_hip_scatter_gather_conv_nhwc_f32, (sige::CountOf<10, 11>), x, y, B, Cin, H, W, Rx, Sx, bH, bW, active_indices, N, scatter_map, scale, scaleB, scaleC, shift, shiftB, shiftC, activation, packed, bias, Cout, kH, kW, strideH, strideW, out, stream);
-    return scatter_gather_conv_nhwc_impl<0>(SIGE_SG_CONV_ARGS);
-}
-extern "C" int sige_hip_scatter_gather_conv_nhwc_f16c(const float *x, const float *y, int B, int Cin, int H, int W,
-                                                     int Rx, int Sx, int bH, int bW,
-                                                     const int32_t *active_indices, int N, const int32_t *scatter_map,
-                                                     const float *scale, int scaleB, int scaleC,
-                                                     const float *shift, int shiftB, int shiftC,
-                                                     int activation,
-                                                     const float *packed, const float *bias, int Cout, int kH, int kW,
-                                                     int strideH, int strideW, float *out, void *stream) {
-    SIGE_PLAN_HOOK_N(sige_hip_scatter_gather_conv_nhwc_f16c, (sige::CountOf<10, 11>), x, y, B, Cin, H, W, Rx, Sx, bH, bW, active_indices, N, scatter_map, scale, scaleB, scaleC, shift, shiftB, shiftC, activation, packed, bias, Cout, kH, kW, strideH, strideW, out, stream);
-    return scatter_gather_conv_nhwc_impl<1>(SIGE_SG_CONV_ARGS);
-}
-extern "C" int sige_hip_scatter_gather_conv_nhwc_f16x3(const float *x, const float *y, int B, int Cin, int H, int W,
-                                                     int Rx, int Sx, int bH, int bW,
-                                                     const int32_t *active_indices, int N, const int32_t *scatter_map,
-                                                     const float *scale, int scaleB, int scaleC,
-                                                     const float *shift, int shiftB, int shiftC,
-                                                     int activation,
-                                                     const float *packed, const float *bias, int Cout, int kH, int kW,
-                                                     int strideH, int strideW, float *out, void *stream) {
-    SIGE_PLAN_HOOK_N(sige_hip_scatter_gather_conv_nhwc_f16x3, (sige::CountOf<10, 11>), x, y, B, Cin, H, W, Rx, Sx, bH, bW, active_indices, N, scatter_map, scale, scaleB, scaleC, shift, shiftB, shiftC, activation, packed, bias, Cout, kH, kW, strideH, strideW, out, stream);
-    return scatter_gather_conv_nhwc_impl<2>(SIGE_SG_CONV_ARGS);
-}
-
-// scatter_gather -> conv -> Scatter / ScatterWithBlockResidual in ONE launch: the conv's output tiles go straight
-// into `out` [B,H,W,Cout], a buffer that already holds the cached tensor outside this mask's tiles (in-place scatter).
-template <int PREC>
-static int scatter_gather_conv_scatter_nhwc_impl(
-        const float *x, const float *y, int B, int Cin, int H, int W, int Rx, int Sx, int bH, int bW,
-        const int32_t *active_indices, int N, const int32_t *scatter_map,
-        const float *scale, int scaleB, int scaleC, const float *shift, int shiftB, int shiftC, int activation,
-        const float *packed, const float *bias, int Cout, int kH, int kW,
-        int offsetH, int offsetW, const float *residual,
-        const float *x1, const int32_t *table1, int gH1, int gW1, int N1, int R1, int S1,
-        float *twin0, const float *twin0_scale, const float *twin0_shift,
-        float *twin1, const float *twin1_scale, const float *twin1_shift,
-        float *out, void *stream, int y_f16 = 0, int res_f16 = 0) {
-    if (B < 0 || Cin <= 0 || Cout <= 0 || H <= 0 || W <= 0 || N < 0 || Rx <= 0 || Sx <= 0) return SIGE_HIP_EINVAL;
-    if (kH != 3 || kW != 3 || bH != 6 || bW != 6) return SIGE_HIP_EUNSUPPORTED;  // the stride-1 3x3 geometry of a ResBlock's conv2
-    if (activation != SIGE_HIP_ACT_IDENTITY && activation != SIGE_HIP_ACT_SWISH) return SIGE_HIP_EUNSUPPORTED;
-    if ((long)B * Cin * H * W >= (1L << 29) || (long)B * N * Cin * Rx * Sx >= (1L << 29)) return SIGE_HIP_EUNSUPPORTED;
-    if ((long)B * N == 0) return SIGE_HIP_OK;
-    if (!x || !y || !packed || !out || !active_indices || !scatter_map) return SIGE_HIP_EINVAL;
-    if (x1 && (!residual || !table1 || R1 <= 0 || S1 <= 0 || gH1 < (H + R1 - 1) / R1 || gW1 < (W + S1 - 1) / S1)) return SIGE_HIP_EINVAL;
-    if (!nhwc_ok(Cin, Cin, Cout, x, y, out, bias) || (reinterpret_cast<uintptr_t>(packed) & 15) ||
-        (reinterpret_cast<uintptr_t>(residual) & 15) || (reinterpret_cast<uintptr_t>(x1) & 15))
-        return SIGE_HIP_EUNSUPPORTED;
-    if (res_f16 && !residual) return SIGE_HIP_EINVAL;
-    ConvArgs a{};
-    a.y_f16 = y_f16 ? 1 : 0; a.res_f16 = res_f16 ? 1 : 0;
-    a.x = x; a.y = y; a.idx = active_indices; a.map = scatter_map; a.packed = packed; a.bias = bias; a.out = out;
-    a.T = B * N; a.Cin = Cin; a.Cout = Cout; a.B = B; a.N = N; a.H = H; a.W = W;
-    a.hp_shift = stacked_shift(H);  // (stacked edits: sige_hip_set_edit_batch)
-    if (a.hp_shift < 0 || (a.hp_shift && B != 1)) return SIGE_HIP_EUNSUPPORTED;
-    a.RxSx = Rx * Sx; a.Sx = Sx;
-    a.scale = scale; a.shift = shift;
-    const int mode = staging_mode(scale, scaleB, scaleC, shift, shiftB, shiftC, activation, B, Cin, &a.aff_sb, &a.aff_sc);
-    if (mode < 0) return SIGE_HIP_EUNSUPPORTED;
-    a.residual = residual; a.Ho = H; a.Wo = W; a.offH = offsetH; a.offW = offsetW; a.strH = 1; a.strW = 1;
-    a.x1 = x1; a.table1 = table1; a.gW1 = gW1; a.N1 = N1; a.R1 = R1 > 0 ? R1 : 1; a.S1 = S1 > 0 ? S1 : 1;
-    if ((twin0 && (!twin0_scale || !twin0_shift)) || (twin1 && (!twin1_scale || !twin1_shift))) return SIGE_HIP_EINVAL;
-    if ((reinterpret_cast<uintptr_t>(twin0) | reinterpret_cast<uintptr_t>(twin1) | reinterpret_cast<uintptr_t>(twin0_scale) |
-         reinterpret_cast<uintptr_t>(twin0_shift) | reinterpret_cast<uintptr_t>(twin1_scale) | reinterpret_cast<uintptr_t>(twin1_shift)) & 15)
-        return SIGE_HIP_EUNSUPPORTED;
-    a.twin0 = twin0; a.tscale0 = twin0_scale; a.tshift0 = twin0_shift;
-    a.twin1 = twin1; a.tscale1 = twin1_scale; a.tshift1 = twin1_shift;
-    return launch_kind<3, 1, 6, SRC_SCATTER_GATHER, DST_NCHW, LAYOUT_NHWC, PREC>(a, mode, as_stream(stream)) != SIGE_HIP_OK
-               ? SIGE_HIP_EUNSUPPORTED : launch_status();
-}
-
-#define SIGE_SGS_CONV_ARGS x, y, B, Cin, H, W, Rx, Sx, bH, bW, active_indices, N, scatter_map, scale, scaleB, scaleC, shift, shiftB, \
-    shiftC, activation, packed, bias, Cout, kH, kW, offsetH, offsetW, residual, x1, table1, gH1, gW1, N1, R1, S1, twin0, twin0_scale, twin0_shift, twin1, \
-    twin1_scale, twin1_shift, out, stream
-extern "C" int sige_hip_scatter_gather_conv_scatter_nhwc_f32(
-        const float *x, const float *y, int B, int Cin, int H, int W, int Rx, int Sx, int bH, int bW,
-        const int32_t *active_indices, int N, const int32_t *scatter_map,
-        const float *scale, int scaleB, int scaleC, const float *shift, int shiftB, int shiftC, int activation,
-        const float *packed, const float *bias, int Cout, int kH, int kW,
-        int offsetH, int offsetW, const float *residual,
-        const float *x1, const int32_t *table1, int gH1, int gW1, int N1, int R1, int S1,
-        float *twin0, const float *twin0_scale, const float *twin0_shift,
-        float *twin1, const float *twin1_scale, const float *twin1_shift,
-        float *out, void *stream) {
-    SIGE_PLAN_HOOK_N(sige_hip_scatter_gather_conv_scatter_nhwc_f32, (sige::CountOf<10, 11>, sige::CountOf<29, 32>), x, y, B, Cin, H, W, Rx, Sx, bH, bW, active_indices, N, scatter_map, scale, scaleB, scaleC, shift, shiftB, shiftC, activation, packed, bias, Cout, kH, kW, offsetH, offsetW, residual, x1, table1, gH1, gW1, N1, R1, S1, twin0, twin0_scale, twin0_shift, twin1, twin1_scale, twin1_shift, out, stream);
-    return scatter_gather_conv_scatter_nhwc_impl<0>(SIGE_SGS_CONV_ARGS);
-}
-extern "C" int sige_hip_scatter_gather_conv_scatter_nhwc_f16c(
-        const float *x, const float *y, int B, int Cin, int H, int W, int Rx, int Sx, int bH, int bW,
-        const int32_t *active_indices, int N, const int32_t *scatter_map,
-        const float *scale, int scaleB, int scaleC, const float *shift, int shiftB, int shiftC, int activation,
-        const float *packed, const float *bias, int Cout, int kH, int kW,
-        int offsetH, int offsetW, const float *residual,
-        const float *x1, const int32_t *table1, int gH1, int gW1, int N1, int R1, int S1,
-        float *twin0, const float *twin0_scale, const float *twin0_shift,
-        float *twin1, const float *twin1_scale, const float *twin1_shift,
-        float *out, void *stream) {
-    SIGE_PLAN_HOOK_N(sige_hip_scatter_gather_conv_scatter_nhwc_f16c, (sige::CountOf<10, 11>, sige::CountOf<29, 32>), x, y, B, Cin, H, W, Rx, Sx, bH, bW, active_indices, N, scatter_map, scale, scaleB, scaleC, shift, shiftB, shiftC, activation, packed, bias, Cout, kH, kW, offsetH, offsetW, residual, x1, table1, gH1, gW1, N1, R1, S1, twin0, twin0_scale, twin0_shift, twin1, twin1_scale, twin1_shift, out, stream);
-    return scatter_gather_conv_scatter_nhwc_impl<1>(SIGE_SGS_CONV_ARGS);
-}
-extern "C" int sige_hip_scatter_gather_conv_scatter_nhwc_f16x3(
-        const float *x, const float *y, int B, int Cin, int H, int W, int Rx, int Sx, int bH, int bW,
-        const int32_t *active_indices, int N, const int32_t *scatter_map,
-        const float *scale, int scaleB, int scaleC, const float *shift, int shiftB, int shiftC, int activation,
-        const float *packed, const float *bias, int Cout, int kH, int kW,
-        int offsetH, int offsetW, const float *residual,
-        const float *x1, const int32_t *table1, int gH1, int gW1, int N1, int R1, int S1,
-        float *twin0, const float *twin0_scale, const float *twin0_shift,
-        float *twin1, const float *twin1_scale, const float *twin1_shift,
-        float *out, void *stream) {
-    SIGE_PLAN_HOOK_N(sige_hip_scatter_gather_conv_scatter_nhwc_f16x3, (sige::CountOf<10, 11>, sige::CountOf<29, 32>), x, y, B, Cin, H, W, Rx, Sx, bH, bW, active_indices, N, scatter_map, scale, scaleB, scaleC, shift, shiftB, shiftC, activation, packed, bias, Cout, kH, kW, offsetH, offsetW, residual, x1, table1, gH1, gW1, N1, R1, S1, twin0, twin0_scale, twin0_shift, twin1, twin1_scale, twin1_shift, out, stream);
-    return scatter_gather_conv_scatter_nhwc_impl<2>(SIGE_SGS_CONV_ARGS);
-}
-
-// ---- the same two fused launches over fp16-STORED caches (SURVEY.md 8b export list "_f16", 8f row 4) ----
-// `y` (the cached tensor of the ScatterGather, or its activated copy) and -- for a fused ScatterWithBlockResidual (x1 != NULL) --
-// `residual` (the cached shortcut tensor) hold halves; everything else as in the fp32-storage entry points.  `compute`: 0 exact
-// fp32 products | 1 fp16 operands | 2 split fp16 operands (which packing `packed` has).
-extern "C" int sige_hip_scatter_gather_conv_nhwc_c16(int compute, const float *x, const void *y, int B, int Cin, int H, int W,
-                                                     int Rx, int Sx, int bH, int bW,
-                                                     const int32_t *active_indices, int N, const int32_t *scatter_map,
-                                                     const float *scale, int scaleB, int scaleC,
-                                                     const float *shift, int shiftB, int shiftC,
-                                                     int activation,
-                                                     const float *packed, const float *bias, int Cout, int kH, int kW,
-                                                     int strideH, int strideW, float *out, void *stream) {
-    SIGE_PLAN_HOOK_N(sige_hip_scatter_gather_conv_nhwc_c16, (sige::CountOf<11, 12>), compute, x, y, B, Cin, H, W, Rx, Sx, bH, bW, active_indices, N, scatter_map, scale, scaleB, scaleC, shift, shiftB, shiftC, activation, packed, bias, Cout, kH, kW, strideH, strideW, out, stream);
-    const float *yh = static_cast<const float *>(y);  // (halves behind a float pointer: ConvArgs::y_f16)
-    if (compute == 0) return scatter_gather_conv_nhwc_impl<0>(x, yh, B, Cin, H, W, Rx, Sx, bH, bW, active_indices, N, scatter_map, scale, scaleB, scaleC, shift, shiftB, shiftC, activation, packed, bias, Cout, kH, kW, strideH, strideW, out, stream, 1);
-    if (compute == 1) return scatter_gather_conv_nhwc_impl<1>(x, yh, B, Cin, H, W, Rx, Sx, bH, bW, active_indices, N, scatter_map, scale, scaleB, scaleC, shift, shiftB, shiftC, activation, packed, bias, Cout, kH, kW, strideH, strideW, out, stream, 1);
-    if (compute == 2) return scatter_gather_conv_nhwc_impl<2>(x, yh, B, Cin, H, W, Rx, Sx, bH, bW, active_indices, N, scatter_map, scale, scaleB, scaleC, shift, shiftB, shiftC, activation, packed, bias, Cout, kH, kW, strideH, strideW, out, stream, 1);
-    return SIGE_HIP_EINVAL;
-}
-
-extern "C" int sige_hip_scatter_gather_conv_scatter_nhwc_c16(
-        int compute, const float *x, const void *y, int B, int Cin, int H, int W, int Rx, int Sx, int bH, int bW,
-        const int32_t *active_indices, int N, const int32_t *scatter_map,
-        const float *scale, int scaleB, int scaleC, const float *shift, int shiftB, int shiftC, int activation,
-        const float *packed, const float *bias, int Cout, int kH, int kW,
-        int offsetH, int offsetW, const void *residual, int residual_f16,
-        const float *x1, const int32_t *table1, int gH1, int gW1, int N1, int R1, int S1,
-        float *twin0, const float *twin0_scale, const float *twin0_shift,
-        float *twin1, const float *twin1_scale, const float *twin1_shift,
-        float *out, void *stream) {
-    SIGE_PLAN_HOOK_N(sige_hip_scatter_gather_conv_scatter_nhwc_c16, (sige::CountOf<11, 12>, sige::CountOf<31, 34>), compute, x, y, B, Cin, H, W, Rx, Sx, bH, bW, active_indices, N, scatter_map, scale, scaleB, scaleC, shift, shiftB, shiftC, activation, packed, bias, Cout, kH, kW, offsetH, offsetW, residual, residual_f16, x1, table1, gH1, gW1, N1, R1, S1, twin0, twin0_scale, twin0_shift, twin1, twin1_scale, twin1_shift, out, stream);
-    const float *yh = static_cast<const float *>(y), *rh = static_cast<const float *>(residual);
-#define SIGE_SGS_C16_ARGS x, yh, B, Cin, H, W, Rx, Sx, bH, bW, active_indices, N, scatter_map, scale, scaleB, scaleC, shift, shiftB, \
-    shiftC, activation, packed, bias, Cout, kH, kW, offsetH, offsetW, rh, x1, table1, gH1, gW1, N1, R1, S1, twin0, twin0_scale, twin0_shift, twin1, \
-    twin1_scale, twin1_shift, out, stream, 1, residual_f16
-    if (compute == 0) return scatter_gather_conv_scatter_nhwc_impl<0>(SIGE_SGS_C16_ARGS);
-    if (compute == 1) return scatter_gather_conv_scatter_nhwc_impl<1>(SIGE_SGS_C16_ARGS);
-    if (compute == 2) return scatter_gather_conv_scatter_nhwc_impl<2>(SIGE_SGS_C16_ARGS);
-#undef SIGE_SGS_C16_ARGS
-    return SIGE_HIP_EINVAL;
-}
-
-extern "C" int sige_hip_block_conv_direct_f32(const float *x, int T, int Cin, int R, int S,
-                                              const float *w, const float *bias, int Cout, int kH, int kW,
-                                              int strideH, int strideW, int dilationH, int dilationW, int groups,
-                                              float *out, void *stream) {
-    SIGE_PLAN_HOOK_FIXED(sige_hip_block_conv_direct_f32, x, T, Cin, R, S, w, bias, Cout, kH, kW, strideH, strideW, dilationH, dilationW, groups, out, stream);
-    if (T < 0 || Cin <= 0 || Cout <= 0 || kH <= 0 || kW <= 0 || strideH <= 0 || strideW <= 0 || groups <= 0 ||
-        dilationH <= 0 || dilationW <= 0)
-        return SIGE_HIP_EINVAL;
-    const int eH = (kH - 1) * dilationH + 1, eW = (kW - 1) * dilationW + 1;  // extent of the dilated kernel
-    if (Cin % groups || Cout % groups || R < eH || S < eW) return SIGE_HIP_EINVAL;
-    if (T == 0) return SIGE_HIP_OK;
-    if (!x || !w || !out) return SIGE_HIP_EINVAL;
-    const int Ro = (R - eH) / strideH + 1, So = (S - eW) / strideW + 1;
-    const long total = (long)T * Cout * Ro * So;
-    const int blocks = (int)((total + 255) / 256 < 8192 ? (total + 255) / 256 : 8192);
-    block_conv_direct_kernel<<<blocks, 256, 0, as_stream(stream)>>>(x, w, bias, out, T, Cin, R, S, Cout, kH, kW,
-                                                                   strideH, strideW, dilationH, dilationW, groups, Ro, So, total);
-    return launch_status();
-}
-
-extern "C" int sige_hip_release_graph_tickets(void) { return sige::release_graph_tickets(); }
-
-// ---- routing entry points: conv_mfma.hpp or the tile conv v3 (conv_tile3.hpp), decided HERE from the tile count ----
-// The same calls as sige_hip_gather_conv_nhwc_f32 / sige_hip_scatter_gather_conv_scatter_nhwc_f32 plus the weights in the v3
-// layout and a threshold: a launch whose v3 grid -- tile pairs x 64-channel output blocks -- has at least `min_blocks` workgroups
-// runs on the v3 kernel, anything else exactly as before.  The decision is taken in C so that a launch plan, which replays the
-// recorded ENTRY POINT under a new mask's tile count, routes like the module-level forward under that mask does: plan and
-// module path stay bit-identical (round 5: the first router lived in Python and test_launch_plan_follows_mask_changes caught
-// the two running different kernels).
+// ---- routing: conv_mfma.hpp or the tile conv v3 (conv_tile3.hpp), decided HERE from the tile count ----
+// sige_hip_gather_conv_nhwc and sige_hip_scatter_gather_conv_scatter_nhwc take the weights in the v3 layout beside `packed` and a
+// threshold: a launch whose v3 grid -- tile pairs x 64-channel output blocks -- has at least `min_blocks` workgroups runs on the
+// v3 kernel, anything else on conv_mfma.hpp.  The decision is taken in C so that a launch plan, which replays the recorded ENTRY
+// POINT under a new mask's tile count, routes like the module-level forward under that mask does: plan and module path stay
+// bit-identical (round 5: the first router lived in Python and test_launch_plan_follows_mask_changes caught the two running
+// different kernels).  The v3 kernel has an exact-fp32 form (fp32-stored caches only) and an fp16-operand form: compute 2 never routes.
 // fp16 operands: a conv1 whose shortcut is held goes to the v3 kernel anyway from this many workgroups on (the shortcut is then
 // launched on its own: tile_conv3_launch -> flush_held_conv); SIGE_HIP_TUNE_TILE3_F16_PAIR_MIN = -1: this value, 0 = never
 constexpr int kTile3F16PairMin = 256;  // (profiles/r6j_tile3_f16_pairs_bench.json: -2.6 % at a 15 % edit, -3.3 % at 20 %, nothing lost below)
@@ -1367,94 +1084,132 @@ static bool tile3_takes(const float *packed_tile3, int min_blocks, int B, int N,
     return true;
 }
 
-extern "C" int sige_hip_gather_conv_nhwc_v3_f32(const float *x, const float *x2, int B, int C1, int C2, int H, int W,
-                                                int bH, int bW, const int32_t *active_indices, int N,
-                                                const float *scale, int scaleB, int scaleC,
-                                                const float *shift, int shiftB, int shiftC,
-                                                int activation,
-                                                const float *packed, const float *bias, int Cout, int kH, int kW,
-                                                int strideH, int strideW,
-                                                int to_full, int offsetH, int offsetW, const float *residual, int Ho, int Wo,
-                                                float *workspace, size_t workspace_floats,
-                                                const float *out_scale, const float *out_shift, int out_activation,
-                                                int upsample2x,
-                                                float *twin0, const float *twin0_scale, const float *twin0_shift,
-                                                float *twin1, const float *twin1_scale, const float *twin1_shift,
-                                                const float *packed_tile3, int min_blocks,
-                                                float *out, void *stream) {
-    SIGE_PLAN_HOOK_N(sige_hip_gather_conv_nhwc_v3_f32, (sige::CountOf<9, 10>), x, x2, B, C1, C2, H, W, bH, bW, active_indices, N, scale, scaleB, scaleC, shift, shiftB, shiftC, activation, packed, bias, Cout, kH, kW, strideH, strideW, to_full, offsetH, offsetW, residual, Ho, Wo, workspace, workspace_floats, out_scale, out_shift, out_activation, upsample2x, twin0, twin0_scale, twin0_shift, twin1, twin1_scale, twin1_shift, packed_tile3, min_blocks, out, stream);
+extern "C" int sige_hip_gather_conv_nhwc(int compute, const float *x, const float *x2, int B, int C1, int C2, int H, int W,
+                                         int bH, int bW, const int32_t *active_indices, int N,
+                                         const float *scale, int scaleB, int scaleC,
+                                         const float *shift, int shiftB, int shiftC,
+                                         int activation,
+                                         const float *packed, const float *bias, int Cout, int kH, int kW,
+                                         int strideH, int strideW,
+                                         int to_full, int offsetH, int offsetW, const float *residual, int Ho, int Wo,
+                                         float *workspace, size_t workspace_floats,
+                                         const float *out_scale, const float *out_shift, int out_activation,
+                                         int upsample2x,
+                                         float *twin0, const float *twin0_scale, const float *twin0_shift,
+                                         float *twin1, const float *twin1_scale, const float *twin1_shift,
+                                         const float *packed_tile3, int min_blocks,
+                                         float *out, void *stream) {
+    SIGE_PLAN_HOOK_N(sige_hip_gather_conv_nhwc, (sige::CountOf<10, 11>), compute, x, x2, B, C1, C2, H, W, bH, bW, active_indices, N, scale, scaleB, scaleC, shift, shiftB, shiftC, activation, packed, bias, Cout, kH, kW, strideH, strideW, to_full, offsetH, offsetW, residual, Ho, Wo, workspace, workspace_floats, out_scale, out_shift, out_activation, upsample2x, twin0, twin0_scale, twin0_shift, twin1, twin1_scale, twin1_shift, packed_tile3, min_blocks, out, stream);
     const int Cin = C1 + C2;
+    const bool f16 = compute == 1;
     const bool aff_ok = (!scale && !shift) || (scale && shift && scaleC == Cin && shiftC == Cin && scaleB == shiftB && (scaleB == 1 || scaleB == B));
-    if (B > 0 && N > 0 && aff_ok && tile3_takes(packed_tile3, min_blocks, B, N, C1, C2, Cout, kH, kW, bH, bW, strideH, strideW, as_stream(stream))) {
+    if ((compute == 0 || f16) && B > 0 && N > 0 && aff_ok &&
+        tile3_takes(packed_tile3, min_blocks, B, N, C1, C2, Cout, kH, kW, bH, bW, strideH, strideW, as_stream(stream), f16, f16 ? H : 0, f16 ? W : 0)) {
         const int rc = tile_conv3_launch(T3_GATHER, x, x2, B, C1, C2, H, W, upsample2x, active_indices, N, nullptr, 0, 0, scale, shift,
                                          scale ? scaleB : 0, activation, packed_tile3, bias, Cout, to_full, offsetH, offsetW, Ho, Wo,
                                          to_full ? residual : nullptr, nullptr, nullptr, 0, 0, 0, 0, 0, out_scale, out_shift, out_activation,
-                                         twin0, twin0_scale, twin0_shift, twin1, twin1_scale, twin1_shift, out, stream);
+                                         twin0, twin0_scale, twin0_shift, twin1, twin1_scale, twin1_shift, out, stream, f16 ? WIDE_F16 : WIDE_F32, 0, 0);
         if (rc != SIGE_HIP_EUNSUPPORTED) return rc;
     }
-    return gather_conv_nhwc_impl<0>(SIGE_GATHER_CONV_ARGS);
+    return SIGE_BY_COMPUTE(compute, gather_conv_nhwc_impl, x, x2, B, C1, C2, H, W, bH, bW, active_indices, N, scale, scaleB, scaleC, shift, shiftB,
+                           shiftC, activation, packed, bias, Cout, kH, kW, strideH, strideW, to_full, offsetH, offsetW, residual, Ho, Wo,
+                           workspace, workspace_floats, out_scale, out_shift, out_activation, upsample2x, twin0, twin0_scale, twin0_shift,
+                           twin1, twin1_scale, twin1_shift, out, stream);
 }
 
-extern "C" int sige_hip_scatter_gather_conv_scatter_nhwc_v3_f32(
-        const float *x, const float *y, int B, int Cin, int H, int W, int Rx, int Sx, int bH, int bW,
-        const int32_t *active_indices, int N, const int32_t *scatter_map,
-        const float *scale, int scaleB, int scaleC, const float *shift, int shiftB, int shiftC, int activation,
-        const float *packed, const float *bias, int Cout, int kH, int kW,
-        int offsetH, int offsetW, const float *residual,
-        const float *x1, const int32_t *table1, int gH1, int gW1, int N1, int R1, int S1,
-        float *twin0, const float *twin0_scale, const float *twin0_shift,
-        float *twin1, const float *twin1_scale, const float *twin1_shift,
-        const float *packed_tile3, int min_blocks,
-        float *out, void *stream) {
-    SIGE_PLAN_HOOK_N(sige_hip_scatter_gather_conv_scatter_nhwc_v3_f32, (sige::CountOf<10, 11>, sige::CountOf<29, 32>), x, y, B, Cin, H, W, Rx, Sx, bH, bW, active_indices, N, scatter_map, scale, scaleB, scaleC, shift, shiftB, shiftC, activation, packed, bias, Cout, kH, kW, offsetH, offsetW, residual, x1, table1, gH1, gW1, N1, R1, S1, twin0, twin0_scale, twin0_shift, twin1, twin1_scale, twin1_shift, packed_tile3, min_blocks, out, stream);
-    const bool aff_ok = (!scale && !shift && activation == SIGE_HIP_ACT_IDENTITY) ||
-                        (scale && shift && scaleC == Cin && shiftC == Cin && scaleB == shiftB && (scaleB == 1 || scaleB == B));
-    if (B > 0 && N > 0 && aff_ok &&
-        tile3_takes(packed_tile3, min_blocks, B, N, Cin, 0, Cout, kH, kW, bH, bW, 1, 1, as_stream(stream))) {
-        const int rc = tile_conv3_launch(T3_SCATTER_GATHER, x, y, B, Cin, 0, H, W, 0, active_indices, N, scatter_map, Rx, Sx, scale, shift, scale ? scaleB : 0,
-                                         activation, packed_tile3, bias, Cout, 1, offsetH, offsetW, H, W, residual,
-                                         x1, table1, gH1, gW1, N1, R1, S1, nullptr, nullptr, 0,
-                                         twin0, twin0_scale, twin0_shift, twin1, twin1_scale, twin1_shift, out, stream);
-        if (rc != SIGE_HIP_EUNSUPPORTED) return rc;
-    }
-    return scatter_gather_conv_scatter_nhwc_impl<0>(SIGE_SGS_CONV_ARGS);
+// `y` -- the cached tensor of the ScatterGather, or its activated copy -- holds halves when y_f16 != 0 (fp16-STORED caches:
+// SURVEY.md 8b export list "_f16", 8f row 4; 3x3 / stride 1 only), floats otherwise; every `compute` reads either.
+template <int PREC>
+static int scatter_gather_conv_nhwc_impl(const float *x, const void *y, int y_f16, int B, int Cin, int H, int W,
+                                                     int Rx, int Sx, int bH, int bW,
+                                                     const int32_t *active_indices, int N, const int32_t *scatter_map,
+                                                     const float *scale, int scaleB, int scaleC,
+                                                     const float *shift, int shiftB, int shiftC,
+                                                     int activation,
+                                                     const float *packed, const float *bias, int Cout, int kH, int kW,
+                                                     int strideH, int strideW, float *out, void *stream) {
+    if (B < 0 || Cin <= 0 || Cout <= 0 || H <= 0 || W <= 0 || N < 0 || Rx <= 0 || Sx <= 0) return SIGE_HIP_EINVAL;
+    if (activation != SIGE_HIP_ACT_IDENTITY && activation != SIGE_HIP_ACT_SWISH) return SIGE_HIP_EUNSUPPORTED;
+    if ((long)B * Cin * H * W >= (1L << 29) || (long)B * N * Cin * Rx * Sx >= (1L << 29)) return SIGE_HIP_EUNSUPPORTED;
+    if ((long)B * N == 0) return SIGE_HIP_OK;
+    if (!x || !y || !packed || !out || !active_indices || !scatter_map) return SIGE_HIP_EINVAL;
+    if (!nhwc_ok(Cin, Cin, Cout, x, y, out, bias) || (reinterpret_cast<uintptr_t>(packed) & 15)) return SIGE_HIP_EUNSUPPORTED;
+    if (y_f16 && (kH != 3 || kW != 3 || strideH != 1 || strideW != 1)) return SIGE_HIP_EUNSUPPORTED;
+    ConvArgs a{};
+    a.y_f16 = y_f16 ? 1 : 0;
+    a.x = x; a.y = static_cast<const float *>(y); a.idx = active_indices; a.map = scatter_map; a.packed = packed; a.bias = bias; a.out = out;
+    a.T = B * N; a.Cin = Cin; a.Cout = Cout; a.B = B; a.N = N; a.H = H; a.W = W;
+    a.hp_shift = stacked_shift(H);  // (stacked edits: sige_hip_set_edit_batch)
+    if (a.hp_shift < 0 || (a.hp_shift && B != 1)) return SIGE_HIP_EUNSUPPORTED;
+    a.RxSx = Rx * Sx; a.Sx = Sx;
+    a.scale = scale; a.shift = shift;
+    const int mode = staging_mode(scale, scaleB, scaleC, shift, shiftB, shiftC, activation, B, Cin, &a.aff_sb, &a.aff_sc);
+    if (mode < 0) return SIGE_HIP_EUNSUPPORTED;
+    return launch_conv<SRC_SCATTER_GATHER, DST_TILES, LAYOUT_NHWC, PREC>(a, mode, kH, kW, bH, bW, strideH, strideW, as_stream(stream));
 }
 
-
-// ... and for fp16 operands (round 6, BASELINE.json configs[4]): sige_hip_gather_conv_nhwc_f16c /
-// sige_hip_scatter_gather_conv_scatter_nhwc_f16c | _c16(compute = 1) with the weights in the v3 fp16 layout
-// (`packed_tile3` = sige_hip_wide_conv_pack(prec = 0)) and a threshold beside them; routed exactly like the fp32 pair above.
-extern "C" int sige_hip_gather_conv_nhwc_v3_f16c(const float *x, const float *x2, int B, int C1, int C2, int H, int W,
-                                                 int bH, int bW, const int32_t *active_indices, int N,
+extern "C" int sige_hip_scatter_gather_conv_nhwc(int compute, const float *x, const void *y, int y_f16, int B, int Cin, int H, int W,
+                                                 int Rx, int Sx, int bH, int bW,
+                                                 const int32_t *active_indices, int N, const int32_t *scatter_map,
                                                  const float *scale, int scaleB, int scaleC,
                                                  const float *shift, int shiftB, int shiftC,
                                                  int activation,
                                                  const float *packed, const float *bias, int Cout, int kH, int kW,
-                                                 int strideH, int strideW,
-                                                 int to_full, int offsetH, int offsetW, const float *residual, int Ho, int Wo,
-                                                 float *workspace, size_t workspace_floats,
-                                                 const float *out_scale, const float *out_shift, int out_activation,
-                                                 int upsample2x,
-                                                 float *twin0, const float *twin0_scale, const float *twin0_shift,
-                                                 float *twin1, const float *twin1_scale, const float *twin1_shift,
-                                                 const float *packed_tile3, int min_blocks,
-                                                 float *out, void *stream) {
-    SIGE_PLAN_HOOK_N(sige_hip_gather_conv_nhwc_v3_f16c, (sige::CountOf<9, 10>), x, x2, B, C1, C2, H, W, bH, bW, active_indices, N, scale, scaleB, scaleC, shift, shiftB, shiftC, activation, packed, bias, Cout, kH, kW, strideH, strideW, to_full, offsetH, offsetW, residual, Ho, Wo, workspace, workspace_floats, out_scale, out_shift, out_activation, upsample2x, twin0, twin0_scale, twin0_shift, twin1, twin1_scale, twin1_shift, packed_tile3, min_blocks, out, stream);
-    const int Cin = C1 + C2;
-    const bool aff_ok = (!scale && !shift) || (scale && shift && scaleC == Cin && shiftC == Cin && scaleB == shiftB && (scaleB == 1 || scaleB == B));
-    if (B > 0 && N > 0 && aff_ok && tile3_takes(packed_tile3, min_blocks, B, N, C1, C2, Cout, kH, kW, bH, bW, strideH, strideW, as_stream(stream), true, H, W)) {
-        const int rc = tile_conv3_launch(T3_GATHER, x, x2, B, C1, C2, H, W, upsample2x, active_indices, N, nullptr, 0, 0, scale, shift,
-                                         scale ? scaleB : 0, activation, packed_tile3, bias, Cout, to_full, offsetH, offsetW, Ho, Wo,
-                                         to_full ? residual : nullptr, nullptr, nullptr, 0, 0, 0, 0, 0, out_scale, out_shift, out_activation,
-                                         twin0, twin0_scale, twin0_shift, twin1, twin1_scale, twin1_shift, out, stream, WIDE_F16, 0, 0);
-        if (rc != SIGE_HIP_EUNSUPPORTED) return rc;
-    }
-    return gather_conv_nhwc_impl<1>(SIGE_GATHER_CONV_ARGS);
+                                                 int strideH, int strideW, float *out, void *stream) {
+    SIGE_PLAN_HOOK_N(sige_hip_scatter_gather_conv_nhwc, (sige::CountOf<12, 13>), compute, x, y, y_f16, B, Cin, H, W, Rx, Sx, bH, bW, active_indices, N, scatter_map, scale, scaleB, scaleC, shift, shiftB, shiftC, activation, packed, bias, Cout, kH, kW, strideH, strideW, out, stream);
+    return SIGE_BY_COMPUTE(compute, scatter_gather_conv_nhwc_impl, x, y, y_f16, B, Cin, H, W, Rx, Sx, bH, bW, active_indices, N, scatter_map, scale, scaleB,
+                           scaleC, shift, shiftB, shiftC, activation, packed, bias, Cout, kH, kW, strideH, strideW, out, stream);
 }
 
-// y_f16 / residual_f16: the cached tensor / the cached shortcut tensor hold halves (the _c16 form); 0 / 0 = the _f16c form
-extern "C" int sige_hip_scatter_gather_conv_scatter_nhwc_v3_f16c(
+// scatter_gather -> conv -> Scatter / ScatterWithBlockResidual in ONE launch: the conv's output tiles go straight
+// into `out` [B,H,W,Cout], a buffer that already holds the cached tensor outside this mask's tiles (in-place scatter).
+// y_f16 / residual_f16: `y` / `residual` (with x1 != NULL the cached shortcut tensor) hold halves -- the fp16-stored caches again.
+template <int PREC>
+static int scatter_gather_conv_scatter_nhwc_impl(
         const float *x, const void *y, int y_f16, int B, int Cin, int H, int W, int Rx, int Sx, int bH, int bW,
+        const int32_t *active_indices, int N, const int32_t *scatter_map,
+        const float *scale, int scaleB, int scaleC, const float *shift, int shiftB, int shiftC, int activation,
+        const float *packed, const float *bias, int Cout, int kH, int kW,
+        int offsetH, int offsetW, const void *residual, int residual_f16,
+        const float *x1, const int32_t *table1, int gH1, int gW1, int N1, int R1, int S1,
+        float *twin0, const float *twin0_scale, const float *twin0_shift,
+        float *twin1, const float *twin1_scale, const float *twin1_shift,
+        float *out, void *stream) {
+    if (B < 0 || Cin <= 0 || Cout <= 0 || H <= 0 || W <= 0 || N < 0 || Rx <= 0 || Sx <= 0) return SIGE_HIP_EINVAL;
+    if (kH != 3 || kW != 3 || bH != 6 || bW != 6) return SIGE_HIP_EUNSUPPORTED;  // the stride-1 3x3 geometry of a ResBlock's conv2
+    if (activation != SIGE_HIP_ACT_IDENTITY && activation != SIGE_HIP_ACT_SWISH) return SIGE_HIP_EUNSUPPORTED;
+    if ((long)B * Cin * H * W >= (1L << 29) || (long)B * N * Cin * Rx * Sx >= (1L << 29)) return SIGE_HIP_EUNSUPPORTED;
+    if ((long)B * N == 0) return SIGE_HIP_OK;
+    if (!x || !y || !packed || !out || !active_indices || !scatter_map) return SIGE_HIP_EINVAL;
+    if (x1 && (!residual || !table1 || R1 <= 0 || S1 <= 0 || gH1 < (H + R1 - 1) / R1 || gW1 < (W + S1 - 1) / S1)) return SIGE_HIP_EINVAL;
+    if (!nhwc_ok(Cin, Cin, Cout, x, y, out, bias) || (reinterpret_cast<uintptr_t>(packed) & 15) ||
+        (reinterpret_cast<uintptr_t>(residual) & 15) || (reinterpret_cast<uintptr_t>(x1) & 15))
+        return SIGE_HIP_EUNSUPPORTED;
+    if (residual_f16 && !residual) return SIGE_HIP_EINVAL;
+    ConvArgs a{};
+    a.y_f16 = y_f16 ? 1 : 0; a.res_f16 = residual_f16 ? 1 : 0;
+    a.x = x; a.y = static_cast<const float *>(y); a.idx = active_indices; a.map = scatter_map; a.packed = packed; a.bias = bias; a.out = out;
+    a.T = B * N; a.Cin = Cin; a.Cout = Cout; a.B = B; a.N = N; a.H = H; a.W = W;
+    a.hp_shift = stacked_shift(H);  // (stacked edits: sige_hip_set_edit_batch)
+    if (a.hp_shift < 0 || (a.hp_shift && B != 1)) return SIGE_HIP_EUNSUPPORTED;
+    a.RxSx = Rx * Sx; a.Sx = Sx;
+    a.scale = scale; a.shift = shift;
+    const int mode = staging_mode(scale, scaleB, scaleC, shift, shiftB, shiftC, activation, B, Cin, &a.aff_sb, &a.aff_sc);
+    if (mode < 0) return SIGE_HIP_EUNSUPPORTED;
+    a.residual = static_cast<const float *>(residual); a.Ho = H; a.Wo = W; a.offH = offsetH; a.offW = offsetW; a.strH = 1; a.strW = 1;
+    a.x1 = x1; a.table1 = table1; a.gW1 = gW1; a.N1 = N1; a.R1 = R1 > 0 ? R1 : 1; a.S1 = S1 > 0 ? S1 : 1;
+    if ((twin0 && (!twin0_scale || !twin0_shift)) || (twin1 && (!twin1_scale || !twin1_shift))) return SIGE_HIP_EINVAL;
+    if ((reinterpret_cast<uintptr_t>(twin0) | reinterpret_cast<uintptr_t>(twin1) | reinterpret_cast<uintptr_t>(twin0_scale) |
+         reinterpret_cast<uintptr_t>(twin0_shift) | reinterpret_cast<uintptr_t>(twin1_scale) | reinterpret_cast<uintptr_t>(twin1_shift)) & 15)
+        return SIGE_HIP_EUNSUPPORTED;
+    a.twin0 = twin0; a.tscale0 = twin0_scale; a.tshift0 = twin0_shift;
+    a.twin1 = twin1; a.tscale1 = twin1_scale; a.tshift1 = twin1_shift;
+    return launch_kind<3, 1, 6, SRC_SCATTER_GATHER, DST_NCHW, LAYOUT_NHWC, PREC>(a, mode, as_stream(stream)) != SIGE_HIP_OK
+               ? SIGE_HIP_EUNSUPPORTED : launch_status();
+}
+
+extern "C" int sige_hip_scatter_gather_conv_scatter_nhwc(
+        int compute, const float *x, const void *y, int y_f16, int B, int Cin, int H, int W, int Rx, int Sx, int bH, int bW,
         const int32_t *active_indices, int N, const int32_t *scatter_map,
         const float *scale, int scaleB, int scaleC, const float *shift, int shiftB, int shiftC, int activation,
         const float *packed, const float *bias, int Cout, int kH, int kW,
@@ -1464,19 +1219,45 @@ extern "C" int sige_hip_scatter_gather_conv_scatter_nhwc_v3_f16c(
         float *twin1, const float *twin1_scale, const float *twin1_shift,
         const float *packed_tile3, int min_blocks,
         float *out, void *stream) {
-    SIGE_PLAN_HOOK_N(sige_hip_scatter_gather_conv_scatter_nhwc_v3_f16c, (sige::CountOf<11, 12>, sige::CountOf<31, 34>), x, y, y_f16, B, Cin, H, W, Rx, Sx, bH, bW, active_indices, N, scatter_map, scale, scaleB, scaleC, shift, shiftB, shiftC, activation, packed, bias, Cout, kH, kW, offsetH, offsetW, residual, residual_f16, x1, table1, gH1, gW1, N1, R1, S1, twin0, twin0_scale, twin0_shift, twin1, twin1_scale, twin1_shift, packed_tile3, min_blocks, out, stream);
-    const float *yh = static_cast<const float *>(y), *rh = static_cast<const float *>(residual);
+    SIGE_PLAN_HOOK_N(sige_hip_scatter_gather_conv_scatter_nhwc, (sige::CountOf<12, 13>, sige::CountOf<32, 35>), compute, x, y, y_f16, B, Cin, H, W, Rx, Sx, bH, bW, active_indices, N, scatter_map, scale, scaleB, scaleC, shift, shiftB, shiftC, activation, packed, bias, Cout, kH, kW, offsetH, offsetW, residual, residual_f16, x1, table1, gH1, gW1, N1, R1, S1, twin0, twin0_scale, twin0_shift, twin1, twin1_scale, twin1_shift, packed_tile3, min_blocks, out, stream);
+    const bool f16 = compute == 1;
     const bool aff_ok = (!scale && !shift && activation == SIGE_HIP_ACT_IDENTITY) ||
                         (scale && shift && scaleC == Cin && shiftC == Cin && scaleB == shiftB && (scaleB == 1 || scaleB == B));
-    if (B > 0 && N > 0 && aff_ok &&
-        tile3_takes(packed_tile3, min_blocks, B, N, Cin, 0, Cout, kH, kW, bH, bW, 1, 1, as_stream(stream), true, H, W)) {
-        const int rc = tile_conv3_launch(T3_SCATTER_GATHER, x, yh, B, Cin, 0, H, W, 0, active_indices, N, scatter_map, Rx, Sx, scale, shift, scale ? scaleB : 0,
-                                         activation, packed_tile3, bias, Cout, 1, offsetH, offsetW, H, W, rh,
-                                         x1, table1, gH1, gW1, N1, R1, S1, nullptr, nullptr, 0,
-                                         twin0, twin0_scale, twin0_shift, twin1, twin1_scale, twin1_shift, out, stream, WIDE_F16, y_f16, residual_f16);
+    // (the exact-fp32 v3 kernel reads fp32-stored caches only)
+    if ((f16 || (compute == 0 && !y_f16 && !residual_f16)) && B > 0 && N > 0 && aff_ok &&
+        tile3_takes(packed_tile3, min_blocks, B, N, Cin, 0, Cout, kH, kW, bH, bW, 1, 1, as_stream(stream), f16, f16 ? H : 0, f16 ? W : 0)) {
+        const int rc = tile_conv3_launch(T3_SCATTER_GATHER, x, static_cast<const float *>(y), B, Cin, 0, H, W, 0, active_indices, N, scatter_map, Rx, Sx,
+                                         scale, shift, scale ? scaleB : 0, activation, packed_tile3, bias, Cout, 1, offsetH, offsetW, H, W,
+                                         static_cast<const float *>(residual), x1, table1, gH1, gW1, N1, R1, S1, nullptr, nullptr, 0,
+                                         twin0, twin0_scale, twin0_shift, twin1, twin1_scale, twin1_shift, out, stream,
+                                         f16 ? WIDE_F16 : WIDE_F32, y_f16, residual_f16);
         if (rc != SIGE_HIP_EUNSUPPORTED) return rc;
     }
-    return scatter_gather_conv_scatter_nhwc_impl<1>(x, yh, B, Cin, H, W, Rx, Sx, bH, bW, active_indices, N, scatter_map, scale, scaleB, scaleC, shift, shiftB,
-                                                    shiftC, activation, packed, bias, Cout, kH, kW, offsetH, offsetW, rh, x1, table1, gH1, gW1, N1, R1, S1,
-                                                    twin0, twin0_scale, twin0_shift, twin1, twin1_scale, twin1_shift, out, stream, y_f16, residual_f16);
+    return SIGE_BY_COMPUTE(compute, scatter_gather_conv_scatter_nhwc_impl, x, y, y_f16, B, Cin, H, W, Rx, Sx, bH, bW, active_indices, N, scatter_map,
+                           scale, scaleB, scaleC, shift, shiftB, shiftC, activation, packed, bias, Cout, kH, kW, offsetH, offsetW,
+                           residual, residual_f16, x1, table1, gH1, gW1, N1, R1, S1, twin0, twin0_scale, twin0_shift, twin1, twin1_scale,
+                           twin1_shift, out, stream);
 }
+#undef SIGE_BY_COMPUTE
+
+extern "C" int sige_hip_block_conv_direct_f32(const float *x, int T, int Cin, int R, int S,
+                                              const float *w, const float *bias, int Cout, int kH, int kW,
+                                              int strideH, int strideW, int dilationH, int dilationW, int groups,
+                                              float *out, void *stream) {
+    SIGE_PLAN_HOOK_FIXED(sige_hip_block_conv_direct_f32, x, T, Cin, R, S, w, bias, Cout, kH, kW, strideH, strideW, dilationH, dilationW, groups, out, stream);
+    if (T < 0 || Cin <= 0 || Cout <= 0 || kH <= 0 || kW <= 0 || strideH <= 0 || strideW <= 0 || groups <= 0 ||
+        dilationH <= 0 || dilationW <= 0)
+        return SIGE_HIP_EINVAL;
+    const int eH = (kH - 1) * dilationH + 1, eW = (kW - 1) * dilationW + 1;  // extent of the dilated kernel
+    if (Cin % groups || Cout % groups || R < eH || S < eW) return SIGE_HIP_EINVAL;
+    if (T == 0) return SIGE_HIP_OK;
+    if (!x || !w || !out) return SIGE_HIP_EINVAL;
+    const int Ro = (R - eH) / strideH + 1, So = (S - eW) / strideW + 1;
+    const long total = (long)T * Cout * Ro * So;
+    const int blocks = (int)((total + 255) / 256 < 8192 ? (total + 255) / 256 : 8192);
+    block_conv_direct_kernel<<<blocks, 256, 0, as_stream(stream)>>>(x, w, bias, out, T, Cin, R, S, Cout, kH, kW,
+                                                                   strideH, strideW, dilationH, dilationW, groups, Ro, So, total);
+    return launch_status();
+}
+
+extern "C" int sige_hip_release_graph_tickets(void) { return sige::release_graph_tickets(); }

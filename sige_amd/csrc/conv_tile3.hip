@@ -1,5 +1,5 @@
-// Tile conv v3 (conv_tile3.hpp): C ABI.  One entry point for both staging sources and both destinations; weights in the
-// exact-fp32 layout of the dense-layer kernel (sige_hip_wide_conv_pack(prec = 2)).
+// Tile conv v3 (conv_tile3.hpp): C ABI.  One entry point for both staging sources, both destinations and both operand forms;
+// weights in the layouts of the dense-layer kernel (sige_hip_wide_conv_pack).
 #include "conv_tile3.hpp"
 
 namespace sige {
@@ -92,28 +92,12 @@ int sige::tile_conv3_launch(
     return launch_status(1);
 }
 
-extern "C" int sige_hip_tile_conv3_nhwc_f32(
-        int source, const float *x, const float *x2, int B, int C1, int C2, int H, int W, int upsample2x,
-        const int32_t *active_indices, int N, const int32_t *scatter_map, int Rx, int Sx,
-        const float *scale, const float *shift, int affineB, int activation,
-        const float *packed, const float *bias, int Cout,
-        int to_full, int offsetH, int offsetW, int Ho, int Wo, const float *residual,
-        const float *x1, const int32_t *table1, int gH1, int gW1, int N1, int R1, int S1,
-        const float *out_scale, const float *out_shift, int out_activation,
-        float *twin0, const float *twin_scale0, const float *twin_shift0,
-        float *twin1, const float *twin_scale1, const float *twin_shift1,
-        float *out, void *stream) {
-    SIGE_PLAN_HOOK_N(sige_hip_tile_conv3_nhwc_f32, (sige::CountOf<9, 10>, sige::CountOf<28, 31>), source, x, x2, B, C1, C2, H, W, upsample2x, active_indices, N, scatter_map, Rx, Sx, scale, shift, affineB, activation, packed, bias, Cout, to_full, offsetH, offsetW, Ho, Wo, residual, x1, table1, gH1, gW1, N1, R1, S1, out_scale, out_shift, out_activation, twin0, twin_scale0, twin_shift0, twin1, twin_scale1, twin_shift1, out, stream);
-    return tile_conv3_launch(source, x, x2, B, C1, C2, H, W, upsample2x, active_indices, N, scatter_map, Rx, Sx, scale, shift, affineB, activation,
-                             packed, bias, Cout, to_full, offsetH, offsetW, Ho, Wo, residual, x1, table1, gH1, gW1, N1, R1, S1,
-                             out_scale, out_shift, out_activation, twin0, twin_scale0, twin_shift0, twin1, twin_scale1, twin_shift1, out, stream);
-}
-
-// fp16 operands (BASELINE.json configs[4]): `packed` = sige_hip_wide_conv_pack(prec = 0) of the same weight; activations are fp32 in
-// HBM and rounded to fp16 (RNE) in the staging path, products exact, accumulation fp32.  y_f16: source 2's cached tensor x2 holds
-// halves; residual_f16: `residual` holds halves (the fp16-stored caches of SIGEModel.set_cache_dtype("f16")).
-extern "C" int sige_hip_tile_conv3_nhwc_f16c(
-        int source, const float *x, const void *x2, int y_f16, int B, int C1, int C2, int H, int W, int upsample2x,
+// compute 0: exact fp32, `packed` = sige_hip_wide_conv_pack(prec = 2), fp32-stored tensors only.  compute 1: fp16 operands
+// (BASELINE.json configs[4]), `packed` = sige_hip_wide_conv_pack(prec = 0) of the same weight; activations are fp32 in HBM and
+// rounded to fp16 (RNE) in the staging path, products exact, accumulation fp32.  y_f16: source 2's cached tensor x2 holds halves;
+// residual_f16: `residual` holds halves (the fp16-stored caches of SIGEModel.set_cache_dtype("f16")).  compute 2: no such kernel.
+extern "C" int sige_hip_tile_conv3_nhwc(
+        int compute, int source, const float *x, const void *x2, int y_f16, int B, int C1, int C2, int H, int W, int upsample2x,
         const int32_t *active_indices, int N, const int32_t *scatter_map, int Rx, int Sx,
         const float *scale, const float *shift, int affineB, int activation,
         const float *packed, const float *bias, int Cout,
@@ -123,9 +107,11 @@ extern "C" int sige_hip_tile_conv3_nhwc_f16c(
         float *twin0, const float *twin_scale0, const float *twin_shift0,
         float *twin1, const float *twin_scale1, const float *twin_shift1,
         float *out, void *stream) {
-    SIGE_PLAN_HOOK_N(sige_hip_tile_conv3_nhwc_f16c, (sige::CountOf<10, 11>, sige::CountOf<30, 33>), source, x, x2, y_f16, B, C1, C2, H, W, upsample2x, active_indices, N, scatter_map, Rx, Sx, scale, shift, affineB, activation, packed, bias, Cout, to_full, offsetH, offsetW, Ho, Wo, residual, residual_f16, x1, table1, gH1, gW1, N1, R1, S1, out_scale, out_shift, out_activation, twin0, twin_scale0, twin_shift0, twin1, twin_scale1, twin_shift1, out, stream);
+    SIGE_PLAN_HOOK_N(sige_hip_tile_conv3_nhwc, (sige::CountOf<11, 12>, sige::CountOf<31, 34>), compute, source, x, x2, y_f16, B, C1, C2, H, W, upsample2x, active_indices, N, scatter_map, Rx, Sx, scale, shift, affineB, activation, packed, bias, Cout, to_full, offsetH, offsetW, Ho, Wo, residual, residual_f16, x1, table1, gH1, gW1, N1, R1, S1, out_scale, out_shift, out_activation, twin0, twin_scale0, twin_shift0, twin1, twin_scale1, twin_shift1, out, stream);
+    if (compute < 0 || compute > 2) return SIGE_HIP_EINVAL;
+    if (compute == 2) return SIGE_HIP_EUNSUPPORTED;
     return tile_conv3_launch(source, x, static_cast<const float *>(x2), B, C1, C2, H, W, upsample2x, active_indices, N, scatter_map, Rx, Sx, scale, shift,
                              affineB, activation, packed, bias, Cout, to_full, offsetH, offsetW, Ho, Wo, static_cast<const float *>(residual),
                              x1, table1, gH1, gW1, N1, R1, S1, out_scale, out_shift, out_activation, twin0, twin_scale0, twin_shift0,
-                             twin1, twin_scale1, twin_shift1, out, stream, WIDE_F16, y_f16, residual_f16);
+                             twin1, twin_scale1, twin_shift1, out, stream, compute == 1 ? WIDE_F16 : WIDE_F32, y_f16, residual_f16);
 }

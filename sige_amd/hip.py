@@ -82,37 +82,23 @@ _SIGNATURES = {
     "sige_hip_attention_workspace": (_c_sz, [_c_int] * 3),
     "sige_hip_attention_f32": (_c_int, [_c_vp, _c_int, _c_int, _c_int, ctypes.c_float, _c_vp, _c_vp, _c_vp]),
     "sige_hip_copy_f32": (_c_int, [_c_vp, _c_vp, _c_sz, _c_vp]),
-    # channels-last forms
-    "sige_hip_block_conv_nhwc_f32": (_c_int, [_c_vp] + [_c_int] * 4 + [_c_vp, _c_vp] + [_c_int] * 5 + [_c_vp, _c_vp]),
-    "sige_hip_gather_conv_nhwc_f32": (
-        _c_int, [_c_vp, _c_vp] + [_c_int] * 7 + [_c_vp, _c_int] + [_c_vp, _c_int, _c_int] * 2 + [_c_int, _c_vp, _c_vp]
-        + [_c_int] * 5 + [_c_int, _c_int, _c_int, _c_vp, _c_int, _c_int, _c_vp, _c_sz, _c_vp, _c_vp, _c_int, _c_int] + [_c_vp] * 6
-        + [_c_vp, _c_vp]),
-    "sige_hip_gather_conv_nhwc_v3_f32": (
-        _c_int, [_c_vp, _c_vp] + [_c_int] * 7 + [_c_vp, _c_int] + [_c_vp, _c_int, _c_int] * 2 + [_c_int, _c_vp, _c_vp]
+    # channels-last forms; the tile convs take `compute` (0 f32 | 1 f16 | 2 f16x3) first
+    "sige_hip_block_conv_nhwc": (_c_int, [_c_int, _c_vp] + [_c_int] * 4 + [_c_vp, _c_vp] + [_c_int] * 5 + [_c_vp, _c_vp]),
+    "sige_hip_block_conv_nhwc_keyed": (_c_int, [_c_int, _c_vp, _c_vp] + [_c_int] * 5 + [_c_vp, _c_vp] + [_c_int] * 5 + [_c_vp, _c_vp]),
+    "sige_hip_gather_conv_nhwc": (
+        _c_int, [_c_int, _c_vp, _c_vp] + [_c_int] * 7 + [_c_vp, _c_int] + [_c_vp, _c_int, _c_int] * 2 + [_c_int, _c_vp, _c_vp]
         + [_c_int] * 5 + [_c_int, _c_int, _c_int, _c_vp, _c_int, _c_int, _c_vp, _c_sz, _c_vp, _c_vp, _c_int, _c_int] + [_c_vp] * 6
         + [_c_vp, _c_int] + [_c_vp, _c_vp]),
-    "sige_hip_scatter_gather_conv_scatter_nhwc_v3_f32": (
-        _c_int, [_c_vp, _c_vp] + [_c_int] * 8 + [_c_vp, _c_int, _c_vp] + [_c_vp, _c_int, _c_int] * 2 + [_c_int, _c_vp, _c_vp]
-        + [_c_int] * 3 + [_c_int, _c_int, _c_vp] + [_c_vp, _c_vp] + [_c_int] * 5 + [_c_vp] * 6 + [_c_vp, _c_int] + [_c_vp, _c_vp]),
+    "sige_hip_scatter_gather_conv_nhwc": (
+        _c_int, [_c_int, _c_vp, _c_vp, _c_int] + [_c_int] * 8 + [_c_vp, _c_int, _c_vp] + [_c_vp, _c_int, _c_int] * 2 + [_c_int, _c_vp, _c_vp]
+        + [_c_int] * 5 + [_c_vp, _c_vp]),
+    "sige_hip_scatter_gather_conv_scatter_nhwc": (
+        _c_int, [_c_int, _c_vp, _c_vp, _c_int] + [_c_int] * 8 + [_c_vp, _c_int, _c_vp] + [_c_vp, _c_int, _c_int] * 2 + [_c_int, _c_vp, _c_vp]
+        + [_c_int] * 3 + [_c_int, _c_int, _c_vp, _c_int] + [_c_vp, _c_vp] + [_c_int] * 5 + [_c_vp] * 6 + [_c_vp, _c_int] + [_c_vp, _c_vp]),
+    "sige_hip_tile_conv3_nhwc": (
+        _c_int, [_c_int, _c_int, _c_vp, _c_vp, _c_int] + [_c_int] * 6 + [_c_vp, _c_int, _c_vp, _c_int, _c_int] + [_c_vp, _c_vp, _c_int, _c_int]
+        + [_c_vp, _c_vp, _c_int] + [_c_int] * 5 + [_c_vp, _c_int] + [_c_vp, _c_vp] + [_c_int] * 5 + [_c_vp, _c_vp, _c_int] + [_c_vp] * 6 + [_c_vp, _c_vp]),
     "sige_hip_conv_ksplit_hint": (_c_int, [_c_int] * 7),
-    "sige_hip_block_conv_nhwc_f16c": (_c_int, [_c_vp] + [_c_int] * 4 + [_c_vp, _c_vp] + [_c_int] * 5 + [_c_vp, _c_vp]),
-    "sige_hip_gather_conv_nhwc_f16c": (
-        _c_int, [_c_vp, _c_vp] + [_c_int] * 7 + [_c_vp, _c_int] + [_c_vp, _c_int, _c_int] * 2 + [_c_int, _c_vp, _c_vp]
-        + [_c_int] * 5 + [_c_int, _c_int, _c_int, _c_vp, _c_int, _c_int, _c_vp, _c_sz, _c_vp, _c_vp, _c_int, _c_int] + [_c_vp] * 6
-        + [_c_vp, _c_vp]),
-    "sige_hip_scatter_gather_conv_nhwc_f16c": (
-        _c_int, [_c_vp, _c_vp] + [_c_int] * 8 + [_c_vp, _c_int, _c_vp] + [_c_vp, _c_int, _c_int] * 2 + [_c_int, _c_vp, _c_vp]
-        + [_c_int] * 5 + [_c_vp, _c_vp]),
-    "sige_hip_scatter_gather_conv_scatter_nhwc_f16c": (
-        _c_int, [_c_vp, _c_vp] + [_c_int] * 8 + [_c_vp, _c_int, _c_vp] + [_c_vp, _c_int, _c_int] * 2 + [_c_int, _c_vp, _c_vp]
-        + [_c_int] * 3 + [_c_int, _c_int, _c_vp] + [_c_vp, _c_vp] + [_c_int] * 5 + [_c_vp] * 6 + [_c_vp, _c_vp]),
-    "sige_hip_scatter_gather_conv_nhwc_f32": (
-        _c_int, [_c_vp, _c_vp] + [_c_int] * 8 + [_c_vp, _c_int, _c_vp] + [_c_vp, _c_int, _c_int] * 2 + [_c_int, _c_vp, _c_vp]
-        + [_c_int] * 5 + [_c_vp, _c_vp]),
-    "sige_hip_scatter_gather_conv_scatter_nhwc_f32": (
-        _c_int, [_c_vp, _c_vp] + [_c_int] * 8 + [_c_vp, _c_int, _c_vp] + [_c_vp, _c_int, _c_int] * 2 + [_c_int, _c_vp, _c_vp]
-        + [_c_int] * 3 + [_c_int, _c_int, _c_vp] + [_c_vp, _c_vp] + [_c_int] * 5 + [_c_vp] * 6 + [_c_vp, _c_vp]),
     "sige_hip_gather_nhwc_f32": (
         _c_int, [_c_vp] + [_c_int] * 6 + [_c_vp, _c_int] + [_c_vp, _c_int, _c_int] * 2 + [_c_int, _c_vp, _c_vp]),
     "sige_hip_scatter_gather_nhwc_f32": (
@@ -141,17 +127,6 @@ _SIGNATURES = {
     # split fp16 operands (tile kernels)
     "sige_hip_block_conv_packed_size_f16x3": (_c_sz, [_c_int] * 9),
     "sige_hip_block_conv_pack_f16x3": (_c_int, [_c_vp] + [_c_int] * 4 + [_c_vp, _c_vp]),
-    "sige_hip_block_conv_nhwc_f16x3": (_c_int, [_c_vp] + [_c_int] * 4 + [_c_vp, _c_vp] + [_c_int] * 5 + [_c_vp, _c_vp]),
-    "sige_hip_gather_conv_nhwc_f16x3": (
-        _c_int, [_c_vp, _c_vp] + [_c_int] * 7 + [_c_vp, _c_int] + [_c_vp, _c_int, _c_int] * 2 + [_c_int, _c_vp, _c_vp]
-        + [_c_int] * 5 + [_c_int, _c_int, _c_int, _c_vp, _c_int, _c_int, _c_vp, _c_sz, _c_vp, _c_vp, _c_int, _c_int] + [_c_vp] * 6
-        + [_c_vp, _c_vp]),
-    "sige_hip_scatter_gather_conv_nhwc_f16x3": (
-        _c_int, [_c_vp, _c_vp] + [_c_int] * 8 + [_c_vp, _c_int, _c_vp] + [_c_vp, _c_int, _c_int] * 2 + [_c_int, _c_vp, _c_vp]
-        + [_c_int] * 5 + [_c_vp, _c_vp]),
-    "sige_hip_scatter_gather_conv_scatter_nhwc_f16x3": (
-        _c_int, [_c_vp, _c_vp] + [_c_int] * 8 + [_c_vp, _c_int, _c_vp] + [_c_vp, _c_int, _c_int] * 2 + [_c_int, _c_vp, _c_vp]
-        + [_c_int] * 3 + [_c_int, _c_int, _c_vp] + [_c_vp, _c_vp] + [_c_int] * 5 + [_c_vp] * 6 + [_c_vp, _c_vp]),
     "sige_hip_affine_act_nhwc_f32": (_c_int, [_c_vp] + [_c_int] * 4 + [_c_vp, _c_vp, _c_int, _c_int, _c_vp, _c_vp]),
     # dense layers on the fp16 matrix cores (conv_wide)
     "sige_hip_wide_conv_supported": (_c_int, [_c_int] * 5),
@@ -180,33 +155,13 @@ _SIGNATURES = {
     "sige_hip_affine_act_nhwc_f16": (_c_int, [_c_vp] + [_c_int] * 4 + [_c_vp, _c_vp, _c_int, _c_int, _c_vp, _c_int, _c_vp]),
     "sige_hip_convert_f16_f32": (_c_int, [_c_vp, _c_vp, _c_sz, _c_vp]),
     "sige_hip_convert_f32_f16": (_c_int, [_c_vp, _c_vp, _c_sz, _c_vp]),
-    "sige_hip_scatter_gather_conv_nhwc_c16": (
-        _c_int, [_c_int, _c_vp, _c_vp] + [_c_int] * 8 + [_c_vp, _c_int, _c_vp] + [_c_vp, _c_int, _c_int] * 2 + [_c_int, _c_vp, _c_vp]
-        + [_c_int] * 5 + [_c_vp, _c_vp]),
-    "sige_hip_scatter_gather_conv_scatter_nhwc_c16": (
-        _c_int, [_c_int, _c_vp, _c_vp] + [_c_int] * 8 + [_c_vp, _c_int, _c_vp] + [_c_vp, _c_int, _c_int] * 2 + [_c_int, _c_vp, _c_vp]
-        + [_c_int] * 3 + [_c_int, _c_int, _c_vp, _c_int] + [_c_vp, _c_vp] + [_c_int] * 5 + [_c_vp] * 6 + [_c_vp, _c_vp]),
     "sige_hip_conv3x3_small_cout_act_nhwc_f32": (_c_int, [_c_vp] + [_c_int] * 5 + [ctypes.c_float, _c_vp, _c_vp, _c_int, _c_int, _c_vp, _c_vp]),
     "sige_hip_resize_nearest_nhwc_f32": (_c_int, [_c_vp] + [_c_int] * 6 + [_c_vp, _c_vp]),
     "sige_hip_act_split_nhwc_f32": (_c_int, [_c_vp, ctypes.c_int64, _c_int, _c_int, ctypes.c_int64, _c_int, ctypes.c_float, _c_vp, _c_vp]),
     "sige_hip_scatter_gather_split_nhwc_f32": (
         _c_int, [_c_vp, _c_vp] + [_c_int] * 8 + [_c_vp, _c_int, _c_vp, _c_int, ctypes.c_float, _c_int, ctypes.c_int64, _c_vp, _c_vp]),
     "sige_hip_spade_modulate_dense_nhwc_f32": (_c_int, [_c_vp, _c_vp, _c_vp, _c_int, _c_vp] + [_c_int] * 5 + [ctypes.c_float, _c_vp, _c_vp]),
-    "sige_hip_block_conv_nhwc_keyed": (_c_int, [_c_int, _c_vp, _c_vp] + [_c_int] * 5 + [_c_vp, _c_vp] + [_c_int] * 5 + [_c_vp, _c_vp]),
     "sige_hip_tile_conv3_supported": (_c_int, [_c_int] * 3),
-    "sige_hip_tile_conv3_nhwc_f32": (
-        _c_int, [_c_int, _c_vp, _c_vp] + [_c_int] * 6 + [_c_vp, _c_int, _c_vp, _c_int, _c_int] + [_c_vp, _c_vp, _c_int, _c_int]
-        + [_c_vp, _c_vp, _c_int] + [_c_int] * 5 + [_c_vp] + [_c_vp, _c_vp] + [_c_int] * 5 + [_c_vp, _c_vp, _c_int] + [_c_vp] * 6 + [_c_vp, _c_vp]),
-    "sige_hip_tile_conv3_nhwc_f16c": (
-        _c_int, [_c_int, _c_vp, _c_vp, _c_int] + [_c_int] * 6 + [_c_vp, _c_int, _c_vp, _c_int, _c_int] + [_c_vp, _c_vp, _c_int, _c_int]
-        + [_c_vp, _c_vp, _c_int] + [_c_int] * 5 + [_c_vp, _c_int] + [_c_vp, _c_vp] + [_c_int] * 5 + [_c_vp, _c_vp, _c_int] + [_c_vp] * 6 + [_c_vp, _c_vp]),
-    "sige_hip_gather_conv_nhwc_v3_f16c": (
-        _c_int, [_c_vp, _c_vp] + [_c_int] * 7 + [_c_vp, _c_int] + [_c_vp, _c_int, _c_int] * 2 + [_c_int, _c_vp, _c_vp]
-        + [_c_int] * 5 + [_c_int, _c_int, _c_int, _c_vp, _c_int, _c_int, _c_vp, _c_sz, _c_vp, _c_vp, _c_int, _c_int] + [_c_vp] * 6
-        + [_c_vp, _c_int] + [_c_vp, _c_vp]),
-    "sige_hip_scatter_gather_conv_scatter_nhwc_v3_f16c": (
-        _c_int, [_c_vp, _c_vp, _c_int] + [_c_int] * 8 + [_c_vp, _c_int, _c_vp] + [_c_vp, _c_int, _c_int] * 2 + [_c_int, _c_vp, _c_vp]
-        + [_c_int] * 3 + [_c_int, _c_int, _c_vp, _c_int] + [_c_vp, _c_vp] + [_c_int] * 5 + [_c_vp] * 6 + [_c_vp, _c_int] + [_c_vp, _c_vp]),
     "sige_hip_add_layer_norm_tokens_f32": (_c_int, [_c_vp] * 5 + [ctypes.c_int64, _c_int, ctypes.c_float, _c_vp, _c_vp, _c_vp]),
     "sige_hip_geglu_tokens_f32": (_c_int, [_c_vp, ctypes.c_int64, _c_int, _c_vp, _c_vp]),
     "sige_hip_add_bias_tokens_f32": (_c_int, [_c_vp, _c_vp, _c_vp, ctypes.c_int64, _c_int, _c_vp, _c_vp]),
@@ -902,17 +857,18 @@ def conv_pack_weights(weight: torch.Tensor, R: int, S: int, stride: Tuple[int, i
     return packed
 
 
-def _conv_fn(name: str, packed):
-    """The fp32, the f16-compute or the split-fp16 entry point, according to how `packed` was laid out."""
-    return getattr(lib(), name + {"f16": "_f16c", "f16x3": "_f16x3"}.get(getattr(packed, "compute", "f32"), "_f32"))
-
-
 # ---- dense layers on the fp16 matrix cores (csrc/conv_wide.hpp) ----
 COMPUTE_DTYPES = ("f32", "f16", "f16x3")
 
 
-_COMPUTE_ID = {"f32": 0, "f16": 1, "f16x3": 2}  # the `compute` argument of the "_c16" entry points (tile kernels: how `packed` is laid out)
+_COMPUTE_ID = {"f32": 0, "f16": 1, "f16x3": 2}  # the `compute` argument of the channels-last tile-conv entry points
 _WIDE_PREC = {"f16": 0, "f16x3": 1, "f32": 2}  # the `prec` argument of sige_hip_wide_conv_* (conv_wide.hpp: WIDE_F16 / _X3 / _F32)
+
+
+def _compute_id(packed) -> int:
+    """How `packed` was laid out = the arithmetic its conv runs in; evaluated once per tile-conv call (tools/probe/prefetch_probe.py
+    hooks this to see the weights of a forward in call order)."""
+    return _COMPUTE_ID[getattr(packed, "compute", "f32")]
 
 
 def wide_conv_supported(C1: int, C2: int, Cout: int, kernel: Tuple[int, int]) -> bool:
@@ -1441,7 +1397,7 @@ def _req_cl(t: torch.Tensor, name: str) -> torch.Tensor:
 
 def _req_cl_cache(t: torch.Tensor, name: str) -> torch.Tensor:
     """A CACHED tensor: channels-last, fp32 or -- SIGEModel.set_cache_dtype("f16") -- fp16 storage (read through the "_f16" /
-    "_c16" entry points of include/sige_hip.h; widened exactly when read)."""
+    y_f16 / residual_f16 arguments of include/sige_hip.h; widened exactly when read)."""
     if t.dtype == torch.float16:
         if not t.is_cuda or t.dim() != 4:
             raise NotImplementedError("sige_amd.hip: `%s` (fp16 cache) must be a 4-D GPU tensor" % name)
@@ -1509,28 +1465,25 @@ def block_conv_cl(x, packed, bias, Cout: int, kernel: Tuple[int, int], stride: T
     x = _req_cl(x, "x")
     T, Cin, R, S = x.shape
     Ro, So = (R - kernel[0]) // stride[0] + 1, (S - kernel[1]) // stride[1] + 1
-    if key is not None and key[0].shape[0] * key[1] == T and T > 0:
+    keyed = key is not None and key[0].shape[0] * key[1] == T and T > 0
+    if keyed:  # (the tile count is the index list's: a launch plan follows it)
         idx, B = key
         out = _empty_tiles_cl(B, idx, Cout, Ro, So, x.device)
-        status = lib().sige_hip_block_conv_nhwc_keyed(_COMPUTE_ID[getattr(packed, "compute", "f32")], x.data_ptr(), idx.data_ptr(), B,
-                                                      idx.shape[0], Cin, R, S, packed.data_ptr(), _p(bias_keep), Cout,
-                                                      kernel[0], kernel[1], stride[0], stride[1], out.data_ptr(), _stream(x))
-        if status == UNSUPPORTED:
-            return None
-        _check(status, "block_conv_cl")
-        return tag_tiles(out, idx, B)
-    out = _empty_cl((T, Cout, Ro, So), x.device)
-    status = _conv_fn("sige_hip_block_conv_nhwc", packed)(x.data_ptr(), T, Cin, R, S, packed.data_ptr(), _p(bias_keep), Cout,
-                                                kernel[0], kernel[1], stride[0], stride[1], out.data_ptr(), _stream(x))
+        fn, tiles = lib().sige_hip_block_conv_nhwc_keyed, (idx.data_ptr(), B, idx.shape[0])
+    else:
+        out = _empty_cl((T, Cout, Ro, So), x.device)
+        fn, tiles = lib().sige_hip_block_conv_nhwc, (T,)
+    status = fn(_compute_id(packed), x.data_ptr(), *tiles, Cin, R, S, packed.data_ptr(), _p(bias_keep), Cout,
+                kernel[0], kernel[1], stride[0], stride[1], out.data_ptr(), _stream(x))
     if status == UNSUPPORTED:
         return None
     _check(status, "block_conv_cl")
-    return out
+    return tag_tiles(out, idx, B) if keyed else out
 
 
 # ---- tile conv v3 (csrc/conv_tile3.hpp): routing --------------------------------------------------------------------------
 # The two calls a sparse forward makes for its 3x3 convs -- gather -> conv and scatter_gather -> conv -> scatter -- go through
-# the ROUTING entry points (sige_hip_*_v3_f32): the same arguments plus the weights in the v3 layout and TILE3_MIN_BLOCKS; a launch
+# ROUTING entry points: beside `packed` they take the weights in the v3 layout and TILE3_MIN_BLOCKS; a launch
 # whose v3 grid -- tile pairs x 64-channel output blocks -- has at least that many workgroups, and that is not about to share its
 # launch with a held 1x1 shortcut (conv_pair()), runs on the v3 kernel, every other launch on conv_mfma.hpp as before.  The
 # decision is taken in C from the tile count, so a launch plan replaying the call under another mask routes like the module path.
@@ -1541,10 +1494,10 @@ def block_conv_cl(x, packed, bias, Cout: int, kernel: Tuple[int, int], stride: T
 # (affine + SiLU staging: the activation is computed once per 64 output channels instead of once per 32), 4 % (scatter_gather)
 # and 0 % (raw gather): the forward moves by 1 % at 15 %, 2 % at 20 %, nothing at 1.2 % and 5 % (no launch reaches the threshold).
 # TILE3_MIN_BLOCKS = None switches the router off (no v3 weights are packed); TILE3 = False does the same per call (tests, A/B);
-# TILE3 = True sends every eligible call to sige_hip_tile_conv3_nhwc_f32 directly, whatever its grid (tests, tools/tile3_bench.py).
+# TILE3 = True sends every eligible call to sige_hip_tile_conv3_nhwc directly, whatever its grid (tests, tools/tile3_bench.py).
 TILE3 = None
 TILE3_MIN_BLOCKS = 512
-# fp16 operands (round 6; conv_tile3.hpp Tile3Geo<2, WIDE_F16>): the same routing for compute dtype "f16" (sige_hip_*_v3_f16c)
+# fp16 operands (round 6; conv_tile3.hpp Tile3Geo<2, WIDE_F16>): the same routing for compute dtype "f16"
 TILE3_MIN_BLOCKS_F16 = 256
 
 
@@ -1574,6 +1527,11 @@ def _tile3_packed(packed):
     return t3
 
 
+def _tile3_args(packed, t3r):
+    """(packed_tile3, min_blocks) of a routing entry point; (None, 0) = no routing."""
+    return (None, 0) if t3r is None else (t3r.data_ptr(), _tile3_min_blocks(packed))
+
+
 def _tile3_route(packed, T: int, C1: int, C2: int, Cout: int, kernel, stride, block):
     """TILE3 = True only: the v3 weights if this call can run on the v3 kernel at all (the forced form of the tests and tools)."""
     if TILE3 is not True:
@@ -1584,9 +1542,9 @@ def _tile3_route(packed, T: int, C1: int, C2: int, Cout: int, kernel, stride, bl
 
 
 def tile_conv3_cl(source: int, x, x2, B, C1, C2, H, W, up, idx, smap, rx_sx, scale, shift, activationName, t3, bias, Cout,
-                  full, residual, bargs, out_affine, targs, out, f16: bool = False):
-    """One launch of sige_hip_tile_conv3_nhwc_f32 / _f16c (include/sige_hip.h); `full` = None (tiles) | (offH, offW, Ho, Wo).
-    UNSUPPORTED -> None."""
+                  full, residual, bargs, out_affine, targs, out, compute: int = 0):
+    """One launch of sige_hip_tile_conv3_nhwc (include/sige_hip.h); `full` = None (tiles) | (offH, offW, Ho, Wo); `compute`: the
+    id of the packing `t3` was made from (x2 / residual may be fp16-stored caches under compute 1).  UNSUPPORTED -> None."""
     bias_keep = _vec(bias, "bias")
     sc = sh = None
     affB = 0
@@ -1604,20 +1562,13 @@ def tile_conv3_cl(source: int, x, x2, B, C1, C2, H, W, up, idx, smap, rx_sx, sca
     else:
         oargs = (None, None, 0)
     fargs = (0, 0, 0, 0, 0) if full is None else (1, *full)
-    if f16:  # (fp16 operands; x2 / residual may be fp16-stored caches)
-        y16 = int(x2 is not None and x2.dtype == torch.float16)
-        r16 = int(residual is not None and residual.dtype == torch.float16)
-        status = lib().sige_hip_tile_conv3_nhwc_f16c(
-            source, x.data_ptr(), None if x2 is None else x2.data_ptr(), y16, B, C1, C2, H, W, int(bool(up)), idx.data_ptr(), idx.shape[0],
-            None if smap is None else smap.data_ptr(), rx_sx[0], rx_sx[1], sc, sh, affB, _act(activationName),
-            t3.data_ptr(), _p(bias_keep), Cout, *fargs, None if residual is None else residual.data_ptr(), r16, *bargs, *oargs, *targs,
-            out.data_ptr(), _stream(x))
-    else:
-        status = lib().sige_hip_tile_conv3_nhwc_f32(
-            source, x.data_ptr(), None if x2 is None else x2.data_ptr(), B, C1, C2, H, W, int(bool(up)), idx.data_ptr(), idx.shape[0],
-            None if smap is None else smap.data_ptr(), rx_sx[0], rx_sx[1], sc, sh, affB, _act(activationName),
-            t3.data_ptr(), _p(bias_keep), Cout, *fargs, None if residual is None else residual.data_ptr(), *bargs, *oargs, *targs,
-            out.data_ptr(), _stream(x))
+    y16 = int(x2 is not None and x2.dtype == torch.float16)
+    r16 = int(residual is not None and residual.dtype == torch.float16)
+    status = lib().sige_hip_tile_conv3_nhwc(
+        compute, source, x.data_ptr(), None if x2 is None else x2.data_ptr(), y16, B, C1, C2, H, W, int(bool(up)), idx.data_ptr(), idx.shape[0],
+        None if smap is None else smap.data_ptr(), rx_sx[0], rx_sx[1], sc, sh, affB, _act(activationName),
+        t3.data_ptr(), _p(bias_keep), Cout, *fargs, None if residual is None else residual.data_ptr(), r16, *bargs, *oargs, *targs,
+        out.data_ptr(), _stream(x))
     if status == UNSUPPORTED:
         return None
     _check(status, "tile_conv3_cl")
@@ -1660,6 +1611,7 @@ def gather_conv_cl(x, x2, block: Tuple[int, int], activeIndices, scale, shift, a
             if tuple(r.shape) != tuple(out.shape):
                 raise RuntimeError("gather_conv_cl: residual %s != output %s" % (tuple(r.shape), tuple(out.shape)))
         fargs = (1, full["offset"][0], full["offset"][1], None if r is None else r.data_ptr(), Ho, Wo)
+    compute = _compute_id(packed)
     t3 = _tile3_route(packed, B * N, C1, C2, Cout, kernel, stride, block)  # (TILE3 = True: the v3 kernel, forced)
     if t3 is not None and N > 0:
         if twins and full is None:
@@ -1667,8 +1619,7 @@ def gather_conv_cl(x, x2, block: Tuple[int, int], activeIndices, scale, shift, a
         targs3, twin_keep3 = _twin_args(twins if twins else None, out, Cout, "gather_conv_cl")
         got = tile_conv3_cl(1, x, x2, B, C1, C2, H, W, upsample2x, idx, None, (0, 0), scale, shift, activationName, t3, bias, Cout,
                             None if full is None else (full["offset"][0], full["offset"][1], Ho, Wo),
-                            None if full is None else r, (None, None, 0, 0, 0, 0, 0), out_affine, targs3, out,
-                            f16=getattr(packed, "compute", "f32") == "f16")
+                            None if full is None else r, (None, None, 0, 0, 0, 0, 0), out_affine, targs3, out, compute=compute)
         if got is not None:
             return got if full is not None else tag_tiles(got, idx, B)
     # deep-K convs over a handful of tiles: workspace for the cross-workgroup K split
@@ -1702,19 +1653,12 @@ def gather_conv_cl(x, x2, block: Tuple[int, int], activeIndices, scale, shift, a
         raise RuntimeError("gather_conv_cl: twins need a full-tensor destination")
     targs, twin_keep = _twin_args(twins if twins else None, out, Cout, "gather_conv_cl")
     fargs = fargs + (int(bool(upsample2x)), *targs)
-    compute = getattr(packed, "compute", "f32")
-    t3r = _tile3_packed(packed) if (TILE3 is None and compute in ("f32", "f16")) else None
-    if t3r is not None:  # (the routing entry point: conv_mfma.hpp or the v3 kernel, decided in C from N)
-        fn = lib().sige_hip_gather_conv_nhwc_v3_f16c if compute == "f16" else lib().sige_hip_gather_conv_nhwc_v3_f32
-        status = fn(
-            x.data_ptr(), None if x2 is None else x2.data_ptr(), B, C1, C2, H, W, block[0], block[1], idx.data_ptr(), N,
-            *sa, *ta, _act(activationName), packed.data_ptr(), _p(bias_keep), Cout, kernel[0], kernel[1],
-            stride[0], stride[1], *fargs, t3r.data_ptr(), _tile3_min_blocks(packed), out.data_ptr(), _stream(x))
-    else:
-        status = _conv_fn("sige_hip_gather_conv_nhwc", packed)(
-            x.data_ptr(), None if x2 is None else x2.data_ptr(), B, C1, C2, H, W, block[0], block[1], idx.data_ptr(), N,
-            *sa, *ta, _act(activationName), packed.data_ptr(), _p(bias_keep), Cout, kernel[0], kernel[1],
-            stride[0], stride[1], *fargs, out.data_ptr(), _stream(x))
+    # with v3 weights beside `packed` the entry point routes: conv_mfma.hpp or the v3 kernel, decided in C from N
+    t3r = _tile3_packed(packed) if (TILE3 is None and compute in (0, 1)) else None
+    status = lib().sige_hip_gather_conv_nhwc(
+        compute, x.data_ptr(), None if x2 is None else x2.data_ptr(), B, C1, C2, H, W, block[0], block[1], idx.data_ptr(), N,
+        *sa, *ta, _act(activationName), packed.data_ptr(), _p(bias_keep), Cout, kernel[0], kernel[1],
+        stride[0], stride[1], *fargs, *_tile3_args(packed, t3r), out.data_ptr(), _stream(x))
     if status == UNSUPPORTED:
         return None
     _check(status, "gather_conv_cl")
@@ -1735,13 +1679,10 @@ def scatter_gather_conv_cl(x, y, block: Tuple[int, int], activeIndices, scatterM
     N = idx.shape[0]
     Ro, So = (block[0] - kernel[0]) // stride[0] + 1, (block[1] - kernel[1]) // stride[1] + 1
     out = _empty_tiles_cl(B, idx, Cout, Ro, So, y.device)
-    args = (x.data_ptr(), y.data_ptr(), B, C, H, W, x.shape[2], x.shape[3], block[0], block[1], idx.data_ptr(), N,
-            smap.data_ptr(), *sa, *ta, _act(activationName), packed.data_ptr(), _p(bias_keep), Cout, kernel[0], kernel[1],
-            stride[0], stride[1], out.data_ptr(), _stream(y))
-    if y.dtype == torch.float16:  # (fp16-stored cache)
-        status = lib().sige_hip_scatter_gather_conv_nhwc_c16(_COMPUTE_ID[getattr(packed, "compute", "f32")], *args)
-    else:
-        status = _conv_fn("sige_hip_scatter_gather_conv_nhwc", packed)(*args)
+    status = lib().sige_hip_scatter_gather_conv_nhwc(
+        _compute_id(packed), x.data_ptr(), y.data_ptr(), int(y.dtype == torch.float16), B, C, H, W, x.shape[2], x.shape[3],
+        block[0], block[1], idx.data_ptr(), N, smap.data_ptr(), *sa, *ta, _act(activationName), packed.data_ptr(), _p(bias_keep),
+        Cout, kernel[0], kernel[1], stride[0], stride[1], out.data_ptr(), _stream(y))
     if status == UNSUPPORTED:
         return None
     _check(status, "scatter_gather_conv_cl")
@@ -1775,31 +1716,22 @@ def scatter_gather_conv_scatter_cl(x, y, block, activeIndices, scatterMap, scale
     else:
         bargs = (None, None, 0, 0, 0, 0, 0)
     targs, twin_keep = _twin_args(twins if twins else None, out, Cout, "scatter_gather_conv_scatter_cl")
+    compute = _compute_id(packed)
     t3 = _tile3_route(packed, B * idx.shape[0], C, 0, Cout, kernel, (1, 1), block)
-    f16c = getattr(packed, "compute", "f32") == "f16"
+    f16c = compute == 1
     if (t3 is not None and idx.shape[0] > 0 and (f16c or (y.dtype == torch.float32 and (r is None or r.dtype == torch.float32)))
             and ((scale is None and shift is None and activationName == "identity") or (scale is not None and shift is not None))):
         got = tile_conv3_cl(2, x, y, B, C, 0, H, W, False, idx, smap, (x.shape[2], x.shape[3]), scale, shift, activationName, t3, bias, Cout,
-                            (offset[0], offset[1], H, W), r, bargs, None, targs, out, f16=f16c)
+                            (offset[0], offset[1], H, W), r, bargs, None, targs, out, compute=compute)
         if got is not None:
             return got
-    head = (x.data_ptr(), y.data_ptr(), B, C, H, W, x.shape[2], x.shape[3], block[0], block[1], idx.data_ptr(), idx.shape[0],
-            smap.data_ptr(), *sa, *ta, _act(activationName), packed.data_ptr(), _p(bias_keep), Cout, kernel[0], kernel[1],
-            offset[0], offset[1], None if r is None else r.data_ptr())
-    t3r = _tile3_packed(packed) if (TILE3 is None and ((getattr(packed, "compute", "f32") == "f32" and y.dtype == torch.float32) or f16c)) else None
-    if f16c and t3r is not None:  # (fp16 operands, fp32- or fp16-stored caches: routed in C like the fp32 pair)
-        status = lib().sige_hip_scatter_gather_conv_scatter_nhwc_v3_f16c(
-            head[0], head[1], int(y.dtype == torch.float16), *head[2:], int(r is not None and r.dtype == torch.float16), *bargs, *targs,
-            t3r.data_ptr(), _tile3_min_blocks(packed), out.data_ptr(), _stream(y))
-    elif y.dtype == torch.float16:  # (fp16-stored caches)
-        status = lib().sige_hip_scatter_gather_conv_scatter_nhwc_c16(
-            _COMPUTE_ID[getattr(packed, "compute", "f32")], *head, int(r is not None and r.dtype == torch.float16), *bargs, *targs,
-            out.data_ptr(), _stream(y))
-    elif t3r is not None:  # (the routing entry point: conv_mfma.hpp or the v3 kernel, decided in C from N)
-        status = lib().sige_hip_scatter_gather_conv_scatter_nhwc_v3_f32(*head, *bargs, *targs, t3r.data_ptr(), _tile3_min_blocks(packed),
-                                                                        out.data_ptr(), _stream(y))
-    else:
-        status = _conv_fn("sige_hip_scatter_gather_conv_scatter_nhwc", packed)(*head, *bargs, *targs, out.data_ptr(), _stream(y))
+    # routed in C like gather_conv_cl: fp16 operands over fp32- or fp16-stored caches, fp32 compute only over an fp32 cache
+    t3r = _tile3_packed(packed) if (TILE3 is None and ((compute == 0 and y.dtype == torch.float32) or f16c)) else None
+    status = lib().sige_hip_scatter_gather_conv_scatter_nhwc(
+        compute, x.data_ptr(), y.data_ptr(), int(y.dtype == torch.float16), B, C, H, W, x.shape[2], x.shape[3], block[0], block[1],
+        idx.data_ptr(), idx.shape[0], smap.data_ptr(), *sa, *ta, _act(activationName), packed.data_ptr(), _p(bias_keep), Cout,
+        kernel[0], kernel[1], offset[0], offset[1], None if r is None else r.data_ptr(), int(r is not None and r.dtype == torch.float16),
+        *bargs, *targs, *_tile3_args(packed, t3r), out.data_ptr(), _stream(y))
     if status == UNSUPPORTED:
         return None
     _check(status, "scatter_gather_conv_scatter_cl")

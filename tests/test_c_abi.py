@@ -105,7 +105,7 @@ def test_preload_without_a_gpu(lib):
 def test_version_and_error_strings(lib):
     lib.sige_hip_version.restype = ctypes.c_int
     lib.sige_hip_error_string.restype = ctypes.c_char_p
-    assert lib.sige_hip_version() == 309
+    assert lib.sige_hip_version() == 310
     assert lib.sige_hip_error_string(0) == b"ok"
     assert b"invalid" in lib.sige_hip_error_string(-1)
 
@@ -230,3 +230,76 @@ def test_plan_marks_count_arguments_on_unknown_pointers_without_a_gpu():
             assert L.sige_hip_plan_unbound(p) == 0 and L.sige_hip_plan_shape_bound(p) == 0
         finally:
             assert L.sige_hip_plan_destroy(p) == 0
+
+
+def _tile_conv_calls(L):
+    """{entry point: call(idx_ptr, N, table1_ptr)} over the raw ctypes functions (no device guard) of the channels-last tile convs whose
+    plan hook carries a count: valid geometry -- C1 = Cout = 64 on 16x16, 6x6 blocks, 3x3 / stride 1, B = 1, compute 0 -- and every
+    tensor null, so nothing can reach a device.  table1_ptr: the entry points with a second count (N1 under table1) only."""
+    nul3, nul6 = (None, 0, 0), (None,) * 6
+    return {
+        "sige_hip_block_conv_nhwc_keyed": lambda idx, N, t1=None: L.sige_hip_block_conv_nhwc_keyed.fn(
+            0, None, idx, 1, N, 64, 6, 6, None, None, 64, 3, 3, 1, 1, None, None),
+        "sige_hip_gather_conv_nhwc": lambda idx, N, t1=None: L.sige_hip_gather_conv_nhwc.fn(
+            0, None, None, 1, 64, 0, 16, 16, 6, 6, idx, N, *nul3, *nul3, 0, None, None, 64, 3, 3, 1, 1,
+            0, 0, 0, None, 0, 0, None, 0, None, None, 0, 0, *nul6, None, 0, None, None),
+        "sige_hip_scatter_gather_conv_nhwc": lambda idx, N, t1=None: L.sige_hip_scatter_gather_conv_nhwc.fn(
+            0, None, None, 0, 1, 64, 16, 16, 4, 4, 6, 6, idx, N, None, *nul3, *nul3, 0, None, None, 64, 3, 3, 1, 1, None, None),
+        "sige_hip_scatter_gather_conv_scatter_nhwc": lambda idx, N, t1=None: L.sige_hip_scatter_gather_conv_scatter_nhwc.fn(
+            0, None, None, 0, 1, 64, 16, 16, 4, 4, 6, 6, idx, N, None, *nul3, *nul3, 0, None, None, 64, 3, 3,
+            1, 1, None, 0, None, t1, 0, 0, 0, 0, 0, *nul6, None, 0, None, None),
+        "sige_hip_tile_conv3_nhwc": lambda idx, N, t1=None: L.sige_hip_tile_conv3_nhwc.fn(
+            0, 1, None, None, 0, 1, 64, 0, 16, 16, 0, idx, N, None, 0, 0, None, None, 0, 0, None, None, 64,
+            0, 0, 0, 0, 0, None, 0, None, t1, 0, 0, 0, 0, 0, None, None, 0, *nul6, None, None),
+    }
+
+
+def test_tile_conv_hooks_count_the_right_arguments_without_a_gpu():
+    """The (index list, count) positions of every channels-last tile-conv hook (plan.hpp: CountOf<ip, np>), pinned before anything
+    runs on a GPU: a mis-counted position only shows there as a plan replaying stale counts.  These entry points answer
+    B * N == 0 with OK before they look at a pointer and a null tensor with EINVAL after, so the status of a replay tells which
+    count the call saw: the slot's (np right, ip right), the recorded one (ip wrong) or the slot's in another argument (np wrong)."""
+    from sige_amd import hip
+
+    L = hip.lib()
+    EINVAL, IDX, TABLE1 = -1, 0x3000, 0x5000
+    for name, call in _tile_conv_calls(L).items():
+        for recorded in (5, 0):
+            p = L.sige_hip_plan_create()
+            try:
+                assert L.sige_hip_plan_new_slots(p, 1) == 0 and L.sige_hip_plan_bind_ptr(p, IDX, 0) == 0
+                assert L.sige_hip_plan_begin(p, 1, 0) == 0
+                assert call(IDX, recorded) == (EINVAL if recorded else 0), name     # (x is null; no tiles: nothing to do)
+                assert L.sige_hip_plan_end(p) == 0 and L.sige_hip_plan_calls(p, 1) == 1
+                assert L.sige_hip_plan_unbound(p) == 0 and L.sige_hip_plan_shape_bound(p) == 0, name
+                assert L.sige_hip_plan_set_slot(p, 0, 5) == 0 and L.sige_hip_plan_run(p, 1, None) == EINVAL, (name, recorded)
+                if recorded:
+                    assert L.sige_hip_plan_set_slot(p, 0, 0) == 0 and L.sige_hip_plan_run(p, 1, None) == 0, name
+            finally:
+                assert L.sige_hip_plan_destroy(p) == 0
+        # the index list not bound: its count cannot follow a mask
+        p = L.sige_hip_plan_create()
+        try:
+            assert L.sige_hip_plan_begin(p, 1, 0) == 0 and call(IDX, 5) == EINVAL and L.sige_hip_plan_end(p) == 0
+            assert L.sige_hip_plan_unbound(p) == 1 and L.sige_hip_plan_shape_bound(p) == 1, name
+        finally:
+            assert L.sige_hip_plan_destroy(p) == 0
+        # the second count: N1 hangs on table1
+        if name in ("sige_hip_scatter_gather_conv_scatter_nhwc", "sige_hip_tile_conv3_nhwc"):
+            for bound in (False, True):
+                p = L.sige_hip_plan_create()
+                try:
+                    assert L.sige_hip_plan_new_slots(p, 2) == 0 and L.sige_hip_plan_bind_ptr(p, IDX, 0) == 0
+                    assert not bound or L.sige_hip_plan_bind_ptr(p, TABLE1, 1) == 0
+                    assert L.sige_hip_plan_begin(p, 1, 0) == 0 and call(IDX, 5, TABLE1) == EINVAL and L.sige_hip_plan_end(p) == 0
+                    assert L.sige_hip_plan_unbound(p) == (0 if bound else 1), (name, bound)
+                finally:
+                    assert L.sige_hip_plan_destroy(p) == 0
+    # the conv over a slab without an index list: a plan that holds it only replays under the recorded tile count
+    p = L.sige_hip_plan_create()
+    try:
+        assert L.sige_hip_plan_begin(p, 1, 0) == 0
+        assert L.sige_hip_block_conv_nhwc.fn(0, None, 5, 64, 6, 6, None, None, 64, 3, 3, 1, 1, None, None) == EINVAL
+        assert L.sige_hip_plan_end(p) == 0 and L.sige_hip_plan_calls(p, 1) == 1 and L.sige_hip_plan_shape_bound(p) == 1
+    finally:
+        assert L.sige_hip_plan_destroy(p) == 0

@@ -163,7 +163,7 @@ def test_tile_conv3_f16_scatter_gather_to_full(hip, cache_f16):
 
 
 def test_tile_conv3_f16_router_decides_from_the_tile_count(hip):
-    """The routing entry points (sige_hip_gather_conv_nhwc_v3_f16c): below TILE3_MIN_BLOCKS_F16 workgroups the conv_mfma.hpp launch,
+    """The routing entry points (sige_hip_gather_conv_nhwc, compute = 1): below TILE3_MIN_BLOCKS_F16 workgroups the conv_mfma.hpp launch,
     bit for bit; from the threshold on the v3 kernel, bit for bit the forced v3 launch.  A SPARSE tile list (fewer tiles than 4 x 4
     cells) is routed from 128 workgroups on whatever the general threshold (block_conv.hip kTile3F16SparseMin); a dense one is not."""
     torch.manual_seed(5)
@@ -219,6 +219,61 @@ def test_tile_conv3_f16_router_decides_from_the_tile_count(hip):
     finally:
         hip.TILE3, hip.TILE3_MIN_BLOCKS_F16 = None, keep
     assert any(distinct), "forced v3 and conv_mfma.hpp gave the same bits in every case: the routing checks above prove nothing"
+
+
+@pytest.mark.selfcheck
+def test_routing_entry_points_ignore_v3_weights_the_v3_kernel_has_no_form_for(hip):
+    """One entry point per operation can be asked for what no entry point offered before: v3 weights beside split-fp16 operands
+    (compute 2), or beside exact fp32 (compute 0) over an fp16-stored cache.  The v3 kernel has neither form, so the call must not
+    route, whatever `min_blocks` says: OK, and bit for bit the same call with packed_tile3 = NULL.  Raw entry points (the Python
+    wrappers never hand v3 weights over in these cases)."""
+    torch.manual_seed(11)
+    L, C, res = hip.lib(), 64, 16
+    from sige_amd.utils import reduce_mask
+
+    mask = torch.zeros(res, res, dtype=torch.bool)
+    mask[5:9, 5:9] = True
+    idx = reduce_mask(mask.to(DEV), 6, 4, 1)
+    N = idx.shape[0]
+    assert 3 <= N <= 5
+    smap = hip.get_scatter_map(res, res, 6, 6, 3, 3, 1, 1, 1, 1, idx)
+    w = torch.randn(C, C, 3, 3, device=DEV) / (3 * C ** 0.5)
+    bias = torch.randn(C, device=DEV)
+    t3 = hip.wide_conv_pack_weights(w, "f32")  # (the v3 layout a launch of >= 1 workgroup would be routed to)
+    assert t3 is not None and L.sige_hip_tile_conv3_supported(C, 0, C)
+    x = _cl(torch.randn(1, C, res, res, device=DEV))
+    y = _cl(torch.randn(1, C, res, res, device=DEV))
+    tiles = _cl(torch.randn(N, C, 4, 4, device=DEV))
+    keep = _cl(torch.randn(1, C, res, res, device=DEV))
+    nul3, nul6 = (None, 0, 0), (None,) * 6
+
+    def gather(compute, packed, route):
+        out = _cl(torch.full((N, C, 4, 4), float("nan"), device=DEV))
+        status = L.sige_hip_gather_conv_nhwc(
+            compute, x.data_ptr(), None, 1, C, 0, res, res, 6, 6, idx.data_ptr(), N, *nul3, *nul3, 0, packed.data_ptr(), bias.data_ptr(),
+            C, 3, 3, 1, 1, 0, 0, 0, None, 0, 0, None, 0, None, None, 0, 0, *nul6, *((t3.data_ptr(), 1) if route else (None, 0)),
+            out.data_ptr(), hip._stream(x))
+        assert status == 0 and not bool(torch.isnan(out).any()), status   # (OK, and every tile written)
+        return out
+
+    def sgs(compute, packed, cache, route):
+        out = keep.clone(memory_format=torch.preserve_format)
+        status = L.sige_hip_scatter_gather_conv_scatter_nhwc(
+            compute, tiles.data_ptr(), cache.data_ptr(), int(cache.dtype == torch.float16), 1, C, res, res, 4, 4, 6, 6, idx.data_ptr(), N,
+            smap.data_ptr(), *nul3, *nul3, 0, packed.data_ptr(), bias.data_ptr(), C, 3, 3, 1, 1, None, 0, None, None, 0, 0, 0, 0, 0,
+            *nul6, *((t3.data_ptr(), 1) if route else (None, 0)), out.data_ptr(), hip._stream(cache))
+        assert status == 0 and not torch.equal(out, keep), status         # (OK, and the tiles written into the buffer)
+        return out
+
+    px3, pf32 = hip.conv_pack_weights(w, 6, 6, (1, 1), "f16x3"), hip.conv_pack_weights(w, 6, 6, (1, 1), "f32")
+    assert px3.compute == "f16x3" and pf32.compute == "f32"
+    y16 = _cl(y.half())
+    for name, call in (("gather, compute 2", lambda r: gather(2, px3, r)),
+                       ("scatter_gather -> conv -> scatter, compute 2", lambda r: sgs(2, px3, y, r)),
+                       ("scatter_gather -> conv -> scatter, compute 0 over an fp16-stored y", lambda r: sgs(0, pf32, y16, r))):
+        assert torch.equal(call(True), call(False)), name
+    # the premise: the same weights and threshold DO route where the v3 kernel has the form (exact fp32 over fp32 caches)
+    assert not torch.equal(sgs(0, pf32, y, True), sgs(0, pf32, y, False)) or not torch.equal(gather(0, pf32, True), gather(0, pf32, False))
 
 
 @pytest.mark.parametrize("compute", ["f32", "f16"])

@@ -35,7 +35,7 @@ def main():
     x0, noise = (t.to(dev).contiguous(memory_format=torch.channels_last) for t in bench.make_inputs())
     t = torch.zeros(1, device=dev)
     res = {"edit_ratio": args.ratio, "rows": {}}
-    orig_conv_fn = hip._conv_fn
+    orig_compute_id = hip._compute_id
     with torch.no_grad():
         model.set_mode("full")
         model(x0, t)
@@ -48,13 +48,13 @@ def main():
         # the weights of one forward, in call order
         order = []
 
-        def logging_conv_fn(name, packed):
+        def logging_compute_id(packed):  # (hip._compute_id: once per tile-conv call)
             order.append(packed)
-            return orig_conv_fn(name, packed)
+            return orig_compute_id(packed)
 
-        hip._conv_fn = logging_conv_fn
+        hip._compute_id = logging_compute_id
         model(x1, t)
-        hip._conv_fn = orig_conv_fn
+        hip._compute_id = orig_compute_id
         res["conv_calls"] = len(order)
         res["weight_MB"] = round(sum(p.numel() * 4 for p in order) / 1e6, 1)
 
@@ -78,7 +78,7 @@ def main():
         for dist, stride in ((1, 32), (2, 32), (3, 32), (2, 16), (4, 32)):
             state = {"i": 0}
 
-            def prefetching_conv_fn(name, packed):
+            def prefetching_compute_id(packed):
                 i = state["i"]
                 state["i"] += 1
                 j = i + dist
@@ -90,15 +90,15 @@ def main():
                     with torch.cuda.stream(side):
                         w = order[j].as_subclass(torch.Tensor).view(-1)
                         sink[j] = w[::stride].sum()  # one element per `stride` floats: every 128-byte (64-byte) line is fetched
-                return orig_conv_fn(name, packed)
+                return orig_compute_id(packed)
 
             def fwd():
                 state["i"] = 0
-                hip._conv_fn = prefetching_conv_fn
+                hip._compute_id = prefetching_compute_id
                 try:
                     out = model(x1, t)
                 finally:
-                    hip._conv_fn = orig_conv_fn
+                    hip._compute_id = orig_compute_id
                 torch.cuda.current_stream().wait_stream(side)  # (join the side branch: the graph ends when both do)
                 return out
 
