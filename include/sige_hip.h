@@ -473,7 +473,28 @@ int sige_hip_scatter_with_block_residual_nhwc_f32(
         const int32_t *active_indices1, const int32_t *table1, int gH1, int gW1, int N1,
         int in_place, float *out, void *stream);
 
-/* ---- tile conv v3 (csrc/conv_tile3.hpp): the 3x3 / stride-1 stacked-block conv over 6x6 tiles with the dense-layer kernel's
+/* ---- residual blocks that resample INSIDE the block (Progressive Distillation U-Net), on the active tiles, in ONE launch ----
+ * x [B,H,W,C] channels-last; the resampled resolution Ho x Wo is H/2 x W/2 (mode DOWN: 2x2 mean) or 2H x 2W (mode UP:
+ * nearest x2); active_indices [N,2]: tile origins AT THE RESAMPLED RESOLUTION, as sige_hip_reduce_mask_i32 gives them.
+ *   tiles (DOWN only, or NULL)  [B*N,bH,bW,C] in the layout of sige_hip_gather_nhwc_f32: the mean over the 2x2 source pixels of
+ *                               SiLU(scale[c] * x + shift[c]) (scale, shift [C], both or neither; neither = raw pooling) at the
+ *                               pooled position origin + (r, s); exactly 0 outside the pooled image -- zero padding is never
+ *                               transformed.  What conv1 of the block consumes as plain, pre-activated tiles.
+ *   res (or NULL)               [B,Ho,Wo,C], persistent: the resampled RAW x (the block's shortcut), written on the cells
+ *                               (offset + origin) / stride + [0,rH) x [0,rW), clipped -- the cells the fused conv -> scatter
+ *                               epilogue writes for these tiles.  Every other cell is left as it was.
+ *   active_indices == NULL (N = 0, tiles NULL): every cell of res -- the dense levels.
+ * SIGE_HIP_EINVAL: null x with work to do, non-positive dims, a tile count without a list.  SIGE_HIP_EUNSUPPORTED: C % 4,
+ * odd H or W in DOWN, tiles in UP (the fused gather reads the half-resolution tensor: upsample2x), one of scale / shift
+ * alone, a scatter stride other than 1, pointers not 16-byte aligned, B * N or the rows of a launch > 65535, stacked edits.  B * N == 0: SIGE_HIP_OK, nothing launched. */
+enum { SIGE_HIP_RESAMPLE_DOWN = 0, SIGE_HIP_RESAMPLE_UP = 1 };
+int sige_hip_resample_tiles_nhwc_f32(const float *x, int B, int C, int H, int W, int mode,
+                                     const int32_t *active_indices, int N, int bH, int bW,
+                                     const float *scale, const float *shift, float *tiles,
+                                     int offsetH, int offsetW, int strideH, int strideW, int rH, int rW,
+                                     float *res, void *stream);
+
+/* ---- tile conv v3(csrc/conv_tile3.hpp): the 3x3 / stride-1 stacked-block conv over 6x6 tiles with the dense-layer kernel's
  * K loop -- wave-private stages (no workgroup barrier per channel chunk), 64 output channels per workgroup -- for grids that
  * fill the chip (large edits, stacked edits).  What sige_hip_gather_conv_nhwc (source 1) and
  * sige_hip_scatter_gather_conv_scatter_nhwc (source 2) route to on those grids, and the kernel's own entry point:

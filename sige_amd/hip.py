@@ -103,6 +103,8 @@ _SIGNATURES = {
         _c_int, [_c_vp] + [_c_int] * 6 + [_c_vp, _c_int] + [_c_vp, _c_int, _c_int] * 2 + [_c_int, _c_vp, _c_vp]),
     "sige_hip_scatter_gather_nhwc_f32": (
         _c_int, [_c_vp, _c_vp] + [_c_int] * 8 + [_c_vp, _c_int, _c_vp] + [_c_vp, _c_int, _c_int] * 2 + [_c_int, _c_vp, _c_vp]),
+    "sige_hip_resample_tiles_nhwc_f32": (
+        _c_int, [_c_vp] + [_c_int] * 5 + [_c_vp, _c_int, _c_int, _c_int] + [_c_vp] * 3 + [_c_int] * 6 + [_c_vp, _c_vp]),
     "sige_hip_spade_modulate_nhwc_f32": (
         _c_int, [_c_vp, _c_vp, _c_vp, _c_int, _c_int, _c_int] + [_c_vp, _c_int, _c_int] * 2 + [_c_vp, _c_vp, _c_vp, _c_int, _c_int, _c_int]
         + [_c_int] * 6 + [_c_vp, _c_int, _c_int, ctypes.c_float, _c_vp, _c_vp]),
@@ -1749,6 +1751,49 @@ def gather_cl(x, bSizeH, bSizeW, activeIndices, scale=None, shift=None, activati
     _check(fn(x.data_ptr(), B, C, H, W, bSizeH, bSizeW, idx.data_ptr(), N, *sa, *ta, _act(activationName), out.data_ptr(), _stream(x)),
            "gather_cl")
     return tag_tiles(out, idx, B)
+
+
+RESAMPLE = {"down": 0, "up": 1}  # SIGE_HIP_RESAMPLE_*
+
+
+def resample_tiles(x, mode: str, activeIndices=None, block: Optional[Tuple[int, int]] = None, scale=None, shift=None,
+                   res: Optional[torch.Tensor] = None, offset: Tuple[int, int] = (0, 0), stride: Tuple[int, int] = (1, 1),
+                   cells: Optional[Tuple[int, int]] = None):
+    """A residual block that resamples inside the block (include/sige_hip.h: sige_hip_resample_tiles_nhwc_f32), ONE launch.
+    `x` [B,C,H,W] channels-last; `mode` "down" (2x2 mean) or "up" (nearest x2); `activeIndices` [N,2] at the RESAMPLED resolution.
+      block (down only): also returns conv1's input tiles [B*N,C,bH,bW] = mean 2x2 of SiLU(scale * x + shift), zero padded
+                         (`scale` / `shift` [C] or [1,C,1,1]; neither: raw pooling) -- plain, pre-activated tiles;
+      res:               the persistent [B,C,Ho,Wo] channels-last shortcut buffer; the resampled raw `x` is written on the cells
+                         (offset + origin) / stride + [0,cells) of the active tiles only -- every other cell keeps what it held.
+    `activeIndices=None`: every cell of `res` (the dense levels).  Returns the tiles, or None when `block` is None."""
+    x = _req_cl(x, "x")
+    B, C, H, W = x.shape
+    m = RESAMPLE[mode]
+    Ho, Wo = (2 * H, 2 * W) if m else (H // 2, W // 2)
+    idx = None if activeIndices is None else _req(activeIndices, torch.int32, "activeIndices", 2)
+    N = 0 if idx is None else idx.shape[0]
+    sc = None if scale is None else _req(scale.reshape(-1), torch.float32, "scale", 1)
+    sh = None if shift is None else _req(shift.reshape(-1), torch.float32, "shift", 1)
+    if (sc is not None and sc.numel() != C) or (sh is not None and sh.numel() != C):
+        raise RuntimeError("sige_amd.hip.resample_tiles: one affine for the batch, `scale` / `shift` of [C]")
+    if res is not None:
+        if tuple(res.shape) != (B, C, Ho, Wo) or res.dtype != torch.float32 or not res.is_cuda or not res.is_contiguous(memory_format=CL):
+            raise RuntimeError("sige_amd.hip.resample_tiles: `res` must be a channels-last fp32 GPU tensor of shape %s" % ((B, C, Ho, Wo),))
+        if idx is not None and cells is None:
+            raise RuntimeError("sige_amd.hip.resample_tiles: `cells` = the output cells per tile (rH, rW)")
+    tiles = None
+    bH, bW = block if block is not None else (0, 0)
+    if block is not None:
+        if idx is None:
+            raise RuntimeError("sige_amd.hip.resample_tiles: tiles need an index list")
+        tiles = _empty_tiles_cl(B, idx, C, bH, bW, x.device)
+    if idx is not None and N == 0:
+        return None if tiles is None else tag_tiles(tiles, idx, B)
+    rH, rW = cells if cells is not None else (0, 0)
+    _check(lib().sige_hip_resample_tiles_nhwc_f32(
+        x.data_ptr(), B, C, H, W, m, _p(idx), N, bH, bW, _p(sc), _p(sh), _p(tiles),
+        offset[0], offset[1], stride[0], stride[1], rH, rW, _p(res), _stream(x)), "resample_tiles")
+    return None if tiles is None else tag_tiles(tiles, idx, B)
 
 
 def scatter_gather_cl(x, y, bSizeH, bSizeW, activeIndices, scatterMap, scale=None, shift=None,
