@@ -233,6 +233,21 @@ int sige_hip_demand_tiles_i32(const int32_t *indices, const int32_t *count, int 
                               int inH, int inW, int upsample2x, int Hp, int Wp, int tileH, int tileW,
                               int padH, int padW, int depth, int32_t *lists, int32_t *counts, void *stream);
 
+/* ---- change regions of a dense stage behind a tiled producer (not in the reference) ----
+ * A dense [Hp,Wp] stage on cached GroupNorm affines is a chain of local operators, and its input -- the persistent output of
+ * a tiled layer -- equals the original's outside S0 = the (outH x outW) output tiles that layer's Scatter writes: `indices` /
+ * `*count` (device int32, at most `capacity` rows used) are its reduce_mask list for (bH x bW) blocks, tile origin =
+ * (index + offset) / stride.  The output of the stage's k-th 3x3 conv can differ from the original's only on S_k = S0 dilated
+ * k times by one pixel (3x3 box, clamped to the image).  For k = 1 .. depth the launch writes the (tileH x tileW) output
+ * cells that intersect S_k, row-major, as index lists in reduce_mask form: lists[k-1] = cell origin - (padH, padW) (the 3x3
+ * geometry), lists[depth + k-1] = cell origin (the 1x1 geometry), each int32 [cells,2] with cells =
+ * sige_hip_demand_tiles_capacity(Hp, Wp, tileH, tileW), and counts[k-1] (device int32) = how many.  One workgroup, no host
+ * synchronisation; limits as for sige_hip_demand_tiles_i32. */
+int sige_hip_change_tiles_i32(const int32_t *indices, const int32_t *count, int capacity, int bH, int bW,
+                              int strideH, int strideW, int offsetH, int offsetW, int outH, int outW,
+                              int Hp, int Wp, int tileH, int tileW, int padH, int padW, int depth,
+                              int32_t *lists, int32_t *counts, void *stream);
+
 /* ---- stacked-block convolution : replaces the F.conv2d call of
  * SIGEConv2d.forward in sparse mode (sige/nn/base.py:88-89) ----------------
  * x [T,Cin,R,S] (*) w [Cout,Cin/groups,kH,kW] + bias -> out [T,Cout,Ro,So],

@@ -139,13 +139,54 @@ __global__ __launch_bounds__(kMPThreads) void mask_pyramid_kernel(
 // it), keeps the pixel set in LDS and, per depth, compacts the (oH x oW) cells that intersect it in row-major order.
 constexpr int kDTThreads = 1024, kDTMaxPix = 16384, kDTMaxCells = 4096;
 
+// the (oH x oW) cells that intersect the pixel set `m`, compacted in row-major order into the list of either geometry
+// (cell origin - pad: the 3x3 form; cell origin: the 1x1 form); *n_out = how many.  Ends behind a barrier.
+__device__ __forceinline__ void dt_compact(const uint8_t *m, uint8_t *s_flag, int Hp, int Wp, int oH, int oW, int padH, int padW,
+                                           int32_t *__restrict__ main_list, int32_t *__restrict__ flat_list, int32_t *__restrict__ n_out) {
+    const int tid = threadIdx.x;
+    const int gh = (Hp + oH - 1) / oH, gw = (Wp + oW - 1) / oW, ncell = gh * gw;
+    for (int c = tid; c < ncell; c += kDTThreads) {
+        const int y0 = (c / gw) * oH, x0 = (c % gw) * oW;
+        const int y1 = y0 + oH < Hp ? y0 + oH : Hp, x1 = x0 + oW < Wp ? x0 + oW : Wp;
+        uint8_t any = 0;
+        for (int y = y0; y < y1; ++y)
+            for (int x = x0; x < x1; ++x) any |= m[y * Wp + x];
+        s_flag[c] = any;
+    }
+    __syncthreads();
+    for (int c = tid; c < ncell; c += kDTThreads) {
+        if (!s_flag[c] && c != ncell - 1) continue;
+        int rank = 0;
+        for (int j = 0; j < c; ++j) rank += s_flag[j];
+        if (s_flag[c]) {
+            const int y0 = (c / gw) * oH, x0 = (c % gw) * oW;
+            main_list[2 * rank] = y0 - padH; main_list[2 * rank + 1] = x0 - padW;
+            flat_list[2 * rank] = y0; flat_list[2 * rank + 1] = x0;
+        }
+        if (c == ncell - 1) *n_out = rank + s_flag[c];
+    }
+    __syncthreads();
+}
+
+// d = m dilated by one pixel (3x3 box, clamped to the image).  Ends behind a barrier.
+__device__ __forceinline__ void dt_dilate(const uint8_t *m, uint8_t *d, int Hp, int Wp) {
+    for (int p = threadIdx.x; p < Hp * Wp; p += kDTThreads) {
+        const int y = p / Wp, x = p % Wp;
+        uint8_t any = 0;
+        for (int yy = (y > 0 ? y - 1 : 0); yy <= (y + 1 < Hp ? y + 1 : Hp - 1); ++yy)
+            for (int xx = (x > 0 ? x - 1 : 0); xx <= (x + 1 < Wp ? x + 1 : Wp - 1); ++xx) any |= m[yy * Wp + xx];
+        d[p] = any;
+    }
+    __syncthreads();
+}
+
 __global__ __launch_bounds__(kDTThreads) void demand_tiles_kernel(
         const int32_t *__restrict__ idx, const int32_t *__restrict__ count, int capacity, int bH, int bW, int inH, int inW, int up,
         int Hp, int Wp, int oH, int oW, int padH, int padW, int depth, int32_t *__restrict__ lists, int32_t *__restrict__ counts) {
     __shared__ uint8_t s_map[2][kDTMaxPix];
     __shared__ uint8_t s_flag[kDTMaxCells];
     const int tid = threadIdx.x;
-    const int npix = Hp * Wp, gh = (Hp + oH - 1) / oH, gw = (Wp + oW - 1) / oW, ncell = gh * gw;
+    const int npix = Hp * Wp, ncell = ((Hp + oH - 1) / oH) * ((Wp + oW - 1) / oW);
     for (int p = tid; p < npix; p += kDTThreads) s_map[0][p] = 0;
     __syncthreads();
     int n = *count;
@@ -161,40 +202,46 @@ __global__ __launch_bounds__(kDTThreads) void demand_tiles_kernel(
     __syncthreads();
     int cur = 0;
     for (int k = 0; k < depth; ++k) {
-        const uint8_t *m = s_map[cur];
-        for (int c = tid; c < ncell; c += kDTThreads) {
-            const int y0 = (c / gw) * oH, x0 = (c % gw) * oW;
-            const int y1 = y0 + oH < Hp ? y0 + oH : Hp, x1 = x0 + oW < Wp ? x0 + oW : Wp;
-            uint8_t any = 0;
-            for (int y = y0; y < y1; ++y)
-                for (int x = x0; x < x1; ++x) any |= m[y * Wp + x];
-            s_flag[c] = any;
-        }
-        __syncthreads();
-        int32_t *main_list = lists + (size_t)k * ncell * 2, *flat_list = lists + ((size_t)depth + k) * ncell * 2;
-        for (int c = tid; c < ncell; c += kDTThreads) {
-            if (!s_flag[c] && c != ncell - 1) continue;
-            int rank = 0;
-            for (int j = 0; j < c; ++j) rank += s_flag[j];
-            if (s_flag[c]) {
-                const int y0 = (c / gw) * oH, x0 = (c % gw) * oW;
-                main_list[2 * rank] = y0 - padH; main_list[2 * rank + 1] = x0 - padW;
-                flat_list[2 * rank] = y0; flat_list[2 * rank + 1] = x0;
-            }
-            if (c == ncell - 1) counts[k] = rank + s_flag[c];
-        }
-        if (k + 1 < depth) {
-            uint8_t *d = s_map[cur ^ 1];
-            for (int p = tid; p < npix; p += kDTThreads) {
-                const int y = p / Wp, x = p % Wp;
-                uint8_t any = 0;
-                for (int yy = (y > 0 ? y - 1 : 0); yy <= (y + 1 < Hp ? y + 1 : Hp - 1); ++yy)
-                    for (int xx = (x > 0 ? x - 1 : 0); xx <= (x + 1 < Wp ? x + 1 : Wp - 1); ++xx) any |= m[yy * Wp + xx];
-                d[p] = any;
-            }
-        }
-        __syncthreads();
+        dt_compact(s_map[cur], s_flag, Hp, Wp, oH, oW, padH, padW, lists + (size_t)k * ncell * 2,
+                   lists + ((size_t)depth + k) * ncell * 2, counts + k);
+        if (k + 1 < depth) dt_dilate(s_map[cur], s_map[cur ^ 1], Hp, Wp);
         cur ^= 1;
+    }
+}
+
+// ---- change regions: which output cells of a DENSE stage behind a tiled producer can an edit change? -----------------------
+// A dense stage on cached GroupNorm affines is a chain of local operators, and its input -- the persistent output of a tiled
+// producer -- equals the original's outside S0 = the (tH x tW) output tiles that producer's Scatter writes under the current
+// mask (tile origin = (index + offset) / stride).  The output of the stage's k-th 3x3 conv can differ from the original's only
+// on S_k = S0 dilated k times by one pixel (3x3 box, clamped to the image).  Same pixel set in LDS and the same compaction as
+// above: per k = 1 .. depth the (oH x oW) cells that intersect S_k, row-major.
+__global__ __launch_bounds__(kDTThreads) void change_tiles_kernel(
+        const int32_t *__restrict__ idx, const int32_t *__restrict__ count, int capacity, int sH, int sW, int offH, int offW,
+        int tH, int tW, int Hp, int Wp, int oH, int oW, int padH, int padW, int depth, int32_t *__restrict__ lists,
+        int32_t *__restrict__ counts) {
+    __shared__ uint8_t s_map[2][kDTMaxPix];
+    __shared__ uint8_t s_flag[kDTMaxCells];
+    const int tid = threadIdx.x;
+    const int npix = Hp * Wp, ncell = ((Hp + oH - 1) / oH) * ((Wp + oW - 1) / oW);
+    for (int p = tid; p < npix; p += kDTThreads) s_map[0][p] = 0;
+    __syncthreads();
+    int n = *count;
+    n = n < 0 ? 0 : (n > capacity ? capacity : n);
+    const int tpix = tH * tW;
+    for (long i = tid; i < (long)n * tpix; i += kDTThreads) {
+        const int t = (int)(i / tpix), r = (int)(i % tpix);
+        const int ty = idx[2 * t] + offH, tx = idx[2 * t + 1] + offW;
+        if (ty < 0 || tx < 0) continue;  // (reduce_mask lists start at -offset: never)
+        const int y = ty / sH + r / tW, x = tx / sW + r % tW;
+        if (y < Hp && x < Wp) s_map[0][y * Wp + x] = 1;  // (a tile over the border writes its inside part)
+    }
+    __syncthreads();
+    int cur = 0;
+    for (int k = 0; k < depth; ++k) {
+        dt_dilate(s_map[cur], s_map[cur ^ 1], Hp, Wp);
+        cur ^= 1;
+        dt_compact(s_map[cur], s_flag, Hp, Wp, oH, oW, padH, padW, lists + (size_t)k * ncell * 2,
+                   lists + ((size_t)depth + k) * ncell * 2, counts + k);
     }
 }
 
@@ -221,6 +268,24 @@ extern "C" int sige_hip_demand_tiles_i32(const int32_t *indices, const int32_t *
     if ((long)Hp * Wp > kDTMaxPix || sige_hip_demand_tiles_capacity(Hp, Wp, tileH, tileW) > kDTMaxCells) return SIGE_HIP_EUNSUPPORTED;
     demand_tiles_kernel<<<1, kDTThreads, 0, as_stream(stream)>>>(indices, count, capacity, bH, bW, inH, inW, up, Hp, Wp, tileH, tileW,
                                                                 padH, padW, depth, lists, counts);
+    return launch_status();
+}
+
+extern "C" int sige_hip_change_tiles_i32(const int32_t *indices, const int32_t *count, int capacity, int bH, int bW,
+                                         int strideH, int strideW, int offsetH, int offsetW, int outH, int outW,
+                                         int Hp, int Wp, int tileH, int tileW, int padH, int padW, int depth,
+                                         int32_t *lists, int32_t *counts, void *stream) {
+    SIGE_PLAN_HOOK(sige_hip_change_tiles_i32, indices, count, capacity, bH, bW, strideH, strideW, offsetH, offsetW, outH, outW, Hp, Wp, tileH, tileW, padH, padW, depth, lists, counts, stream);
+    if (capacity < 0 || bH <= 0 || bW <= 0 || strideH <= 0 || strideW <= 0 || offsetH < 0 || offsetW < 0 || outH <= 0 || outW <= 0 ||
+        Hp <= 0 || Wp <= 0 || tileH <= 0 || tileW <= 0 || padH < 0 || padW < 0 || depth <= 0)
+        return SIGE_HIP_EINVAL;
+    if (!count || !lists || !counts || (capacity > 0 && !indices)) return SIGE_HIP_EINVAL;
+    // (the windows of one output tile lie inside the block: (out - 1) * stride < block)
+    if ((long)(outH - 1) * strideH >= bH || (long)(outW - 1) * strideW >= bW) return SIGE_HIP_EINVAL;
+    if (stacked_shift(Hp) != 0) return SIGE_HIP_EUNSUPPORTED;  // (stacked edits: the dense stages run every tile)
+    if ((long)Hp * Wp > kDTMaxPix || sige_hip_demand_tiles_capacity(Hp, Wp, tileH, tileW) > kDTMaxCells) return SIGE_HIP_EUNSUPPORTED;
+    change_tiles_kernel<<<1, kDTThreads, 0, as_stream(stream)>>>(indices, count, capacity, strideH, strideW, offsetH, offsetW, outH, outW,
+                                                                Hp, Wp, tileH, tileW, padH, padW, depth, lists, counts);
     return launch_status();
 }
 

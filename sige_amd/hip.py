@@ -60,6 +60,7 @@ _SIGNATURES = {
     "sige_hip_reduce_mask_i32": (_c_int, [_c_vp] + [_c_int] * 8 + [_c_vp, _c_int, _c_vp, _c_vp]),
     "sige_hip_demand_tiles_capacity": (_c_int, [_c_int] * 4),
     "sige_hip_demand_tiles_i32": (_c_int, [_c_vp, _c_vp] + [_c_int] * 13 + [_c_vp, _c_vp, _c_vp]),
+    "sige_hip_change_tiles_i32": (_c_int, [_c_vp, _c_vp] + [_c_int] * 16 + [_c_vp, _c_vp, _c_vp]),
     "sige_hip_block_conv_packed_size": (_c_sz, [_c_int] * 9),
     "sige_hip_block_conv_packed_size_f16c": (_c_sz, [_c_int] * 9),
     "sige_hip_block_conv_pack_f16c": (_c_int, [_c_vp] + [_c_int] * 4 + [_c_vp, _c_vp]),
@@ -661,17 +662,24 @@ class DemandTiles:
         return [int(t.shape[0]) for t in self.main]
 
 
-def reduce_mask_batch(requests, demands=None):
+class ChangeTiles(DemandTiles):
+    """Index lists of a dense stage's change regions (include/sige_hip.h: sige_hip_change_tiles_i32): `main[k-1]` / `flat[k-1]` =
+    the cells on which the output of the stage's k-th 3x3 conv can differ from the original's, in the 3x3 and the 1x1 geometry."""
+
+
+def reduce_mask_batch(requests, demands=None, changes=None):
     """`reduce_mask` for many (mask [H,W], block, stride, padding) requests with ONE device -> host read for all
     their counts (SIGEModel.set_masks: one request per distinct tile geometry and resolution of the network).
     `demands`: [(i, in_res, upsample2x, producer_res, out_tile, pad, depth)] -- the demand regions of a dense stage read only
     through the windows of request i (one more launch each, fed by that request's list and DEVICE-side count; their counts
-    ride on the same read).  Returns the index lists, and with `demands` given (lists, [DemandTiles])."""
+    ride on the same read).  `changes`: [(i, conv stride, written tile, offset, producer_res, out_tile, pad, depth)] -- the change
+    regions of a dense stage whose input the Scatter behind request i writes (likewise).  Returns the index lists, with
+    `demands` given (lists, [DemandTiles]) and with `changes` given (lists, [DemandTiles], [ChangeTiles])."""
     if not requests:
-        return [] if demands is None else ([], [])
+        return [] if demands is None else (([], []) if changes is None else ([], [], []))
     dev = requests[0][0].device
     n_req = len(requests)
-    counts = torch.empty(n_req + sum(d[6] for d in demands or ()), dtype=torch.int32, device=dev)
+    counts = torch.empty(n_req + sum(d[6] for d in demands or ()) + sum(c[7] for c in changes or ()), dtype=torch.int32, device=dev)
     bufs = []
     for i, (mask, block, stride, padding) in enumerate(requests):
         if mask.dim() != 2 or not mask.is_cuda or mask.device != dev:
@@ -696,7 +704,21 @@ def reduce_mask_batch(requests, demands=None):
         _check(lib().sige_hip_demand_tiles_i32(buf.data_ptr(), counts.data_ptr() + 4 * i, cap, block[0], block[1], in_res[0], in_res[1],
                                                int(bool(up)), prod_res[0], prod_res[1], out_tile[0], out_tile[1], pad[0], pad[1],
                                                depth, lists.data_ptr(), counts.data_ptr() + 4 * at, _stream(m)), "demand_tiles")
-        dbufs.append((lists, at, depth, cells))
+        dbufs.append((lists, at, depth, cells, DemandTiles))
+        at += depth
+    n_dem = len(dbufs)
+    for (i, stride, wrote, offset, prod_res, out_tile, pad, depth) in changes or ():
+        buf, m, cap = bufs[i]
+        block = requests[i][1]
+        cells = lib().sige_hip_demand_tiles_capacity(prod_res[0], prod_res[1], out_tile[0], out_tile[1])
+        if cells <= 0:
+            raise RuntimeError("sige_amd.hip.reduce_mask_batch: bad change-region geometry")
+        lists = torch.empty((2, depth, cells, 2), dtype=torch.int32, device=dev)
+        _check(lib().sige_hip_change_tiles_i32(buf.data_ptr(), counts.data_ptr() + 4 * i, cap, block[0], block[1], stride[0], stride[1],
+                                               offset[0], offset[1], wrote[0], wrote[1], prod_res[0], prod_res[1],
+                                               out_tile[0], out_tile[1], pad[0], pad[1], depth, lists.data_ptr(),
+                                               counts.data_ptr() + 4 * at, _stream(m)), "change_tiles")
+        dbufs.append((lists, at, depth, cells, ChangeTiles))
         at += depth
     rec = plan_recorder()
     if rec is not None:
@@ -711,22 +733,22 @@ def reduce_mask_batch(requests, demands=None):
             rec.keep.extend((buf, m))
             out.append(buf[:n])
         dout = []
-        for lists, at, depth, cells in dbufs:
+        for lists, at, depth, cells, kind in dbufs:
             for g in range(2):  # (the two geometries of one depth share a count, hence a slot)
                 for k in range(depth):
                     rec.bind_index_list(lists[g, k], first + at + k, ns[at + k])
             rec.keep.append(lists)
-            dout.append(DemandTiles([lists[0, k, :ns[at + k]] for k in range(depth)],
-                                    [lists[1, k, :ns[at + k]] for k in range(depth)], cells))
+            dout.append(kind([lists[0, k, :ns[at + k]] for k in range(depth)],
+                             [lists[1, k, :ns[at + k]] for k in range(depth)], cells))
         rec.keep.append(counts)
-        return out if demands is None else (out, dout)
-    ns = counts.cpu().tolist()  # the one synchronisation of the mask -> index pipeline
-    out = [buf[:n].clone() for (buf, _, _), n in zip(bufs, ns)]
-    if demands is None:
-        return out
-    dout = [DemandTiles([lists[0, k, :ns[at + k]] for k in range(depth)], [lists[1, k, :ns[at + k]] for k in range(depth)], cells)
-            for lists, at, depth, cells in dbufs]
-    return out, dout
+    else:
+        ns = counts.cpu().tolist()  # the one synchronisation of the mask -> index pipeline
+        out = [buf[:n].clone() for (buf, _, _), n in zip(bufs, ns)]
+        dout = [kind([lists[0, k, :ns[at + k]] for k in range(depth)], [lists[1, k, :ns[at + k]] for k in range(depth)], cells)
+                for lists, at, depth, cells, kind in dbufs]
+    if changes is not None:
+        return out, dout[:n_dem], dout[n_dem:]
+    return out if demands is None else (out, dout)
 
 
 def difference_mask(tensor1: torch.Tensor, tensor2: torch.Tensor, eps: float) -> torch.Tensor:

@@ -285,15 +285,26 @@ class SIGEModel(nn.Module):
             if key in keys:
                 demands.append((name, ("demand_tiles", *key[1:], int(up), *prod_res, *g.out_tile, *g.offset, depth),
                                 (keys.index(key), tuple(g.input_res), up, tuple(prod_res), tuple(g.out_tile), tuple(g.offset), depth)))
+        # change regions (dense stages fed by a tiled layer's persistent output): likewise, one launch per stage
+        self._change_lists = {}
+        changes = []
+        for name, g, prod_res, depth in self._change_requests(masks):
+            key = g.index_key(tuple(g.input_res))
+            if key in keys:
+                changes.append((name, ("change_tiles", *key[1:], *g.model_stride, *g.out_tile, *prod_res, depth),
+                                (keys.index(key), tuple(g.model_stride), tuple(g.out_tile), tuple(g.offset), tuple(prod_res), (4, 4), (1, 1), depth)))
         if reqs:
             from .. import hip
 
-            lists, regions = hip.reduce_mask_batch(reqs, [d[2] for d in demands])
+            lists, regions, cregions = hip.reduce_mask_batch(reqs, [d[2] for d in demands], [c[2] for c in changes])
             for key, idx in zip(keys, lists):
                 cache[key] = idx
             for (name, key, _), region in zip(demands, regions):
                 cache[key] = region
                 self._demand_lists[name] = region
+            for (name, key, _), region in zip(changes, cregions):
+                cache[key] = region
+                self._change_lists[name] = region
 
     def _demand_requests(self, masks):
         """[(name, consumer Gather, upsample2x, producer resolution, depth)]: the dense stages of this network whose output is
@@ -301,9 +312,15 @@ class SIGEModel(nn.Module):
         `self._demand_lists[name]` after set_masks).  None by default."""
         return []
 
+    def _change_requests(self, masks):
+        """[(name, producer Gather, stage resolution, depth)]: the dense stages of this network whose input is the persistent
+        output of that Gather's Scatter and that can run on their change regions (hip.ChangeTiles, kept in
+        `self._change_lists[name]` after set_masks).  None by default."""
+        return []
+
     def adopt_index_lists(self, view_of):
         """(LaunchPlan.bind_mask) `view_of(list)` = the plan's view of a persistent index list under the new mask, or None."""
-        for region in getattr(self, "_demand_lists", {}).values():
+        for region in list(getattr(self, "_demand_lists", {}).values()) + list(getattr(self, "_change_lists", {}).values()):
             for lists in (region.main, region.flat):
                 for k, t in enumerate(lists):
                     v = view_of(t)

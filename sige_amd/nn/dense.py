@@ -259,8 +259,13 @@ def demand_buffer(conv: nn.Conv2d, name, shape, device) -> torch.Tensor:
 
 def _demand_twin_buffers(conv: nn.Conv2d, keys, shape, device):
     """One persistent twin buffer per registered consumer key (registrations of an affine that is gone are dropped)."""
+    from .scatter import twin_key_cache_id
+
     bufs = conv.__dict__.setdefault("_sige_demand_bufs", {})
-    for name in [n for n in bufs if isinstance(n, tuple) and n[0] == "twin" and n[1] not in keys]:
+    cids = {twin_key_cache_id(k) for k in keys}
+    # (a launch serves the registrations of ONE cache id: those of another id keep their buffers until that id runs again)
+    for name in [n for n in bufs if isinstance(n, tuple) and n[0] == "twin" and n[1] not in keys
+                 and (twin_key_cache_id(n[1]) is None or twin_key_cache_id(n[1]) in cids)]:
         del bufs[name]
     return [demand_buffer(conv, ("twin", k), shape, device) for k in keys]
 

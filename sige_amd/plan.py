@@ -135,6 +135,10 @@ class LaunchPlan:
                 for m in self._scatter_modules():
                     m.plan_tables()
                     m.refresh_outputs(new_mask=True)
+                # (dense levels that run on change regions: behind the restore, every cell into their persistent buffers)
+                refresh = getattr(self.model, "refresh_change_stages", None)
+                if refresh is not None:
+                    refresh()
             torch.cuda.synchronize(self.device)
             # section 1: the forward, recorded under a hipGraph capture -- every tensor it allocates comes from the capture's
             # private pool, which stays alive with `_record_graph`: the pointers the plan holds stay valid

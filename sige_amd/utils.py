@@ -192,3 +192,53 @@ def demand_tiles(
                     grown[max(dy, 0):hp - max(-dy, 0), max(dx, 0):wp - max(-dx, 0)] |= src
             need = grown
     return main, flat
+
+
+def change_tiles(
+    active_indices: torch.Tensor,
+    block_size: IntPair,
+    stride: IntPair,
+    offset: IntPair,
+    written_tile: IntPair,
+    stage_res: IntPair,
+    out_tile: IntPair = 4,
+    padding: IntPair = 1,
+    depth: int = 1,
+):
+    """Host restatement of libsige_hip.so's change-region lists (include/sige_hip.h: sige_hip_change_tiles_i32).
+
+    A dense [Hp,Wp] stage on cached affines, fed by the persistent output of a tiled layer (`active_indices` in that layer's
+    `block_size` / `stride` / `offset` geometry, each tile writing `written_tile` output pixels at (index + offset) / stride),
+    can differ from the original's values only near S0 = the pixels those tiles write: the output of its k-th 3x3 conv on
+    S0 dilated k times by one pixel (3x3 box, clamped to the image).  Returns (main, flat): for k = 1 .. depth the `out_tile`
+    cells that intersect that set, row-major, int32 [n,2], as origins cell - padding (the 3x3 geometry) and cell (the 1x1
+    geometry)."""
+    (bh, bw), (sh, sw), (fh, fw) = _pair(block_size), _pair(stride), _pair(offset)
+    (th, tw), (hp, wp) = _pair(written_tile), _pair(stage_res)
+    (oh, ow), (ph, pw) = _pair(out_tile), _pair(padding)
+    if min(bh, bw, sh, sw, th, tw, hp, wp, oh, ow, depth) <= 0 or min(fh, fw, ph, pw) < 0:
+        raise ValueError("change_tiles: sizes must be positive, offsets and paddings non-negative")
+    if (th - 1) * sh >= bh or (tw - 1) * sw >= bw:
+        raise ValueError("change_tiles: the written tile does not fit the block at this stride")
+    changed = torch.zeros((hp, wp), dtype=torch.bool)
+    for y0, x0 in active_indices.cpu().tolist():
+        if y0 + fh < 0 or x0 + fw < 0:
+            continue
+        y, x = (y0 + fh) // sh, (x0 + fw) // sw
+        changed[y:y + th, x:x + tw] = True  # (a tile over the border writes its inside part)
+    gh, gw = -(-hp // oh), -(-wp // ow)
+    main, flat = [], []
+    for _ in range(depth):
+        grown = changed.clone()
+        for dy in (-1, 0, 1):
+            for dx in (-1, 0, 1):
+                src = changed[max(-dy, 0):hp - max(dy, 0), max(-dx, 0):wp - max(dx, 0)]
+                grown[max(dy, 0):hp - max(-dy, 0), max(dx, 0):wp - max(-dx, 0)] |= src
+        changed = grown
+        padded = torch.zeros((gh * oh, gw * ow), dtype=torch.bool)
+        padded[:hp, :wp] = changed
+        cells = torch.nonzero(padded.reshape(gh, oh, gw, ow).any(dim=3).any(dim=1))
+        origin = torch.stack((cells[:, 0] * oh, cells[:, 1] * ow), dim=1).to(torch.int32)
+        flat.append(origin.contiguous())
+        main.append((origin - torch.tensor([ph, pw], dtype=torch.int32)).contiguous())
+    return main, flat

@@ -319,7 +319,8 @@ class ResBlock(SIGEModule, _TwinProducer):
         """`x` may be a pair (h, skip): the up path's torch.cat, which the dense
         sparse-mode blocks fold into their convs' two-pointer input.
         `demand` = (hip.DemandTiles, depth of this block's conv2) for a dense block of a stage that runs on its demand regions
-        (DDPMSparseUNet.DENSE_ON_DEMAND): conv2 and the shortcut compute the cells of that depth, conv1 those one deeper."""
+        (DDPMSparseUNet.DENSE_ON_DEMAND): conv2 and the shortcut compute the cells of that depth, conv1 those one deeper -- or on
+        its change regions (DDPMSparseUNet.DENSE_ON_CHANGE: the lists of this block, conv2's first, and depth 0)."""
         pair = x if isinstance(x, (tuple, list)) else None
         if self.mode == "full":
             if pair and not self.plain and self._fast_full() and pair[0].is_cuda:
@@ -330,7 +331,7 @@ class ResBlock(SIGEModule, _TwinProducer):
                 return self._sparse_dense(pair[0], pair[1], demand)
             if pair and self.mode == "sparse" and self.cin != self.cout:
                 return self._sparse(lazy_cat(pair[0], pair[1]))  # consumed by the block's two Gathers only
-            return self._sparse(torch.cat(pair, dim=1) if pair else x)
+            return self._sparse(torch.cat(pair, dim=1) if pair else x, demand)
         raise NotImplementedError("Unknown mode [%s]!!!" % self.mode)
 
     def _fast_full(self) -> bool:
@@ -398,7 +399,7 @@ class ResBlock(SIGEModule, _TwinProducer):
         h = full_conv2d(self.conv2, h, _as4(s2), _as4(t2), "swish", residual=skip, stats=fast)
         return self.scatter(h) if self.sparse_main else h
 
-    def _sparse(self, x):
+    def _sparse(self, x, demand=None):
         s1, t1, s2, t2 = self.affine[self.cache_id]
         if self.sparse_main and self.preactivate and self.mode == "sparse":
             parts = list(x.parts) if hasattr(x, "parts") else [x]
@@ -416,7 +417,7 @@ class ResBlock(SIGEModule, _TwinProducer):
             join()
             return self._produced(self.scatter.forward_fused(self.conv2, tiles, skip))
         if not self.sparse_main:
-            return self._sparse_dense(x, None)
+            return self._sparse_dense(x, None, demand)
         skip = self._shortcut(x)
         h = self.conv1(self.main_gather(x, s1, t1))
         if self.mode == "sparse":
@@ -434,10 +435,13 @@ class ResBlock(SIGEModule, _TwinProducer):
         region, depth = demand
         lists = region.flat if tuple(conv.kernel_size) == (1, 1) else region.main
         tiles = lists[depth + deeper]
-        if tiles.shape[0] == region.cells and hip.plan_recorder() is None:
+        # (change regions: `tag` = the cache id the persistent buffers belong to -- what they hold outside the lists is READ;
+        #  `keep` = the launch that establishes it: every cell, into those buffers)
+        tag, keep = getattr(region, "tag", None), getattr(region, "keep", False)
+        if tiles.shape[0] == region.cells and hip.plan_recorder() is None and not keep:
             return {}
         shape = (x.shape[0], conv.out_channels, x.shape[2], x.shape[3])
-        return dict(tiles=tiles, out=demand_buffer(conv, "out", shape, x.device))
+        return dict(tiles=tiles, out=demand_buffer(conv, "out" if tag is None else ("out", tag), shape, x.device))
 
     def _sparse_dense(self, x, x2, demand=None):
         """Dense block on the cached affine: 2-3 fused launches (shortcut 1x1, conv1, conv2+skip)."""
@@ -918,6 +922,173 @@ class DDPMSparseUNet(SIGEModel):
             return None
         return region
 
+    # ---- a dense down level behind a tiled Downsample, on the cells an edit can change (DESIGN.md 5.14) ----------------------------
+    # A sparse pass runs the dense blocks on the CACHED GroupNorm affines, so each of their convs is a local operator, and the
+    # level's input -- the persistent output of the tiled Downsample above it -- equals the original's outside the tiles S0 that
+    # Downsample's Scatter writes.  The k-th 3x3 conv of the level can therefore differ from the original's values only on S_k =
+    # S0 dilated k times by one pixel (hip.ChangeTiles: built on the device behind the index compactions of set_masks): conv1 of
+    # block i runs the cells of S_{2i+1}, conv2 and a shortcut those of S_{2i+2}.  Unlike the demand regions above, what lies
+    # outside the lists IS read (the level's Downsample, the up path's skips, the 6x6 windows of the next conv): outputs and twins
+    # are persistent buffers per cache id that hold the values derived from the current original there.  That is established by
+    # running the level on EVERY cell into those buffers -- in front of the lists in the first forward after anything they derive
+    # from has changed (`_change_signature`), `refresh_change_stages()` behind a launch plan's restore of the Scatter outputs, and
+    # `rebuild_derived_caches()` after an in-place rewrite of the cache.  False: every tile, fresh tensors (A/B runs, tests).
+    DENSE_ON_CHANGE = True
+
+    def _change_stages(self):
+        """[(level, stage, the Downsample that feeds it)]: dense, no attention, input from a tiled Downsample, and wider than
+        its region can grow (2 pixels per ResBlock on each side of a written tile)."""
+        out = []
+        for lvl in range(1, len(self.down)):
+            stage, prev = self.down[lvl], getattr(self.down[lvl - 1], "downsample", None)
+            if prev is None or not prev.sparse or len(stage.attn) or prev.gather.input_res is None:
+                continue
+            if any(b.sparse_main or not b.preactivate or b.overlap for b in stage.block):
+                continue
+            if min(prev.gather.input_res) // 2 <= 4 * len(stage.block):
+                continue
+            out.append((lvl, stage, prev))
+        return out
+
+    def _change_requests(self, masks):
+        if not self.DENSE_ON_CHANGE or self.edit_batch != 1:
+            return []
+        reqs = []
+        for lvl, stage, prev in self._change_stages():
+            g = prev.gather
+            res = tuple(g.input_res)
+            mask = masks.get(res)
+            if mask is None or not mask.is_cuda or mask.dim() != 2 or res[0] % 2 or res[1] % 2 or tuple(g.model_stride) != (2, 2):
+                continue
+            reqs.append(("down.%d" % lvl, g, (res[0] // 2, res[1] // 2), 2 * len(stage.block)))
+        if reqs:
+            from .. import hip
+
+            if hip.get_edit_batch() != 1:  # (stacked edits run every tile)
+                return []
+        return reqs
+
+    def _change_signature(self, lvl: int, stage, h):
+        """Everything the level's persistent buffers are derived from, the current edit aside: the mask, the producer's
+        persistent output and the generation of its cache, the cached affines (tensors and generation: a full pass, clear_cache,
+        pack_caches) and the registered twins of every block.  A forward whose signature differs from the one the buffers were
+        built under runs every cell."""
+        cid = stage.block[0].cache_id
+        sct = self.down[lvl - 1].downsample.scatter
+        blocks = tuple((b._aff_gen, tuple(v.data_ptr() for v in b.affine[cid]), tuple(b._my_twins())) for b in stage.block)
+        return (self.timestamp, h.data_ptr(), tuple(h.shape), str(h.device), sct._out_bufs.gen.get(cid, 0), blocks)
+
+    @staticmethod
+    def _change_buffers(stage, cid):
+        """The persistent outputs and twins of the level's convs for cache id `cid`, by name and address: a buffer that is new
+        (or gone) holds nothing outside the lists yet."""
+        from ..nn.scatter import twin_key_cache_id
+
+        out = []
+        for b in stage.block:
+            for conv in (b.conv1, b.conv2, getattr(b, "nin_shortcut", None)):
+                for name, buf in (conv.__dict__.get("_sige_demand_bufs", {}) if conv is not None else {}).items():
+                    if name == ("out", cid) or (isinstance(name, tuple) and name[0] == "twin" and twin_key_cache_id(name[1]) == cid):
+                        out.append((id(conv), repr(name), buf.data_ptr()))
+        return tuple(out)
+
+    def _stage_change(self, lvl: int, stage, h, refresh: bool = False):
+        """For the dense down level `stage` in this forward: (per-block lists, None) where its buffers are built, (per-block
+        every-cell lists, (state key, signature)) where they have to be built first (`refresh`: in any case), or None (every
+        tile, fresh tensors): sparse mode, channels-last fp32 on the GPU, one edit, exact-fp32 convs, batch 1."""
+        if not (self.DENSE_ON_CHANGE and self.mode == "sparse" and self.edit_batch == 1 and isinstance(h, torch.Tensor) and h.is_cuda):
+            return None
+        region = getattr(self, "_change_lists", {}).get("down.%d" % lvl)
+        if region is None or h.shape[0] != 1 or len(region.main) != 2 * len(stage.block):
+            return None
+        from .. import hip
+
+        convs = [c for b in stage.block for c in (b.conv1, b.conv2, getattr(b, "nin_shortcut", None)) if c is not None]
+        if not hip.is_cl(h) or h.dtype != torch.float32 or any(getattr(c, "compute_dtype", "f32") != "f32" for c in convs):
+            return None
+        if any(b.sparse_update or b.mode != "sparse" for b in stage.block):
+            return None
+        g = self.down[lvl - 1].downsample.gather
+        if tuple(g.input_res) != (2 * h.shape[2], 2 * h.shape[3]) or region.cells != -(-h.shape[2] // 4) * -(-h.shape[3] // 4):
+            return None
+        cid = stage.block[0].cache_id
+        self.__dict__.setdefault("_change_inputs", {})[(lvl, cid)] = h  # (persistent: the producer Scatter's output buffer)
+        planned = hip.plan_recorder() is not None
+        counts = region.counts
+        if not planned and not refresh and (counts[0] == 0 or counts[0] == region.cells):
+            return None  # (nothing written, or every list holds every cell: the launches of the all-tiles forward exactly)
+        sig = self._change_signature(lvl, stage, h)
+        state = self.__dict__.setdefault("_change_state", {})
+        if refresh or state.get((lvl, cid)) != (sig, self._change_buffers(stage, cid)):
+            every = (hip.all_tiles(h.shape[2], h.shape[3], (4, 4), (1, 1), (1, 1), h.device),
+                     hip.all_tiles(h.shape[2], h.shape[3], (4, 4), (1, 1), (0, 0), h.device))
+            per_block = []
+            for _ in stage.block:
+                r = hip.DemandTiles([every[0]] * 2, [every[1]] * 2, region.cells)
+                r.tag, r.keep = cid, True
+                per_block.append(r)
+            state.pop((lvl, cid), None)
+            return per_block, ((lvl, cid), sig)
+        return self._change_steady(stage, region, cid), None
+
+    @staticmethod
+    def _change_steady(stage, region, cid):
+        """The lists of each block of a level whose buffers are built (S_k = main[k - 1]): conv2 / shortcut of block i on
+        S_{2i+2}, conv1 on S_{2i+1}."""
+        from .. import hip
+
+        per_block = []
+        for i in range(len(stage.block)):
+            r = hip.DemandTiles([region.main[2 * i + 1], region.main[2 * i]], [region.flat[2 * i + 1], region.flat[2 * i]], region.cells)
+            r.tag, r.keep = cid, False
+            per_block.append(r)
+        return per_block
+
+    def refresh_change_stages(self):
+        """Run every change-region level on all cells, into its persistent buffers, from the input its last forward had: the
+        Scatter outputs it derives from were restored to the original's (LaunchPlan: recorded behind `refresh_outputs`, so that
+        `bind_mask` replays it) or re-copied from a cache rewritten in place (`rebuild_derived_caches`).  Same addresses: graphs
+        and plans captured earlier stay valid."""
+        inputs = self.__dict__.get("_change_inputs", {})
+        state = self.__dict__.setdefault("_change_state", {})
+        for (lvl, cid), h in list(inputs.items()):
+            stage = self.down[lvl]
+            state.pop((lvl, cid), None)
+            if stage.block[0].cache_id != cid or cid not in stage.block[0].affine:
+                continue  # (another cache id is current: that one's buffers are rebuilt by its next forward)
+            found = self._stage_change(lvl, stage, h, refresh=True)
+            if found is None:
+                continue
+            per_block, (key, sig) = found
+            with torch.no_grad():
+                built = self._change_build(lvl, stage, h, per_block, sig)
+            if built is not None:
+                state[key] = (built, self._change_buffers(stage, cid))
+
+    def _change_build(self, lvl: int, stage, h, per_block, sig):
+        """Every cell of the level into its persistent buffers.  A block that meets its input for the first time registers its
+        activated twin with the block in front of it WHILE this runs, and the twin's buffer then exists only from the next launch of
+        that block on: the run is repeated until the signature stands.  Returns the signature the buffers are built under, or None
+        (it did not settle)."""
+        for _ in range(3):
+            x = h
+            for i, block in enumerate(stage.block):
+                x = block(x, None, demand=(per_block[i], 0))
+            after = self._change_signature(lvl, stage, h)
+            if after == sig:
+                return sig
+            sig = after
+        return None
+
+    def rebuild_derived_caches(self):
+        # (parallel.refresh_derived: caches rewritten in place, Scatter outputs re-copied -- the levels' buffers follow)
+        self.refresh_change_stages()
+
+    def clear_cache(self):
+        super().clear_cache()
+        self.__dict__.pop("_change_inputs", None)
+        self.__dict__.pop("_change_state", None)
+
     def forward(self, x: torch.Tensor, t: torch.Tensor) -> torch.Tensor:
         assert x.shape[2] == x.shape[3] == self.resolution
         temb = self._temb(t)
@@ -943,8 +1114,20 @@ class DDPMSparseUNet(SIGEModel):
             h0 = tall(h0)
         hs = [h0]
         for lvl, stage in enumerate(self.down):
+            change = self._stage_change(lvl, stage, hs[-1]) if lvl else None
+            if change is not None and change[0][0].keep:
+                # the level's buffers are not built for this signature: every cell first, then the lists like any later forward --
+                # so that this forward's result is, bit for bit, what the steady forwards (and a graph of one) compute
+                # (a capture in this state records the every-cell launches in front of the lists: its replays are right under any
+                #  later state of the buffers, and nothing has run yet, so the buffers do not count as built)
+                key, sig = change[1]
+                built = self._change_build(lvl, stage, hs[-1], change[0], sig)
+                if built is not None:
+                    if not torch.cuda.is_current_stream_capturing():
+                        self._change_state[key] = (built, self._change_buffers(stage, key[1]))
+                    change = (self._change_steady(stage, self._change_lists["down.%d" % lvl], key[1]), None)
             for i, block in enumerate(stage.block):
-                h = block(hs[-1], nxt())
+                h = block(hs[-1], nxt()) if change is None else block(hs[-1], nxt(), demand=(change[0][i], 0))
                 if len(stage.attn):
                     h = stage.attn[i](h)
                 hs.append(h)
