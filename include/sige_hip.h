@@ -769,6 +769,21 @@ int sige_hip_attention_tokens_supported(int Nq, int Nk, int C, int heads);
 int sige_hip_attention_tokens_f32(const float *q, const float *k, const float *v, int B, int Nq, int Nk, int C,
                                   int heads, float scale, float *out, void *stream);
 
+/* ---- the same attention for WIDE heads: 160 < d <= 512, d % 16 == 0 (the SD VAE decoder's single 512-channel head) -----
+ * q [B,Nq,ldq], k [B,Nk,ldk], v [B,Nk,ldv], out [B,Nq,ldo]: every operand comes with its ROW STRIDE in elements (>= C, a
+ * multiple of 4; batch stride = rows * row stride), so k and v may be the two halves of one [B,Nk,2C] tensor and q / out
+ * column slices of wider matrices.  Nq % 16 == 0, Nk arbitrary (tail keys masked, fewer key blocks than waves allowed).
+ * One launch: exact fp32 products, online softmax; Q staged in LDS, K / V streamed in 64-channel groups; with few query
+ * tiles the key blocks are split over workgroups and added up inside the launch (tickets + a library-owned workspace, as the
+ * conv K split; first use inside a stream capture or an exhausted region: no split).  The workspace of captured launches is
+ * handed out again by sige_hip_release_graph_tickets().
+ * SIGE_HIP_EINVAL: non-positive dims, a row stride below C, null pointers with work to do.  SIGE_HIP_EUNSUPPORTED: d <= 160
+ * (sige_hip_attention_tokens_f32 serves those), d > 512, d % 16, Nq % 16, pointers not 16-byte aligned, row strides not a
+ * multiple of 4, one batch's K or V >= 2 GiB, B * heads or Nq / 16 > 65535.  B * Nq == 0: SIGE_HIP_OK, nothing launched.  */
+int sige_hip_attention_wide_supported(int Nq, int Nk, int C, int heads);
+int sige_hip_attention_wide_f32(const float *q, int ldq, const float *k, int ldk, const float *v, int ldv,
+                                int B, int Nq, int Nk, int C, int heads, float scale, float *out, int ldo, void *stream);
+
 /* ---- fp16-STORED caches: the "_f16" forms of SURVEY.md 8b's export list (8f row 4: fp16 cache) ---------------------
  * The reference is fp32-only (sige/nn/base.py:15,55-63).  Here the CACHED tensors of a SIGE model -- Scatter /
  * ScatterGather `original_outputs`, ScatterWithBlockResidual `original_outputs` / `original_residuals`, and the activated

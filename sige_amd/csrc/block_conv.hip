@@ -409,9 +409,12 @@ int32_t *split_tickets(hipStream_t st, long blocks) {
     return p;
 }
 
+void attention_wide_release_graph_workspace(int dev);  // (attention_wide.hip: the key split's workspace of captured launches)
+
 int release_graph_tickets() {
     int dev = -1;
     if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 32) return SIGE_HIP_EINVAL;
+    attention_wide_release_graph_workspace(dev);
     std::lock_guard<std::mutex> lock(g_tickets_mu);
     g_tickets[dev].graph_pos = 0;
     return SIGE_HIP_OK;

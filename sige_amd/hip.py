@@ -146,6 +146,8 @@ _SIGNATURES = {
         _c_int, [_c_vp, _c_int, _c_int, _c_int, _c_vp, _c_int, _c_int, _c_int, _c_int, _c_int, ctypes.c_float] + [_c_vp] * 6),
     "sige_hip_attention_tokens_supported": (_c_int, [_c_int] * 4),
     "sige_hip_attention_tokens_f32": (_c_int, [_c_vp] * 3 + [_c_int] * 5 + [ctypes.c_float, _c_vp, _c_vp]),
+    "sige_hip_attention_wide_supported": (_c_int, [_c_int] * 4),
+    "sige_hip_attention_wide_f32": (_c_int, [_c_vp, _c_int] * 3 + [_c_int] * 5 + [ctypes.c_float, _c_vp, _c_int, _c_vp]),
     # fp16-stored caches
     "sige_hip_gather_nhwc_f16": (
         _c_int, [_c_vp] + [_c_int] * 6 + [_c_vp, _c_int] + [_c_vp, _c_int, _c_int] * 2 + [_c_int, _c_vp, _c_vp]),
@@ -2249,6 +2251,43 @@ def attention_tokens(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, heads: i
     if status == UNSUPPORTED:
         return None
     _check(status, "attention_tokens")
+    return out
+
+
+def _token_rows(t: torch.Tensor):
+    """`t` [B,N,C] as (tensor, row stride) for the strided token-matrix entry points: a view whose last dimension is contiguous,
+    whose row stride is a multiple of 4 and whose batch stride is N rows is passed as it lies; anything else is copied."""
+    B, N, C = t.shape
+    if not (t.stride(2) == 1 and t.stride(1) >= C and t.stride(1) % 4 == 0 and (B == 1 or t.stride(0) == N * t.stride(1))
+            and t.data_ptr() % 16 == 0):
+        t = t.contiguous()
+    return t, t.stride(1)
+
+
+def attention_wide(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, heads: int, scale: float,
+                   out: Optional[torch.Tensor] = None) -> Optional[torch.Tensor]:
+    """attention_tokens for WIDE heads (160 < d <= 512, d % 16 == 0; include/sige_hip.h: sige_hip_attention_wide_f32): ONE launch.
+    q [B,Nq,C], k / v [B,Nk,C] may be strided views whose last dimension is contiguous (the two halves of a [B,Nk,2C] tensor,
+    a column slice): they are read in place.  `out`: a [B,Nq,C] destination of the same kind (default: a fresh tensor).  None if
+    unsupported (the caller runs the bmm / softmax / bmm chain)."""
+    if not (q.is_cuda and q.dtype == k.dtype == v.dtype == torch.float32 and q.dim() == k.dim() == v.dim() == 3):
+        return None
+    B, Nq, C = q.shape
+    if tuple(k.shape) != tuple(v.shape) or k.shape[0] != B or k.shape[2] != C:
+        return None
+    Nk = k.shape[1]
+    if not lib().sige_hip_attention_wide_supported(Nq, Nk, C, heads):
+        return None
+    (q, ldq), (k, ldk), (v, ldv) = _token_rows(q), _token_rows(k), _token_rows(v)
+    if out is None:
+        out = torch.empty((B, Nq, C), dtype=torch.float32, device=q.device)
+    elif tuple(out.shape) != (B, Nq, C) or out.dtype != torch.float32 or _token_rows(out)[0] is not out:
+        raise ValueError("attention_wide: `out` must be a [B,Nq,C] fp32 tensor with contiguous rows")
+    status = lib().sige_hip_attention_wide_f32(q.data_ptr(), ldq, k.data_ptr(), ldk, v.data_ptr(), ldv, B, Nq, Nk, C, heads,
+                                               float(scale), out.data_ptr(), out.stride(1), _stream(q))
+    if status == UNSUPPORTED:
+        return None
+    _check(status, "attention_wide")
     return out
 
 

@@ -1,0 +1,359 @@
+"""Stable Diffusion's VAE decoder as a sparse workload (the reference's SIGEDecoder: stable-diffusion/ldm/modules/
+diffusionmodules/sige_model.py:279, built by ldm/models/sige_autoencoder.py with the `ddconfig` of configs/sige.yaml) on sige_amd.nn.
+
+Module tree and state-dict keys are the reference's (`conv_in`, `mid.{block_1,attn_1,block_2}`, `up.L.block.B.{norm1,conv1,norm2,
+conv2,nin_shortcut}`, `up.L.upsample.conv`, `norm_out`, `conv_out`; `mid.attn_1.{norm,q,k,v,proj_out}`), so a checkpoint's
+`first_stage_model.decoder.*` loads strictly.  Every level is tiled: residual blocks with cached GroupNorm affines and no timestep
+embedding (6x6 tiles for the 3x3 convs, 4x4 for the 1x1 shortcuts), Upsample = Gather(upsample2x) in front of a 3x3 tile conv,
+norm_out as a TRUE GroupNorm of the edited activation in front of conv_out.
+
+The attention block (model.py:180-252, SIGEAttnBlock) is single-head attention over ALL channels of the middle block -- 512 in
+the real configuration: queries = the tokens of the active 4x4 tiles, keys / values = every position of the scattered K / V
+tensors.  In sparse mode on channels-last fp32 GPU tensors:
+    gather (cached affine) -> q on the tiles                                      1 launch
+    gather -> (k | v), ONE C -> 2C conv whose weight is the derived concatenation of `k` and `v`, written into the persistent
+              [B,2C,H,W] tensor that holds the original's K | V outside the active tiles          1 launch
+    attention: hip.attention_tokens (C <= 160) or hip.attention_wide (above), q / k / v read in place    1 launch
+    proj_out on the tiles, then the scatter with the residual x                   2 launches
+`NATIVE_ATTENTION = False` -- and any backend without the fused path: CPU, NCHW -- runs the reference's module chain (bmm, softmax
+over a [B,Nq,HW] score tensor, bmm, with its reshapes and copies); a shape the attention entry refuses runs that bmm chain on the
+fused q and K | V.  With in-place scatters (SIGEModel.set_scatter_inplace) the persistent K | V tensor and the attention's output rows
+are allocated by set_masks() / set_mode(), never inside a forward; without, every Scatter returns a fresh tensor as the reference's does.  Batch 1 (the reference's sparse mode calls scale.view(1, -1, 1, 1): one cached original)."""
+from dataclasses import dataclass
+from typing import Tuple
+
+import torch
+from torch import nn
+from torch.nn import functional as F
+
+from ..nn import Gather, Scatter, ScatterGather, ScatterWithBlockResidual, SIGEConv2d, SIGEModel, SIGEModule, paired_convs
+from ..nn.dense import group_norm_affine
+from .ddpm_unet import Upsample, norm_affine
+from .pd_unet import _as4, _fused_layout
+
+# The attention launch of the library in the tiled attention block.  False: the reference's bmm / softmax / bmm chain (A/B runs:
+# tools/vae_bench.py; tests).
+NATIVE_ATTENTION = True
+
+
+@dataclass
+class VAEDecoderConfig:
+    """Defaults: configs/sige.yaml, first_stage_config.params.ddconfig."""
+    ch: int = 128
+    out_ch: int = 3
+    ch_mult: Tuple[int, ...] = (1, 2, 4, 4)
+    num_res_blocks: int = 2
+    attn_resolutions: Tuple[int, ...] = ()
+    in_channels: int = 3
+    resolution: int = 256
+    z_channels: int = 4
+    main_block: int = 6      # tile edge of the 3x3 convs
+    shortcut_block: int = 4  # tile edge of the 1x1 shortcuts
+    attn_block: int = 4      # tile edge of the attention block's 1x1 convs
+    groups: int = 32
+    eps: float = 1e-6
+
+
+class VAEResBlock(SIGEModule):
+    """SIGEResnetBlock with temb_channels = 0 (sige_model.py:10-139): no temb_proj."""
+
+    def __init__(self, cfg: VAEDecoderConfig, cin: int, cout: int):
+        super().__init__()
+        self.cin, self.cout = cin, cout
+        self.norm1 = nn.GroupNorm(cfg.groups, cin, eps=cfg.eps)
+        self.conv1 = SIGEConv2d(cin, cout, 3, 1, 1)
+        self.norm2 = nn.GroupNorm(cfg.groups, cout, eps=cfg.eps)
+        self.conv2 = SIGEConv2d(cout, cout, 3, 1, 1)
+        self.main_gather = Gather(self.conv1, cfg.main_block, activation_name="swish")
+        self.scatter_gather = ScatterGather(self.main_gather, activation_name="swish")
+        if cin != cout:
+            self.nin_shortcut = SIGEConv2d(cin, cout, 1, 1, 0)
+            self.shortcut_gather = Gather(self.nin_shortcut, cfg.shortcut_block)
+            self.scatter = ScatterWithBlockResidual(self.main_gather, self.shortcut_gather)
+        else:
+            self.scatter = Scatter(self.main_gather)
+        self.affine = {}  # cache_id -> (scale1, shift1, scale2, shift2) as [1,C,1,1]
+        self.plain = False
+
+    def clear_cache(self):
+        self.affine = {}
+
+    def forward(self, x: torch.Tensor) -> torch.Tensor:
+        if self.mode == "full" and self.plain:
+            # the stock dense block (model.py:119-139): F.group_norm, no cache bookkeeping
+            h = self.conv1(F.silu(self.norm1(x)))
+            h = self.conv2(F.silu(self.norm2(h)))
+            return (x if self.cin == self.cout else self.nin_shortcut(x)) + h
+        if self.mode == "full":
+            skip = x if self.cin == self.cout else self.nin_shortcut(self.shortcut_gather(x))
+            h = self.main_gather(x)  # records the input resolution
+            s1, t1 = norm_affine(h, self.norm1)
+            h = self.scatter_gather(self.conv1(F.silu(h * _as4(s1) + _as4(t1))))
+            s2, t2 = norm_affine(h, self.norm2)
+            self.affine[self.cache_id] = tuple(_as4(v).contiguous() for v in (s1, t1, s2, t2))
+            return self.scatter(self.conv2(F.silu(h * _as4(s2) + _as4(t2))), skip)
+        if self.mode in ("sparse", "profile"):
+            s1, t1, s2, t2 = self.affine[self.cache_id]
+            # (channels-last GPU tensors: the 1x1 shortcut rides in conv1's launch, conv2 + scatter + residual are one launch)
+            with paired_convs(x, enabled=self.cin != self.cout and self.mode == "sparse"):
+                skip = x if self.cin == self.cout else self.nin_shortcut(self.shortcut_gather(x))
+                h = self.conv1(self.main_gather(x, s1, t1))
+            tiles = self.scatter_gather(h, s2, t2)
+            if self.mode == "sparse":
+                return self.scatter.forward_fused(self.conv2, tiles, skip)
+            return self.scatter(self.conv2(tiles), skip)
+        raise NotImplementedError("Unknown mode [%s]!!!" % self.mode)
+
+
+class VAEAttnBlock(SIGEModule):
+    """SIGEAttnBlock (model.py:180-252)."""
+
+    def __init__(self, cfg: VAEDecoderConfig, ch: int):
+        super().__init__()
+        self.ch, self.block = ch, cfg.attn_block
+        self.norm = nn.GroupNorm(cfg.groups, ch, eps=cfg.eps)
+        self.q = SIGEConv2d(ch, ch, 1, 1, 0)
+        self.k = SIGEConv2d(ch, ch, 1, 1, 0)
+        self.v = SIGEConv2d(ch, ch, 1, 1, 0)
+        self.proj_out = SIGEConv2d(ch, ch, 1, 1, 0)
+        self.gather = Gather(self.q, cfg.attn_block)
+        self.k_scatter = Scatter(self.gather)
+        self.v_scatter = Scatter(self.gather)
+        self.out_scatter = Scatter(self.gather)
+        # (not in the reference; no parameters: the state dict keeps its keys) K | V as ONE [B,2C,H,W] tensor: cache + persistent output
+        self.kv_scatter = Scatter(self.gather)
+        self.affine = {}      # cache_id -> (scale, shift) as [1,C,1,1]
+        self._attn_out = None  # [1, 16 * active tiles, C]: the attention launch's output rows (alloc_buffers)
+        self.plain = False
+
+    def clear_cache(self):
+        self.affine = {}
+        self._attn_out = None
+        self.__dict__.pop("_kv_conv", None)
+
+    # ---- derived: the C -> 2C conv (k | v) ------------------------------------------------------------------------------------
+    def folded_kv(self) -> SIGEConv2d:
+        """The 1x1 conv with outputs (k(x) | v(x)): the weights and biases of `k` and `v` concatenated.  Not a Parameter, a buffer or
+        a submodule -- the state dict keeps the reference's keys; rebuilt when a parameter of `k` / `v` has been replaced, moved or
+        edited in place (address, version counter, shape, device, dtype: the key of ddpm_unet.AttnBlock.folded_qv) and after
+        clear_cache()."""
+        params = (self.k.weight, self.k.bias, self.v.weight, self.v.bias)
+        key = tuple(None if p is None else (p.data_ptr(), p._version, tuple(p.shape), p.device, p.dtype) for p in params)
+        entry = self.__dict__.get("_kv_conv")
+        if entry is None or entry[0] != key:
+            C = self.ch
+            with torch.device("meta"):
+                conv = SIGEConv2d(C, 2 * C, 1, 1, 0)
+            conv.weight = nn.Parameter(torch.cat([self.k.weight.detach(), self.v.weight.detach()]).contiguous(), requires_grad=False)
+            conv.bias = nn.Parameter(torch.cat([self.k.bias.detach(), self.v.bias.detach()]).contiguous(), requires_grad=False)
+            conv.set_mode("sparse")
+            entry = (key, conv)
+            self.__dict__["_kv_conv"] = entry  # (not through nn.Module.__setattr__: that would register the conv as a submodule)
+        return entry[1]
+
+    # ---- persistent buffers: SparseVAEDecoder.set_masks / set_mode -----------------------------------------------------------------
+    def _fused_cache(self):
+        kv = self.kv_scatter.original_outputs.get(self.cache_id)
+        return kv if kv is not None and _fused_layout(kv) else None
+
+    def alloc_buffers(self):
+        """Outside any forward (a forward may run under a graph capture): the persistent K | V tensor of the current cache id --
+        the original's K | V, restored in place when only the mask changed -- and the attention's output rows for the current
+        mask's tile count."""
+        kv = self._fused_cache()
+        g = self.gather
+        if kv is None or g.active_indices is None:
+            return
+        if self.kv_scatter.inplace:
+            self.kv_scatter._out_bufs.get(self.cache_id, kv, g.timestamp)
+        self.folded_kv()
+        rows = 16 * int(g.active_indices.shape[0]) * kv.shape[0]
+        buf = self._attn_out
+        if buf is None or buf.shape[1] != rows or buf.device != kv.device:
+            self._attn_out = torch.empty((1, rows, self.ch), dtype=torch.float32, device=kv.device)
+
+    def persistent_buffers(self):
+        """(tests) [(name, tensor, rewritten)]: `rewritten` = the forward writes every element it later reads -- K | V is rewritten
+        on the active tiles only; everywhere else it carries the original's values (a cache)."""
+        out = []
+        entry = self.kv_scatter._out_bufs.bufs.get(self.cache_id)
+        if entry is not None:
+            out.append(("kv", entry[1], False))
+        if self._attn_out is not None:
+            out.append(("attn_out", self._attn_out, True))
+        return out
+
+    # ---- the reference's attention (model.py:218-247) ---------------------------------------------------------------------------
+    def _chain(self, q: torch.Tensor, k: torch.Tensor, v: torch.Tensor) -> torch.Tensor:
+        """q [b,nq,c] tokens, k / v [b,c,h,w] -> [b,c,nq]."""
+        b, c, h, w = k.shape
+        w_ = torch.bmm(q, k.reshape(b, c, h * w)) * (int(c) ** (-0.5))
+        w_ = F.softmax(w_, dim=2)
+        return torch.bmm(v.reshape(b, c, h * w), w_.permute(0, 2, 1))
+
+    def forward(self, x: torch.Tensor) -> torch.Tensor:
+        if self.mode == "full" and self.plain:
+            # the stock dense block (model.py:153-177)
+            h = self.norm(x)
+            q, k, v = self.q(h), self.k(h), self.v(h)
+            b, c, hh, ww = q.shape
+            h = self._chain(q.reshape(b, c, hh * ww).permute(0, 2, 1), k, v).reshape(b, c, hh, ww)
+            return x + self.proj_out(h)
+        if self.mode == "full":
+            h = self.gather(x)
+            s, t = norm_affine(h, self.norm)
+            self.affine[self.cache_id] = (_as4(s).contiguous(), _as4(t).contiguous())
+            h = h * _as4(s) + _as4(t)
+            q = self.q(h)
+            k, v = self.k_scatter(self.k(h)), self.v_scatter(self.v(h))
+            if _fused_layout(x):
+                self.kv_scatter(torch.cat([k, v], dim=1).contiguous(memory_format=torch.channels_last))
+            b, c, hh, ww = q.shape
+            h = self._chain(q.reshape(b, c, hh * ww).permute(0, 2, 1), k, v).reshape(b, c, hh, ww)
+            return self.out_scatter(self.proj_out(h), x)
+        if self.mode not in ("sparse", "profile"):
+            raise NotImplementedError("Unknown mode [%s]!!!" % self.mode)
+        s, t = self.affine[self.cache_id]
+        if self.mode == "sparse" and NATIVE_ATTENTION and _fused_layout(x) and x.shape[0] == 1:
+            out = self._sparse_fused(x, s, t)
+            if out is not None:
+                return out
+        # the reference's module chain: CPU, NCHW, NATIVE_ATTENTION off
+        tiles = self.gather(x, s, t)
+        q = self.q(tiles)  # [b * nb, c, bh, bw]
+        k, v = self.k_scatter(self.k(tiles)), self.v_scatter(self.v(tiles))
+        b, c, bs = x.size(0), q.shape[1], self.block
+        q = q.reshape(b, -1, c, bs * bs).permute(0, 1, 3, 2).reshape(b, -1, c)  # [b, nb * hw, c]
+        h = self._chain(q, k, v)  # [b, c, nb * hw]
+        h = h.reshape(b, c, -1, bs, bs).permute(0, 2, 1, 3, 4).reshape(-1, c, bs, bs)
+        return self.out_scatter(self.proj_out(h), x)
+
+    def _sparse_fused(self, x, s, t):
+        """None: no fused form as things stand (the caller runs the module chain)."""
+        from .. import hip
+
+        kv_cache = self._fused_cache()
+        C, g = self.ch, self.gather
+        if kv_cache is None or C % 4 or self.sparse_update:
+            return None
+        T = int(g.active_indices.shape[0])
+        if T == 0:
+            return None
+        q = self.q(self.gather(x, s, t))  # [T,C,4,4] channels-last tiles = the token matrix [16 T, C]
+        kv = self.kv_scatter.forward_fused(self.folded_kv(), self.gather(x, s, t))  # persistent [1,2C,H,W]: new K | V on the tiles
+        if not (hip.is_cl(q) and hip.is_cl(kv)):
+            return None
+        _, _, H, W = kv.shape
+        qt = q.permute(0, 2, 3, 1).reshape(1, 16 * T, C)            # (views: no copy on either side)
+        tok = kv.permute(0, 2, 3, 1).reshape(1, H * W, 2 * C)
+        scale = int(C) ** (-0.5)
+        if C <= 160:
+            o = hip.attention_tokens(qt, tok[:, :, :C], tok[:, :, C:], 1, scale)
+        else:
+            buf = self._attn_out
+            if buf is None or buf.shape[1] != 16 * T or buf.device != x.device:
+                # (not reached after set_masks() / set_mode(): only a block driven module by module allocates here)
+                buf = self._attn_out = torch.empty((1, 16 * T, C), dtype=torch.float32, device=x.device)
+            o = hip.attention_wide(qt, tok[:, :, :C], tok[:, :, C:], 1, scale, out=buf)
+        if o is None:
+            # a shape the entry does not take: the reference's bmm chain on the fused q and K | V
+            o = self._chain(qt, kv[:, :C], kv[:, C:]).permute(0, 2, 1)
+        h = o.reshape(T, 4, 4, C).permute(0, 3, 1, 2)  # channels-last tiles again
+        return self.out_scatter(self.proj_out(h), x)
+
+
+class SparseVAEDecoder(SIGEModel):
+    def __init__(self, cfg: VAEDecoderConfig = VAEDecoderConfig()):
+        super().__init__()
+        self.cfg = cfg
+        ch, mult = cfg.ch, tuple(cfg.ch_mult)
+        self.num_resolutions, self.num_res_blocks = len(mult), cfg.num_res_blocks
+        cur = ch * mult[-1]
+        res = cfg.resolution // 2 ** (self.num_resolutions - 1)
+        self.z_shape = (1, cfg.z_channels, res, res)
+
+        self.conv_in = nn.Conv2d(cfg.z_channels, cur, 3, 1, 1)
+        self.mid = nn.Module()
+        self.mid.block_1 = VAEResBlock(cfg, cur, cur)
+        self.mid.attn_1 = VAEAttnBlock(cfg, cur)
+        self.mid.block_2 = VAEResBlock(cfg, cur, cur)
+
+        ups = []
+        for lvl in reversed(range(self.num_resolutions)):
+            stage = nn.Module()
+            stage.block, stage.attn = nn.ModuleList(), nn.ModuleList()
+            cout = ch * mult[lvl]
+            for _ in range(cfg.num_res_blocks + 1):
+                stage.block.append(VAEResBlock(cfg, cur, cout))
+                cur = cout
+                if res in cfg.attn_resolutions:
+                    stage.attn.append(VAEAttnBlock(cfg, cur))
+            if lvl != 0:
+                stage.upsample = Upsample(cfg, cur)
+                res *= 2
+            ups.insert(0, stage)
+        self.up = nn.ModuleList(ups)
+
+        self.norm_out = nn.GroupNorm(cfg.groups, cur, eps=cfg.eps)
+        self.conv_out = nn.Conv2d(cur, cfg.out_ch, 3, 1, 1)
+
+    # ---- bookkeeping -------------------------------------------------------------------------------------------------------------
+    def _attn_blocks(self):
+        return [m for m in self.modules() if isinstance(m, VAEAttnBlock)]
+
+    def _alloc_buffers(self):
+        for m in self._attn_blocks():
+            m.alloc_buffers()
+
+    def persistent_buffers(self):
+        """(tests) every persistent buffer the attention blocks own: [(name, tensor, rewritten)], see VAEAttnBlock."""
+        return [(name, buf, rw) for m in self._attn_blocks() for name, buf, rw in m.persistent_buffers()]
+
+    def set_plain_dense(self, plain: bool):
+        """full mode = the stock dense decoder (F.group_norm, no cache bookkeeping): what a speedup is quoted against."""
+        for m in self.modules():
+            if isinstance(m, (VAEResBlock, VAEAttnBlock, Upsample)):
+                m.plain = plain
+
+    def set_masks(self, masks):
+        super().set_masks(masks)
+        self._alloc_buffers()
+
+    def set_mode(self, mode: str):
+        super().set_mode(mode)
+        if mode == "sparse":
+            self._alloc_buffers()
+
+    def set_cache_id(self, cache_id: int):
+        super().set_cache_id(cache_id)
+        if self.mode == "sparse":
+            self._alloc_buffers()
+
+    # ---- forward -----------------------------------------------------------------------------------------------------------------
+    def _head(self, h):
+        """norm_out is a TRUE GroupNorm of the edited activation (sige_model.py:386-388)."""
+        if self.mode == "sparse" and _fused_layout(h) and h.shape[1] % 4 == 0:
+            from .. import hip
+
+            so, to = group_norm_affine(h, self.norm_out)
+            out = hip.conv3x3_small_cout_cl(h, self.conv_out.weight, self.conv_out.bias, so, to, "swish")
+            if out is not None:
+                return out
+        return self.conv_out(F.silu(self.norm_out(h)))
+
+    def forward(self, z: torch.Tensor) -> torch.Tensor:
+        h = self.conv_in(z)
+        if z.is_contiguous(memory_format=torch.channels_last) and not z.is_contiguous():
+            h = h.contiguous(memory_format=torch.channels_last)  # (MIOpen may hand back NCHW for 4 input channels)
+        h = self.mid.block_1(h)
+        h = self.mid.attn_1(h)
+        h = self.mid.block_2(h)
+        for lvl in reversed(range(self.num_resolutions)):
+            stage = self.up[lvl]
+            for i, block in enumerate(stage.block):
+                h = block(h)
+                if len(stage.attn):
+                    h = stage.attn[i](h)
+            if lvl != 0:
+                h = stage.upsample(h)
+        return self._head(h)
