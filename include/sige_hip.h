@@ -315,6 +315,23 @@ int sige_hip_block_conv_pack_f16c(const float *w, int Cout, int Cin, int kH, int
 int sige_hip_conv_pair_begin(void);
 int sige_hip_conv_pair_end(void);
 int64_t sige_hip_conv_pairs_fused(void);
+/* Deferred "side" convs: independent work computed on the CUs that later, small launches leave idle.  After
+ * side_begin(budget > 0) the NEXT sige_hip_gather_conv_nhwc call of this thread, if it is eligible -- compute 0, 3x3 / stride 1,
+ * raw staging, a full-tensor destination, no twins, and a grid that a launch of its own would not K-split -- is planned
+ * (16-pixel output blocks) and QUEUED: the call returns SIGE_HIP_OK without launching.  A call that is not eligible launches
+ * as ever; either way side_begin is spent on that one call (it never waits for a later, unrelated conv).  Every later eligible HOST launch on the
+ * same stream -- a single exact-fp32 3x3 / stride 1 gather -> conv launch into a full tensor with 16 x 16 output blocks, 4
+ * waves, no K split and no held shortcut -- runs min(remaining, budget, 256 - its own grid) blocks of the queue's head in the
+ * same kernel.  A block computes exactly what it would in a launch of its own: results do not depend on the slicing.
+ * side_flush() launches whatever is left, first queued first, one launch per conv, and disarms a side_begin whose call has
+ * not come.  Other launches leave the queue alone, except that a conv launch on another stream, or one whose operands overlap
+ * a queued conv's (it reads the queued output, or writes a queued input), flushes the queue first; everything else is the
+ * caller's to order: the operands of a queued conv must stay valid and unchanged until it is hosted or flushed, and nothing
+ * may read its output before side_flush().  Per host thread.  side_workgroups(0 | 1): side workgroups hosted | flushed so far
+ * in this process (atomic; a measurement aid). */
+int sige_hip_conv_side_begin(int max_side_workgroups_per_host);
+int sige_hip_conv_side_flush(void);
+int64_t sige_hip_conv_side_workgroups(int flushed);
 /* A K-split launch is finished inside the launch: the last workgroup to finish an output block adds the partial copies of
  * that block up in split order and runs the epilogue (tickets in a library-owned, per-device buffer); when no tickets are to
  * be had, by a second launch over the whole output.  Both add in the same order: identical results. */

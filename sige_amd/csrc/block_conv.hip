@@ -6,6 +6,7 @@
 // see a batch of T tiny 6x6 images) after a separate gather kernel
 // (sige/cuda/gather_kernel.cu:7-67) or scatter_gather kernel
 // (scatter_gather_kernel.cu:8-67).
+#include <deque>
 #include <mutex>
 
 #include "conv_mfma.hpp"
@@ -370,6 +371,55 @@ SIGE_PAIR_DECLARE_H(DST_TILES) SIGE_PAIR_DECLARE_H(DST_NCHW)
     template <> void launch_conv_pair<X31_32, 1, X11_32, DST, 4>(ConvArgs, ConvArgs, int, hipStream_t);
 SIGE_PAIR_DECLARE_X(DST_TILES) SIGE_PAIR_DECLARE_X(DST_NCHW)
 
+// ---- deferred "side" convs: a queued 3x3 conv computed on the idle CUs of LATER launches ----
+// sige_hip_conv_side_begin(budget): the next sige_hip_gather_conv_nhwc call of this thread, if eligible (exact fp32, 3x3 / stride 1,
+// raw staging, full-tensor destination, unsplit, no twins), is planned and QUEUED instead of launched; if not, it launches as ever.  Every later eligible
+// host launch on the same stream (a single exact-fp32 3x3 launch of 16 x 16 blocks, 4 waves, unsplit, nothing held for pairing)
+// takes min(remaining, budget, 256 - own grid) blocks of the queue's head along in one conv_side_kernel launch;
+// sige_hip_conv_side_flush() launches what is left, FIFO.  Other launches leave the queue alone; a conv launch on another
+// stream, or one that reads a queued conv's output or writes one of its inputs, flushes it first.
+struct SideConv {
+    ConvArgs a;           // as planned: 16-pixel blocks, NB = nb, all tiles of an output-channel block consecutive (ng_fast = 0)
+    int nb = 1, next = 0, total = 0, budget = 0;
+    hipStream_t st = nullptr;
+};
+static thread_local std::deque<SideConv> g_side;
+constexpr int kSideChipWorkgroups = 256;  // one workgroup per CU: a host takes at most (this - its own grid) side workgroups
+constexpr int kSideNB2MaxK = 2304;        // side convs of at most this K (= 9 Cin) take 16 x 32 blocks
+static thread_local int g_side_armed = 0;  // > 0: sige_hip_conv_side_begin's budget, waiting for its conv
+static std::atomic<long> g_side_hosted{0}, g_side_flushed{0};
+
+template <typename GA, int NBA, typename GB, int NBB, int DST, int W>
+void launch_conv_side(ConvArgs a, ConvArgs b, int mode_a, int na, int b_off, int nb_blocks, hipStream_t st);
+template <> void launch_conv_side<K31_16, 1, K31_16, 1, DST_NCHW, 4>(ConvArgs, ConvArgs, int, int, int, int, hipStream_t);
+template <> void launch_conv_side<K31_16, 1, K31_16, 2, DST_NCHW, 4>(ConvArgs, ConvArgs, int, int, int, int, hipStream_t);
+
+// launch every queued conv's remaining blocks, FIFO: each is one (counted) launch
+static int flush_side() {
+    while (!g_side.empty()) {
+        const SideConv s = g_side.front();
+        g_side.pop_front();
+        const int left = s.total - s.next;
+        if (left <= 0) continue;
+        if (s.nb == 2) launch_conv_side<K31_16, 1, K31_16, 2, DST_NCHW, 4>(s.a, s.a, MODE_RAW, 0, s.next, left, s.st);
+        else launch_conv_side<K31_16, 1, K31_16, 1, DST_NCHW, 4>(s.a, s.a, MODE_RAW, 0, s.next, left, s.st);
+        g_side_flushed.fetch_add(left, std::memory_order_relaxed);
+        note_launches(1);
+    }
+    return hipGetLastError() == hipSuccess ? SIGE_HIP_OK : SIGE_HIP_ELAUNCH;
+}
+
+// does launch `a` read what a queued conv has yet to write, or write what it has yet to read?
+static bool side_hazard(const ConvArgs &a) {
+    for (const SideConv &s : g_side) {
+        const float *o = s.a.out;
+        if (a.x == o || a.x2 == o || a.y == o || a.residual == o || a.out == o) return true;
+        for (const float *w : {(const float *)a.out, (const float *)a.twin0, (const float *)a.twin1, (const float *)a.fout})
+            if (w && (w == s.a.x || w == s.a.x2 || w == s.a.residual)) return true;
+    }
+    return false;
+}
+
 // Tickets of the in-kernel K-split finish (conv_mfma.hpp): one int per output block of a split launch, zero whenever no
 // such launch is running.  One buffer per device: a ring for eager launches (a slice is only live while its launch runs;
 // 2^20 tickets = hundreds of launches in flight before a wrap could meet a running one) and a bump-allocated region for
@@ -429,7 +479,7 @@ using GeoOf = std::conditional_t<PREC == 2, ConvGeoX<KH, STR, R, MT>, std::condi
 // Everything a launch decides on the host: output block, waves, grid order, K split.  `want_waves` != 0 / `nb1`: the
 // constraints of the second conv of a pair (same workgroup size as the first, NB = 1, no K split: cap = 1).
 template <int KH, int STR, int R, int SRC, int LAY, int PREC>
-static int plan_conv(ConvArgs &a, int cap, int want_waves, bool nb1, ConvPlan &p) {
+static int plan_conv(ConvArgs &a, int cap, int want_waves, bool nb1, ConvPlan &p, int side_nb = 0) {
     using G32 = GeoOf<PREC, KH, STR, R, 32>;
     using G16 = GeoOf<PREC, KH, STR, R, 16>;
     const bool kHasNB2 = STR == 1 && !nb1 && PREC != 2;  // (split operands: the (hi, lo) weight registers of two sub-blocks do not fit)
@@ -447,6 +497,8 @@ static int plan_conv(ConvArgs &a, int cap, int want_waves, bool nb1, ConvPlan &p
     const int force_mt = tuning(SIGE_HIP_TUNE_CONV_TILE_MT), force_nb = tuning(SIGE_HIP_TUNE_CONV_TILE_NB), force_waves = tuning(SIGE_HIP_TUNE_CONV_WAVES);
     const int large_grid_nb1 = tuning(SIGE_HIP_TUNE_CONV_LARGE_GRID_NB1), force_ksplit = tuning(SIGE_HIP_TUNE_CONV_KSPLIT);
     if (force_mt && !want_waves) { mt = force_mt == 32 ? 32 : 16; nb = (force_nb == 2 && kHasNB2) ? 2 : 1; if (!usable(mt)) mt = 0; }
+    // a side conv (above): 16-pixel blocks, the caller's NB
+    if (side_nb && !mt) { if (!usable(16)) return SIGE_HIP_EUNSUPPORTED; mt = 16; nb = (side_nb == 2 && kHasNB2) ? 2 : 1; }
     // Exact fp32, channels-last, stride 1: 128 unsplit 16-channel blocks beat 32 blocks x 4 K splits -- the 8x8 layers of the
     // DDPM U-Net, 13.4 vs 14.4 us per launch, 1.437 -> 1.419 ms per forward (tools/probe/ksplit_forward_probe.py, round 3): the
     // split's second phase (partial sums out, ticket, the last workgroup's sum over the copies) costs more than the 4x shorter
@@ -595,6 +647,34 @@ static int launch_kind(ConvArgs a, int mode, hipStream_t st) {
         return SIGE_HIP_OK;
     }
     const int cap = (LAY == LAYOUT_NHWC && a.ws) ? a.ksplit_max : 1;
+    // side convs (above): what this launch must not overtake goes first; an armed sige_hip_conv_side_begin takes this call if eligible
+    constexpr bool kSideGeo = KH == 3 && STR == 1 && SRC == SRC_GATHER && DST == DST_NCHW && LAY == LAYOUT_NHWC && PREC == 0;
+    if (!g_side.empty() && (g_side.front().st != st || side_hazard(a))) {
+        const int rc = flush_side();
+        if (rc != SIGE_HIP_OK) return rc;
+    }
+    if constexpr (kSideGeo) {
+        if (g_side_armed > 0 && !g_held.active && mode == MODE_RAW && !a.twin0 && !a.twin1 && !a.up && !a.x1 && !a.hp_shift) {
+            ConvArgs q = a;
+            ConvPlan pq;
+            // (eligible only if a launch of its own would not split K: the sum order, hence the bits, stay what they were)
+            if (plan_conv<KH, STR, R, SRC, LAY, PREC>(q, cap, 0, false, pq) == SIGE_HIP_OK && q.ksplit == 1) {
+                q = a;
+                // block shape: a side workgroup should not outlast a host workgroup -- the hosts this library has are 16 x 16
+                // blocks over K = 4608 (the dense 8x8 level of the U-Net), which a 16 x 32 block matches at half that K
+                const int want_nb = 9 * a.Cin <= kSideNB2MaxK ? 2 : 1;
+                if (plan_conv<KH, STR, R, SRC, LAY, PREC>(q, 1, 0, false, pq, want_nb) == SIGE_HIP_OK && pq.mt == 16 && pq.waves == 4 && q.ksplit == 1) {
+                    q.ng_fast = 0;  // all tiles of an output-channel block are consecutive workgroups: a slice streams its weights once
+                    SideConv sc;
+                    sc.a = q; sc.nb = pq.nb; sc.total = q.mbk * q.ngk; sc.budget = g_side_armed; sc.st = st;
+                    g_side.push_back(sc);
+                    g_side_armed = 0;
+                    note_launches(-1);  // (as for a held shortcut: hosted blocks ride in other launches, a flushed rest counts there)
+                    return SIGE_HIP_OK;
+                }
+            }
+        }
+    }
     ConvPlan p;
     const ConvArgs a0 = a;  // (as handed in: plan_conv rewrites the packed-weight pointer and the grid fields)
     const int prc = plan_conv<KH, STR, R, SRC, LAY, PREC>(a, cap, 0, false, p);
@@ -630,6 +710,24 @@ static int launch_kind(ConvArgs a, int mode, hipStream_t st) {
             else {
                 const int rc = flush_held();
                 if (rc != SIGE_HIP_OK) return rc;
+            }
+        }
+    }
+    if constexpr (kSideGeo) {
+        // an eligible host: its idle CUs run the next blocks of the queue's head
+        if (!done && !g_side.empty() && mt == 16 && nb == 1 && waves == 4 && a.ksplit == 1 && (mode == MODE_RAW || mode == MODE_AFFINE_SWISH)) {
+            SideConv &sc = g_side.front();
+            const int na = conv_grid_x(a);
+            int take = sc.total - sc.next;
+            take = take < sc.budget ? take : sc.budget;
+            take = take < kSideChipWorkgroups - na ? take : kSideChipWorkgroups - na;
+            if (take > 0) {
+                if (sc.nb == 2) launch_conv_side<K31_16, 1, K31_16, 2, DST_NCHW, 4>(a, sc.a, mode, na, sc.next, take, st);
+                else launch_conv_side<K31_16, 1, K31_16, 1, DST_NCHW, 4>(a, sc.a, mode, na, sc.next, take, st);
+                sc.next += take;
+                g_side_hosted.fetch_add(take, std::memory_order_relaxed);
+                if (sc.next >= sc.total) g_side.pop_front();
+                done = true;
             }
         }
     }
@@ -720,11 +818,30 @@ extern "C" int sige_hip_conv_pair_begin(void) {
 extern "C" int sige_hip_conv_pair_end(void) {
     SIGE_PLAN_HOOK0(sige_hip_conv_pair_end);
     g_pairing = false;
+    g_side_armed = 0;  // (a side_begin whose conv never came does not outlive the block)
     const int rc = flush_held();
+    if (rc != SIGE_HIP_OK) (void)flush_side();  // (an error exit leaves nothing queued)
     return rc != SIGE_HIP_OK ? rc : launch_status(0);
 }
 
 extern "C" int64_t sige_hip_conv_pairs_fused(void) { return (int64_t)g_pairs_fused.load(std::memory_order_relaxed); }
+
+extern "C" int sige_hip_conv_side_begin(int max_side_workgroups_per_host) {
+    SIGE_PLAN_HOOK_NOSTREAM(sige_hip_conv_side_begin, max_side_workgroups_per_host);
+    if (max_side_workgroups_per_host <= 0) return SIGE_HIP_EINVAL;
+    g_side_armed = max_side_workgroups_per_host;
+    return SIGE_HIP_OK;
+}
+
+extern "C" int sige_hip_conv_side_flush(void) {
+    SIGE_PLAN_HOOK0(sige_hip_conv_side_flush);
+    g_side_armed = 0;
+    return flush_side();
+}
+
+extern "C" int64_t sige_hip_conv_side_workgroups(int flushed) {
+    return (int64_t)(flushed ? g_side_flushed : g_side_hosted).load(std::memory_order_relaxed);
+}
 
 extern "C" size_t sige_hip_block_conv_packed_size(int Cout, int Cin, int kH, int kW, int R, int S,
                                                   int strideH, int strideW, int groups) {
@@ -1106,18 +1223,21 @@ extern "C" int sige_hip_gather_conv_nhwc(int compute, const float *x, const floa
     const int Cin = C1 + C2;
     const bool f16 = compute == 1;
     const bool aff_ok = (!scale && !shift) || (scale && shift && scaleC == Cin && shiftC == Cin && scaleB == shiftB && (scaleB == 1 || scaleB == B));
-    if ((compute == 0 || f16) && B > 0 && N > 0 && aff_ok &&
+    // (a conv that sige_hip_conv_side_begin waits for stays on the stacked-block kernels, where it can be queued)
+    if ((compute == 0 || f16) && B > 0 && N > 0 && aff_ok && !(g_side_armed > 0 && compute == 0 && to_full) &&
         tile3_takes(packed_tile3, min_blocks, B, N, C1, C2, Cout, kH, kW, bH, bW, strideH, strideW, as_stream(stream), f16, f16 ? H : 0, f16 ? W : 0)) {
         const int rc = tile_conv3_launch(T3_GATHER, x, x2, B, C1, C2, H, W, upsample2x, active_indices, N, nullptr, 0, 0, scale, shift,
                                          scale ? scaleB : 0, activation, packed_tile3, bias, Cout, to_full, offsetH, offsetW, Ho, Wo,
                                          to_full ? residual : nullptr, nullptr, nullptr, 0, 0, 0, 0, 0, out_scale, out_shift, out_activation,
                                          twin0, twin0_scale, twin0_shift, twin1, twin1_scale, twin1_shift, out, stream, f16 ? WIDE_F16 : WIDE_F32, 0, 0);
-        if (rc != SIGE_HIP_EUNSUPPORTED) return rc;
+        if (rc != SIGE_HIP_EUNSUPPORTED) { g_side_armed = 0; return rc; }
     }
-    return SIGE_BY_COMPUTE(compute, gather_conv_nhwc_impl, x, x2, B, C1, C2, H, W, bH, bW, active_indices, N, scale, scaleB, scaleC, shift, shiftB,
-                           shiftC, activation, packed, bias, Cout, kH, kW, strideH, strideW, to_full, offsetH, offsetW, residual, Ho, Wo,
-                           workspace, workspace_floats, out_scale, out_shift, out_activation, upsample2x, twin0, twin0_scale, twin0_shift,
-                           twin1, twin1_scale, twin1_shift, out, stream);
+    const int rc = SIGE_BY_COMPUTE(compute, gather_conv_nhwc_impl, x, x2, B, C1, C2, H, W, bH, bW, active_indices, N, scale, scaleB, scaleC, shift, shiftB,
+                                   shiftC, activation, packed, bias, Cout, kH, kW, strideH, strideW, to_full, offsetH, offsetW, residual, Ho, Wo,
+                                   workspace, workspace_floats, out_scale, out_shift, out_activation, upsample2x, twin0, twin0_scale, twin0_shift,
+                                   twin1, twin1_scale, twin1_shift, out, stream);
+    g_side_armed = 0;  // (sige_hip_conv_side_begin is spent on THIS call, queued or not: it never waits for a later, unrelated conv)
+    return rc;
 }
 
 // `y` -- the cached tensor of the ScatterGather, or its activated copy -- holds halves when y_f16 != 0 (fp16-STORED caches:

@@ -1208,6 +1208,35 @@ void launch_conv_pair(ConvArgs a, ConvArgs b, int mode_a, hipStream_t st);
     }
 
 
+// A conv launch that takes a slice of ANOTHER, deferred conv along (a "side" conv: sige_hip_conv_side_begin).  Workgroups
+// [0, na) run conv A exactly as in a launch of its own; workgroup na + i runs block b_off + i of conv B's OWN grid -- B is a 3x3
+// body here, with its own NB -- so B's result does not depend on how its grid is sliced over hosts.  Both stage raw or
+// activated values through a channels-last gather into a full tensor.  LDS and registers: the larger of the two bodies.  As in
+// conv_pair_kernel B is never K-split (its workgroups with blockIdx.y > 0 leave at once).  na = 0: the rest of B alone.
+template <typename GA, int NBA, typename GB, int NBB, int DST, int W, int MODEA>
+__global__ __launch_bounds__(64 * W) void conv_side_kernel(const ConvArgs a, const ConvArgs b, const int na, const int b_off) {
+    kernarg_touch<2 * sizeof(ConvArgs)>();
+    constexpr int LA = conv_lds_floats<GA, NBA, MODEA, LAYOUT_NHWC, W>();
+    constexpr int LB = conv_lds_floats<GB, NBB, MODE_RAW, LAYOUT_NHWC, W>();
+    __shared__ __attribute__((aligned(16))) float smem[cmax(LA, LB)];
+    if ((int)blockIdx.x < na)
+        conv_mfma_body<GA, NBA, SRC_GATHER, MODEA, DST, LAYOUT_NHWC, W>(a, blockIdx.x, blockIdx.y, smem);
+    else if (blockIdx.y == 0)
+        conv_mfma_body<GB, NBB, SRC_GATHER, MODE_RAW, DST, LAYOUT_NHWC, W>(b, b_off + (int)blockIdx.x - na, 0, smem);
+}
+
+// a: the host (na = 0: unused, nothing of it runs), b: the side conv, blocks [b_off, b_off + nb_blocks) of its grid
+template <typename GA, int NBA, typename GB, int NBB, int DST, int W>
+void launch_conv_side(ConvArgs a, ConvArgs b, int mode_a, int na, int b_off, int nb_blocks, hipStream_t st);
+
+#define SIGE_CONV_SIDE_INSTANTIATE(GA, NBA, GB, NBB, DST, W)                                              \
+    template <> void launch_conv_side<GA, NBA, GB, NBB, DST, W>(ConvArgs a, ConvArgs b, int mode_a, int na, int b_off, \
+                                                                int nb_blocks, hipStream_t st) {          \
+        const dim3 grid(na + nb_blocks, na ? a.ksplit : 1);                                               \
+        if (mode_a == MODE_RAW) conv_side_kernel<GA, NBA, GB, NBB, DST, W, MODE_RAW><<<grid, 64 * W, 0, st>>>(a, b, na, b_off); \
+        else conv_side_kernel<GA, NBA, GB, NBB, DST, W, MODE_AFFINE_SWISH><<<grid, 64 * W, 0, st>>>(a, b, na, b_off); \
+    }
+
 template <typename G, int NB, int SRC, int DST, int LAYOUT, int W>
 void launch_conv_geo(ConvArgs a, int mode, hipStream_t st);
 

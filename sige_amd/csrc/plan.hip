@@ -162,6 +162,7 @@ extern "C" int sige_hip_plan_run(void *plan, int section, void *stream) {
         //  kernels cover: the caller records again under the new mask)
         if (rc != SIGE_HIP_OK) {
             (void)sige_hip_conv_pair_end();  // (a replay that stops between pair_begin and pair_end must not leave a held conv behind)
+            (void)sige_hip_conv_side_flush();  // (... nor a queued side conv)
             return rc;
         }
     }

@@ -141,7 +141,12 @@ inline void plan_record(int (*fn)(A...), B... b) {
     do {                                                                                                \
         if (sige::g_plan_rec) sige::plan_record<true, SIGE_PLAN_UNPAREN patches>(&fn, __VA_ARGS__);   \
     } while (0)
-// entry points without arguments (conv_pair_begin / _end)
+// entry points whose arguments hold neither a count nor a stream (conv_side_begin)
+#define SIGE_PLAN_HOOK_NOSTREAM(fn, ...)                                               \
+    do {                                                                               \
+        if (sige::g_plan_rec) sige::plan_record<false>(&fn, __VA_ARGS__);             \
+    } while (0)
+// entry points without arguments (conv_pair_begin / _end, conv_side_flush)
 #define SIGE_PLAN_HOOK0(fn)                                        \
     do {                                                           \
         if (sige::g_plan_rec) sige::plan_record<false>(&fn);       \

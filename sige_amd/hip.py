@@ -80,6 +80,9 @@ _SIGNATURES = {
     "sige_hip_conv_pair_begin": (_c_int, []),
     "sige_hip_conv_pair_end": (_c_int, []),
     "sige_hip_conv_pairs_fused": (ctypes.c_int64, []),
+    "sige_hip_conv_side_begin": (_c_int, [_c_int]),
+    "sige_hip_conv_side_flush": (_c_int, []),
+    "sige_hip_conv_side_workgroups": (ctypes.c_int64, [_c_int]),
     "sige_hip_attention_workspace": (_c_sz, [_c_int] * 3),
     "sige_hip_attention_f32": (_c_int, [_c_vp, _c_int, _c_int, _c_int, ctypes.c_float, _c_vp, _c_vp, _c_vp]),
     "sige_hip_copy_f32": (_c_int, [_c_vp, _c_vp, _c_sz, _c_vp]),
@@ -1144,6 +1147,38 @@ def conv_pairs_fused() -> int:
     return int(lib().sige_hip_conv_pairs_fused())
 
 
+_side_state = threading.local()  # .keep: operands of the convs queued by conv_side_begin() and not yet flushed; .armed
+
+
+def conv_side_begin(budget: int = 256):
+    """The next gather_conv_cl call of this thread, if eligible -- exact fp32, 3x3 / stride 1, raw staging, full-tensor
+    destination, no twins -- is queued instead of launched (if not, it launches as ever: the call spends the begin either way); later single 3x3 launches of 16 x 16 blocks on the same stream take
+    up to min(`budget`, 256 - their own grid) of its workgroups along (sige_hip_conv_side_begin, include/sige_hip.h).  Its
+    output may be read after conv_side_flush() only; its operands are kept alive until then."""
+    _check(lib().sige_hip_conv_side_begin(int(budget)), "conv_side_begin")
+    _side_state.armed = True
+    if getattr(_side_state, "keep", None) is None:
+        _side_state.keep = []
+
+
+def conv_side_flush(like: Optional[torch.Tensor] = None):
+    """Launch what no host has taken of the queued side convs (first queued first; `like`: a tensor of their device)."""
+    try:
+        with conv_pair(like)._on_device():
+            _check(lib().sige_hip_conv_side_flush(), "conv_side_flush")
+    finally:
+        _side_state.armed = False
+        rec = plan_recorder()
+        if rec is not None and getattr(_side_state, "keep", None):
+            rec.keep.append(_side_state.keep)  # (a launch plan replays the queued calls: their operands live as long as it does)
+        _side_state.keep = None
+
+
+def conv_side_workgroups() -> Tuple[int, int]:
+    """(hosted, flushed): side-conv workgroups that ran inside host launches | in launches of their own, so far in this process."""
+    return int(lib().sige_hip_conv_side_workgroups(0)), int(lib().sige_hip_conv_side_workgroups(1))
+
+
 def conv_force_ksplit(ksplit: int = 0):
     """Benchmark knob: cross-workgroup K split of the channels-last launches with a workspace (0 = automatic)."""
     tuning_set("conv_ksplit", ksplit)
@@ -1639,6 +1674,8 @@ def gather_conv_cl(x, x2, block: Tuple[int, int], activeIndices, scale, shift, a
         fargs = (1, full["offset"][0], full["offset"][1], None if r is None else r.data_ptr(), Ho, Wo)
     compute = _compute_id(packed)
     t3 = _tile3_route(packed, B * N, C1, C2, Cout, kernel, stride, block)  # (TILE3 = True: the v3 kernel, forced)
+    if getattr(_side_state, "armed", False):
+        t3 = None  # (conv_side_begin() waits for THIS call: it stays on the kernels that can queue it)
     if t3 is not None and N > 0:
         if twins and full is None:
             raise RuntimeError("gather_conv_cl: twins need a full-tensor destination")
@@ -1691,6 +1728,9 @@ def gather_conv_cl(x, x2, block: Tuple[int, int], activeIndices, scale, shift, a
     keep = getattr(_pair_state, "keep", None)
     if keep is not None:  # (conv_pair(): a held launch reads these after this call has returned)
         keep.append((x, x2, idx, s_keep, t_keep, packed, bias_keep, out, ws, out_affine, full, twin_keep))
+    if getattr(_side_state, "armed", False):  # (conv_side_begin(): so do the hosts of a queued conv, until conv_side_flush())
+        _side_state.armed = False
+        _side_state.keep.append((x, x2, idx, s_keep, t_keep, packed, bias_keep, out, ws, out_affine, full, twin_keep))
     return out
 
 

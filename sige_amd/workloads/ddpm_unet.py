@@ -237,6 +237,77 @@ class ResBlock(SIGEModule, _TwinProducer):
     def clear_cache(self):
         self.affine = {}
         self._drop_twin_links()
+        self.__dict__.pop("_split1", None)
+        self.__dict__.pop("_side_product", None)
+
+    # ---- conv1 of an up block split at the torch.cat (DDPMSparseUNet.SIDE_SKIP_PRODUCTS) ----
+    def split_conv1(self, ch: int):
+        """(conv_h, conv_s): conv1 over cat(h, skip) as two convs, W[:, :ch] with the bias and W[:, ch:] without, so that
+        conv1(cat(a, b)) = conv_h(a) + conv_s(b).  Derived nn.Conv2d objects like AttnBlock.folded_proj(): neither a Parameter, a
+        buffer nor a submodule (the state dict keeps the reference's keys); rebuilt when conv1's weight or bias has been replaced,
+        moved or edited in place (address, version counter, shape, device, dtype), when its compute dtype changes, and after
+        clear_cache()."""
+        params = (self.conv1.weight, self.conv1.bias)
+        key = tuple(None if p is None else (p.data_ptr(), p._version, tuple(p.shape), p.device, p.dtype) for p in params)
+        key += (getattr(self.conv1, "compute_dtype", "f32"), ch)
+        entry = self.__dict__.get("_split1")
+        if entry is None or entry[0] != key:
+            w, b = (None if p is None else p.detach() for p in params)
+            cin, cout = w.shape[1], w.shape[0]
+            conv_h = nn.Conv2d(ch, cout, 3, 1, 1, bias=b is not None, device="meta")
+            conv_s = nn.Conv2d(cin - ch, cout, 3, 1, 1, bias=False, device="meta")
+            conv_h.weight = nn.Parameter(w[:, :ch].contiguous(), requires_grad=False)
+            conv_s.weight = nn.Parameter(w[:, ch:].contiguous(), requires_grad=False)
+            if b is not None:
+                conv_h.bias = nn.Parameter(b.clone(), requires_grad=False)
+            conv_h.compute_dtype = conv_s.compute_dtype = key[-2]
+            entry = (key, conv_h, conv_s)
+            self.__dict__["_split1"] = entry  # (not through nn.Module.__setattr__: that would register the convs as submodules)
+        return entry[1], entry[2]
+
+    def side_product_ready(self, skip: torch.Tensor):
+        """The activated twin of `skip` if this block can take conv1's skip half as a precomputed product in this forward -- a
+        dense up block in sparse mode on channels-last fp32 GPU tensors, one image, exact-fp32 conv1, the skip's twin written and
+        the twin of h promised by its producer -- else None (conv1 runs unsplit, as without the flag)."""
+        from .. import hip
+
+        if self.sparse_main or self.mode != "sparse" or not (self.use_twins and self.preactivate) or self.overlap:
+            return None
+        if hip.TILE3:  # (every eligible launch forced onto the tile conv v3: no launch is left that could host a product)
+            return None
+        if not (isinstance(skip, torch.Tensor) and skip.is_cuda and skip.dtype == torch.float32 and skip.shape[0] == 1 and hip.is_cl(skip)):
+            return None
+        if getattr(self.conv1, "compute_dtype", "f32") != "f32" or hip.get_edit_batch() != 1 or self.cache_id not in self.affine:
+            return None
+        ch = self.cin - skip.shape[1]
+        if ch <= 0 or not hip.cl_supported(ch, skip.shape[1], self.cout) or self.affine[self.cache_id][0].shape[0] != 1:
+            return None
+        # (the derived convs are built and packed as soon as the block qualifies by shape -- in the first sparse forward, next
+        #  to every other weight -- so that no later forward launches pack kernels)
+        from ..nn.dense import _packed
+
+        for conv in self.split_conv1(ch):
+            _packed(conv, (6, 6))
+        key_h, key_s = ((id(self), i, self._aff_gen, self.cache_id) for i in (0, 1))
+        if key_h not in self._twin_links:
+            return None
+        return getattr(skip, "_sige_twins", {}).get(key_s)
+
+    def submit_side_product(self, skip: torch.Tensor) -> bool:
+        """Queue W[:, ch:] * act(skip) as a side conv (hip.conv_side_begin) into a persistent buffer; _sparse_dense picks it up."""
+        from .. import hip
+
+        tw = self.side_product_ready(skip)
+        if tw is None:
+            return False
+        _, conv_s = self.split_conv1(self.cin - skip.shape[1])
+        B, _, H, W = skip.shape
+        buf = demand_buffer(conv_s, ("side", self.cache_id), (B, self.cout, H, W), skip.device)
+        tiles = hip.all_tiles(H, W, (4, 4), (1, 1), (1, 1), skip.device)
+        hip.conv_side_begin()
+        fused_conv2d(conv_s, tw, tiles=tiles, out=buf)
+        self.__dict__["_side_product"] = (buf, tw)
+        return True
 
     # ---- activated twins (cfg.conv1_twins) ----
     def _twin_scatter(self):
@@ -449,6 +520,13 @@ class ResBlock(SIGEModule, _TwinProducer):
         join = lambda: None  # noqa: E731
         if self.preactivate:
             tw = self._twin_inputs([x] if x2 is None else [x, x2], s1, t1)
+            side = self.__dict__.pop("_side_product", None)
+            if side is not None:
+                from .. import hip
+
+                hip.conv_side_flush(x)  # (what no host has taken runs now: the product is complete behind this)
+                if tw is None or demand is not None or tw[1] is not side[1]:
+                    side = None  # (no twin of h after all: the unsplit conv1, as without the flag)
             with self._pairing(x):
                 if self.cin == self.cout:
                     skip = x if x2 is None else torch.cat([x, x2], dim=1)
@@ -456,7 +534,10 @@ class ResBlock(SIGEModule, _TwinProducer):
                     # (the shortcut is needed where conv2 adds it: on conv2's cells)
                     skip, join = self._shortcut_async(lambda: fused_conv2d(self.nin_shortcut, x, x2=x2,
                                                                            **self._demand_args(self.nin_shortcut, demand, 0, x)), x)
-                if tw is not None:  # the producers wrote SiLU(s1 * x + t1): conv1 stages raw values
+                if side is not None:  # conv1 = W[:, :ch] * act(h) + b + the skip product computed behind earlier launches
+                    conv_h, _ = self.split_conv1(x.shape[1])
+                    h = fused_conv2d(conv_h, tw[0], None, None, "identity", residual=side[0], out_affine=(s2, t2, "swish"))
+                elif tw is not None:  # the producers wrote SiLU(s1 * x + t1): conv1 stages raw values
                     h = fused_conv2d(self.conv1, tw[0], None, None, "identity", x2=(tw[1] if len(tw) > 1 else None),
                                      out_affine=(s2, t2, "swish"), **self._demand_args(self.conv1, demand, 1, x))
                 else:
@@ -935,6 +1016,40 @@ class DDPMSparseUNet(SIGEModel):
     # `rebuild_derived_caches()` after an in-place rewrite of the cache.  False: every tile, fresh tensors (A/B runs, tests).
     DENSE_ON_CHANGE = True
 
+    # ---- the skip half of a dense up level's conv1, computed behind the small launches of the levels below ---------
+    # conv1 of an up block reads cat(h, skip); on the cached affine with activated twins it splits into W[:, :ch] * act(h) + b and
+    # W[:, ch:] * act(skip), and the second depends on the down path only.  Once the down blocks of such a level are done, its skip
+    # products are queued as side convs (hip.conv_side_begin) in the order the up path consumes them; the single 3x3 launches of
+    # the levels below -- half a chip of workgroups each -- take their blocks along, and the up block's conv1 runs over half the K
+    # with the product as its residual.  False: today's launches exactly.
+    SIDE_SKIP_PRODUCTS = True
+
+    def _side_levels(self):
+        """The up levels whose skip products are submitted: dense, with a level below them (its launches are the hosts), and no
+        demand stage -- whether or not DENSE_ON_DEMAND is on: with the flag off such a level runs every tile, but its products would
+        take the hosts of the levels below it first and leave the others' to launches of their own."""
+        demand = {name for name, _ in self._demand_stages()}
+        out = []
+        for lvl, stage in enumerate(self.up):
+            if lvl >= self.num_levels - 1 or any(b.sparse_main for b in stage.block):
+                continue
+            if ("up.%d" % lvl) in demand or ("up.%d" % lvl) in (getattr(self, "_demand_lists", None) or {}):
+                continue
+            out.append(lvl)
+        return out
+
+    def _submit_side_products(self, lvl: int, hs):
+        """Behind the blocks of down[lvl]: hs[-1], hs[-2], ... are the skips of up[lvl].block[0], [1], ..."""
+        blocks = self.up[lvl].block
+        for block in blocks:
+            block.__dict__.pop("_side_product", None)  # (nothing of an earlier forward survives)
+        if not (self.SIDE_SKIP_PRODUCTS and self.mode == "sparse" and self.edit_batch == 1 and lvl in self._side_levels()):
+            return
+        if len(hs) < len(blocks) or not all(isinstance(h, torch.Tensor) and h.is_cuda for h in hs[-len(blocks):]):
+            return
+        for i, block in enumerate(blocks):
+            block.submit_side_product(hs[-1 - i])
+
     def _change_stages(self):
         """[(level, stage, the Downsample that feeds it)]: dense, no attention, input from a tiled Downsample, and wider than
         its region can grow (2 pixels per ResBlock on each side of a written tile)."""
@@ -1131,6 +1246,7 @@ class DDPMSparseUNet(SIGEModel):
                 if len(stage.attn):
                     h = stage.attn[i](h)
                 hs.append(h)
+            self._submit_side_products(lvl, hs)
             if lvl != self.num_levels - 1:
                 hs.append(stage.downsample(hs[-1]))
 
