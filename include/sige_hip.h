@@ -599,6 +599,22 @@ int sige_hip_conv3x3_small_cout_act_nhwc_f32(const float *x, int B, int C, int H
                                              const float *weight, const float *bias, int Cout, int out_activation,
                                              float *out, void *stream);
 
+/* ---- latent head of the SD VAE encoder (csrc/conv_latent_head.hip): norm_out -> SiLU -> conv_out with the autoencoder's 1x1
+ * quant_conv folded into the weights (sige_model.py:272-275, ldm/models/autoencoder.py encode()), which the reference runs densely in
+ * every mode.  out [B,H,W,Cout] = conv3x3_pad1(act(scale*x + shift)) + bias with the conventions of
+ * sige_hip_conv3x3_small_cout_nhwc_f32 (zero padding of the ACTIVATED tensor; act in SIGE_HIP_ACT_IDENTITY | _SWISH), for
+ * 5 <= Cout <= 16, C % 64 == 0, C <= 512, all pointers 16-byte aligned; anything else is SIGE_HIP_EUNSUPPORTED without a launch.
+ * Exact fp32 operands on the matrix cores, ONE launch; a channel split over workgroups is added up in split order inside the
+ * launch, so the result is bit-identical from run to run.
+ * z != NULL (Cout even): the posterior of DiagonalGaussianDistribution as a second output, z [B,H,W,Cout/2] =
+ * latent_scale * (mean + exp(0.5 * clamp(logvar, -30, 20)) * noise), mean = out[..., :Cout/2], logvar = out[..., Cout/2:],
+ * noise [B,H,W,Cout/2] (NULL: the mode, latent_scale * mean).  The moments `out` are always written. */
+int sige_hip_conv3x3_latent_head_nhwc_f32(const float *x, int B, int C, int H, int W,
+                                          const float *scale, int scaleB, int scaleC,
+                                          const float *shift, int shiftB, int shiftC, int activation,
+                                          const float *weight, const float *bias, int Cout, float *out,
+                                          const float *noise, float latent_scale, float *z, void *stream);
+
 /* ---- channels-last helpers of the GauGAN SPADE generator's sparse forward (csrc/spade_ops.hip): what was left to torch kernels
  * in round 4, so that the whole forward goes through this library and a launch plan can record it.
  * resize_nearest: F.interpolate(mode="nearest") by an INTEGER factor up or down, x [B,H,W,C] -> out [B,Ho,Wo,C]

@@ -346,7 +346,7 @@ struct WideWsPool { float *buf = nullptr; size_t ring_pos = 0, graph_pos = 0; bo
 static WideWsPool g_wide_ws[32];
 static std::mutex g_wide_ws_mu;
 
-static float *wide_workspace(hipStream_t st, size_t floats) {
+float *split_workspace(hipStream_t st, size_t floats) {  // (common.hpp: the latent head's channel split draws on it too)
     int dev = -1;
     if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 32 || floats > kWideRing) return nullptr;
     hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
@@ -414,7 +414,7 @@ extern "C" int sige_hip_attention_wide_f32(const float *q, int ldq, const float 
     a.ws = nullptr; a.tickets = nullptr;
     if (ksplit > 1) {
         a.tickets = split_tickets(st, units);
-        if (a.tickets) a.ws = wide_workspace(st, (size_t)units * ksplit * (4 * G + 1) * 256);
+        if (a.tickets) a.ws = split_workspace(st, (size_t)units * ksplit * (4 * G + 1) * 256);
         if (!a.tickets || !a.ws) ksplit = 1;
     }
     if (ksplit < 1) ksplit = 1;

@@ -111,6 +111,10 @@ inline int launch_status(int kernels = 1) {
 // (or, during a hipGraph capture, for the life of the graph); nullptr = unavailable, the caller must not split
 int32_t *split_tickets(hipStream_t st, long blocks);
 
+// (attention_wide.hip) workspace of a split whose slices are added up inside the launch: `floats` floats that stay valid like the
+// tickets do; nullptr = unavailable (first use during a capture, region exhausted), the caller must not split
+float *split_workspace(hipStream_t st, size_t floats);
+
 // All-reduce over the 16 lanes of a DPP row (lanes 16r .. 16r+15 of a wave) on the VALU's data-parallel-primitive path: quad
 // swaps (xor 1, xor 2), then the mirror of a half row and of the row -- four VALU operations, every lane ends with the same
 // bits (each step combines two disjoint, complete groups symmetrically).  __shfl_xor compiles to ds_bpermute_b32: a trip

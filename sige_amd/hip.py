@@ -164,6 +164,8 @@ _SIGNATURES = {
     "sige_hip_convert_f16_f32": (_c_int, [_c_vp, _c_vp, _c_sz, _c_vp]),
     "sige_hip_convert_f32_f16": (_c_int, [_c_vp, _c_vp, _c_sz, _c_vp]),
     "sige_hip_conv3x3_small_cout_act_nhwc_f32": (_c_int, [_c_vp] + [_c_int] * 5 + [ctypes.c_float, _c_vp, _c_vp, _c_int, _c_int, _c_vp, _c_vp]),
+    "sige_hip_conv3x3_latent_head_nhwc_f32": (
+        _c_int, [_c_vp] + [_c_int] * 4 + [_c_vp, _c_int, _c_int] * 2 + [_c_int, _c_vp, _c_vp, _c_int, _c_vp, _c_vp, ctypes.c_float, _c_vp, _c_vp]),
     "sige_hip_resize_nearest_nhwc_f32": (_c_int, [_c_vp] + [_c_int] * 6 + [_c_vp, _c_vp]),
     "sige_hip_act_split_nhwc_f32": (_c_int, [_c_vp, ctypes.c_int64, _c_int, _c_int, ctypes.c_int64, _c_int, ctypes.c_float, _c_vp, _c_vp]),
     "sige_hip_scatter_gather_split_nhwc_f32": (
@@ -2349,6 +2351,47 @@ def conv3x3_small_cout_cl(x, weight, bias, scale=None, shift=None, activationNam
         return None
     _check(status, "conv3x3_small_cout_cl")
     return out
+
+
+def conv3x3_latent_head_cl(x, weight, bias, scale=None, shift=None, activationName="identity", noise=None, latent_scale=None,
+                           out=None, z_out=None):
+    """conv(act(scale*x + shift)) + bias for a 3x3 / padding-1 conv with 5..16 output channels on a full channels-last tensor with
+    C % 64 == 0, C <= 512 (the SD VAE encoder's norm_out -> swish -> conv_out tail, quant_conv folded into `weight` by the caller):
+    one launch, exact fp32 on the matrix cores (include/sige_hip.h: sige_hip_conv3x3_latent_head_nhwc_f32).  Returns the moments
+    [B,Cout,H,W]; with `latent_scale` given, (moments, z): z [B,Cout/2,H,W] = latent_scale * (mean + exp(0.5 * clamp(logvar, -30,
+    20)) * noise), `noise` [B,Cout/2,H,W] or None for the mode.  `out` / `z_out`: channels-last fp32 destinations (default: fresh
+    tensors).  None if unsupported (nothing is launched)."""
+    x = _req_cl(x, "x")
+    B, C, H, W = x.shape
+    w = _req(weight.detach(), torch.float32, "weight")
+    Cout = w.shape[0]
+    if tuple(w.shape[1:]) != (C, 3, 3):
+        return None
+    bias_keep = _vec(bias, "bias")
+    (sa, s_keep), (ta, t_keep) = _cvec(scale, "scale"), _cvec(shift, "shift")
+    want_z = latent_scale is not None or noise is not None
+    if want_z and Cout % 2:
+        return None
+    if noise is not None:
+        if tuple(noise.shape) != (B, Cout // 2, H, W):
+            raise ValueError("conv3x3_latent_head_cl: `noise` must be [B,Cout/2,H,W]")
+        noise = _req_cl(noise, "noise")
+    def dest(t, shape, name):
+        if t is None:
+            return _empty_cl(shape, x.device)
+        if tuple(t.shape) != shape or t.dtype != torch.float32 or not t.is_cuda or not t.is_contiguous(memory_format=CL):
+            raise ValueError("conv3x3_latent_head_cl: `%s` must be a channels-last fp32 %s GPU tensor" % (name, list(shape)))
+        return t
+
+    out = dest(out, (B, Cout, H, W), "out")
+    z = dest(z_out, (B, Cout // 2, H, W), "z_out") if want_z else None
+    status = lib().sige_hip_conv3x3_latent_head_nhwc_f32(x.data_ptr(), B, C, H, W, *sa, *ta, _act(activationName), w.data_ptr(),
+                                                         _p(bias_keep), Cout, out.data_ptr(), _p(noise),
+                                                         1.0 if latent_scale is None else float(latent_scale), _p(z), _stream(x))
+    if status == UNSUPPORTED:
+        return None
+    _check(status, "conv3x3_latent_head_cl")
+    return (out, z) if want_z else out
 
 
 def conv3x3_small_cout_force_scalar(on: bool):

@@ -18,7 +18,9 @@ tensors.  In sparse mode on channels-last fp32 GPU tensors:
 `NATIVE_ATTENTION = False` -- and any backend without the fused path: CPU, NCHW -- runs the reference's module chain (bmm, softmax
 over a [B,Nq,HW] score tensor, bmm, with its reshapes and copies); a shape the attention entry refuses runs that bmm chain on the
 fused q and K | V.  With in-place scatters (SIGEModel.set_scatter_inplace) the persistent K | V tensor and the attention's output rows
-are allocated by set_masks() / set_mode(), never inside a forward; without, every Scatter returns a fresh tensor as the reference's does.  Batch 1 (the reference's sparse mode calls scale.view(1, -1, 1, 1): one cached original)."""
+are allocated by set_masks() / set_mode(), never inside a forward; without, every Scatter returns a fresh tensor as the reference's does.  Batch 1 (the reference's sparse mode calls scale.view(1, -1, 1, 1): one cached original).
+
+The encoder (SIGEEncoder, sige_model.py:177) is built from the same blocks: SparseVAEEncoder, at the end of the file."""
 from dataclasses import dataclass
 from typing import Tuple
 
@@ -27,13 +29,16 @@ from torch import nn
 from torch.nn import functional as F
 
 from ..nn import Gather, Scatter, ScatterGather, ScatterWithBlockResidual, SIGEConv2d, SIGEModel, SIGEModule, paired_convs
-from ..nn.dense import group_norm_affine
-from .ddpm_unet import Upsample, norm_affine
+from ..nn.dense import group_norm_affine, input_conv2d
+from .ddpm_unet import Downsample, Upsample, norm_affine
 from .pd_unet import _as4, _fused_layout
 
 # The attention launch of the library in the tiled attention block.  False: the reference's bmm / softmax / bmm chain (A/B runs:
 # tools/vae_bench.py; tests).
 NATIVE_ATTENTION = True
+# The latent-head launch of the library (hip.conv3x3_latent_head_cl) as the encoder's tail in sparse mode.  False: the reference's
+# chain, conv_out(silu(norm_out(h))) -> quant_conv -> the posterior in torch (A/B runs: tools/vae_encoder_bench.py; tests).
+NATIVE_HEAD = True
 
 
 @dataclass
@@ -357,3 +362,214 @@ class SparseVAEDecoder(SIGEModel):
             if lvl != 0:
                 h = stage.upsample(h)
         return self._head(h)
+
+
+# ---- the encoder (sige_model.py:177-276, SIGEEncoder) ------------------------------------------------------------------------------
+@dataclass
+class VAEEncoderConfig:
+    """Defaults: configs/sige.yaml, first_stage_config.params.ddconfig (with its double_z)."""
+    ch: int = 128
+    out_ch: int = 3
+    ch_mult: Tuple[int, ...] = (1, 2, 4, 4)
+    num_res_blocks: int = 2
+    attn_resolutions: Tuple[int, ...] = ()
+    in_channels: int = 3
+    resolution: int = 256
+    z_channels: int = 4
+    double_z: bool = True
+    main_block: int = 6
+    shortcut_block: int = 4
+    attn_block: int = 4
+    groups: int = 32
+    eps: float = 1e-6
+
+
+class SparseVAEEncoder(SIGEModel):
+    """Stable Diffusion's VAE encoder as a sparse workload: the SDEdit runner encodes the original image in full mode once and every
+    edited image in sparse mode under the edit's masks (runners/sdedit_runner.py:54-62).  Module tree and state-dict keys are the
+    reference's (`conv_in`, `down.L.block.B.*`, `down.L.attn.*`, `down.L.downsample.conv`, `mid.{block_1,attn_1,block_2}`,
+    `norm_out`, `conv_out`): a checkpoint's `first_stage_model.encoder.*` loads strictly.  Every level is tiled -- the decoder's
+    residual and attention blocks, Downsample = Gather in front of a stride-2 tile conv whose zero fill is the (0,1,0,1) padding.
+
+    The tail, norm_out -> SiLU -> conv_out and the autoencoder's 1x1 `quant_conv` behind it, is dense in every mode (norm_out is a
+    TRUE GroupNorm of the edited activation).  In sparse mode on channels-last fp32 GPU tensors it is group_norm_affine + ONE
+    launch of hip.conv3x3_latent_head_cl: quant_conv is folded into conv_out's weights (no nonlinearity between them) and the
+    posterior sample rides in the launch's epilogue.  `NATIVE_HEAD = False`, CPU, NCHW and shapes the entry refuses run the
+    reference's chain.  Batch 1 in sparse mode, as the decoder."""
+
+    def __init__(self, cfg: VAEEncoderConfig = VAEEncoderConfig()):
+        super().__init__()
+        self.cfg = cfg
+        ch, mult = cfg.ch, tuple(cfg.ch_mult)
+        self.num_resolutions, self.num_res_blocks = len(mult), cfg.num_res_blocks
+        self.conv_in = nn.Conv2d(cfg.in_channels, ch, 3, 1, 1)
+        in_mult = (1,) + mult
+        res, cur = cfg.resolution, ch
+        self.down = nn.ModuleList()
+        for lvl in range(self.num_resolutions):
+            stage = nn.Module()
+            stage.block, stage.attn = nn.ModuleList(), nn.ModuleList()
+            cur, cout = ch * in_mult[lvl], ch * mult[lvl]
+            for _ in range(cfg.num_res_blocks):
+                stage.block.append(VAEResBlock(cfg, cur, cout))
+                cur = cout
+                if res in cfg.attn_resolutions:
+                    stage.attn.append(VAEAttnBlock(cfg, cur))
+            if lvl != self.num_resolutions - 1:
+                stage.downsample = Downsample(cfg, cur, sparse=True)
+                res //= 2
+            self.down.append(stage)
+        self.mid = nn.Module()
+        self.mid.block_1 = VAEResBlock(cfg, cur, cur)
+        self.mid.attn_1 = VAEAttnBlock(cfg, cur)
+        self.mid.block_2 = VAEResBlock(cfg, cur, cur)
+        self.norm_out = nn.GroupNorm(cfg.groups, cur, eps=cfg.eps)
+        self.conv_out = nn.Conv2d(cur, 2 * cfg.z_channels if cfg.double_z else cfg.z_channels, 3, 1, 1)
+        self._h0_buf = None  # conv_in's output on the active windows (alloc_buffers)
+
+    # ---- bookkeeping: as SparseVAEDecoder ----------------------------------------------------------------------------------------
+    def _attn_blocks(self):
+        return [m for m in self.modules() if isinstance(m, VAEAttnBlock)]
+
+    def _conv_in_windows(self):
+        """The Gather whose windows are all a sparse forward reads of hs[0] = conv_in(x), or None (conv_in runs densely).  The
+        encoder has no skip connections (sige_model.py:256-264): hs[0] goes to down[0].block[0] alone.  With cin == cout that block
+        reads it through `main_gather` and, as the residual, through `scatter` = Scatter(main_gather) -- one index list, the
+        residual inside the windows' 4x4 output blocks.  With cin != cout `shortcut_gather` reads it under a second index list:
+        dense then."""
+        first = self.down[0].block[0]
+        g = first.main_gather
+        if first.cin != first.cout or not isinstance(first.scatter, Scatter) or first.scatter.gather.module is not g:
+            return None
+        if g.active_indices is None or g.input_res is None or tuple(g.model_stride) != (1, 1):
+            return None
+        return g
+
+    def _alloc_buffers(self):
+        for m in self._attn_blocks():
+            m.alloc_buffers()
+        g = self._conv_in_windows()
+        if g is not None and g.active_indices.is_cuda:
+            shape = (1, self.conv_in.out_channels) + tuple(g.input_res)
+            buf = self._h0_buf
+            if buf is None or tuple(buf.shape) != shape or buf.device != g.active_indices.device:
+                self._h0_buf = torch.zeros(shape, dtype=torch.float32, device=g.active_indices.device).contiguous(memory_format=torch.channels_last)
+
+    def persistent_buffers(self):
+        """(tests) [(name, tensor, rewritten)], see VAEAttnBlock; `conv_in`: the first conv's output, written on the active windows
+        of down[0].block[0] and read nowhere else."""
+        out = [(name, buf, rw) for m in self._attn_blocks() for name, buf, rw in m.persistent_buffers()]
+        if self._h0_buf is not None:
+            out.append(("conv_in", self._h0_buf, True))
+        return out
+
+    def clear_cache(self):
+        super().clear_cache()
+        self._h0_buf = None
+        self.__dict__.pop("_head_fold", None)
+
+    def set_plain_dense(self, plain: bool):
+        """full mode = the stock dense encoder (F.group_norm, no cache bookkeeping): what a speedup is quoted against."""
+        for m in self.modules():
+            if isinstance(m, (VAEResBlock, VAEAttnBlock, Downsample)):
+                m.plain = plain
+
+    def set_masks(self, masks):
+        super().set_masks(masks)
+        self._alloc_buffers()
+
+    def set_mode(self, mode: str):
+        super().set_mode(mode)
+        if mode == "sparse":
+            self._alloc_buffers()
+
+    def set_cache_id(self, cache_id: int):
+        super().set_cache_id(cache_id)
+        if self.mode == "sparse":
+            self._alloc_buffers()
+
+    # ---- derived: conv_out with quant_conv folded in ----------------------------------------------------------------------------
+    def folded_head(self, quant_conv: nn.Conv2d):
+        """(weight [2z,C,3,3], bias [2z]) of quant_conv(conv_out(.)): W' = Wq Wc, b' = Wq bc + bq, products in fp64.  Not a
+        Parameter or a buffer -- the state dict keeps the reference's keys; rebuilt when one of the four parameters has been
+        replaced, moved or edited in place (the key of VAEAttnBlock.folded_kv) and after clear_cache()."""
+        params = (self.conv_out.weight, self.conv_out.bias, quant_conv.weight, quant_conv.bias)
+        key = tuple(None if p is None else (p.data_ptr(), p._version, tuple(p.shape), p.device, p.dtype) for p in params)
+        entry = self.__dict__.get("_head_fold")
+        if entry is None or entry[0] != key:
+            with torch.no_grad():
+                wq = quant_conv.weight.detach().double().flatten(1)  # [2z, 2z]
+                wc, bc = self.conv_out.weight.detach().double(), self.conv_out.bias.detach().double()
+                w = torch.einsum("oi,ichw->ochw", wq, wc)
+                b = wq @ bc
+                if quant_conv.bias is not None:
+                    b = b + quant_conv.bias.detach().double()
+                entry = (key, w.float().contiguous(), b.float().contiguous())
+            self.__dict__["_head_fold"] = entry
+        return entry[1], entry[2]
+
+    # ---- forward -----------------------------------------------------------------------------------------------------------------
+    def _conv_in(self, x):
+        if self.mode != "sparse":
+            h = self.conv_in(x)
+        else:
+            g, buf = self._conv_in_windows(), self._h0_buf
+            if (g is not None and buf is not None and x.is_cuda and x.shape[0] == 1 and tuple(buf.shape[2:]) == tuple(x.shape[2:])
+                    and buf.device == x.device):
+                h = input_conv2d(self.conv_in, x, tiles=(g.active_indices, tuple(g.block_size)), out=buf)
+            else:
+                h = input_conv2d(self.conv_in, x)
+        if x.is_contiguous(memory_format=torch.channels_last) and not x.is_contiguous():
+            h = h.contiguous(memory_format=torch.channels_last)  # (MIOpen may hand back NCHW for 3 input channels)
+        return h
+
+    def _body(self, x):
+        h = self._conv_in(x)
+        for lvl in range(self.num_resolutions):
+            stage = self.down[lvl]
+            for i, block in enumerate(stage.block):
+                h = block(h)
+                if len(stage.attn):
+                    h = stage.attn[i](h)
+            if lvl != self.num_resolutions - 1:
+                h = stage.downsample(h)
+        h = self.mid.block_1(h)
+        h = self.mid.attn_1(h)
+        return self.mid.block_2(h)
+
+    def _tail(self, h, quant_conv=None, posterior=False, noise=None, scale_factor=1.0):
+        """norm_out (a TRUE GroupNorm of the edited activation, sige_model.py:272-275) -> SiLU -> conv_out [-> quant_conv [-> the
+        posterior]].  Returns the moments, or (moments, z)."""
+        if (NATIVE_HEAD and self.mode == "sparse" and _fused_layout(h) and (quant_conv is None or
+                (tuple(quant_conv.kernel_size) == (1, 1) and quant_conv.groups == 1 and quant_conv.in_channels == self.conv_out.out_channels))):
+            from .. import hip
+
+            w, b = (self.conv_out.weight, self.conv_out.bias) if quant_conv is None else self.folded_head(quant_conv)
+            if noise is not None:
+                noise = noise.to(h.device, torch.float32)
+            so, to = group_norm_affine(h, self.norm_out)
+            out = hip.conv3x3_latent_head_cl(h, w, b, so, to, "swish", noise=noise, latent_scale=scale_factor if posterior else None)
+            if out is not None:
+                return out
+        m = self.conv_out(F.silu(self.norm_out(h)))
+        if quant_conv is not None:
+            m = quant_conv(m)
+        if not posterior:
+            return m
+        # DiagonalGaussianDistribution (ldm/modules/distributions/distributions.py:24-44): sample() or, without noise, mode()
+        mean, logvar = torch.chunk(m, 2, dim=1)
+        z = mean if noise is None else mean + torch.exp(0.5 * torch.clamp(logvar, -30.0, 20.0)) * noise.to(m.device, m.dtype)
+        return m, scale_factor * z
+
+    def forward(self, x: torch.Tensor) -> torch.Tensor:
+        """[B, 2z, H/8, W/8]: the reference encoder's output."""
+        return self._tail(self._body(x))
+
+    def moments(self, x: torch.Tensor, quant_conv: nn.Conv2d) -> torch.Tensor:
+        """quant_conv(forward(x)): the parameters of the posterior (SIGEAutoencoderKL.encode up to the distribution)."""
+        return self._tail(self._body(x), quant_conv)
+
+    def encode(self, x: torch.Tensor, quant_conv: nn.Conv2d, noise=None, scale_factor: float = 0.18215):
+        """(moments, z): z = scale_factor * posterior.sample() with the caller's `noise` [B,z,H/8,W/8] (get_first_stage_encoding),
+        or scale_factor * posterior.mode() with noise=None."""
+        return self._tail(self._body(x), quant_conv, True, noise, scale_factor)
