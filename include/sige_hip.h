@@ -615,6 +615,22 @@ int sige_hip_conv3x3_latent_head_nhwc_f32(const float *x, int B, int C, int H, i
                                           const float *weight, const float *bias, int Cout, float *out,
                                           const float *noise, float latent_scale, float *z, void *stream);
 
+/* ---- gamma | beta of a GAN-Compression ("sub-mobile") SPADE layer (csrc/spade_separable.hip): the two SIGESeparableConv2d of
+ * gaugan/models/sige_normalization.py:124-127 -- depthwise 3x3 / padding 1 with bias, the InstanceNorm as the per-channel affine the
+ * full pass cached (mobile_modules.py:104-114), pointwise 1x1 with bias -- for both branches b in {gamma, beta} in ONE launch:
+ *   out[p][b*oc + o] = pw_bias[b][o] + sum_c pw_weight[b][o][c] * (in_shift[b][c] + in_scale[b][c] * (dw_bias[b][c] + sum_tap
+ *                      dw_weight[b][c][tap] * actv[p + tap][c]))
+ * tiled != 0: actv = T tile slabs [T,6,6,Ch] that carry their halo, out = [T,4,4,2*oc] (H = W = 6; T = 0 is OK without a launch);
+ * tiled == 0: actv = one full tensor [H,W,Ch] (T = 1), zero padding at the image border, out = [H,W,2*oc]; refused while edits are
+ *   stacked (sige_hip_set_edit_batch).
+ * dw_weight [2,Ch,3,3], dw_bias / in_scale / in_shift [2,Ch], pw_weight [2,oc,Ch], pw_bias [2,oc]: the nn.Conv2d layouts, stacked per
+ * branch.  Ch % 4 == 0, 8 <= Ch <= 128, oc % 4 == 0, 4 <= oc <= 1024, all pointers 16-byte aligned; anything else is
+ * SIGE_HIP_EUNSUPPORTED without a launch.  The depthwise part is fp32 VALU arithmetic in tap order, the pointwise part exact fp32
+ * operands on the matrix cores; no atomics: bit-identical from run to run, and the two forms agree bit for bit on the same pixels. */
+int sige_hip_spade_separable_nhwc_f32(const float *actv, int tiled, int T, int H, int W, int Ch,
+                                      const float *dw_weight, const float *dw_bias, const float *in_scale, const float *in_shift,
+                                      const float *pw_weight, const float *pw_bias, int oc, float *out, void *stream);
+
 /* ---- channels-last helpers of the GauGAN SPADE generator's sparse forward (csrc/spade_ops.hip): what was left to torch kernels
  * in round 4, so that the whole forward goes through this library and a launch plan can record it.
  * resize_nearest: F.interpolate(mode="nearest") by an INTEGER factor up or down, x [B,H,W,C] -> out [B,Ho,Wo,C]

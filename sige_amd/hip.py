@@ -166,6 +166,7 @@ _SIGNATURES = {
     "sige_hip_conv3x3_small_cout_act_nhwc_f32": (_c_int, [_c_vp] + [_c_int] * 5 + [ctypes.c_float, _c_vp, _c_vp, _c_int, _c_int, _c_vp, _c_vp]),
     "sige_hip_conv3x3_latent_head_nhwc_f32": (
         _c_int, [_c_vp] + [_c_int] * 4 + [_c_vp, _c_int, _c_int] * 2 + [_c_int, _c_vp, _c_vp, _c_int, _c_vp, _c_vp, ctypes.c_float, _c_vp, _c_vp]),
+    "sige_hip_spade_separable_nhwc_f32": (_c_int, [_c_vp] + [_c_int] * 5 + [_c_vp] * 6 + [_c_int, _c_vp, _c_vp]),
     "sige_hip_resize_nearest_nhwc_f32": (_c_int, [_c_vp] + [_c_int] * 6 + [_c_vp, _c_vp]),
     "sige_hip_act_split_nhwc_f32": (_c_int, [_c_vp, ctypes.c_int64, _c_int, _c_int, ctypes.c_int64, _c_int, ctypes.c_float, _c_vp, _c_vp]),
     "sige_hip_scatter_gather_split_nhwc_f32": (
@@ -2058,6 +2059,56 @@ def spade_modulate_dense_cl(x, scale, shift, gb, slope: Optional[float] = None):
     _check(lib().sige_hip_spade_modulate_dense_nhwc_f32(x.data_ptr(), sa[0], ta[0], sa[1], gb.data_ptr(), B, C, H, W,
                                                         int(slope is not None), float(slope or 0.0), out.data_ptr(), _stream(x)),
            "spade_modulate_dense_cl")
+    return out
+
+
+def spade_separable_cl(actv, dw_w, dw_b, in_scale, in_shift, pw_w, pw_b, out=None, tiled: Optional[bool] = None):
+    """gamma | beta of a sub-mobile SPADE layer in one launch (include/sige_hip.h: sige_hip_spade_separable_nhwc_f32): per branch
+    depthwise 3x3 + bias, the cached InstanceNorm affine, pointwise 1x1 + bias.  The operands are stacked per branch (gamma, beta):
+    dw_w [2,Ch,3,3], dw_b / in_scale / in_shift [2,Ch], pw_w [2,oc,Ch] (or [2,oc,Ch,1,1]), pw_b [2,oc], contiguous fp32 -- the
+    caller builds them once per weight version.  `actv` channels-last fp32: tile slabs [T,Ch,6,6] that carry their halo ->
+    [T,2*oc,4,4], or a full tensor [1,Ch,H,W] -> [1,2*oc,H,W] (zero padding at the border).  `tiled` None: tile slabs are 6x6
+    tensors that carry a tile tag (tag_tiles).  None if unsupported (nothing is launched)."""
+    key = getattr(actv, "_sige_count_key", None)
+    actv = _req_cl(actv, "actv")
+    N, Ch, H, W = actv.shape
+    if tiled is None:
+        tiled = (H, W) == (6, 6) and key is not None
+    ops = []
+    for t, shape, name in ((dw_w, (2, Ch, 3, 3), "dw_w"), (dw_b, (2, Ch), "dw_b"), (in_scale, (2, Ch), "in_scale"),
+                           (in_shift, (2, Ch), "in_shift")):
+        if tuple(t.shape) != shape:
+            raise ValueError("spade_separable_cl: `%s` must be %s" % (name, list(shape)))
+        ops.append(_req(t.detach(), torch.float32, name, None))
+    if pw_w.dim() not in (3, 5) or pw_w.shape[0] != 2 or pw_w.shape[2] != Ch or pw_w.numel() != 2 * pw_w.shape[1] * Ch:
+        raise ValueError("spade_separable_cl: `pw_w` must be [2, oc, Ch]")
+    oc = pw_w.shape[1]
+    if tuple(pw_b.shape) != (2, oc):
+        raise ValueError("spade_separable_cl: `pw_b` must be [2, oc]")
+    ops.append(_req(pw_w.detach(), torch.float32, "pw_w", None))
+    ops.append(_req(pw_b.detach(), torch.float32, "pw_b", None))
+    if tiled:
+        if (H, W) != (6, 6):
+            return None
+        shape = (N, 2 * oc, 4, 4)
+    else:
+        if N != 1:
+            return None
+        shape = (1, 2 * oc, H, W)
+    if out is None:
+        if tiled and key is not None and key[0].shape[0] * key[1] == N:
+            out = _empty_tiles_cl(key[1], key[0], 2 * oc, 4, 4, actv.device)
+        else:
+            out = _empty_cl(shape, actv.device)
+    elif tuple(out.shape) != shape or out.dtype != torch.float32 or not out.is_cuda or not out.is_contiguous(memory_format=CL):
+        raise ValueError("spade_separable_cl: `out` must be a channels-last fp32 %s GPU tensor" % list(shape))
+    status = lib().sige_hip_spade_separable_nhwc_f32(base_ptr(actv), int(bool(tiled)), N if tiled else 1, H, W, Ch,
+                                                     *(t.data_ptr() for t in ops), oc, base_ptr(out), _stream(actv))
+    if status == UNSUPPORTED:
+        return None
+    _check(status, "spade_separable_cl")
+    if tiled and key is not None and key[0].shape[0] * key[1] == N:
+        tag_tiles(out, key[0], key[1])
     return out
 
 

@@ -142,9 +142,12 @@ class SpadeNorm(SIGEModule):
             n = x
         else:
             raise NotImplementedError("Unknown mode [%s]!!!" % self.mode)
-        gb = _dense_conv(self.mlp_gamma_beta, actv) if (not self.tiled and self.mode == "sparse") else self.mlp_gamma_beta(actv)
-        gamma, beta = torch.split(self._retile(gb), self.channels, dim=1)
+        gamma, beta = torch.split(self._retile(self._gamma_beta(actv)), self.channels, dim=1)
         return n * (1 + gamma) + beta
+
+    def _gamma_beta(self, actv: torch.Tensor) -> torch.Tensor:
+        """gamma | beta [*, 2C, h, w] of the label features `actv` (a subclass with another label branch overrides this)."""
+        return _dense_conv(self.mlp_gamma_beta, actv) if (not self.tiled and self.mode == "sparse") else self.mlp_gamma_beta(actv)
 
     # -- fused sparse forms ---------------------------------------------------------
     def modulated_dense(self, x: torch.Tensor, actv: torch.Tensor, slope: Optional[float]) -> Optional[torch.Tensor]:
@@ -155,7 +158,7 @@ class SpadeNorm(SIGEModule):
             return None
         from .. import hip
 
-        gb = _dense_conv(self.mlp_gamma_beta, actv)
+        gb = self._gamma_beta(actv)
         if not _cl_gpu(gb):
             return None
         sc, sh = self.affine4()
@@ -187,7 +190,7 @@ class SpadeNorm(SIGEModule):
             tgt = mod.gather.module
         if not (_cl_gpu(x_full) and _cl_gpu(gb_full)) or tuple(tgt.block_size) != tuple(out_gather.block_size):
             return None
-        gb = self.mlp_gamma_beta(actv_tiles)  # [N, 2C, 4, 4] on the label branch's tile list
+        gb = self._gamma_beta(actv_tiles)  # [N, 2C, 4, 4] on the label branch's tile list
         gb = deferred.resolve(gb)
         if not hip.is_cl(gb):
             gb = gb.contiguous(memory_format=torch.channels_last)
@@ -201,13 +204,18 @@ class SpadeNorm(SIGEModule):
 
 
 class SpadeResBlock(SIGEModule):
-    def __init__(self, cfg: SPADEConfig, fin: int, fout: int, tiled: bool):
+    def __init__(self, cfg: SPADEConfig, fin: int, fout: int, tiled: bool, fmid: Optional[int] = None, nhidden: Optional[int] = None,
+                 learned_shortcut: Optional[bool] = None, make_norm=None):
+        """`fmid`, `nhidden`, `learned_shortcut`, `make_norm(channels, seg_gather, shortcut_conv=None)`: what a generator with
+        per-block widths and another SPADE layer passes (gaugan_sub_mobile.py); the defaults are this generator's."""
         super().__init__()
         self.cfg = cfg
         self.fin, self.fout = fin, fout
-        self.nhidden = cfg.ngf * 2
-        self.learned_shortcut = fin != fout
-        fmid = min(fin, fout)
+        self.nhidden = cfg.ngf * 2 if nhidden is None else nhidden
+        self.learned_shortcut = (fin != fout) if learned_shortcut is None else learned_shortcut
+        fmid = min(fin, fout) if fmid is None else fmid
+        if make_norm is None:
+            make_norm = lambda channels, seg_gather, shortcut_conv=None: SpadeNorm(cfg, channels, seg_gather, shortcut_conv)  # noqa: E731
         self.tiled = tiled and cfg.main_block_size is not None
         self.tiled_shortcut = self.learned_shortcut and self.tiled and cfg.shortcut_block_size is not None
         Conv = SIGEConv2d if self.tiled else nn.Conv2d
@@ -229,10 +237,10 @@ class SpadeResBlock(SIGEModule):
                 self.scatter = ScatterWithBlockResidual(self.main_gather, self.shortcut_gather)
         if self.tiled and not self.tiled_shortcut:
             self.scatter = Scatter(self.main_gather)
-        self.norm_0 = SpadeNorm(cfg, fin, seg_gather)
-        self.norm_1 = SpadeNorm(cfg, fmid, seg_gather)
+        self.norm_0 = make_norm(fin, seg_gather)
+        self.norm_1 = make_norm(fmid, seg_gather)
         if self.learned_shortcut:
-            self.norm_s = SpadeNorm(cfg, fin, seg_gather, shortcut_conv=self.conv_s)
+            self.norm_s = make_norm(fin, seg_gather, shortcut_conv=self.conv_s)
         if self.tiled:
             for n in (self.norm_0, self.norm_1, getattr(self, "norm_s", None)):
                 if n is not None:
