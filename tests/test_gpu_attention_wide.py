@@ -16,6 +16,7 @@ if REPO not in sys.path:
     sys.path.insert(0, REPO)
 
 from tests import util  # noqa: E402
+from tests.attention_stress import chain as _chain  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda"
@@ -40,19 +41,6 @@ def _inputs(B, Nq, Nk, heads, d, strided=False):
         return wide[:, :, :C], kv[:, :, :C], kv[:, :, C:]
     q, k, v = (torch.randn(B, n, C, generator=g).to(DEV) for n in (Nq, Nk, Nk))
     return q * 2.0, k, v
-
-
-def _heads(t, heads, dtype):
-    b, n, c = t.shape
-    return t.to(dtype).reshape(b, n, heads, c // heads).permute(0, 2, 1, 3).reshape(b * heads, n, c // heads)
-
-
-def _chain(q, k, v, heads, scale, dtype):
-    """bmm / softmax / bmm per (batch, head) in `dtype` -> [B,Nq,C]."""
-    B, Nq, C = q.shape
-    qh, kh, vh = (_heads(t, heads, dtype) for t in (q, k, v))
-    att = torch.bmm(torch.softmax(torch.bmm(qh, kh.transpose(1, 2)) * scale, dim=2), vh)
-    return att.reshape(B, heads, Nq, C // heads).permute(0, 2, 1, 3).reshape(B, Nq, C)
 
 
 CASES = [
