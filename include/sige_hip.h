@@ -437,7 +437,20 @@ int sige_hip_gather_conv_nhwc(int compute, const float *x, const float *x2, int 
  * -- the CONSUMER's cached GroupNorm affine + SiLU applied by the producer, once per element; the consumer then
  * gathers with no affine (e.g. conv1 -> conv2 of a ResBlock, sige_fused_unet.py:112-125).
  * `upsample2x` = 1: x / x2 are [B,H/2,W/2,C] and the gather reads pixel (h/2, w/2): the x2 nearest-neighbour
- * upsampling in front of the U-Net's Upsample conv (sige_fused_unet.py: F.interpolate) fused into the gather. */
+ * upsampling in front of the U-Net's Upsample conv (sige_fused_unet.py: F.interpolate) fused into the gather.
+ * `upsample2x` = 2: the same conv (3x3, stride 1, 6x6 tiles, to_full) as four 2x2 "phase" convs on the half-resolution
+ * tensor: the 3x3 window of upsampled pixel (2y + a, 2x + b) covers 2x2 source pixels, rows {y - 1 + a, y + a}, columns
+ * likewise with b, so 4 multiply-adds per output and channel pair instead of 9.  `packed` is then the phase pack directly
+ * followed by the 9-tap pack of the same weights:
+ *   n = sige_hip_upsample_phase_packed_size(Cout, Cin)         floats of the phase pack
+ *   sige_hip_upsample_phase_pack_f32(w_phases, ..., packed)     w_phases [4,Cout,Cin,2,2], phase 2a + b: the tap sums
+ *   sige_hip_block_conv_pack_f32(w, ..., packed + n)            the 9-tap pack (launches the library routes away from the
+ *                                                              phase form by their tile count run on it, or on packed_tile3)
+ * Exact fp32 (compute 0), one input tensor, no gather affine; bias, residual, out_scale / out_shift and twins as in the
+ * 9-tap form.  Anything else (and stacked edits, and a call that sige_hip_conv_side_begin waits for) is
+ * SIGE_HIP_EUNSUPPORTED: repeat the call with upsample2x = 1 and the 9-tap pack. */
+size_t sige_hip_upsample_phase_packed_size(int Cout, int Cin);
+int sige_hip_upsample_phase_pack_f32(const float *w_phases, int Cout, int Cin, float *packed, void *stream);
 /* `workspace` (optional, NULL = none): room for up to 8 copies of the output.  When the conv has
  * too few tiles to cover the chip with ANY block shape (the 8x8 layers: 64 pixels, K up to 9216),
  * the channel chunks are split across workgroups that write partial sums there, and a second

@@ -229,6 +229,15 @@ SIGE_CONV_DECLARE_C16(K31_16, 1) SIGE_CONV_DECLARE_C16(K31_16, 2) SIGE_CONV_DECL
 SIGE_CONV_DECLARE_C16(H31_16, 1) SIGE_CONV_DECLARE_C16(H31_16, 2) SIGE_CONV_DECLARE_C16(H31_32, 1) SIGE_CONV_DECLARE_C16(H31_32, 2)
 SIGE_CONV_DECLARE_C16(X31_16, 1) SIGE_CONV_DECLARE_C16(X31_32, 1)
 
+// the phase form of the Upsample conv (conv_up_phase_nhwc.hip): 2x2 taps on a 3x3 low-res window
+using P22_16 = ConvGeo<2, 1, 3, 16>;
+using P22_32 = ConvGeo<2, 1, 3, 32>;
+template <typename G, int NB>
+void launch_conv_phase(ConvArgs a, hipStream_t st);
+template <> void launch_conv_phase<P22_16, 1>(ConvArgs, hipStream_t);
+template <> void launch_conv_phase<P22_16, 2>(ConvArgs, hipStream_t);
+template <> void launch_conv_phase<P22_32, 1>(ConvArgs, hipStream_t);
+
 // ---- cross-workgroup K split: deterministic second pass ------------------------
 // out[i] = sum_s ws[s][i] + bias[channel(i)] + residual[i]   (channels-last: channel = i mod C)
 __global__ __launch_bounds__(256) void splitk_reduce_nhwc_kernel(const float *__restrict__ ws, int S, size_t stride, size_t n4, int C,
@@ -775,6 +784,44 @@ static int launch_kind(ConvArgs a, int mode, hipStream_t st) {
     return SIGE_HIP_OK;
 }
 
+// ---- nearest-x2 Upsample conv in the phase form (upsample2x = 2 of sige_hip_gather_conv_nhwc) ----
+// `a` as for the 9-tap launch of the same call (up = 1, full-tensor destination), a.packed = the phase pack
+// (sige_hip_upsample_phase_pack_f32): [32-pixel layout: phases 0..3][16-pixel layout: phases 0..3].  The output block is the one
+// the 9-tap form picks for this call; a tile gives each phase 4 pixels, so an M block holds MT / 4 tiles and the grid is
+// (M blocks x output-channel blocks) x 4 phases.  Never K-split, never a pair, a side-conv host or a queued side conv.
+static int launch_phase_up(ConvArgs a, hipStream_t st) {
+    int rc = flush_held();
+    if (rc != SIGE_HIP_OK) return rc;
+    if (!g_side.empty() && (g_side.front().st != st || side_hazard(a))) {
+        rc = flush_side();
+        if (rc != SIGE_HIP_OK) return rc;
+    }
+    ConvArgs q = a;
+    ConvPlan p;
+    rc = plan_conv<3, 1, 6, SRC_GATHER, LAYOUT_NHWC, 0>(q, 1, 0, false, p);
+    if (rc != SIGE_HIP_OK) return rc;
+    const int mt = p.mt, nb = (mt == 16 && p.nb == 2) ? 2 : 1;
+    const int cc = mt == 32 ? P22_32::CC : P22_16::CC;
+    a.mbk = ceil_div(a.T, mt / 4);
+    a.ngk = ceil_div(a.Cout, mt * nb);
+    a.nchunks = ceil_div(a.Cin, cc);
+    a.nblk = ((a.nchunks + 1) & ~1) * 4;  // as packed (chunk count padded to even)
+    a.ksplit = 1;
+    a.chunks_per_split = a.nchunks;
+    a.counters = nullptr;
+    // (one phase's weights against the staged low-res windows: the rule of plan_conv)
+    a.ng_fast = 4.0 * a.Cout * a.Cin > 9.0 * a.T * a.Cin ? 1 : ((a.mbk >= 16 && a.ngk > 1) ? 2 : 0);
+    if (mt == 16) a.packed += 4 * packed_floats(a.Cout, a.Cin, 4, 32);
+    a.phase_up = 1;
+#ifdef SIGE_CONV_PROBE
+    a.probe = nullptr;
+#endif
+    if (mt == 32) launch_conv_phase<P22_32, 1>(a, st);
+    else if (nb == 2) launch_conv_phase<P22_16, 2>(a, st);
+    else launch_conv_phase<P22_16, 1>(a, st);
+    return launch_status();
+}
+
 template <int SRC, int DST = DST_TILES, int LAY = LAYOUT_NCHW, int PREC = 0>
 static int launch_conv(const ConvArgs &a, int mode, int kH, int kW, int R, int S, int strH, int strW, hipStream_t st) {
     int rc;
@@ -866,6 +913,24 @@ extern "C" int sige_hip_block_conv_pack_f32(const float *w, int Cout, int Cin, i
         pack_weights_kernel<1, 16><<<blocks(n16), 256, 0, st>>>(w, Cout, Cin, packed + n32, n16);
     }
     return launch_status(2);
+}
+
+extern "C" size_t sige_hip_upsample_phase_packed_size(int Cout, int Cin) {
+    if (Cout <= 0 || Cin <= 0) return 0;
+    return 4 * (packed_floats(Cout, Cin, 4, 32) + packed_floats(Cout, Cin, 4, 16));
+}
+
+extern "C" int sige_hip_upsample_phase_pack_f32(const float *w_phases, int Cout, int Cin, float *packed, void *stream) {
+    if (!w_phases || !packed || Cout <= 0 || Cin <= 0) return SIGE_HIP_EINVAL;
+    hipStream_t st = as_stream(stream);
+    const long n32 = (long)packed_floats(Cout, Cin, 4, 32), n16 = (long)packed_floats(Cout, Cin, 4, 16);
+    auto blocks = [](long n) { return (int)((n + 255) / 256 < 4096 ? (n + 255) / 256 : 4096); };
+    for (int ph = 0; ph < 4; ++ph) {
+        const float *w = w_phases + (size_t)ph * Cout * Cin * 4;
+        pack_weights_kernel<4, 32><<<blocks(n32), 256, 0, st>>>(w, Cout, Cin, packed + ph * n32, n32);
+        pack_weights_kernel<4, 16><<<blocks(n16), 256, 0, st>>>(w, Cout, Cin, packed + 4 * n32 + ph * n16, n16);
+    }
+    return launch_status(8);
 }
 
 extern "C" size_t sige_hip_block_conv_packed_size_f16c(int Cout, int Cin, int kH, int kW, int R, int S,
@@ -1117,7 +1182,9 @@ static int gather_conv_nhwc_impl(const float *x, const float *x2, int B, int C1,
                                              float *twin1, const float *twin1_scale, const float *twin1_shift,
                                              float *out, void *stream) {
     const int Cin = C1 + C2;
+    if (upsample2x < 0 || upsample2x > 2) return SIGE_HIP_EINVAL;
     if (upsample2x && ((H | W) & 1)) return SIGE_HIP_EINVAL;  // (H, W) = the upsampled size
+    if (upsample2x == 2 && PREC != 0) return SIGE_HIP_EUNSUPPORTED;  // (the entry point has checked what else the phase form needs)
     if (B < 0 || C1 <= 0 || C2 < 0 || Cout <= 0 || H <= 0 || W <= 0 || N < 0) return SIGE_HIP_EINVAL;
     if (to_full && (Ho <= 0 || Wo <= 0)) return SIGE_HIP_EINVAL;
     if (activation != SIGE_HIP_ACT_IDENTITY && activation != SIGE_HIP_ACT_SWISH) return SIGE_HIP_EUNSUPPORTED;
@@ -1159,10 +1226,15 @@ static int gather_conv_nhwc_impl(const float *x, const float *x2, int B, int C1,
     a.twin1 = twin1; a.tscale1 = twin1_scale; a.tshift1 = twin1_shift;
     if (to_full) {
         a.residual = residual; a.Ho = Ho; a.Wo = Wo; a.offH = offsetH; a.offW = offsetW; a.strH = strideH; a.strW = strideW;
+        if constexpr (PREC == 0) {
+            if (upsample2x == 2) return launch_phase_up(a, as_stream(stream));
+        }
         return launch_conv<SRC_GATHER, DST_NCHW, LAYOUT_NHWC, PREC>(a, mode, kH, kW, bH, bW, strideH, strideW, as_stream(stream));
     }
     return launch_conv<SRC_GATHER, DST_TILES, LAYOUT_NHWC, PREC>(a, mode, kH, kW, bH, bW, strideH, strideW, as_stream(stream));
 }
+
+extern "C" size_t sige_hip_upsample_phase_packed_size(int Cout, int Cin);
 
 // ---- routing: conv_mfma.hpp or the tile conv v3 (conv_tile3.hpp), decided HERE from the tile count ----
 // sige_hip_gather_conv_nhwc and sige_hip_scatter_gather_conv_scatter_nhwc take the weights in the v3 layout beside `packed` and a
@@ -1223,8 +1295,26 @@ extern "C" int sige_hip_gather_conv_nhwc(int compute, const float *x, const floa
     const int Cin = C1 + C2;
     const bool f16 = compute == 1;
     const bool aff_ok = (!scale && !shift) || (scale && shift && scaleC == Cin && shiftC == Cin && scaleB == shiftB && (scaleB == 1 || scaleB == B));
+    if (upsample2x == 2) {
+        // `packed` = the phase pack (sige_hip_upsample_phase_pack_f32) directly followed by the 9-tap pack of the same conv
+        // (sige_hip_block_conv_pack_f32).  What the phase form does not cover is refused: the caller repeats the call with
+        // upsample2x = 1.  What it covers but another form runs faster is routed HERE, from the tile count, so that a launch plan
+        // replayed under another mask takes the form the module forward takes under that mask.
+        if (compute != 0 || C2 || kH != 3 || kW != 3 || bH != 6 || bW != 6 || strideH != 1 || strideW != 1 || !to_full || scale || shift ||
+            activation != SIGE_HIP_ACT_IDENTITY || stacked_shift(H) != 0 || g_side_armed > 0)
+            return SIGE_HIP_EUNSUPPORTED;
+        // (measured inside the DDPM-256 forward, DESIGN.md 5.19: all five Upsample launches are faster in the phase form, the two
+        //  512-channel ones with 6 and 9 tiles included, so the only rule is the v3 tile conv's own: from the tile count at which it
+        //  takes the 9-tap call it keeps it)
+        const bool nine_tap = B > 0 && N > 0 &&
+                              tile3_takes(packed_tile3, min_blocks, B, N, C1, C2, Cout, kH, kW, bH, bW, strideH, strideW, as_stream(stream));
+        if (nine_tap) {
+            upsample2x = 1;
+            packed += sige_hip_upsample_phase_packed_size(Cout, Cin);
+        }
+    }
     // (a conv that sige_hip_conv_side_begin waits for stays on the stacked-block kernels, where it can be queued)
-    if ((compute == 0 || f16) && B > 0 && N > 0 && aff_ok && !(g_side_armed > 0 && compute == 0 && to_full) &&
+    if (upsample2x != 2 && (compute == 0 || f16) && B > 0 && N > 0 && aff_ok && !(g_side_armed > 0 && compute == 0 && to_full) &&
         tile3_takes(packed_tile3, min_blocks, B, N, C1, C2, Cout, kH, kW, bH, bW, strideH, strideW, as_stream(stream), f16, f16 ? H : 0, f16 ? W : 0)) {
         const int rc = tile_conv3_launch(T3_GATHER, x, x2, B, C1, C2, H, W, upsample2x, active_indices, N, nullptr, 0, 0, scale, shift,
                                          scale ? scaleB : 0, activation, packed_tile3, bias, Cout, to_full, offsetH, offsetW, Ho, Wo,

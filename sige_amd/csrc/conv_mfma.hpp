@@ -211,6 +211,10 @@ struct ConvArgs {
     // stacked edits (sige_hip_set_edit_batch): log2 of one image's height when E images are stacked along H (0 = off): a
     // tile's halo rows beyond ITS image are zero padding (channels-last gather / scatter_gather staging)
     int hp_shift;
+    // GATHER, PH form of the body (conv_phase_kernel): the nearest-x2 Upsample conv as four 2x2 phase convs on the half-resolution
+    // tensor.  `idx` stays the hi-res 6x6 list, `packed` holds four sub-packs (phase = 2a + b = blockIdx.y) of the tile shape in
+    // use, (H, W) is the upsampled size (up = 1).  Set by the host only; the kernel form is a compile-time choice.
+    int phase_up;
 #ifdef SIGE_CONV_PROBE
     unsigned long long *probe;  // tools/conv_phase_probe.py build only: 8 timestamps per workgroup
 #endif
@@ -367,9 +371,16 @@ __host__ __device__ constexpr int conv_lds_floats() {
 }
 
 // The whole launch of one workgroup (bx, by) = what blockIdx would be in a launch of its own.
-template <typename G, int NB, int SRC, int MODE, int DST, int LAYOUT, int W, bool Y16 = false>
+// PH: the phase form of a nearest-x2 Upsample conv (ConvArgs::phase_up).  G is the 2x2 geometry on a 3x3 low-res window; `by` is
+// the phase (a, b) = (by >> 1, by & 1) instead of a K split: output pixel (2y + a, 2x + b) of a hi-res tile reads the low-res rows
+// {y - 1 + a, y + a} and columns {x - 1 + b, x + b} with the four weight sums of its phase (never K-split).
+template <typename G, int NB, int SRC, int MODE, int DST, int LAYOUT, int W, bool Y16 = false, bool PH = false>
 __device__ __forceinline__ void conv_mfma_body(const ConvArgs &a, const int bx, const int by, float *const smem) {
     static_assert(!Y16 || (SRC == SRC_SCATTER_GATHER && LAYOUT == LAYOUT_NHWC), "fp16-stored cache: the channels-last scatter_gather source");
+    static_assert(!PH || (SRC == SRC_GATHER && MODE == MODE_RAW && DST == DST_NCHW && LAYOUT == LAYOUT_NHWC && W == 4 && !G::F16 &&
+                          G::K == 2 && G::S == 1 && G::R == 3),
+                  "phase form: exact fp32, channels-last raw gather into a full tensor, 2x2 taps on a 3x3 window");
+    const int ph_a = PH ? (by >> 1) : 0, ph_b = PH ? (by & 1) : 0;
     constexpr unsigned YB = Y16 ? 2u : 4u;       // bytes per element of the cached tensor `y`
     constexpr bool F16 = G::F16;                 // fp16 operands in LDS / registers (ConvGeoH)
     using M = std::conditional_t<F16, MfmaH<G::MT>, Mfma<G::MT>>;
@@ -419,13 +430,14 @@ __device__ __forceinline__ void conv_mfma_body(const ConvArgs &a, const int bx, 
     const int Cin = a.Cin;
     const int HW = (SRC == SRC_GATHER) ? (a.H >> a.up) * (a.W >> a.up) : a.H * a.W;  // pixels of the SOURCE tensor
     // cross-workgroup K split (deep-K, small-M layers): by owns chunks [first, last]
-    const int split = by;
+    const int split = PH ? 0 : by;
     const int first = split * a.chunks_per_split;
     const int last = min(a.nchunks, first + a.chunks_per_split) - 1;
 
     // ---- B: F float4 per lane per chunk and N sub-block, contiguous per (ng, chunk, wave) ----
     const int ngtot = (a.Cout + G::MT - 1) / G::MT;
     const long packed_floats_total = (long)ngtot * a.nblk * G::F * 64 * 4;  // nblk = (4-wave chunks, padded to even) * 4
+    const float *const packed = PH ? a.packed + (size_t)by * packed_floats_total : a.packed;  // (phase form: this phase's sub-pack)
     int gsel[NB];
 #pragma unroll
     for (int nb = 0; nb < NB; ++nb) gsel[nb] = min(ng * NB + nb, ngtot - 1);  // past-the-end sub-blocks re-read the last one; stores are masked
@@ -433,7 +445,7 @@ __device__ __forceinline__ void conv_mfma_body(const ConvArgs &a, const int bx, 
     auto set_b_chunk = [&](int chunk) {
 #pragma unroll
         for (int nb = 0; nb < NB; ++nb)
-            r_b[nb] = make_rsrc(a.packed, ((long)gsel[nb] * a.nblk + chunk * W + wave) * G::F * 64 * 4, packed_floats_total);
+            r_b[nb] = make_rsrc(packed, ((long)gsel[nb] * a.nblk + chunk * W + wave) * G::F * 64 * 4, packed_floats_total);
     };
     float4 bset[2][NB][G::F];
     auto b_load = [&](float4 &dst, int nb, int f) { dst = buf_f32x4(r_b[nb], lane * 16, f * 1024); };
@@ -516,7 +528,9 @@ __device__ __forceinline__ void conv_mfma_body(const ConvArgs &a, const int bx, 
                 const int pxo = m % G::PX;
                 const int t = mb * G::TPB + m / G::PX, co = (ng * NB + nb) * G::MT + 4 * n4;
                 const int b = min(t, a.T - 1) / a.N;
-                const int h = (a.offH + e_h[k]) / a.strH + pxo / G::RO, w = (a.offW + e_w[k]) / a.strW + pxo % G::RO;
+                // (phase form: pixel (y, x) of the tile's 2x2 phase block is hi-res pixel (2y + a, 2x + b) of the tile's 4x4 outputs)
+                const int h = PH ? a.offH + e_h[k] + 2 * (pxo / G::RO) + ph_a : (a.offH + e_h[k]) / a.strH + pxo / G::RO;
+                const int w = PH ? a.offW + e_w[k] + 2 * (pxo % G::RO) + ph_b : (a.offW + e_w[k]) / a.strW + pxo % G::RO;
                 const bool in = o < OUT_UNITS && t < a.T && co < a.Cout && h >= 0 && h < a.Ho && w >= 0 && w < a.Wo;
                 e_h[k] = h; e_w[k] = w; e_in[k] = in;
                 e_q[k] = in ? (((size_t)b * a.Ho + h) * a.Wo + w) * a.Cout + co : 0;  // (dead units: a valid address, never stored)
@@ -552,7 +566,11 @@ __device__ __forceinline__ void conv_mfma_body(const ConvArgs &a, const int bx, 
                 const int tt = min(z_t[i], a.T - 1);  // (clamped: always a valid address; dead slots are masked below)
                 const int b = tt / a.N, n = tt - b * a.N;
                 const int2 o = *reinterpret_cast<const int2 *>(a.idx + 2 * n);
-                z_b[i] = b; z_h[i] = o.x + z_p[i] / G::R; z_w[i] = o.y + z_p[i] % G::R;
+                if constexpr (PH) {  // the 3x3 low-res window of this phase under the hi-res tile at (o.x, o.y) = (4i - pad, 4j - pad)
+                    z_b[i] = b; z_h[i] = ((o.x + 1) >> 1) - 1 + ph_a + z_p[i] / G::R; z_w[i] = ((o.y + 1) >> 1) - 1 + ph_b + z_p[i] % G::R;
+                } else {
+                    z_b[i] = b; z_h[i] = o.x + z_p[i] / G::R; z_w[i] = o.y + z_p[i] % G::R;
+                }
             });
         }
         if constexpr (EPRE) {
@@ -602,9 +620,11 @@ __device__ __forceinline__ void conv_mfma_body(const ConvArgs &a, const int bx, 
                     hlo = ((h - z_p[i] / G::R + 2) >> a.hp_shift) << a.hp_shift;
                     hhi = hlo + (1 << a.hp_shift);
                 }
-                const bool in = z_live[i] && h >= hlo && h < hhi && w >= 0 && w < a.W;
+                // (phase form: (h, w) are low-res coordinates already)
+                const bool in = PH ? (z_live[i] && h >= 0 && h < (a.H >> 1) && w >= 0 && w < (a.W >> 1))
+                                   : (z_live[i] && h >= hlo && h < hhi && w >= 0 && w < a.W);
                 z_live[i] = in;
-                const int hw = (SRC == SRC_GATHER) ? (h >> a.up) * (a.W >> a.up) + (w >> a.up) : h * a.W + w;
+                const int hw = PH ? h * (a.W >> 1) + w : (SRC == SRC_GATHER) ? (h >> a.up) * (a.W >> a.up) + (w >> a.up) : h * a.W + w;
                 if (SRC == SRC_GATHER) {
                     off = in ? (unsigned)((b * HW + hw) * a.Csplit + c_l) * 4u : kOOB;
                     off2 = in ? (unsigned)(hw * (Cin - a.Csplit) + c_l) * 4u : kOOB;  // (x2: B == 1, host side)
@@ -1177,6 +1197,21 @@ __global__ __launch_bounds__(64 * W) void conv_mfma_kernel(const ConvArgs a) {
     __shared__ __attribute__((aligned(16))) float smem[conv_lds_floats<G, NB, MODE, LAYOUT, W>()];
     conv_mfma_body<G, NB, SRC, MODE, DST, LAYOUT, W, Y16>(a, blockIdx.x, blockIdx.y, smem);
 }
+
+// The phase form of an Upsample conv (conv_mfma_body, PH): grid.y = the four phases, each over all M blocks and output-channel blocks
+template <typename G, int NB>
+__global__ __launch_bounds__(256) void conv_phase_kernel(const ConvArgs a) {
+    kernarg_touch<sizeof(ConvArgs)>();
+    __shared__ __attribute__((aligned(16))) float smem[conv_lds_floats<G, NB, MODE_RAW, LAYOUT_NHWC, 4>()];
+    conv_mfma_body<G, NB, SRC_GATHER, MODE_RAW, DST_NCHW, LAYOUT_NHWC, 4, false, true>(a, blockIdx.x, blockIdx.y, smem);
+}
+
+template <typename G, int NB>
+void launch_conv_phase(ConvArgs a, hipStream_t st);
+#define SIGE_CONV_PHASE_INSTANTIATE(G, NB)                                                                \
+    template <> void launch_conv_phase<G, NB>(ConvArgs a, hipStream_t st) {                               \
+        conv_phase_kernel<G, NB><<<dim3(conv_grid_x(a), 4), 256, 0, st>>>(a);                             \
+    }
 
 // Two independent convs of a residual block in ONE launch (horizontal fusion): workgroups [0, na) run conv A
 // (3x3, gather + cached affine + SiLU: the block's conv1), the rest conv B (the 1x1 shortcut on the same input).  Both are

@@ -65,6 +65,8 @@ _SIGNATURES = {
     "sige_hip_block_conv_packed_size_f16c": (_c_sz, [_c_int] * 9),
     "sige_hip_block_conv_pack_f16c": (_c_int, [_c_vp] + [_c_int] * 4 + [_c_vp, _c_vp]),
     "sige_hip_block_conv_pack_f32": (_c_int, [_c_vp] + [_c_int] * 4 + [_c_vp, _c_vp]),
+    "sige_hip_upsample_phase_packed_size": (_c_sz, [_c_int] * 2),
+    "sige_hip_upsample_phase_pack_f32": (_c_int, [_c_vp] + [_c_int] * 2 + [_c_vp, _c_vp]),
     "sige_hip_block_conv_f32": (_c_int, [_c_vp] + [_c_int] * 4 + [_c_vp, _c_vp] + [_c_int] * 5 + [_c_vp, _c_vp]),
     "sige_hip_gather_conv_f32": (
         _c_int, [_c_vp] + [_c_int] * 6 + [_c_vp, _c_int] + _BC + _BC + [_c_int, _c_vp, _c_vp] + [_c_int] * 5 + [_c_vp, _c_vp]),
@@ -889,6 +891,44 @@ def conv_pack_weights(weight: torch.Tensor, R: int, S: int, stride: Tuple[int, i
     return packed
 
 
+def upsample_phase_kernels(weight: torch.Tensor) -> torch.Tensor:
+    """The four 2x2 kernels [4,Cout,Cin,2,2] (phase 2a + b) that "nearest x2, then this 3x3 conv with padding 1" applies to the
+    half-resolution tensor: output pixel (2y + a, 2x + b) reads low-res rows {y - 1 + a, y + a} and columns {x - 1 + b, x + b}.
+    Rows collapse as a = 0: (w0, w1 + w2), a = 1: (w0 + w1, w2), columns likewise with b; a tap in the zero padding of the hi-res
+    image lands on a low-res row or column outside the image.  Summed in fp64, rounded to the weight's dtype once."""
+    w = weight.detach().to(torch.float64)
+    if w.dim() != 4 or tuple(w.shape[2:]) != (3, 3):
+        raise ValueError("upsample_phase_kernels: a [Cout,Cin,3,3] weight")
+
+    def collapse(t, dim, p):
+        t0, t1, t2 = t.select(dim, 0), t.select(dim, 1), t.select(dim, 2)
+        return torch.stack([t0, t1 + t2] if p == 0 else [t0 + t1, t2], dim)
+
+    return torch.stack([collapse(collapse(w, 2, a), 3, b) for a in (0, 1) for b in (0, 1)], 0).to(weight.dtype).contiguous()
+
+
+def upsample_phase_pack(weight: torch.Tensor, kernels: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The `packed` operand of sige_hip_gather_conv_nhwc(upsample2x = 2) for a [Cout,Cin,3,3] weight: the phase pack of
+    `kernels` = upsample_phase_kernels(weight) directly followed by the exact-fp32 9-tap pack (launches the library routes away from the
+    phase form by their tile count read that).  `out`: an earlier pack of the same shape, rewritten in place."""
+    w = _req(weight.detach(), torch.float32, "weight")
+    Cout, Cin, kH, kW = w.shape
+    n = int(lib().sige_hip_upsample_phase_packed_size(Cout, Cin))
+    n9 = conv_packed_size(Cout, Cin, 3, 3, 6, 6, 1, 1, 1)
+    if (kH, kW) != (3, 3) or n == 0 or n9 == 0:
+        raise ValueError("upsample_phase_pack: a [Cout,Cin,3,3] weight")
+    if out is not None and (out.numel() != n + n9 or out.device != w.device):
+        raise ValueError("upsample_phase_pack: `out` is not a pack of this shape")
+    packed = torch.empty((n + n9,), dtype=torch.float32, device=w.device).as_subclass(PackedWeights) if out is None else out
+    packed.compute = "f32"
+    wp = _req(upsample_phase_kernels(w) if kernels is None else kernels, torch.float32, "kernels", 5)
+    if tuple(wp.shape) != (4, Cout, Cin, 2, 2):
+        raise ValueError("upsample_phase_pack: `kernels` must be [4,Cout,Cin,2,2]")
+    _check(lib().sige_hip_upsample_phase_pack_f32(wp.data_ptr(), Cout, Cin, packed.data_ptr(), _stream(w)), "upsample_phase_pack")
+    _check(lib().sige_hip_block_conv_pack_f32(w.data_ptr(), Cout, Cin, 3, 3, packed.data_ptr() + 4 * n, _stream(w)), "upsample_phase_pack")
+    return packed
+
+
 # ---- dense layers on the fp16 matrix cores (csrc/conv_wide.hpp) ----
 COMPUTE_DTYPES = ("f32", "f16", "f16x3")
 
@@ -1642,11 +1682,13 @@ def tile_conv3_cl(source: int, x, x2, B, C1, C2, H, W, up, idx, smap, rx_sx, sca
 def gather_conv_cl(x, x2, block: Tuple[int, int], activeIndices, scale, shift, activationName: str,
                    packed, bias, Cout: int, kernel: Tuple[int, int], stride: Tuple[int, int],
                    full: Optional[dict] = None, out_affine: Optional[tuple] = None, upsample2x: bool = False,
-                   out: Optional[torch.Tensor] = None, twins=None):
+                   out: Optional[torch.Tensor] = None, twins=None, phase=None):
     """Channels-last gather -> conv.  `full` = dict(offset=(oh, ow), out_res=(Ho, Wo), residual=tensor|None)
     writes the output tiles straight into a [B,Cout,Ho,Wo] tensor (dense layers).  `twins` (full only): up to two
     (buffer, scale, shift): buffer = SiLU(scale * result + shift), the activated input of a consumer's conv1, written by
-    the same launch.  None if unsupported."""
+    the same launch.  `phase` (with upsample2x and `full`): the conv's phase pack (upsample_phase_pack) -- the launch is tried in
+    the phase form first (include/sige_hip.h: upsample2x = 2) and repeated in the 9-tap form where the library refuses it.
+    None if unsupported."""
     bias_keep = _vec(bias, "bias")
     x = _req_cl(x, "x")
     B, C1, H, W = x.shape
@@ -1721,16 +1763,24 @@ def gather_conv_cl(x, x2, block: Tuple[int, int], activeIndices, scale, shift, a
     fargs = fargs + (int(bool(upsample2x)), *targs)
     # with v3 weights beside `packed` the entry point routes: conv_mfma.hpp or the v3 kernel, decided in C from N
     t3r = _tile3_packed(packed) if (TILE3 is None and compute in (0, 1)) else None
-    status = lib().sige_hip_gather_conv_nhwc(
-        compute, x.data_ptr(), None if x2 is None else x2.data_ptr(), B, C1, C2, H, W, block[0], block[1], idx.data_ptr(), N,
-        *sa, *ta, _act(activationName), packed.data_ptr(), _p(bias_keep), Cout, kernel[0], kernel[1],
-        stride[0], stride[1], *fargs, *_tile3_args(packed, t3r), out.data_ptr(), _stream(x))
+    status = UNSUPPORTED
+    if phase is not None and upsample2x and full is not None and compute == 0:
+        fargs2 = fargs[:-(1 + len(targs))] + (2, *targs)
+        status = lib().sige_hip_gather_conv_nhwc(
+            compute, x.data_ptr(), None if x2 is None else x2.data_ptr(), B, C1, C2, H, W, block[0], block[1], idx.data_ptr(), N,
+            *sa, *ta, _act(activationName), phase.data_ptr(), _p(bias_keep), Cout, kernel[0], kernel[1],
+            stride[0], stride[1], *fargs2, *_tile3_args(packed, t3r), out.data_ptr(), _stream(x))
+    if status == UNSUPPORTED:
+        status = lib().sige_hip_gather_conv_nhwc(
+            compute, x.data_ptr(), None if x2 is None else x2.data_ptr(), B, C1, C2, H, W, block[0], block[1], idx.data_ptr(), N,
+            *sa, *ta, _act(activationName), packed.data_ptr(), _p(bias_keep), Cout, kernel[0], kernel[1],
+            stride[0], stride[1], *fargs, *_tile3_args(packed, t3r), out.data_ptr(), _stream(x))
     if status == UNSUPPORTED:
         return None
     _check(status, "gather_conv_cl")
     keep = getattr(_pair_state, "keep", None)
     if keep is not None:  # (conv_pair(): a held launch reads these after this call has returned)
-        keep.append((x, x2, idx, s_keep, t_keep, packed, bias_keep, out, ws, out_affine, full, twin_keep))
+        keep.append((x, x2, idx, s_keep, t_keep, packed, phase, bias_keep, out, ws, out_affine, full, twin_keep))
     if getattr(_side_state, "armed", False):  # (conv_side_begin(): so do the hosts of a queued conv, until conv_side_flush())
         _side_state.armed = False
         _side_state.keep.append((x, x2, idx, s_keep, t_keep, packed, bias_keep, out, ws, out_affine, full, twin_keep))

@@ -129,6 +129,7 @@ class SIGEConv2d(nn.Conv2d, SIGEModule):
         nn.Conv2d.__init__(self, *args, **kwargs)
         SIGEModule.__init__(self, call_super=False)
         self._packed = {}
+        self._phase = None  # [key, phase kernels, their pack | None]: see phase_kernels()
         self._tiles_runtime = self.load_runtime("conv2d_tiles", {})
         # "f32": exact fp32 products (v_mfma_f32_*_f32); "f16": fp16 operands, fp32 accumulation on the 16x faster fp16
         # matrix path (SIGEModel.set_compute_dtype; channels-last tiles only -- BASELINE.json configs[4])
@@ -158,6 +159,48 @@ class SIGEConv2d(nn.Conv2d, SIGEModule):
             entry = (key, hip.conv_pack_weights(w, x.shape[2], x.shape[3], self.stride, compute))
             self._packed[compute] = entry
         return entry[1]
+
+    def _phase_key(self):
+        w = self.weight
+        return (w.data_ptr(), w._version, tuple(w.shape), w.device, self.compute_dtype)
+
+    def phase_kernels(self):
+        """The four 2x2 kernels [4,Cout,Cin,2,2] of this conv as the conv behind a nearest-x2 upsampling
+        (sige_amd.hip.upsample_phase_kernels), or None if it is not a plain 3x3 / stride-1 / padding-1 conv computed in exact fp32.
+        Derived state, like AttnBlock.folded_qv(): keyed on the weight's address, version, shape, device and the compute dtype,
+        dropped by `clear_cache()`, derived again by `rebuild_derived_caches()`, never part of the state dict."""
+        from .. import hip
+
+        if (tuple(self.kernel_size) != (3, 3) or tuple(self.stride) != (1, 1) or tuple(self.padding) != (1, 1) or self.groups != 1
+                or tuple(self.dilation) != (1, 1) or self.compute_dtype != "f32"):
+            return None
+        key = self._phase_key()
+        if self._phase is None or self._phase[0] != key:
+            self._phase = [key, hip.upsample_phase_kernels(self.weight), None]
+        return self._phase[1]
+
+    def phase_packed(self):
+        """`phase_kernels()` laid out for the library (sige_amd.hip.upsample_phase_pack; GPU weights only), or None."""
+        from .. import hip
+
+        wp = self.phase_kernels()
+        if wp is None:
+            return None
+        if self._phase[2] is None:
+            self._phase[2] = hip.upsample_phase_pack(self.weight, wp)
+        return self._phase[2]
+
+    def clear_cache(self):
+        self._phase = None
+
+    def rebuild_derived_caches(self):
+        """Derive the phase kernels again; their pack is rewritten IN PLACE where its size still fits (a captured graph keeps
+        reading the same address)."""
+        old, self._phase = self._phase, None
+        if old is not None and old[2] is not None and self.phase_kernels() is not None and old[0][2:4] == self._phase[0][2:4]:
+            from .. import hip
+
+            self._phase[2] = hip.upsample_phase_pack(self.weight, self._phase[1], out=old[2])
 
     def _block_conv(self, x: torch.Tensor, out_affine=None) -> torch.Tensor:
         from .. import hip

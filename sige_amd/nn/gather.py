@@ -19,6 +19,12 @@ from .utils import activation
 
 
 class Gather(SIGEModule):
+    # `forward(x, upsample2x=True)` in front of a 3x3 conv that writes into a Scatter's persistent output (the U-Nets' and the VAE
+    # decoder's Upsample): the conv runs as four 2x2 phase convs on the half-resolution tensor -- 4 multiply-adds per output and
+    # channel pair instead of 9 on copied pixels (sige_amd.hip.upsample_phase_kernels).  Sparse mode, GPU,
+    # channels-last, exact-fp32 convs, one edit; anything else, and False, gives the 9-tap launch and its bits.
+    PHASE_UPSAMPLE = True
+
     def __init__(
         self,
         conv: nn.Conv2d,
@@ -127,7 +133,7 @@ class Gather(SIGEModule):
                 return deferred.DeferredTiles(
                     (x.shape[0] * idx.shape[0], channels, bh, bw), x.dtype, x.device, run,
                     dict(kind="gather", x=x, x2=x2, block=(bh, bw), idx=idx, scale=scale, shift=shift, act=act, cl=cl,
-                         up=upsample2x))
+                         up=upsample2x, phase=bool(upsample2x and self.PHASE_UPSAMPLE)))
             return run()
         if self.mode == "full":
             self.note_full_input(x.shape[2:])
