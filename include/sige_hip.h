@@ -566,6 +566,29 @@ int sige_hip_tile_conv3_nhwc(
         float *twin0, const float *twin_scale0, const float *twin_shift0,
         float *twin1, const float *twin_scale1, const float *twin_shift1,
         float *out, void *stream);
+/* ... with the window edge as an argument (block size = bH = bW).  6: exactly sige_hip_tile_conv3_nhwc.  10: the same kernel
+ * over ONE 10x10 window per workgroup -- 8x8 = 64 output pixels x 64 output channels, 100 staged pixels per 64 outputs where
+ * four 6x6 windows stage 144, one index entry and one run of scatter-map look-ups where they take four.  Tiles are [B*N,8,8,C]
+ * (source 2: Rx = Sx = 8), the full destination is written at offset + origin, clipped at the bottom and right, with bias,
+ * residual, block residual (x1 / table1 over R1 x S1 cells), twins and the out-affine as above.  Block 10 takes compute 0 over
+ * fp32-stored tensors only, a RAW source 2 (no affine), one edit (sige_hip_set_edit_batch(1)), and nothing held by
+ * sige_hip_conv_pair_begin or armed / queued by sige_hip_conv_side_begin; this entry point has no launch-plan hook and is
+ * refused while a plan records.  Everything else, other edges included: SIGE_HIP_EUNSUPPORTED -- never a wrong answer.
+ * sige_hip_gather_conv_nhwc and sige_hip_scatter_gather_conv_scatter_nhwc called with bH = bW = 10, a 3x3 / stride-1 kernel and
+ * a non-NULL `packed_tile3` run this form whatever `min_blocks` says (the geometry has no other matrix form; `packed` is not read).
+ * sige_hip_tile_conv3_block_supported: 1 if the channel counts and the edge have a kernel. */
+int sige_hip_tile_conv3_block_supported(int C1, int C2, int Cout, int bH, int bW);
+int sige_hip_tile_conv3_block_nhwc(
+        int compute, int source, const float *x, const void *x2, int y_f16, int B, int C1, int C2, int H, int W, int bH, int bW, int upsample2x,
+        const int32_t *active_indices, int N, const int32_t *scatter_map, int Rx, int Sx,
+        const float *scale, const float *shift, int affineB, int activation,
+        const float *packed, const float *bias, int Cout,
+        int to_full, int offsetH, int offsetW, int Ho, int Wo, const void *residual, int residual_f16,
+        const float *x1, const int32_t *table1, int gH1, int gW1, int N1, int R1, int S1,
+        const float *out_scale, const float *out_shift, int out_activation,
+        float *twin0, const float *twin_scale0, const float *twin_shift0,
+        float *twin1, const float *twin_scale1, const float *twin_shift1,
+        float *out, void *stream);
 
 /* ---- token-matrix helpers of Stable Diffusion's spatial transformer (csrc/token_ops.hip; sige_attention.py:86-185): tokens [T,C]
  * row-major fp32.  add_layer_norm: y = x (+ delta + bias[c] when delta != NULL; bias may be NULL); sum_out = y when not NULL;

@@ -853,6 +853,11 @@ static int staging_mode(const float *scale, int sB, int sC, const float *shift, 
 
 }  // namespace sige
 
+namespace sige {
+// (conv_tile3.hip: the 10x10-window form neither joins nor overtakes work held or queued on the stacked-block kernels)
+bool conv_hold_pending() { return g_held.active || g_side_armed > 0 || !g_side.empty(); }
+}  // namespace sige
+
 using namespace sige;
 
 extern "C" int sige_hip_conv_pair_begin(void) {
@@ -1252,6 +1257,12 @@ constexpr int kTile3F16PairMin = 256;  // (profiles/r6j_tile3_f16_pairs_bench.js
 // SIGE_HIP_TUNE_TILE3_F16_SPARSE_MIN = -1: this value, 0 = no separate rule
 constexpr int kTile3F16SparseMin = 128;  // (profiles/r6o_tile3_f16_sparse_min.json: -1 % at 10 - 20 % edits, nothing lost at 1.2 / 5 %; 32 - 96 lose at 1.2 %)
 
+// Block size 10 (10x10 windows of a 3x3 / stride-1 conv): the v3 kernel's one-window form is the ONLY matrix form of this geometry,
+// so with v3 weights the call runs there whatever `min_blocks` says; without them it is refused below as ever.
+static bool tile3_block10(const float *packed_tile3, int kH, int kW, int bH, int bW, int strideH, int strideW) {
+    return packed_tile3 && kH == 3 && kW == 3 && bH == 10 && bW == 10 && strideH == 1 && strideW == 1;
+}
+
 static bool tile3_takes(const float *packed_tile3, int min_blocks, int B, int N, int C1, int C2, int Cout, int kH, int kW, int bH, int bW,
                         int strideH, int strideW, hipStream_t st, bool f16 = false, int H = 0, int W = 0) {
     if (!packed_tile3 || min_blocks <= 0) return false;
@@ -1295,6 +1306,13 @@ extern "C" int sige_hip_gather_conv_nhwc(int compute, const float *x, const floa
     const int Cin = C1 + C2;
     const bool f16 = compute == 1;
     const bool aff_ok = (!scale && !shift) || (scale && shift && scaleC == Cin && shiftC == Cin && scaleB == shiftB && (scaleB == 1 || scaleB == B));
+    if (tile3_block10(packed_tile3, kH, kW, bH, bW, strideH, strideW)) {
+        if (compute != 0 || !aff_ok || upsample2x == 2) return SIGE_HIP_EUNSUPPORTED;
+        return tile_conv3_launch(T3_GATHER, x, x2, B, C1, C2, H, W, upsample2x, active_indices, N, nullptr, 0, 0, scale, shift,
+                                 scale ? scaleB : 0, activation, packed_tile3, bias, Cout, to_full, offsetH, offsetW, Ho, Wo,
+                                 to_full ? residual : nullptr, nullptr, nullptr, 0, 0, 0, 0, 0, out_scale, out_shift, out_activation,
+                                 twin0, twin0_scale, twin0_shift, twin1, twin1_scale, twin1_shift, out, stream, WIDE_F32, 0, 0, 10);
+    }
     if (upsample2x == 2) {
         // `packed` = the phase pack (sige_hip_upsample_phase_pack_f32) directly followed by the 9-tap pack of the same conv
         // (sige_hip_block_conv_pack_f32).  What the phase form does not cover is refused: the caller repeats the call with
@@ -1436,6 +1454,14 @@ extern "C" int sige_hip_scatter_gather_conv_scatter_nhwc(
     const bool f16 = compute == 1;
     const bool aff_ok = (!scale && !shift && activation == SIGE_HIP_ACT_IDENTITY) ||
                         (scale && shift && scaleC == Cin && shiftC == Cin && scaleB == shiftB && (scaleB == 1 || scaleB == B));
+    if (tile3_block10(packed_tile3, kH, kW, bH, bW, 1, 1)) {
+        if (compute != 0 || y_f16 || residual_f16 || scale || shift || activation != SIGE_HIP_ACT_IDENTITY || Rx != 8 || Sx != 8)
+            return SIGE_HIP_EUNSUPPORTED;
+        return tile_conv3_launch(T3_SCATTER_GATHER, x, static_cast<const float *>(y), B, Cin, 0, H, W, 0, active_indices, N, scatter_map, Rx, Sx,
+                                 nullptr, nullptr, 0, activation, packed_tile3, bias, Cout, 1, offsetH, offsetW, H, W,
+                                 static_cast<const float *>(residual), x1, table1, gH1, gW1, N1, R1, S1, nullptr, nullptr, 0,
+                                 twin0, twin0_scale, twin0_shift, twin1, twin1_scale, twin1_shift, out, stream, WIDE_F32, 0, 0, 10);
+    }
     // (the exact-fp32 v3 kernel reads fp32-stored caches only)
     if ((f16 || (compute == 0 && !y_f16 && !residual_f16)) && B > 0 && N > 0 && aff_ok &&
         tile3_takes(packed_tile3, min_blocks, B, N, Cin, 0, Cout, kH, kW, bH, bW, 1, 1, as_stream(stream), f16, f16 ? H : 0, f16 ? W : 0)) {

@@ -37,6 +37,9 @@ struct Tile3Geo {
     static constexpr bool F32 = PREC_ == WIDE_F32;
     static_assert(PREC_ == WIDE_F32 || PREC_ == WIDE_F16, "tile conv v3: exact fp32 or fp16 operands");
     static constexpr int KK = 9;
+    // window geometry (Tile3GeoE10 below: the same kernel over 10x10 windows): edge, output edge = 1 << OSH, pixels of a window /
+    // of its output, staged pixels between the M tiles of a wave
+    static constexpr int EDGE = 6, OSH = 2, OE = 4, WPX = 36, OPX = 16, MT_STRIDE = 72;
     static constexpr int MTN = TPW_ / 2;               // 32-pixel M tiles per wave (two 4x4 tiles each)
     static constexpr int BM = 16 * TPW_;               // output pixels per workgroup
     static constexpr int NP = F32 ? 2 : 1, CW = 16, CC = 64, STEPS = 9;
@@ -63,6 +66,27 @@ struct Tile3Geo {
     static constexpr int OCC = F32 ? (TPW_ == 2 ? 3 : 1) : (TPW_ == 2 ? SIGE_T3H_OCC : 2);  // (fp16, 4 tiles: 70 KB of LDS -- two workgroups per CU)
     static constexpr int LDS_BYTES = cmax(4 * 2 * ABUF, 4 * BM * 68 * 4);
     static_assert((2 * STEPS) % RB == 0, "the ring position of a step must not depend on the chunk");
+};
+
+// The same kernel over ONE 10x10 window per workgroup (block size 10: 8x8 = 64 output pixels, the M extent of the four-tile form
+// above), exact fp32.  A wave's two 32-pixel M tiles are output rows 0-3 and 4-7 of the window, 8 columns each; the staged pixel
+// of output pixel (r, s) at tap (kh, kw) is (r + kh) * 10 + (s + kw).  100 staged pixels x 4 float4 units = 7 staging slots per
+// lane (the last one ragged: 16 lanes).  LDS: 4 waves x 2 stages x 100 x 80 B = 64 000 B of stages under the 69 632 B of the
+// reduction buffer -> two workgroups per CU; registers: see conv_tile3_f32_b10.hip.  Weights, ring and packed layout
+// (sige_hip_wide_conv_pack(prec = 2)) are those of Tile3Geo<2>.  No stacked edits (the host refuses them).
+struct Tile3GeoE10 {
+    static constexpr int TPW = 1, PREC = WIDE_F32;
+    static constexpr bool F32 = true;
+    static constexpr int KK = 9;
+    static constexpr int EDGE = 10, OSH = 3, OE = 8, WPX = 100, OPX = 64, MT_STRIDE = 40;
+    static constexpr int MTN = 2, BM = 64;
+    static constexpr int NP = 2, CW = 16, CC = 64, STEPS = 9;
+    static constexpr int NPX = WPX * TPW, QP = CW / 4, UNITS = NPX * QP, NS = (UNITS + 63) / 64;
+    static constexpr int KSB = 32 * NP, KQB = 32, PLB = 16, ROWB = KSB + 16, ABUF = NPX * ROWB, STEPB = 2 * NP * 1024;
+    static constexpr int RB = 3, OCC = 2;
+    static constexpr int LDS_BYTES = cmax(4 * 2 * ABUF, 4 * BM * 68 * 4);
+    static_assert((2 * STEPS) % RB == 0, "the ring position of a step must not depend on the chunk");
+    static_assert(NS == 7 && LDS_BYTES == 69632, "10x10 windows: 7 staging slots, the reduction buffer bounds the LDS");
 };
 
 struct Tile3Args {
@@ -111,15 +135,15 @@ __device__ __forceinline__ void conv_tile3_body(const Tile3Args &a, const int bx
         constexpr int i = decltype(i_tag)::value;
         const int v = lane + 64 * i;
         const int p = v / G::QP;
-        const int tl = p / 36, q = p - tl * 36;
+        const int tl = p / G::WPX, q = p - tl * G::WPX;
         const int t = mtile * G::TPW + tl;
         z_ok[i] = v < G::UNITS && t < a.T;
         const int tt = min(t, a.T - 1);
         const int b = tt / a.N, n = tt - b * a.N;
         const int2 o = *reinterpret_cast<const int2 *>(a.idx + 2 * n);
         z_b[i] = b;
-        z_h[i] = o.x + q / 6;
-        z_w[i] = o.y + q % 6;
+        z_h[i] = o.x + q / G::EDGE;
+        z_w[i] = o.y + q % G::EDGE;
         int hlo = 0, hhi = a.H;
         if (a.hp_shift) {  // stacked edits: rows beyond the tile's own image are zero padding (its window's third row is inside it)
             hlo = ((o.x + 2) >> a.hp_shift) << a.hp_shift;
@@ -244,14 +268,16 @@ __device__ __forceinline__ void conv_tile3_body(const Tile3Args &a, const int bx
 
     // ---- A operand of this lane: pixel i32 of M tile mt = tiles 2 mt, 2 mt + 1 of the workgroup; k-group kq ----
     const int i32 = lane & 31, kq = lane >> 5;
-    const int abase = ((i32 >> 4) * 36 + ((i32 & 15) >> 2) * 6 + (i32 & 3)) * G::ROWB + kq * G::KQB;  // + mt * 72 * ROWB
+    // (10x10 windows: pixel i32 of M tile mt = output row 4 mt + (i32 >> 3), column i32 & 7 of the workgroup's window)
+    const int abase = (G::EDGE == 6 ? (i32 >> 4) * 36 + ((i32 & 15) >> 2) * 6 + (i32 & 3) : (i32 >> 3) * G::EDGE + (i32 & 7)) * G::ROWB +
+                      kq * G::KQB;  // + mt * MT_STRIDE * ROWB
     struct AHalf { f16x8 v[MTN]; };
     auto a_read = [&](auto s_tag, const unsigned char *buf, int plane) -> AHalf {
         constexpr int tap = decltype(s_tag)::value;
-        constexpr int off = ((tap / 3) * 6 + tap % 3) * G::ROWB;
+        constexpr int off = ((tap / 3) * G::EDGE + tap % 3) * G::ROWB;
         AHalf r;
 #pragma unroll
-        for (int mt = 0; mt < MTN; ++mt) r.v[mt] = *reinterpret_cast<const f16x8 *>(buf + abase + mt * 72 * G::ROWB + off + plane * G::PLB);
+        for (int mt = 0; mt < MTN; ++mt) r.v[mt] = *reinterpret_cast<const f16x8 *>(buf + abase + mt * G::MT_STRIDE * G::ROWB + off + plane * G::PLB);
         return r;
     };
 
@@ -364,7 +390,7 @@ __device__ __forceinline__ void conv_tile3_body(const Tile3Args &a, const int bx
     for (int k = 0; k < EU; ++k) {
         const int o = tid + 256 * k;
         const int n4 = o & 15, m = o >> 4;
-        const int tl = m >> 4, pix = m & 15;
+        const int tl = m >> (2 * G::OSH), pix = m & (G::OPX - 1);
         const int t = mtile * G::TPW + tl;
         const int co = ntile * 64 + 4 * n4;
         const float *r0 = red + m * RP + 4 * n4;
@@ -383,7 +409,7 @@ __device__ __forceinline__ void conv_tile3_body(const Tile3Args &a, const int bx
         if constexpr (FULL) {
             const int b = t / a.N, n = t - b * a.N;
             const int2 og = *reinterpret_cast<const int2 *>(a.idx + 2 * n);
-            const int h = a.offH + og.x + (pix >> 2), w = a.offW + og.y + (pix & 3);
+            const int h = a.offH + og.x + (pix >> G::OSH), w = a.offW + og.y + (pix & (G::OE - 1));
             if (h < 0 || h >= a.Ho || w < 0 || w >= a.Wo) continue;
             addr = (((size_t)b * a.Ho + h) * a.Wo + w) * a.Cout + co;
             if (a.residual) {  // out = conv + residual; with a block residual: + (x1 - residual) where a shortcut tile covers the pixel
@@ -408,7 +434,7 @@ __device__ __forceinline__ void conv_tile3_body(const Tile3Args &a, const int bx
             if (a.twin0) twin(a.twin0, a.tscale0, a.tshift0);
             if (a.twin1) twin(a.twin1, a.tscale1, a.tshift1);
         } else {
-            addr = ((size_t)t * 16 + pix) * a.Cout + co;
+            addr = ((size_t)t * G::OPX + pix) * a.Cout + co;
         }
         if (a.oscale) {
             const float4 os = *reinterpret_cast<const float4 *>(a.oscale + co), oh = *reinterpret_cast<const float4 *>(a.oshift + co);
@@ -437,9 +463,11 @@ int tile_conv3_launch(int source, const float *x, const float *x2, int B, int C1
                       const float *out_scale, const float *out_shift, int out_activation,
                       float *twin0, const float *twin_scale0, const float *twin_shift0,
                       float *twin1, const float *twin_scale1, const float *twin_shift1,
-                      float *out, void *stream, int prec = WIDE_F32, int y_f16 = 0, int residual_f16 = 0);
+                      float *out, void *stream, int prec = WIDE_F32, int y_f16 = 0, int residual_f16 = 0, int block = 6);
 
 // launchers (instantiated in conv_tile3_*.hip)
+void launch_conv_tile3_b10_gather(const Tile3Args &a, bool aff, bool cat, bool full, hipStream_t st);
+void launch_conv_tile3_b10_sg(const Tile3Args &a, bool full, hipStream_t st);
 template <int TPW, int PREC = WIDE_F32>
 void launch_conv_tile3_gather(const Tile3Args &a, bool aff, bool cat, bool full, hipStream_t st);
 template <int TPW, int PREC = WIDE_F32>

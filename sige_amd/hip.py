@@ -104,6 +104,9 @@ _SIGNATURES = {
     "sige_hip_tile_conv3_nhwc": (
         _c_int, [_c_int, _c_int, _c_vp, _c_vp, _c_int] + [_c_int] * 6 + [_c_vp, _c_int, _c_vp, _c_int, _c_int] + [_c_vp, _c_vp, _c_int, _c_int]
         + [_c_vp, _c_vp, _c_int] + [_c_int] * 5 + [_c_vp, _c_int] + [_c_vp, _c_vp] + [_c_int] * 5 + [_c_vp, _c_vp, _c_int] + [_c_vp] * 6 + [_c_vp, _c_vp]),
+    "sige_hip_tile_conv3_block_nhwc": (
+        _c_int, [_c_int, _c_int, _c_vp, _c_vp, _c_int] + [_c_int] * 8 + [_c_vp, _c_int, _c_vp, _c_int, _c_int] + [_c_vp, _c_vp, _c_int, _c_int]
+        + [_c_vp, _c_vp, _c_int] + [_c_int] * 5 + [_c_vp, _c_int] + [_c_vp, _c_vp] + [_c_int] * 5 + [_c_vp, _c_vp, _c_int] + [_c_vp] * 6 + [_c_vp, _c_vp]),
     "sige_hip_conv_ksplit_hint": (_c_int, [_c_int] * 7),
     "sige_hip_gather_nhwc_f32": (
         _c_int, [_c_vp] + [_c_int] * 6 + [_c_vp, _c_int] + [_c_vp, _c_int, _c_int] * 2 + [_c_int, _c_vp, _c_vp]),
@@ -175,6 +178,7 @@ _SIGNATURES = {
         _c_int, [_c_vp, _c_vp] + [_c_int] * 8 + [_c_vp, _c_int, _c_vp, _c_int, ctypes.c_float, _c_int, ctypes.c_int64, _c_vp, _c_vp]),
     "sige_hip_spade_modulate_dense_nhwc_f32": (_c_int, [_c_vp, _c_vp, _c_vp, _c_int, _c_vp] + [_c_int] * 5 + [ctypes.c_float, _c_vp, _c_vp]),
     "sige_hip_tile_conv3_supported": (_c_int, [_c_int] * 3),
+    "sige_hip_tile_conv3_block_supported": (_c_int, [_c_int] * 5),
     "sige_hip_add_layer_norm_tokens_f32": (_c_int, [_c_vp] * 5 + [ctypes.c_int64, _c_int, ctypes.c_float, _c_vp, _c_vp, _c_vp]),
     "sige_hip_geglu_tokens_f32": (_c_int, [_c_vp, ctypes.c_int64, _c_int, _c_vp, _c_vp]),
     "sige_hip_add_bias_tokens_f32": (_c_int, [_c_vp, _c_vp, _c_vp, ctypes.c_int64, _c_int, _c_vp, _c_vp]),
@@ -840,6 +844,7 @@ class PackedWeights(torch.Tensor):
     the tensor through clone / detach / to: a copy read with the wrong kernel family would run past its end)."""
     compute = "f32"
     wshift = 0  # wide packs (compute "f16w" / "f16x3w"): the weights were stored as w * 2^wshift
+    geo = None  # non-default block sizes (conv_pack_weights): "b10" | "k1b8" | "s2b9" -- channels-last kernels only
 
     @classmethod
     def __torch_function__(cls, func, types, args=(), kwargs=None):
@@ -849,6 +854,7 @@ class PackedWeights(torch.Tensor):
             if src is not None and src is not out:
                 out.compute = src.__dict__.get("compute", "f32")
                 out.wshift = src.__dict__.get("wshift", 0)
+                out.geo = src.__dict__.get("geo")
         return out
 
 
@@ -861,6 +867,9 @@ def conv_pack_weights(weight: torch.Tensor, R: int, S: int, stride: Tuple[int, i
     Cout, Cin, kH, kW = w.shape
     if compute not in ("f32", "f16", "f16x3"):
         raise ValueError("compute must be 'f32', 'f16' or 'f16x3'")
+    geo = block_geometry((R, S), (kH, kW), stride)
+    if geo is not None:
+        return _pack_block_geometry(w, geo, compute)
     n = 0
     if compute == "f16":
         n = int(lib().sige_hip_block_conv_packed_size_f16c(Cout, Cin, kH, kW, R, S, stride[0], stride[1], 1))
@@ -889,6 +898,76 @@ def conv_pack_weights(weight: torch.Tensor, R: int, S: int, stride: Tuple[int, i
         if TILE3 is not False and TILE3_MIN_BLOCKS is not None:
             _tile3_pack_now(packed)
     return packed
+
+
+# ---- block size 10 (and what Gather derives from it: 8x8 blocks for 1x1 convs, 9x9 for 3x3 / stride 2) ----------------------------
+# The matrix-core kernels cover three tile geometries (3x3 / s1 on 6x6, 1x1 on 4x4, 3x3 / s2 on 5x5).  Block size 10 adds:
+#   "b10"   3x3 / s1 on 10x10: the tile conv v3 over one 10x10 window per workgroup (csrc/conv_tile3.hpp: Tile3GeoE10), exact fp32;
+#           its PackedWeights hold the v3 layout ONLY (sige_hip_wide_conv_pack(prec = 2)) -- there is no conv_mfma.hpp form to route to
+#   "k1b8"  1x1 on 8x8 (no halo): [T,8,8,C] channels-last is a pixel list, so tiles -> tiles is the 1x1 kernel over [4T,4,4,C];
+#           fused with a full destination it runs over the four 4x4 sub-tiles of every tile (subtile_indices)
+#   "s2b9"  3x3 / s2 on 9x9: exactly four 5x5 windows at offsets {0, 4} x {0, 4} with 2x2 outputs each -- the full-destination launch
+#           runs the 5x5 kernel on the expanded index list; tiles-destination calls stay on the direct kernel
+# Channels-last, exact fp32 for "b10" (another compute dtype: None -> the caller's fallback, as before); launch plans refuse them.
+def block_geometry(block, kernel, stride) -> Optional[str]:
+    key = (tuple(int(v) for v in block), tuple(int(v) for v in kernel), tuple(int(v) for v in stride))
+    return {((10, 10), (3, 3), (1, 1)): "b10", ((8, 8), (1, 1), (1, 1)): "k1b8", ((9, 9), (3, 3), (2, 2)): "s2b9"}.get(key)
+
+
+_SUB_BLOCK = {"k1b8": (4, 4), "s2b9": (5, 5)}
+
+
+def _geometry_of(block, kernel, stride, packed):
+    """(geo, usable): the block-size-10 geometry of a call (None: a default one -- the sub-tiles of a large block included) and
+    whether `packed` was laid out for it."""
+    geo = block_geometry(block, kernel, stride)
+    pg = getattr(packed, "geo", None)
+    if geo is None:
+        return None, pg is None or tuple(int(v) for v in block) == _SUB_BLOCK.get(pg)
+    return geo, geo == pg
+
+
+def _pack_block_geometry(w: torch.Tensor, geo: str, compute: str):
+    Cout, Cin = w.shape[:2]
+    if compute != "f32":
+        return None  # (fp16 / f16x3 compute under a non-default block size: the caller's fallback, as before)
+    if geo == "b10":
+        if Cin % 64 or Cout % 64:
+            return None
+        packed = wide_conv_pack_weights(w, "f32")
+        if packed is None:
+            return None
+        packed.compute = "f32"  # (what the conv computes in; the layout is told by `geo`)
+    else:
+        packed = conv_pack_weights(w, *_SUB_BLOCK[geo], (1, 1) if geo == "k1b8" else (2, 2), compute)
+        if packed is None:
+            return None
+    packed.geo = geo
+    return packed
+
+
+def _refuse_in_plan(what: str):
+    if plan_recorder() is not None:
+        raise RuntimeError("%s: launch plans do not cover block size 10 (8x8 / 9x9 / 10x10 tiles) -- run the module forward, or "
+                           "build the model with the default block sizes" % what)
+
+
+def subtile_indices(idx: torch.Tensor, n: int = 2, step: int = 4) -> torch.Tensor:
+    """[N,2] tile origins -> [N * n * n, 2]: the origins of the n x n sub-tiles of every tile, `step` apart, tile-major
+    (row 4 t + 2 i + j = idx[t] + (step i, step j) for n = 2).  An 8x8 block is four 4x4 blocks, a 9x9 window of a 3x3 / stride-2
+    conv four 5x5 windows at {0, 4} x {0, 4}: with this list the kernels of the default geometries write exactly what one launch
+    over the large tiles would.  Cached on the index list (until it is written in place)."""
+    if idx.dtype != torch.int32 or idx.dim() != 2 or idx.shape[1] != 2:  # (pure index arithmetic: any device)
+        raise RuntimeError("subtile_indices: an int32 [N,2] index list, got %s %s" % (idx.dtype, tuple(idx.shape)))
+    cache = idx.__dict__.setdefault("_sige_subtiles", {})
+    hit = cache.get((n, step))
+    if hit is not None and hit[0] == idx._version:
+        return hit[1]
+    ar = torch.arange(n, dtype=torch.int32, device=idx.device) * step
+    offs = torch.stack(torch.meshgrid(ar, ar, indexing="ij"), dim=-1).reshape(1, n * n, 2)
+    sub = (idx.reshape(-1, 1, 2) + offs).reshape(-1, 2).contiguous()
+    cache[(n, step)] = (idx._version, sub)
+    return sub
 
 
 def upsample_phase_kernels(weight: torch.Tensor) -> torch.Tensor:
@@ -1568,6 +1647,11 @@ def block_conv_cl(x, packed, bias, Cout: int, kernel: Tuple[int, int], stride: T
     key = getattr(x, "_sige_count_key", None)
     x = _req_cl(x, "x")
     T, Cin, R, S = x.shape
+    geo, usable = _geometry_of((R, S), kernel, stride, packed)
+    if not usable:
+        return None
+    if geo is not None:
+        return _block_conv_cl_geometry(geo, x, key, packed, bias, Cout)
     Ro, So = (R - kernel[0]) // stride[0] + 1, (S - kernel[1]) // stride[1] + 1
     keyed = key is not None and key[0].shape[0] * key[1] == T and T > 0
     if keyed:  # (the tile count is the index list's: a launch plan follows it)
@@ -1583,6 +1667,31 @@ def block_conv_cl(x, packed, bias, Cout: int, kernel: Tuple[int, int], stride: T
         return None
     _check(status, "block_conv_cl")
     return tag_tiles(out, idx, B) if keyed else out
+
+
+def _block_conv_cl_geometry(geo: str, x, key, packed, bias, Cout: int):
+    """block_conv_cl over tiles of a block-size-10 geometry (block_geometry)."""
+    _refuse_in_plan("block_conv_cl")
+    T, Cin = x.shape[:2]
+    if geo == "s2b9" or get_edit_batch() != 1:  # (stacked edits: the caller's fallback, as before)
+        return None
+    if T == 0:
+        return _empty_cl((0, Cout, 8, 8), x.device)
+    if geo == "k1b8":
+        # [T,8,8,C] channels-last IS the pixel list [4T,4,4,C]: the 1x1 kernel over 4x4 tiles, no copy on either side
+        px = x.permute(0, 2, 3, 1).reshape(4 * T, 4, 4, Cin).permute(0, 3, 1, 2)
+        out = block_conv_cl(px, packed, bias, Cout, (1, 1), (1, 1))
+        if out is None:
+            return None
+        out = out.permute(0, 2, 3, 1).reshape(T, 8, 8, Cout).permute(0, 3, 1, 2)
+    else:
+        # "b10": a slab of 10x10 tiles is a batch of T images of 10x10 with one window at the origin each
+        origin = torch.zeros((1, 2), dtype=torch.int32, device=x.device)
+        out = tile_conv3_cl(1, x, None, T, Cin, 0, 10, 10, False, origin, None, (0, 0), None, None, "identity", packed, bias, Cout,
+                            None, None, (None, None, 0, 0, 0, 0, 0), None, (None,) * 6, _empty_cl((T, Cout, 8, 8), x.device), block=10)
+        if out is None:
+            return None
+    return tag_tiles(out, *key) if key is not None and key[0].shape[0] * key[1] == T else out
 
 
 # ---- tile conv v3 (csrc/conv_tile3.hpp): routing --------------------------------------------------------------------------
@@ -1646,7 +1755,7 @@ def _tile3_route(packed, T: int, C1: int, C2: int, Cout: int, kernel, stride, bl
 
 
 def tile_conv3_cl(source: int, x, x2, B, C1, C2, H, W, up, idx, smap, rx_sx, scale, shift, activationName, t3, bias, Cout,
-                  full, residual, bargs, out_affine, targs, out, compute: int = 0):
+                  full, residual, bargs, out_affine, targs, out, compute: int = 0, block: int = 6):
     """One launch of sige_hip_tile_conv3_nhwc (include/sige_hip.h); `full` = None (tiles) | (offH, offW, Ho, Wo); `compute`: the
     id of the packing `t3` was made from (x2 / residual may be fp16-stored caches under compute 1).  UNSUPPORTED -> None."""
     bias_keep = _vec(bias, "bias")
@@ -1668,8 +1777,12 @@ def tile_conv3_cl(source: int, x, x2, B, C1, C2, H, W, up, idx, smap, rx_sx, sca
     fargs = (0, 0, 0, 0, 0) if full is None else (1, *full)
     y16 = int(x2 is not None and x2.dtype == torch.float16)
     r16 = int(residual is not None and residual.dtype == torch.float16)
-    status = lib().sige_hip_tile_conv3_nhwc(
-        compute, source, x.data_ptr(), None if x2 is None else x2.data_ptr(), y16, B, C1, C2, H, W, int(bool(up)), idx.data_ptr(), idx.shape[0],
+    fn, bargs6 = lib().sige_hip_tile_conv3_nhwc, ()
+    if block != 6:  # (the entry point with the window edge as an argument: include/sige_hip.h)
+        _refuse_in_plan("tile_conv3_cl")
+        fn, bargs6 = lib().sige_hip_tile_conv3_block_nhwc, (block, block)
+    status = fn(
+        compute, source, x.data_ptr(), None if x2 is None else x2.data_ptr(), y16, B, C1, C2, H, W, *bargs6, int(bool(up)), idx.data_ptr(), idx.shape[0],
         None if smap is None else smap.data_ptr(), rx_sx[0], rx_sx[1], sc, sh, affB, _act(activationName),
         t3.data_ptr(), _p(bias_keep), Cout, *fargs, None if residual is None else residual.data_ptr(), r16, *bargs, *oargs, *targs,
         out.data_ptr(), _stream(x))
@@ -1689,6 +1802,15 @@ def gather_conv_cl(x, x2, block: Tuple[int, int], activeIndices, scale, shift, a
     the same launch.  `phase` (with upsample2x and `full`): the conv's phase pack (upsample_phase_pack) -- the launch is tried in
     the phase form first (include/sige_hip.h: upsample2x = 2) and repeated in the 9-tap form where the library refuses it.
     None if unsupported."""
+    geo, usable = _geometry_of(block, kernel, stride, packed)
+    if not usable:
+        return None
+    if geo is not None:
+        _refuse_in_plan("gather_conv_cl")
+        if geo != "b10":
+            return _gather_conv_cl_subtiles(geo, x, x2, activeIndices, scale, shift, activationName, packed, bias, Cout, kernel, stride,
+                                            full, out_affine, upsample2x, out, twins)
+    b10 = geo == "b10"  # (3x3 / s1 on 10x10 windows: `packed` holds the v3 layout; the routing entry point runs it whatever the count)
     bias_keep = _vec(bias, "bias")
     x = _req_cl(x, "x")
     B, C1, H, W = x.shape
@@ -1735,6 +1857,8 @@ def gather_conv_cl(x, x2, block: Tuple[int, int], activeIndices, scale, shift, a
     ks = lib().sige_hip_conv_ksplit_hint(B * N, C1 + C2, Cout, kernel[0], kernel[1], stride[0], stride[1])
     if full is not None and N * ((block[0] - kernel[0]) // stride[0] + 1) * ((block[1] - kernel[1]) // stride[1] + 1) < Ho * Wo:
         ks = 1  # tiles written into a larger tensor: the second pass would need whole output copies
+    if b10:
+        ks = 1  # (the v3 kernel splits K inside the workgroup)
     cap = _tile_capacity(idx)
     if cap is not None and full is None and KSPLIT:
         # a launch plan records: the SAME call will run under other masks.  The launch splits K only while its 16 x 16 blocks
@@ -1763,21 +1887,24 @@ def gather_conv_cl(x, x2, block: Tuple[int, int], activeIndices, scale, shift, a
     fargs = fargs + (int(bool(upsample2x)), *targs)
     # with v3 weights beside `packed` the entry point routes: conv_mfma.hpp or the v3 kernel, decided in C from N
     t3r = _tile3_packed(packed) if (TILE3 is None and compute in (0, 1)) else None
+    t3args = (packed.data_ptr(), 0) if b10 else _tile3_args(packed, t3r)
     status = UNSUPPORTED
-    if phase is not None and upsample2x and full is not None and compute == 0:
+    if phase is not None and upsample2x and full is not None and compute == 0 and not b10:
         fargs2 = fargs[:-(1 + len(targs))] + (2, *targs)
         status = lib().sige_hip_gather_conv_nhwc(
             compute, x.data_ptr(), None if x2 is None else x2.data_ptr(), B, C1, C2, H, W, block[0], block[1], idx.data_ptr(), N,
             *sa, *ta, _act(activationName), phase.data_ptr(), _p(bias_keep), Cout, kernel[0], kernel[1],
-            stride[0], stride[1], *fargs2, *_tile3_args(packed, t3r), out.data_ptr(), _stream(x))
+            stride[0], stride[1], *fargs2, *t3args, out.data_ptr(), _stream(x))
     if status == UNSUPPORTED:
         status = lib().sige_hip_gather_conv_nhwc(
             compute, x.data_ptr(), None if x2 is None else x2.data_ptr(), B, C1, C2, H, W, block[0], block[1], idx.data_ptr(), N,
             *sa, *ta, _act(activationName), packed.data_ptr(), _p(bias_keep), Cout, kernel[0], kernel[1],
-            stride[0], stride[1], *fargs, *_tile3_args(packed, t3r), out.data_ptr(), _stream(x))
+            stride[0], stride[1], *fargs, *t3args, out.data_ptr(), _stream(x))
     if status == UNSUPPORTED:
         return None
     _check(status, "gather_conv_cl")
+    if b10 and full is None:
+        out = tag_tiles(out, idx, B)
     keep = getattr(_pair_state, "keep", None)
     if keep is not None:  # (conv_pair(): a held launch reads these after this call has returned)
         keep.append((x, x2, idx, s_keep, t_keep, packed, phase, bias_keep, out, ws, out_affine, full, twin_keep))
@@ -1787,8 +1914,43 @@ def gather_conv_cl(x, x2, block: Tuple[int, int], activeIndices, scale, shift, a
     return out
 
 
+def _gather_conv_cl_subtiles(geo, x, x2, activeIndices, scale, shift, activationName, packed, bias, Cout, kernel, stride,
+                             full, out_affine, upsample2x, out, twins):
+    """gather_conv_cl for 1x1 on 8x8 blocks and 3x3 / stride 2 on 9x9 blocks (block_geometry)."""
+    idx = _req(activeIndices, torch.int32, "activeIndices", 2)
+    if get_edit_batch() != 1:  # (stacked edits: a sub-window is not judged like its window at an image seam -- the caller's fallback)
+        return None
+    if full is not None:
+        # one launch of the default geometry's kernel over the four sub-tiles of every tile: same pixels, same places
+        return gather_conv_cl(x, x2, _SUB_BLOCK[geo], subtile_indices(idx, 2, 4), scale, shift, activationName, packed, bias, Cout,
+                              kernel, stride, full=full, out_affine=out_affine, upsample2x=upsample2x, out=out, twins=twins)
+    if geo != "k1b8" or x2 is not None or upsample2x or out_affine is not None or twins:
+        return None
+    if idx.shape[0] == 0:
+        return tag_tiles(_empty_tiles_cl(x.shape[0], idx, Cout, 8, 8, x.device), idx, x.shape[0])
+    tiles = gather_cl(_req_cl(x, "x"), 8, 8, idx, scale, shift, activationName)
+    return block_conv_cl(tag_tiles(tiles, idx, x.shape[0]), packed, bias, Cout, kernel, stride)
+
+
 def scatter_gather_conv_cl(x, y, block: Tuple[int, int], activeIndices, scatterMap, scale, shift, activationName: str,
                            packed, bias, Cout: int, kernel: Tuple[int, int], stride: Tuple[int, int]):
+    geo, usable = _geometry_of(block, kernel, stride, packed)
+    if not usable:
+        return None
+    if geo is not None:
+        if geo != "b10" or scale is not None or shift is not None or activationName != "identity":
+            return None
+        x, y = _req_cl(x, "x"), _req_cl_cache(y, "y")
+        idx = _req(activeIndices, torch.int32, "activeIndices", 2)
+        smap = _req(scatterMap, torch.int32, "scatterMap", 3)
+        B, C, H, W = y.shape
+        if y.dtype != torch.float32:
+            return None
+        if idx.shape[0] == 0:
+            return tag_tiles(_empty_tiles_cl(B, idx, Cout, 8, 8, y.device), idx, B)
+        out = tile_conv3_cl(2, x, y, B, C, 0, H, W, False, idx, smap, (x.shape[2], x.shape[3]), None, None, "identity", packed, bias, Cout,
+                            None, None, (None, None, 0, 0, 0, 0, 0), None, (None,) * 6, _empty_tiles_cl(B, idx, Cout, 8, 8, y.device), block=10)
+        return None if out is None else tag_tiles(out, idx, B)
     bias_keep = _vec(bias, "bias")
     x, y = _req_cl(x, "x"), _req_cl_cache(y, "y")
     idx = _req(activeIndices, torch.int32, "activeIndices", 2)
@@ -1814,6 +1976,12 @@ def scatter_gather_conv_scatter_cl(x, y, block, activeIndices, scatterMap, scale
     """scatter_gather -> 3x3 conv -> Scatter (residual = a full tensor) or ScatterWithBlockResidual (residual = the
     cached shortcut tensor, x1 = the shortcut conv's tiles, table1 = their tile table) in one launch, written into
     `out` (a persistent buffer that already equals the cache outside this mask's tiles).  None if unsupported."""
+    geo, usable = _geometry_of(block, kernel, (1, 1), packed)
+    if not usable or geo not in (None, "b10"):
+        return None
+    if geo is not None:
+        _refuse_in_plan("scatter_gather_conv_scatter_cl")
+    b10 = geo == "b10"
     bias_keep = _vec(bias, "bias")
     x, y = _req_cl(x, "x"), _req_cl_cache(y, "y")
     idx = _req(activeIndices, torch.int32, "activeIndices", 2)
@@ -1846,11 +2014,12 @@ def scatter_gather_conv_scatter_cl(x, y, block, activeIndices, scatterMap, scale
             return got
     # routed in C like gather_conv_cl: fp16 operands over fp32- or fp16-stored caches, fp32 compute only over an fp32 cache
     t3r = _tile3_packed(packed) if (TILE3 is None and ((compute == 0 and y.dtype == torch.float32) or f16c)) else None
+    t3args = (packed.data_ptr(), 0) if b10 else _tile3_args(packed, t3r)
     status = lib().sige_hip_scatter_gather_conv_scatter_nhwc(
         compute, x.data_ptr(), y.data_ptr(), int(y.dtype == torch.float16), B, C, H, W, x.shape[2], x.shape[3], block[0], block[1],
         idx.data_ptr(), idx.shape[0], smap.data_ptr(), *sa, *ta, _act(activationName), packed.data_ptr(), _p(bias_keep), Cout,
         kernel[0], kernel[1], offset[0], offset[1], None if r is None else r.data_ptr(), int(r is not None and r.dtype == torch.float16),
-        *bargs, *targs, *_tile3_args(packed, t3r), out.data_ptr(), _stream(y))
+        *bargs, *targs, *t3args, out.data_ptr(), _stream(y))
     if status == UNSUPPORTED:
         return None
     _check(status, "scatter_gather_conv_scatter_cl")

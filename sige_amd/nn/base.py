@@ -158,6 +158,8 @@ class SIGEConv2d(nn.Conv2d, SIGEModule):
         if entry is None or entry[0] != key:
             entry = (key, hip.conv_pack_weights(w, x.shape[2], x.shape[3], self.stride, compute))
             self._packed[compute] = entry
+        if not channels_last and getattr(entry[1], "geo", None) is not None:
+            return None  # (block size 10: channels-last kernels only -- an NCHW caller takes its fallback)
         return entry[1]
 
     def _phase_key(self):
@@ -326,8 +328,14 @@ class SIGEModel(nn.Module):
         for name, g, up, prod_res, depth in self._demand_requests(masks):
             key = g.index_key(tuple(g.input_res))
             if key in keys:
-                demands.append((name, ("demand_tiles", *key[1:], int(up), *prod_res, *g.out_tile, *g.offset, depth),
-                                (keys.index(key), tuple(g.input_res), up, tuple(prod_res), tuple(g.out_tile), tuple(g.offset), depth)))
+                # (the lists are cells of the DENSE stage's own convs -- 4x4 outputs of 6x6 windows, padding 1: the 3x3 / s1 row of
+                #  nn/dense.py's tile geometry table, as _change_requests below passes it -- whatever block size the consumer
+                #  gather reads them through: its windows only say which pixels are needed)
+                from .dense import _GEOMETRY
+
+                _, cell, pad = _GEOMETRY[((3, 3), (1, 1), (1, 1))]
+                demands.append((name, ("demand_tiles", *key[1:], int(up), *prod_res, *cell, *pad, depth),
+                                (keys.index(key), tuple(g.input_res), up, tuple(prod_res), cell, pad, depth)))
         # change regions (dense stages fed by a tiled layer's persistent output): likewise, one launch per stage
         self._change_lists = {}
         changes = []
@@ -445,12 +453,20 @@ class SIGEModel(nn.Module):
                 module.inplace = inplace
 
 
-def paired_convs(like, enabled: bool = True):
+def paired_convs(like, enabled: bool = True, main=None):
     """Context for the two independent convs at the head of a residual block -- the 1x1 shortcut, then conv1 (3x3, cached
     affine + SiLU), both gathering from the block's input: on the GPU (channels-last, fp32) they share ONE launch
     (sige_amd.hip.conv_pair / sige_hip_conv_pair_begin: horizontal fusion); anywhere else, and whenever the pair cannot be
-    formed, each conv runs on its own.  Results do not depend on it.  `like`: a tensor (or deferred cat) on the convs' device."""
+    formed, each conv runs on its own.  Results do not depend on it.  `like`: a tensor (or deferred cat) on the convs' device.
+    `main`: conv1's Gather -- under a non-default block size (10x10 windows: sige_amd.hip.block_geometry) there is no pair kernel, and
+    a shortcut held for one would keep conv1 off its matrix-core form (the 10x10 tile conv refuses while a conv is held): no pairing."""
     import contextlib
+
+    if main is not None:
+        from .. import hip as _hip
+
+        if _hip.block_geometry(main.block_size, main.kernel_size, main.model_stride) is not None:
+            enabled = False
 
     first = like.parts[0] if hasattr(like, "parts") else like
     if enabled and isinstance(first, torch.Tensor) and first.is_cuda:

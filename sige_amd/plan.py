@@ -121,6 +121,12 @@ class LaunchPlan:
         if mask.dim() != 2 or mask.dtype != torch.bool or not mask.is_cuda:
             raise ValueError("LaunchPlan.record: `mask` must be a 2-D bool tensor on the GPU")
         self.build_masks, self.forward = build_masks, forward
+        for m in self.model.modules():
+            # (refused HERE, before anything records: the forward section is captured, and a refusal inside a capture is too late)
+            if all(hasattr(m, a) for a in ("block_size", "kernel_size", "model_stride")) and \
+                    hip.block_geometry(m.block_size, m.kernel_size, m.model_stride) is not None:
+                raise RuntimeError("LaunchPlan.record: launch plans do not cover block size 10 (%s tiles of %s) -- run the module "
+                                   "forward, or build the model with the default block sizes" % (tuple(m.block_size), type(m).__name__))
         with torch.cuda.device(self.device):
             self.mask = mask.clone()
             self.model.set_mode("sparse")

@@ -384,7 +384,7 @@ class ResBlock(SIGEModule, _TwinProducer):
 
     def _pairing(self, t: torch.Tensor):
         """Context for [shortcut conv, conv1] of a sparse-mode block: on the GPU the two share one launch."""
-        return paired_convs(t, enabled=self.pair and self.cin != self.cout and self.mode == "sparse")
+        return paired_convs(t, enabled=self.pair and self.cin != self.cout and self.mode == "sparse", main=getattr(self, "main_gather", None))
 
     def forward(self, x, temb: Optional[torch.Tensor], demand=None) -> torch.Tensor:
         """`x` may be a pair (h, skip): the up path's torch.cat, which the dense

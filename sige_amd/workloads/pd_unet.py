@@ -248,7 +248,7 @@ class PDResBlock(SIGEModule):
         # a plain tiled block, as the DDPM workload runs it: fused gather (affine + SiLU) -> conv1 with the consumer's affine in its
         # epilogue, scatter_gather of finished values, conv2 + scatter + residual in one launch
         xin = x if len(parts) == 1 else (lazy_cat(parts[0], parts[1]) if self.cin != self.cout else torch.cat(parts, dim=1))
-        with paired_convs(x, enabled=self.cin != self.cout and self.sparse_shortcut):
+        with paired_convs(x, enabled=self.cin != self.cout and self.sparse_shortcut, main=getattr(self, "main_gather", None)):
             if self.cin == self.cout:
                 skip = xin
             elif self.sparse_shortcut:

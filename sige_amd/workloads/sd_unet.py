@@ -95,7 +95,7 @@ class ResBlock(SIGEModule):
             return self.scatter(self.out_layers[3](F.silu(h)), skip)
         if self.mode in ("sparse", "profile"):
             s1, t1, s2, t2 = self.affine
-            with paired_convs(x, enabled=PAIRED_SHORTCUT and self.cin != self.cout and self.mode == "sparse"):  # the 1x1 rides in conv1's launch
+            with paired_convs(x, enabled=PAIRED_SHORTCUT and self.cin != self.cout and self.mode == "sparse", main=getattr(self, "main_gather", None)):  # the 1x1 rides in conv1's launch
                 skip = x if self.cin == self.cout else self.skip_connection(self.shortcut_gather(x))
                 h = self.in_layers[2](self.main_gather(x, s1, t1))
             tiles = self.scatter_gather(h, s2, t2)

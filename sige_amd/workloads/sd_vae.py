@@ -100,7 +100,7 @@ class VAEResBlock(SIGEModule):
         if self.mode in ("sparse", "profile"):
             s1, t1, s2, t2 = self.affine[self.cache_id]
             # (channels-last GPU tensors: the 1x1 shortcut rides in conv1's launch, conv2 + scatter + residual are one launch)
-            with paired_convs(x, enabled=self.cin != self.cout and self.mode == "sparse"):
+            with paired_convs(x, enabled=self.cin != self.cout and self.mode == "sparse", main=getattr(self, "main_gather", None)):
                 skip = x if self.cin == self.cout else self.nin_shortcut(self.shortcut_gather(x))
                 h = self.conv1(self.main_gather(x, s1, t1))
             tiles = self.scatter_gather(h, s2, t2)
