@@ -854,6 +854,22 @@ int sige_hip_attention_tokens_supported(int Nq, int Nk, int C, int heads);
 int sige_hip_attention_tokens_f32(const float *q, const float *k, const float *v, int B, int Nq, int Nk, int C,
                                   int heads, float scale, float *out, void *stream);
 
+/* ---- the same attention with fp16 OPERANDS (the f16 compute mode: SIGEModel.set_compute_dtype("f16")) -----------------
+ * Arguments, layouts, shape predicate (sige_hip_attention_tokens_supported) and status rules of sige_hip_attention_tokens_f32:
+ * q, k, v and out are fp32 token matrices in memory.  Arithmetic contract:
+ *   - q, k, v are rounded to nearest even to fp16 in registers (never truncated);
+ *   - scores are accumulated in fp32 and scaled in fp32, in units of log2 (exp(x) = exp2(x * log2 e)) like the fp32 form;
+ *   - the softmax state (running maximum m, sum l, rescale factor alpha) is fp32; l sums the unrounded probabilities;
+ *   - the probabilities are rounded to nearest even to fp16 for the product with v (carried scaled by 2^15 inside the
+ *     kernel, so none of them down to 2^-29 is an fp16 subnormal; the factor cancels in O / l);
+ *   - O, the merge of the partial results and the division by l are fp32.
+ * Finite inputs beyond fp16's range (|x| > 65504) are OUTSIDE the contract: they round to infinity, and an infinity that meets
+ * the zero padding of a head makes NaN.
+ * B * Nq == 0: SIGE_HIP_OK without a launch.  Null pointers: SIGE_HIP_EINVAL.  A shape the predicate refuses, a pointer that is
+ * not 16-byte aligned, one batch's K or V >= 2 GiB: SIGE_HIP_EUNSUPPORTED.                                                  */
+int sige_hip_attention_tokens_f16c(const float *q, const float *k, const float *v, int B, int Nq, int Nk, int C,
+                                   int heads, float scale, float *out, void *stream);
+
 /* ---- the same attention for WIDE heads: 160 < d <= 512, d % 16 == 0 (the SD VAE decoder's single 512-channel head) -----
  * q [B,Nq,ldq], k [B,Nk,ldk], v [B,Nk,ldv], out [B,Nq,ldo]: every operand comes with its ROW STRIDE in elements (>= C, a
  * multiple of 4; batch stride = rows * row stride), so k and v may be the two halves of one [B,Nk,2C] tensor and q / out

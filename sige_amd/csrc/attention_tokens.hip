@@ -28,7 +28,7 @@
 //
 // q [B,Nq,C], k / v [B,Nk,C], out [B,Nq,C], C = heads * d, all row-major fp32 (a channels-last [B,C,H,W] tensor IS [B,HW,C];
 // channels-last tiles [T,C,4,4] ARE [T*16, C]: no copy on either side).  Nq % 16 == 0; Nk arbitrary (tail keys masked).
-#include "common.hpp"
+#include "attention_rows.hpp"
 
 namespace sige {
 
@@ -232,22 +232,7 @@ void attention_tokens_kernel(const float *__restrict__ q, const float *__restric
 // (profiles/r6aa_attention_pmc.txt): L2 hit rate 98.5 % (the XCD dealing), SQ_VALU_MFMA_BUSY = 57 % of the SIMD cycles, 75 % of the
 // wave cycles are issue stalls behind the matrix pipe -- what is left is the pipe itself, the padding, and 1 008 workgroups on
 // 1 024 slots.
-// (v_permlane32_swap a, b: a's lanes 32..63 <-> b's lanes 0..31; with a == b == v both end up holding a half of v twice, max(a, b)
-//  is max(v[l], v[l ^ 32]) in every lane; v_permlane16_swap likewise for the odd / even rows of 16.  Inline asm: the clang builtin of
-//  ROCm 7.2 returns its first result twice when both operands are copies of one value -- tools/probe/permlane_swap_probe.hip.)
-__device__ __forceinline__ float max_over_rows(float v) {
-#ifdef SIGE_ATTENTION_SHFL
-    v = fmaxf(v, __shfl_xor(v, 32));
-    return fmaxf(v, __shfl_xor(v, 16));
-#else
-    float a = v, b = v;
-    asm volatile("s_nop 1\n\tv_permlane32_swap_b32 %0, %1\n\ts_nop 1" : "+v"(a), "+v"(b));
-    a = fmaxf(a, b); b = a;
-    asm volatile("s_nop 1\n\tv_permlane16_swap_b32 %0, %1\n\ts_nop 1" : "+v"(a), "+v"(b));
-    return fmaxf(a, b);
-#endif
-}
-
+// (the row maximum over the 4 lane rows, max_over_rows: attention_rows.hpp -- shared with the fp16-operand form)
 template <int UNITS>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(UNITS <= 3 ? 4 : 1)))
 void attention_tokens_t_kernel(const float *__restrict__ q, const float *__restrict__ k, const float *__restrict__ v,

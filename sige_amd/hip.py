@@ -154,6 +154,7 @@ _SIGNATURES = {
         _c_int, [_c_vp, _c_int, _c_int, _c_int, _c_vp, _c_int, _c_int, _c_int, _c_int, _c_int, ctypes.c_float] + [_c_vp] * 6),
     "sige_hip_attention_tokens_supported": (_c_int, [_c_int] * 4),
     "sige_hip_attention_tokens_f32": (_c_int, [_c_vp] * 3 + [_c_int] * 5 + [ctypes.c_float, _c_vp, _c_vp]),
+    "sige_hip_attention_tokens_f16c": (_c_int, [_c_vp] * 3 + [_c_int] * 5 + [ctypes.c_float, _c_vp, _c_vp]),
     "sige_hip_attention_wide_supported": (_c_int, [_c_int] * 4),
     "sige_hip_attention_wide_f32": (_c_int, [_c_vp, _c_int] * 3 + [_c_int] * 5 + [ctypes.c_float, _c_vp, _c_int, _c_vp]),
     # fp16-stored caches
@@ -2544,10 +2545,14 @@ def attention_residual_qv_cl(qv: torch.Tensor, keys: torch.Tensor, scale: float,
     return out, {key: b for key, b, _, _ in tw}
 
 
-def attention_tokens(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, heads: int, scale: float) -> Optional[torch.Tensor]:
+def attention_tokens(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, heads: int, scale: float,
+                     compute: str = "f32") -> Optional[torch.Tensor]:
     """softmax(scale * q k^T) v per (batch, head) for token matrices q [B,Nq,C], k / v [B,Nk,C] (C = heads * d), in ONE launch
     with the heads as strides (include/sige_hip.h: sige_hip_attention_tokens_f32) -> [B,Nq,C].  None if unsupported (then the
-    caller runs the reference's rearrange / bmm / softmax / bmm chain)."""
+    caller runs the reference's rearrange / bmm / softmax / bmm chain).  `compute`: "f32" exact fp32 products; "f16" fp16
+    operands with fp32 accumulation on the same fp32 tensors (sige_hip_attention_tokens_f16c states the contract)."""
+    if compute not in ("f32", "f16"):
+        raise ValueError("attention_tokens: compute must be 'f32' or 'f16', got %r" % (compute,))
     if not (q.is_cuda and q.dtype == k.dtype == v.dtype == torch.float32 and q.dim() == k.dim() == v.dim() == 3):
         return None
     B, Nq, C = q.shape
@@ -2558,8 +2563,8 @@ def attention_tokens(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, heads: i
         return None
     q, k, v = (t if t.is_contiguous() else t.contiguous() for t in (q, k, v))
     out = torch.empty((B, Nq, C), dtype=torch.float32, device=q.device)
-    status = lib().sige_hip_attention_tokens_f32(q.data_ptr(), k.data_ptr(), v.data_ptr(), B, Nq, Nk, C, heads, float(scale),
-                                                 out.data_ptr(), _stream(q))
+    entry = lib().sige_hip_attention_tokens_f16c if compute == "f16" else lib().sige_hip_attention_tokens_f32
+    status = entry(q.data_ptr(), k.data_ptr(), v.data_ptr(), B, Nq, Nk, C, heads, float(scale), out.data_ptr(), _stream(q))
     if status == UNSUPPORTED:
         return None
     _check(status, "attention_tokens")

@@ -49,7 +49,12 @@ from ..nn import Gather, Scatter, SIGEConv2d, SIGEModule
 #                     and the GEGLU projection; bias + residual in the epilogue of the three output projections; GEGLU in the
 #                     projection's epilogue -- six library launches instead of six GEMM-library calls plus five helpers, no aten GEMM
 #                     left in the block, no dependence on a tuning table.  Off by default: DESIGN.md 5.12 has the measurements.
+#   ATTENTION_COMPUTE the operands of NATIVE_ATTENTION's launch: "f32" exact fp32 products (sige_hip_attention_tokens_f32), "f16" fp16
+#                     operands with fp32 accumulation on the same fp32 tensors (sige_hip_attention_tokens_f16c: the attention of the
+#                     f16 compute mode) -- in full and in sparse mode, like the convs' compute dtype.  This one CHANGES values, within
+#                     the f16 criterion (sige_amd/tolerance.py).  "f32" by default: DESIGN.md 5.21 has the measurements.
 NATIVE_ATTENTION = True
+ATTENTION_COMPUTE = "f32"
 NATIVE_LINEAR = False
 BATCHED_QKV = True
 FUSED_TOKENS = True
@@ -120,7 +125,7 @@ class Attention(SIGEModule):
         if NATIVE_ATTENTION and q.is_cuda and q.dtype == torch.float32:
             from .. import hip
 
-            out = hip.attention_tokens(q, k, v, self.heads, self.scale)
+            out = hip.attention_tokens(q, k, v, self.heads, self.scale, compute=ATTENTION_COMPUTE)
             if out is not None:
                 if not bias:
                     return F.linear(out, self.to_out[0].weight)
@@ -222,10 +227,10 @@ class TransformerBlock(SIGEModule):
         q_t, k_t, v_t = need(hip.token_linear(x, p_qkv, n_qkv, norm=self.norm1, parts=3), "the q | k | v projection")
         k = sk(as_tiles(k_t))
         v = sv(as_tiles(v_t))
-        o = need(hip.attention_tokens(q_t, as_tokens(k), as_tokens(v), a1.heads, a1.scale), "the self-attention")
+        o = need(hip.attention_tokens(q_t, as_tokens(k), as_tokens(v), a1.heads, a1.scale, compute=ATTENTION_COMPUTE), "the self-attention")
         x1 = need(hip.token_linear(o, p_o1, n_o1, bias=a1.to_out[0].bias, residual=x), "attn1.to_out")
         q2 = need(hip.token_linear(x1, p_q2, n_q2, norm=self.norm2), "attn2.to_q")
-        o = need(hip.attention_tokens(q2, a2.cached_k, a2.cached_v, a2.heads, a2.scale), "the cross-attention")
+        o = need(hip.attention_tokens(q2, a2.cached_k, a2.cached_v, a2.heads, a2.scale, compute=ATTENTION_COMPUTE), "the cross-attention")
         x2 = need(hip.token_linear(o, p_o2, n_o2, bias=a2.to_out[0].bias, residual=x1), "attn2.to_out")
         h = need(hip.token_linear(x2, p_f0, n_f0, bias=ff.net[0].proj.bias, norm=self.norm3, geglu=True), "the GEGLU projection")
         return need(hip.token_linear(h, p_f2, n_f2, bias=ff.net[2].bias, residual=x2), "ff.net.2")
