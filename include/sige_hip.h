@@ -707,8 +707,14 @@ int sige_hip_conv3x3_small_cin_tiles_nhwc_f32(const float *x, int64_t strideB, i
 /* per-group mean / rstd of a [B,C,H,W] tensor -> per-channel (scale, shift) with
  * GroupNorm(x) == x*scale + shift  (scale = gamma*rstd, shift = beta - mean*scale):
  * the producer of the cached affine (diffusion/models/common.py:37-57) as two
- * streaming launches.  `workspace`: 2*B*groups*ceil(...) floats, see
- * sige_hip_group_norm_affine_workspace. */
+ * streaming launches.  `workspace`: sige_hip_group_norm_affine_workspace floats
+ * (always ask: per (batch, group) it holds the splits' partial sums as fp32 pairs in two
+ * planes and one pivot pair; contents are scratch).
+ * The statistics: the variance is E[v^2] - E[v]^2 of v = x - K, K the group's first
+ * element (a one-pass variance of x itself from fp32 sums loses eps32 * (mean / std)^2 of its
+ * accuracy); lanes sum v in fp32, everything across lanes and splits is fp64; scale and shift
+ * are formed in fp64 and rounded once.  |scale - exact| <= 4e-6 |exact| for |mean| / std up to
+ * 3000 and for constant groups (tests/test_gpu_group_norm_offsets.py). */
 size_t sige_hip_group_norm_affine_workspace(int B, int C, int H, int W, int groups);
 int sige_hip_group_norm_affine_f32(const float *x, int B, int C, int H, int W, int groups, float eps,
                                    const float *gamma, const float *beta, float *workspace,
@@ -722,14 +728,19 @@ int sige_hip_group_norm_affine_nhwc_f32(const float *x, int B, int C, int H, int
 
 /* the same with a per-channel bias [C] added BEFORE the statistics (a residual block's GroupNorm of h + temb,
  * diffusion/models/ddpm_arch/sige_fused_unet.py:116-117); the affine is returned for x itself:
- * GroupNorm(x + channel_bias) == x * scale + shift.  One batch-independent bias vector. */
+ * GroupNorm(x + channel_bias) == x * scale + shift.  One batch-independent bias vector.
+ * The pivot includes the bias: v = (x - K_x) + (channel_bias - K_b), K_b the bias of the group's first channel, so a bias that
+ * IS the group's offset (|bias| >> spread of x) costs no accuracy; shift = beta - (mean - channel_bias) * scale in fp64. */
 int sige_hip_group_norm_affine_nhwc_bias_f32(const float *x, int B, int C, int H, int W, int groups, float eps,
                                              const float *gamma, const float *beta, const float *channel_bias,
                                              float *workspace, float *scale, float *shift, void *stream);
 
-/* the same affine from per-channel statistics instead of the tensor: statsK [B * tilesK, CK, 2] = per pixel block and channel
+/* the same affine from per-channel statistics instead of the tensor: statsK [2][B * tilesK, CK, 2] = per pixel block and channel
  * (sum, sum of squares) as sige_hip_wide_conv_nhwc leaves them (tilesK blocks per batch element, countK = pixels per batch
- * element the sums run over).  Two parts = the GroupNorm of torch.cat([a, b], 1) over C1 + C2 channels without the cat
+ * element the sums run over).  Both sums are accumulated in fp64 inside the producing launch (the square of an fp32 value is
+ * exact there) and stored as unevaluated fp32 PAIRS hi + lo: plane [0] holds the leading parts -- on their own the fp32 sums -- and plane [1], B * tilesK * CK * 2 floats behind it,
+ * the low parts; the finisher adds hi + lo in fp64.  A statsK buffer is therefore 2 * B * tilesK * CK * 2 floats, and one
+ * that holds only the first plane is NOT valid input.  Two parts = the GroupNorm of torch.cat([a, b], 1) over C1 + C2 channels without the cat
  * (stats2 NULL / C2 0: one tensor; a group may straddle the parts).  channel_bias [C1 + C2] or NULL as above.  One launch. */
 int sige_hip_group_norm_affine_from_stats_f32(const float *stats1, int tiles1, int C1, int count1,
                                               const float *stats2, int tiles2, int C2, int count2,
@@ -737,7 +748,7 @@ int sige_hip_group_norm_affine_from_stats_f32(const float *stats1, int tiles1, i
                                               const float *channel_bias, float *scale, float *shift, void *stream);
 
 /* per-channel statistics of a channels-last tensor x [B,H,W,C] in that layout, for a tensor whose producer left none:
- * stats [B * sige_hip_channel_stats_tiles(H, W), C, 2], count = H * W.  One pass over x. */
+ * stats [2][B * sige_hip_channel_stats_tiles(H, W), C, 2] (leading parts, then low parts: above), count = H * W.  One pass over x. */
 int sige_hip_channel_stats_tiles(int H, int W);
 int sige_hip_channel_stats_nhwc_f32(const float *x, int B, int C, int H, int W, float *stats, void *stream);
 
@@ -820,7 +831,8 @@ int sige_hip_block_conv_pack_f16x3(const float *w, int Cout, int Cin, int kH, in
  * twinK (optional): twinK = SiLU(twin_scaleK * v + twin_shiftK), v = the value `out` receives before its out-affine.
  * workspace (optional, sige_hip_wide_conv_workspace floats): small layers split K across workgroups and finish inside
  * the launch (deterministic summation order); without it they run unsplit.
- * stats (optional, [B * ceil(H/8) * ceil(W/8), Cout, 2] floats): per 8x8 pixel block and output channel the (sum, sum of
+ * stats (optional, [2][B * ceil(H/8) * ceil(W/8), Cout, 2] floats -- leading parts, then low parts of fp32 pairs, see
+ * sige_hip_group_norm_affine_from_stats_f32): per 8x8 pixel block and output channel the (sum, sum of
  * squares) of what `out` receives (before its out-affine) -- the input of sige_hip_group_norm_affine_from_stats_f32, so that
  * the GroupNorm of the output needs no pass over it.                                                              */
 int sige_hip_wide_conv_supported(int C1, int C2, int Cout, int kH, int kW);

@@ -397,7 +397,10 @@ __device__ __forceinline__ void conv_wide_body(const WideArgs &a, const int bx, 
         return u;
     };
     // (this lane's units all have the same four output channels: n4 = tid & 15)
-    float4 st_s = make_float4(0.f, 0.f, 0.f, 0.f), st_q = make_float4(0.f, 0.f, 0.f, 0.f);
+    // (sum and sum of squares in fp64 -- full-rate adds and fmas on this chip, the square of an fp32 value is exact -- and stored
+    //  as fp32 pairs: a GroupNorm of an output with a large mean takes its variance from them, and one-pass fp32 sums lose
+    //  eps32 * (mean / std)^2 of it)
+    double st_s[4] = {0.0, 0.0, 0.0, 0.0}, st_q[4] = {0.0, 0.0, 0.0, 0.0};
     auto emit = [&](const Unit &u, float4 s) {
         s.x *= a.wscale; s.y *= a.wscale; s.z *= a.wscale; s.w *= a.wscale;  // (a power of two: exact)
         if (a.bias) {
@@ -409,8 +412,9 @@ __device__ __forceinline__ void conv_wide_body(const WideArgs &a, const int bx, 
             s.x += rr.x; s.y += rr.y; s.z += rr.z; s.w += rr.w;
         }
         if (a.stats) {
-            st_s.x += s.x; st_s.y += s.y; st_s.z += s.z; st_s.w += s.w;
-            st_q.x += s.x * s.x; st_q.y += s.y * s.y; st_q.z += s.z * s.z; st_q.w += s.w * s.w;
+            const double d[4] = {(double)s.x, (double)s.y, (double)s.z, (double)s.w};
+#pragma unroll
+            for (int e = 0; e < 4; ++e) { st_s[e] += d[e]; st_q[e] = __builtin_fma(d[e], d[e], st_q[e]); }
         }
         auto twin = [&](float *dst2, const float *ts, const float *tt) {
             const float4 sc = *reinterpret_cast<const float4 *>(ts + u.co), sh = *reinterpret_cast<const float4 *>(tt + u.co);
@@ -435,25 +439,30 @@ __device__ __forceinline__ void conv_wide_body(const WideArgs &a, const int bx, 
     auto flush_stats = [&]() {
         if (!a.stats) return;  // (uniform)
         __syncthreads();       // every lane is done with the reduction buffer
-        float *sb = red;       // [wave][16 quads][8]
+        double *sb = reinterpret_cast<double *>(red);  // [wave][16 quads][8]: sums, sums of squares
 #pragma unroll
-        for (int d = 16; d < 64; d <<= 1) {
-            st_s.x += __shfl_xor(st_s.x, d); st_s.y += __shfl_xor(st_s.y, d); st_s.z += __shfl_xor(st_s.z, d); st_s.w += __shfl_xor(st_s.w, d);
-            st_q.x += __shfl_xor(st_q.x, d); st_q.y += __shfl_xor(st_q.y, d); st_q.z += __shfl_xor(st_q.z, d); st_q.w += __shfl_xor(st_q.w, d);
-        }
+        for (int d = 16; d < 64; d <<= 1)
+#pragma unroll
+            for (int e = 0; e < 4; ++e) { st_s[e] += __shfl_xor(st_s[e], d); st_q[e] += __shfl_xor(st_q[e], d); }
         if (lane < 16) {
-            float *d = sb + (wave * 16 + lane) * 8;
-            *reinterpret_cast<float4 *>(d) = st_s;
-            *reinterpret_cast<float4 *>(d + 4) = st_q;
+            double *d = sb + (wave * 16 + lane) * 8;
+#pragma unroll
+            for (int e = 0; e < 4; ++e) { d[e] = st_s[e]; d[4 + e] = st_q[e]; }
         }
         __syncthreads();
         if (tid < 64) {
             const int q = tid >> 2, e = tid & 3;  // channel quad, channel inside it
-            float s1 = 0.f, s2 = 0.f;
+            double s1 = 0.0, s2 = 0.0;
 #pragma unroll
             for (int w = 0; w < 4; ++w) { s1 += sb[(w * 16 + q) * 8 + e]; s2 += sb[(w * 16 + q) * 8 + 4 + e]; }
             const int co = ntile * 64 + tid;
-            if (co < a.Cout) a.stats[(size_t)mtile * a.Cout + co] = make_float2(s1, s2);
+            if (co < a.Cout) {
+                // fp32 pairs: leading parts, and the low parts one plane (every pixel block of the launch x Cout entries) behind
+                const float h1 = (float)s1, h2 = (float)s2;
+                float2 *o = a.stats + (size_t)mtile * a.Cout + co;
+                o[0] = make_float2(h1, h2);
+                o[(size_t)a.B * tpi * a.Cout] = make_float2((float)(s1 - (double)h1), (float)(s2 - (double)h2));
+            }
         }
     };
     constexpr int EU = G::BM * 16 / 256;  // float4 units per lane

@@ -1117,7 +1117,7 @@ def wide_conv_cl(x, x2, scale, shift, activationName: str, packed, bias, Cout: i
     st = None
     if stats and out_affine is None:
         tiles = ((H + 7) // 8) * ((W + 7) // 8)
-        st = torch.empty((B * tiles, Cout, 2), dtype=torch.float32, device=x.device)
+        st = _stats_buffer(B * tiles, Cout, x.device)
     status = lib().sige_hip_wide_conv_nhwc(
         x.data_ptr(), None if x2 is None else x2.data_ptr(), B, C1, C2, H, W, int(bool(upsample2x)),
         sa[0], ta[0], sa[1] if s_keep is not None else 0, _act(activationName),
@@ -1128,13 +1128,20 @@ def wide_conv_cl(x, x2, scale, shift, activationName: str, packed, bias, Cout: i
         return None
     _check(status, "wide_conv_cl")
     if st is not None:
-        attach_channel_stats(out, ChannelStats(st, tiles, Cout, H * W))
+        attach_channel_stats(out, ChannelStats(st[0], tiles, Cout, H * W))
     return out
+
+
+def _stats_buffer(rows: int, C: int, device) -> torch.Tensor:
+    """[2, rows, C, 2]: the plane of leading parts of the per-block (sum, sum of squares) and, behind it, the plane of their
+    low parts -- both sums are fp32 pairs hi + lo (include/sige_hip.h: sige_hip_group_norm_affine_from_stats_f32)."""
+    return torch.empty((2, rows, C, 2), dtype=torch.float32, device=device)
 
 
 class ChannelStats:
     """Per-channel (sum, sum of squares) of a tensor, as its producer left them: `data` [B * tiles, C, 2] partial sums per pixel
-    block, `count` pixels per batch element.  Attached to the tensor OBJECT (attach_channel_stats) together with the tensor's
+    block, `count` pixels per batch element.  `data` is the plane of LEADING parts of a [2, B * tiles, C, 2] buffer: each sum is
+    an fp32 pair, its low part sits one plane behind (the finisher reads both through data's address).  Attached to the tensor OBJECT (attach_channel_stats) together with the tensor's
     version counter and address: any torch op makes a new object without them, an in-place op bumps the version, so stale
     statistics are never used (channel_stats returns None)."""
 
@@ -1167,12 +1174,12 @@ def channel_stats_cl(x: torch.Tensor) -> Optional[ChannelStats]:
     x = _req_cl(x, "x")
     B, C, H, W = x.shape
     tiles = int(lib().sige_hip_channel_stats_tiles(H, W))
-    data = torch.empty((B * tiles, C, 2), dtype=torch.float32, device=x.device)
+    data = _stats_buffer(B * tiles, C, x.device)
     status = lib().sige_hip_channel_stats_nhwc_f32(x.data_ptr(), B, C, H, W, data.data_ptr(), _stream(x))
     if status == UNSUPPORTED:
         return None
     _check(status, "channel_stats_cl")
-    st = ChannelStats(data, tiles, C, H * W)
+    st = ChannelStats(data[0], tiles, C, H * W)
     attach_channel_stats(x, st)
     return st
 

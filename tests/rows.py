@@ -20,7 +20,11 @@ ROW_TESTS = {
                                    "test_gpu_masks.py::test_one_model_through_every_mask_vs_oracle",
                                    "test_gpu_masks.py::test_launch_plan_follows_every_mask_vs_oracle",
                                    "test_gpu_masks.py::test_stacked_zoo_vs_cpu_oracle"],
-    "a9 cached affine producer": ["test_gpu_parity.py::test_group_norm_affine_vs_torch", "test_gpu_channels_last.py::test_group_norm_affine_cl"],
+    "a9 cached affine producer": ["test_gpu_parity.py::test_group_norm_affine_vs_torch", "test_gpu_channels_last.py::test_group_norm_affine_cl",
+                                  "test_gpu_group_norm_offsets.py::test_group_norm_affine_nchw_on_offset_inputs",
+                                  "test_gpu_group_norm_offsets.py::test_group_norm_affine_cl_on_offset_inputs",
+                                  "test_gpu_group_norm_offsets.py::test_channel_stats_route_on_offset_inputs",
+                                  "test_gpu_group_norm_offsets.py::test_wide_conv_stats_route_on_offset_inputs"],
     "f1 dense remainder": ["test_gpu_parity.py::test_dense_fused_conv_vs_torch", "test_gpu_parity.py::test_attention_vs_torch",
                            "test_gpu_round2.py::test_benchmarked_forward_vs_oracle_at_full_size"],
     "f2 SPADE modulation": ["test_models_golden.py::test_gaugan_generator_on_the_gpu_matches_the_reference_fixture",
