@@ -15,27 +15,17 @@
 //            contiguous bytes), issued before the score MFMAs so that they arrive under them;
 //   finish   one slice (HW <= 64): out = O / l.  Several: (O, m, l) go to the workspace with device-coherent stores, the block's
 //            ticket is taken, and the LAST slice to finish combines all of them in slice order -- out = sum_s O_s 2^(m_s - m) /
-//            sum_s l_s 2^(m_s - m) -- the mechanism of the K-split finish of the conv kernels (csrc/conv_mfma.hpp), same
+//            sum_s l_s 2^(m_s - m) -- the in-launch split finish of the conv kernels (csrc/split_finish.hpp), same
 //            tickets (split_tickets), no second launch, the summation order fixed (bit-reproducible).
 //
 // Exact fp32 products, no score recompute, HW / 16 x HW / 64 workgroups (64 for the 16 x 16 level).
-#include "common.hpp"
+#include "split_finish.hpp"
 
 namespace sige {
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 namespace {
-
-__device__ __forceinline__ void st_coherent(float *p, float v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-__device__ __forceinline__ float ld_coherent(const float *p) { return __hip_atomic_load(const_cast<float *>(p), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-__device__ __forceinline__ float4 ld_coherent4(const float *p) {
-    unsigned long long *q = reinterpret_cast<unsigned long long *>(const_cast<float *>(p));
-    const unsigned long long lo = __hip_atomic_load(q, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    const unsigned long long hi = __hip_atomic_load(q + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    return make_float4(__builtin_bit_cast(float, (unsigned)lo), __builtin_bit_cast(float, (unsigned)(lo >> 32)),
-                       __builtin_bit_cast(float, (unsigned)hi), __builtin_bit_cast(float, (unsigned)(hi >> 32)));
-}
 
 constexpr int kSliceKeys = 64;   // keys per workgroup (4 tiles of 16)
 constexpr int kMaxSlices = 16;   // HW <= 1024
@@ -163,27 +153,20 @@ __global__ __launch_bounds__(256) void attn_fused_nhwc_kernel(const float *__res
     for (int r = 0; r < 4; ++r) {
         float *prow = mine + (size_t)(4 * kq + r) * C + wave * CW + n;
 #pragma unroll
-        for (int nn = 0; nn < NT; ++nn) st_coherent(prow + 16 * nn, o[nn][r]);
+        for (int nn = 0; nn < NT; ++nn) coherent_store(prow + 16 * nn, o[nn][r]);
     }
-    if (tid < 16) st_coherent(mine + 16 * C + tid, m_s[tid]);
-    else if (tid < 32) st_coherent(mine + 16 * C + tid, l_s[tid - 16]);
-    // device-coherent stores are at the coherence point once complete (vmcnt 0); then the block's ticket (csrc/conv_mfma.hpp)
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-    int32_t *const cnt = counters + b * gridDim.y + qb;
-    if (tid == 0) ticket_s = __hip_atomic_fetch_add(cnt, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    __syncthreads();
-    if (ticket_s != KS - 1) return;
-    if (tid == 0) __hip_atomic_store(cnt, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);  // ready for the next launch
+    if (tid < 16) coherent_store(mine + 16 * C + tid, m_s[tid]);
+    else if (tid < 32) coherent_store(mine + 16 * C + tid, l_s[tid - 16]);
+    if (!split_arrive_last(counters + b * gridDim.y + qb, KS, &ticket_s)) return;  // (the protocol: split_finish.hpp)
     // ---- the last slice to arrive: weights of the slices per row, then the combination in slice order ----
     if (tid < 16) {
         float m = -INFINITY;
-        for (int s = 0; s < KS; ++s) m = fmaxf(m, ld_coherent(blk + (size_t)s * slot + 16 * C + tid));
+        for (int s = 0; s < KS; ++s) m = fmaxf(m, coherent_load(blk + (size_t)s * slot + 16 * C + tid));
         float L = 0.f;
         for (int s = 0; s < KS; ++s) {
-            const float w = __builtin_amdgcn_exp2f(ld_coherent(blk + (size_t)s * slot + 16 * C + tid) - m);
+            const float w = __builtin_amdgcn_exp2f(coherent_load(blk + (size_t)s * slot + 16 * C + tid) - m);
             wt[s][tid] = w;
-            L += w * ld_coherent(blk + (size_t)s * slot + 16 * C + 16 + tid);
+            L += w * coherent_load(blk + (size_t)s * slot + 16 * C + 16 + tid);
         }
         inv_s[tid] = 1.0f / L;
     }
@@ -196,7 +179,7 @@ __global__ __launch_bounds__(256) void attn_fused_nhwc_kernel(const float *__res
         const int row = e / UPR, c = (e - row * UPR) * 4;
         float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
         for (int s = 0; s < KS; ++s) {
-            const float4 pv = ld_coherent4(blk + (size_t)s * slot + (size_t)row * C + c);
+            const float4 pv = coherent_load4(blk + (size_t)s * slot + (size_t)row * C + c);
             const float w = wt[s][row];
             acc.x += w * pv.x; acc.y += w * pv.y; acc.z += w * pv.z; acc.w += w * pv.w;
         }

@@ -1,5 +1,6 @@
-// The row maximum of the transposed-score attention kernels (attention_tokens.hip, attention_tokens_f16.hip): lane (kq, j) holds
-// scores of query j, the four lane rows kq of a query meet in two v_permlane*_swap.
+// Shared by the transposed-score attention kernels (attention_tokens.hip, attention_tokens_f16.hip, attention_wide.hip): the row
+// maximum -- lane (kq, j) holds scores of query j, the four lane rows kq of a query meet in two v_permlane*_swap -- and the weight
+// of a partial softmax state in a merge.
 #pragma once
 #include "common.hpp"
 
@@ -20,5 +21,9 @@ __device__ __forceinline__ float max_over_rows(float v) {
     return fmaxf(a, b);
 #endif
 }
+
+// The weight of a partial softmax state with maximum m in a merge under the maximum M >= m (units of log2); a state that saw no
+// key (m = -inf, where M may be -inf too) weighs nothing.
+__device__ __forceinline__ float merge_weight(float m, float M) { return m == -INFINITY ? 0.f : __builtin_amdgcn_exp2f(m - M); }
 
 }  // namespace sige

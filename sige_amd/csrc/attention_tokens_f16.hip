@@ -230,7 +230,7 @@ void attention_tokens_f16_kernel(const float *__restrict__ q, const float *__res
 #pragma unroll
         for (int w = 0; w < 4; ++w) {
             const float mw = m_lds[w][row];
-            const float f = mw == -INFINITY ? 0.f : __builtin_amdgcn_exp2f(mw - M);  // (a wave without a key step)
+            const float f = merge_weight(mw, M);  // (a wave without a key step: 0)
             L += f * ((l_lds[w][0][row] + l_lds[w][1][row]) + (l_lds[w][2][row] + l_lds[w][3][row]));
             const float4 ov = *reinterpret_cast<const float4 *>(o_lds + ((size_t)w * 16 + row) * OS + c);
             acc.x += f * ov.x; acc.y += f * ov.y; acc.z += f * ov.z; acc.w += f * ov.w;

@@ -20,14 +20,14 @@
 // 132 KB of four images side by side).  A 16-query workgroup at d = 512 against 4 096 keys is 134 MFLOP = 218 us of one CU's fp32
 // matrix pipe, and a sparse edit has a handful of query tiles: the host splits the key blocks over `ksplit` workgroups per tile
 // (about one workgroup per CU in all); every split leaves its merged (m, l, O) in a workspace slice as device-coherent stores,
-// takes a ticket, and the LAST one adds the slices up in split order and writes the output -- the pattern of the conv K split
-// (conv_mfma.hpp), no second launch.  Without tickets or workspace (first use inside a capture, regions exhausted) ksplit = 1.
+// takes a ticket, and the LAST one adds the slices up in split order and writes the output -- the in-launch split
+// finish (split_finish.hpp), no second launch.  Without tickets or workspace (first use inside a capture, regions exhausted) ksplit = 1.
 //
 // q [B,Nq,ldq], k [B,Nk,ldk], v [B,Nk,ldv], out [B,Nq,ldo]: row strides in elements, head h at channels [h*d, (h+1)*d) of a row.
 #include <algorithm>
-#include <mutex>
 
-#include "common.hpp"
+#include "attention_rows.hpp"  // (max_over_rows, merge_weight: shared with attention_tokens.hip)
+#include "split_finish.hpp"
 
 namespace sige {
 
@@ -43,33 +43,6 @@ struct WideAttnArgs {
     int q_tiles, ksplit, split_blocks;  // split s takes key blocks [s * split_blocks, (s + 1) * split_blocks)
     float scale_log2e;
 };
-
-// (attention_tokens.hip: max over the 4 lane rows of a wave -- lanes l, l ^ 16, l ^ 32, l ^ 48 -- with two v_permlane*_swap)
-__device__ __forceinline__ float wide_max_over_rows(float v) {
-    float a = v, b = v;
-    asm volatile("s_nop 1\n\tv_permlane32_swap_b32 %0, %1\n\ts_nop 1" : "+v"(a), "+v"(b));
-    a = fmaxf(a, b); b = a;
-    asm volatile("s_nop 1\n\tv_permlane16_swap_b32 %0, %1\n\ts_nop 1" : "+v"(a), "+v"(b));
-    return fmaxf(a, b);
-}
-
-// device-coherent 16 bytes (relaxed agent-scope atomics: at the coherence point once vmcnt reaches 0; conv_mfma.hpp)
-__device__ __forceinline__ void wide_coherent_store(float4 *p, float4 v) {
-    unsigned long long *q = reinterpret_cast<unsigned long long *>(p);
-    const unsigned long long lo = (unsigned long long)__builtin_bit_cast(unsigned, v.x) | ((unsigned long long)__builtin_bit_cast(unsigned, v.y) << 32);
-    const unsigned long long hi = (unsigned long long)__builtin_bit_cast(unsigned, v.z) | ((unsigned long long)__builtin_bit_cast(unsigned, v.w) << 32);
-    __hip_atomic_store(q, lo, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    __hip_atomic_store(q + 1, hi, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-__device__ __forceinline__ float4 wide_coherent_load(const float4 *p) {
-    unsigned long long *q = reinterpret_cast<unsigned long long *>(const_cast<float4 *>(p));
-    const unsigned long long lo = __hip_atomic_load(q, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    const unsigned long long hi = __hip_atomic_load(q + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    return make_float4(__builtin_bit_cast(float, (unsigned)lo), __builtin_bit_cast(float, (unsigned)(lo >> 32)),
-                       __builtin_bit_cast(float, (unsigned)hi), __builtin_bit_cast(float, (unsigned)(hi >> 32)));
-}
-
-__device__ __forceinline__ float wide_weight(float m, float M) { return m == -INFINITY ? 0.f : __builtin_amdgcn_exp2f(m - M); }
 
 // ring depth: the largest divisor of the 2G chunks of a key block that is <= 8 (slots stay compile-time across blocks)
 constexpr int wide_ring(int G) { return (2 * G) % 8 == 0 ? 8 : (2 * G) % 7 == 0 ? 7 : (2 * G) % 6 == 0 ? 6 : 5; }
@@ -187,7 +160,7 @@ void attention_wide_kernel(WideAttnArgs a) {
 #pragma unroll
                             for (int r = 0; r < 4; ++r) sv[r] = key0 + 4 * kq + r < a.Nk ? sv[r] : -INFINITY;
                         }
-                        const float mb = wide_max_over_rows(fmaxf(fmaxf(sv[0], sv[1]), fmaxf(sv[2], sv[3])));  // (finite: a block has a live key)
+                        const float mb = max_over_rows(fmaxf(fmaxf(sv[0], sv[1]), fmaxf(sv[2], sv[3])));  // (finite: a block has a live key)
                         if (__builtin_amdgcn_ballot_w64(mb > m_run) != 0) {  // (wave-uniform; once the maxima have settled no block enters)
                             const float m_new = fmaxf(m_run, mb);
                             const float alpha = __builtin_amdgcn_exp2f(m_run - m_new);  // (exp2(-inf) = 0 on the first block)
@@ -232,7 +205,7 @@ void attention_wide_kernel(WideAttnArgs a) {
     auto take = [&]() {
         const float4 ml = img[(SLOTS - 1) * 64 + lane];
         const float M = fmaxf(m_run, ml.x);
-        const float f1 = wide_weight(m_run, M), f2 = wide_weight(ml.x, M);  // (a wave without a key block: weight 0)
+        const float f1 = merge_weight(m_run, M), f2 = merge_weight(ml.x, M);  // (a wave without a key block: weight 0)
         m_run = M;
         l_run = f1 * l_run + f2 * ml.y;
 #pragma unroll
@@ -288,17 +261,12 @@ void attention_wide_kernel(WideAttnArgs a) {
 #pragma unroll
         for (int g = 0; g < G; ++g) {
 #pragma unroll
-            for (int r = 0; r < 4; ++r) wide_coherent_store(mine + (4 * g + r) * 64 + lane, make_float4(o[g][0][r], o[g][1][r], o[g][2][r], o[g][3][r]));
+            for (int r = 0; r < 4; ++r)
+                coherent_store(reinterpret_cast<float *>(mine + (4 * g + r) * 64 + lane), make_float4(o[g][0][r], o[g][1][r], o[g][2][r], o[g][3][r]));
         }
-        wide_coherent_store(mine + (SLOTS - 1) * 64 + lane, make_float4(m_run, l_run, 0.f, 0.f));
+        coherent_store(reinterpret_cast<float *>(mine + (SLOTS - 1) * 64 + lane), make_float4(m_run, l_run, 0.f, 0.f));
     }
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-    int32_t *const cnt = a.tickets + unit;
-    if (tid == 0) ticket_lds = __hip_atomic_fetch_add(cnt, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    __syncthreads();
-    if (__builtin_amdgcn_readfirstlane(ticket_lds) != a.ksplit - 1) return;  // (one value for the workgroup: a scalar branch)
-    if (tid == 0) __hip_atomic_store(cnt, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);  // ready for the next launch
+    if (!split_arrive_last(a.tickets + unit, a.ksplit, &ticket_lds)) return;  // (the protocol: split_finish.hpp)
     // thread (wave, lane) -> slots wave, wave + 4, ... of lane `lane`: slot 4g + wave = channels 64g + 16kq + 4 wave .. +3 of query j.
     // The slices in split order with a running maximum, four slices' loads in flight at a time (a dependent round trip to the
     // coherence point per slice was most of a small launch)
@@ -311,15 +279,15 @@ void attention_wide_kernel(WideAttnArgs a) {
 #pragma unroll
         for (int u = 0; u < 4; ++u) {
             const float4 *src = ws + (size_t)min(p0 + u, a.ksplit - 1) * (SLOTS * 64);  // (past the end: the last slice again, not used)
-            ml[u] = wide_coherent_load(src + (SLOTS - 1) * 64 + lane);
+            ml[u] = coherent_load4(reinterpret_cast<const float *>(src + (SLOTS - 1) * 64 + lane));
 #pragma unroll
-            for (int g = 0; g < G; ++g) t[u][g] = wide_coherent_load(src + (4 * g + wave) * 64 + lane);
+            for (int g = 0; g < G; ++g) t[u][g] = coherent_load4(reinterpret_cast<const float *>(src + (4 * g + wave) * 64 + lane));
         }
 #pragma unroll
         for (int u = 0; u < 4; ++u) {
             if (p0 + u < a.ksplit) {  // (workgroup-uniform)
                 const float Mn = fmaxf(M, ml[u].x);
-                const float fo = wide_weight(M, Mn), fp = wide_weight(ml[u].x, Mn);
+                const float fo = merge_weight(M, Mn), fp = merge_weight(ml[u].x, Mn);
                 M = Mn;
                 L = fo * L + fp * ml[u].y;
 #pragma unroll
@@ -336,48 +304,6 @@ void attention_wide_kernel(WideAttnArgs a) {
         const int c = 64 * g + 16 * kq + 4 * wave;
         if (c < d) *reinterpret_cast<float4 *>(orow + 64 * g + 4 * wave) = make_float4(acc[g].x * inv, acc[g].y * inv, acc[g].z * inv, acc[g].w * inv);
     }
-}
-
-// Workspace of the key split: one buffer per device, a ring for eager launches (a slice is live while its launch runs) and a
-// bump-allocated region for launches recorded into a hipGraph, whose slice is baked into the graph (block_conv.hip's ticket pool).
-// nullptr (first use during a capture, region exhausted, allocation failure): the launch does not split.
-constexpr size_t kWideRing = size_t(8) << 20, kWideGraph = size_t(24) << 20;  // floats: 32 MiB + 96 MiB
-struct WideWsPool { float *buf = nullptr; size_t ring_pos = 0, graph_pos = 0; bool failed = false; };
-static WideWsPool g_wide_ws[32];
-static std::mutex g_wide_ws_mu;
-
-float *split_workspace(hipStream_t st, size_t floats) {  // (common.hpp: the latent head's channel split draws on it too)
-    int dev = -1;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 32 || floats > kWideRing) return nullptr;
-    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-    if (hipStreamIsCapturing(st, &cs) != hipSuccess) return nullptr;
-    const bool capturing = cs != hipStreamCaptureStatusNone;
-    std::lock_guard<std::mutex> lock(g_wide_ws_mu);
-    WideWsPool &t = g_wide_ws[dev];
-    if (!t.buf) {
-        if (capturing || t.failed) return nullptr;
-        if (hipMalloc(&t.buf, (kWideRing + kWideGraph) * sizeof(float)) != hipSuccess) {
-            t.buf = nullptr; t.failed = true;
-            (void)hipGetLastError();
-            return nullptr;
-        }
-    }
-    if (capturing) {
-        if (t.graph_pos + floats > kWideGraph) return nullptr;
-        float *p = t.buf + kWideRing + t.graph_pos;
-        t.graph_pos += floats;
-        return p;
-    }
-    if (t.ring_pos + floats > kWideRing) t.ring_pos = 0;
-    float *p = t.buf + t.ring_pos;
-    t.ring_pos += floats;
-    return p;
-}
-
-// (sige_hip_release_graph_tickets: every captured graph of the device is gone -- the graph region starts over)
-void attention_wide_release_graph_workspace(int dev) {
-    std::lock_guard<std::mutex> lock(g_wide_ws_mu);
-    if (dev >= 0 && dev < 32) g_wide_ws[dev].graph_pos = 0;
 }
 
 }  // namespace sige

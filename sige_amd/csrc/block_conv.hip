@@ -7,7 +7,6 @@
 // (sige/cuda/gather_kernel.cu:7-67) or scatter_gather kernel
 // (scatter_gather_kernel.cu:8-67).
 #include <deque>
-#include <mutex>
 
 #include "conv_mfma.hpp"
 #include "conv_tile3.hpp"  // (tile_conv3_launch: the routing in sige_hip_gather_conv_nhwc / sige_hip_scatter_gather_conv_scatter_nhwc)
@@ -427,56 +426,6 @@ static bool side_hazard(const ConvArgs &a) {
             if (w && (w == s.a.x || w == s.a.x2 || w == s.a.residual)) return true;
     }
     return false;
-}
-
-// Tickets of the in-kernel K-split finish (conv_mfma.hpp): one int per output block of a split launch, zero whenever no
-// such launch is running.  One buffer per device: a ring for eager launches (a slice is only live while its launch runs;
-// 2^20 tickets = hundreds of launches in flight before a wrap could meet a running one) and a bump-allocated region for
-// launches recorded into a hipGraph, whose slice is baked into the graph and must never be handed out again.  nullptr
-// (first use during a capture, region exhausted, allocation failure): the launch falls back to the second pass.
-constexpr size_t kTicketRing = size_t(1) << 20, kTicketGraph = size_t(3) << 20;
-struct TicketPool { int32_t *buf = nullptr; size_t ring_pos = 0, graph_pos = 0; bool failed = false; };
-static TicketPool g_tickets[32];
-static std::mutex g_tickets_mu;
-
-int32_t *split_tickets(hipStream_t st, long blocks) {
-    int dev = -1;
-    if (tuning(SIGE_HIP_TUNE_CONV_KSPLIT_SECOND_PASS) || hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 32 || blocks > (long)kTicketRing) return nullptr;
-    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-    if (hipStreamIsCapturing(st, &cs) != hipSuccess) return nullptr;
-    const bool capturing = cs != hipStreamCaptureStatusNone;
-    std::lock_guard<std::mutex> lock(g_tickets_mu);
-    TicketPool &t = g_tickets[dev];
-    if (!t.buf) {
-        if (capturing || t.failed) return nullptr;
-        const size_t bytes = (kTicketRing + kTicketGraph) * sizeof(int32_t);
-        if (hipMalloc(&t.buf, bytes) != hipSuccess || hipMemset(t.buf, 0, bytes) != hipSuccess || hipDeviceSynchronize() != hipSuccess) {
-            t.buf = nullptr; t.failed = true;
-            (void)hipGetLastError();
-            return nullptr;
-        }
-    }
-    if (capturing) {
-        if (t.graph_pos + blocks > kTicketGraph) return nullptr;
-        int32_t *p = t.buf + kTicketRing + t.graph_pos;
-        t.graph_pos += blocks;
-        return p;
-    }
-    if (t.ring_pos + blocks > kTicketRing) t.ring_pos = 0;
-    int32_t *p = t.buf + t.ring_pos;
-    t.ring_pos += blocks;
-    return p;
-}
-
-void attention_wide_release_graph_workspace(int dev);  // (attention_wide.hip: the key split's workspace of captured launches)
-
-int release_graph_tickets() {
-    int dev = -1;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 32) return SIGE_HIP_EINVAL;
-    attention_wide_release_graph_workspace(dev);
-    std::lock_guard<std::mutex> lock(g_tickets_mu);
-    g_tickets[dev].graph_pos = 0;
-    return SIGE_HIP_OK;
 }
 
 struct ConvPlan { int mt, nb, waves; };
@@ -1498,5 +1447,3 @@ extern "C" int sige_hip_block_conv_direct_f32(const float *x, int T, int Cin, in
                                                                    strideH, strideW, dilationH, dilationW, groups, Ro, So, total);
     return launch_status();
 }
-
-extern "C" int sige_hip_release_graph_tickets(void) { return sige::release_graph_tickets(); }

@@ -107,11 +107,11 @@ inline int launch_status(int kernels = 1) {
     return hipGetLastError() == hipSuccess ? SIGE_HIP_OK : SIGE_HIP_ELAUNCH;
 }
 
-// (block_conv.hip) tickets of the in-launch K-split finish: `blocks` zeroed ints that stay valid while the launch runs
-// (or, during a hipGraph capture, for the life of the graph); nullptr = unavailable, the caller must not split
+// (split_pool.hip) tickets of the in-launch split finish (split_finish.hpp): `blocks` zeroed ints that stay valid while the launch
+// runs (or, during a hipGraph capture, for the life of the graph); nullptr = unavailable, the caller must not split
 int32_t *split_tickets(hipStream_t st, long blocks);
 
-// (attention_wide.hip) workspace of a split whose slices are added up inside the launch: `floats` floats that stay valid like the
+// (split_pool.hip) workspace of a split whose slices are added up inside the launch: `floats` floats that stay valid like the
 // tickets do; nullptr = unavailable (first use during a capture, region exhausted), the caller must not split
 float *split_workspace(hipStream_t st, size_t floats);
 

@@ -16,11 +16,11 @@
 //     out-of-image taps are skipped by the summing lane: that is the zero padding of the ACTIVATED tensor.
 // The real shape is 64x64 pixels = 121 tiles on 256 CUs, so the channels are split over up to 8 workgroups per tile
 // (blocks <= 512): each writes its 36 Cout partial sums to a workspace slice with device-coherent stores and draws a ticket; the
-// last one to arrive adds the slices IN SPLIT ORDER, its own included -- the K-split finish of conv_mfma.hpp and
-// attention_wide.hip, one launch, no float atomics, bit-identical from run to run.
+// last one to arrive adds the slices IN SPLIT ORDER, its own included -- the in-launch split finish of
+// split_finish.hpp, one launch, no float atomics, bit-identical from run to run.
 #include <algorithm>
 
-#include "common.hpp"
+#include "split_finish.hpp"
 
 namespace sige {
 
@@ -42,13 +42,6 @@ struct LatentHeadArgs {
     float latent_scale;
 };
 static_assert(sizeof(LatentHeadArgs) >= 128, "kernarg_touch<128>");
-
-__device__ __forceinline__ void head_coherent_store(float *p, float v) {
-    __hip_atomic_store(reinterpret_cast<unsigned *>(p), __builtin_bit_cast(unsigned, v), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-__device__ __forceinline__ float head_coherent_load(const float *p) {
-    return __builtin_bit_cast(float, __hip_atomic_load(reinterpret_cast<unsigned *>(const_cast<float *>(p)), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
-}
 
 // NB = 16-wide column blocks of the GEMM: ceil(9 Cout / 16)
 template <int NB>
@@ -208,22 +201,16 @@ __global__ __launch_bounds__(256) void conv_latent_head_kernel(LatentHeadArgs a)
 #pragma unroll
         for (int n = 0; n < NO; ++n) {
             const int idx = tid + 256 * n;
-            if (idx < NOUT) head_coherent_store(ws + (size_t)split * NOUT + idx, val[n]);
+            if (idx < NOUT) coherent_store(ws + (size_t)split * NOUT + idx, val[n]);
         }
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        __syncthreads();
-        int32_t *const cnt = a.tickets + unit;
-        if (tid == 0) ticket_lds = __hip_atomic_fetch_add(cnt, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        __syncthreads();
-        if (__builtin_amdgcn_readfirstlane(ticket_lds) != a.ksplit - 1) return;  // (one value for the workgroup: a scalar branch)
-        if (tid == 0) __hip_atomic_store(cnt, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);  // ready for the next launch
+        if (!split_arrive_last(a.tickets + unit, a.ksplit, &ticket_lds)) return;  // (the protocol: split_finish.hpp)
 #pragma unroll
         for (int n = 0; n < NO; ++n) {
             const int idx = min(tid + 256 * n, NOUT - 1);
             float part[kLMaxSplit];
 #pragma unroll
             for (int u = 0; u < kLMaxSplit; ++u)  // (past the end: the last slice again, not used)
-                part[u] = head_coherent_load(ws + (size_t)min(u, a.ksplit - 1) * NOUT + idx);
+                part[u] = coherent_load(ws + (size_t)min(u, a.ksplit - 1) * NOUT + idx);
             float s = 0.f;
 #pragma unroll
             for (int u = 0; u < kLMaxSplit; ++u) s += u < a.ksplit ? part[u] : 0.f;

@@ -37,6 +37,7 @@
 #include <type_traits>
 
 #include "common.hpp"
+#include "split_finish.hpp"
 
 namespace sige {
 
@@ -341,22 +342,6 @@ enum { LAYOUT_NCHW = 0, LAYOUT_NHWC = 1 };
 // form for grids that cannot give every CU two workgroups.  The packed weight order
 // [ng][chunk][wave][f][lane] read with chunk' = chunk / 2, wave' = 4 * (chunk % 2) + wave is
 // exactly the 8-wave order, so both forms share one packed tensor (chunk count padded to even).
-// 16 bytes to / from the device's coherence point (two relaxed agent-scope 8-byte atomics: visible to every XCD without
-// cache maintenance) -- the partial sums of the in-kernel K-split finish
-__device__ __forceinline__ void coherent_store(float *p, float4 v) {
-    unsigned long long *q = reinterpret_cast<unsigned long long *>(p);
-    const unsigned long long lo = (unsigned long long)__builtin_bit_cast(unsigned, v.x) | ((unsigned long long)__builtin_bit_cast(unsigned, v.y) << 32);
-    const unsigned long long hi = (unsigned long long)__builtin_bit_cast(unsigned, v.z) | ((unsigned long long)__builtin_bit_cast(unsigned, v.w) << 32);
-    __hip_atomic_store(q, lo, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    __hip_atomic_store(q + 1, hi, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-__device__ __forceinline__ float4 coherent_load(const float *p) {
-    unsigned long long *q = reinterpret_cast<unsigned long long *>(const_cast<float *>(p));
-    const unsigned long long lo = __hip_atomic_load(q, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    const unsigned long long hi = __hip_atomic_load(q + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    return make_float4(__builtin_bit_cast(float, (unsigned)lo), __builtin_bit_cast(float, (unsigned)(lo >> 32)),
-                       __builtin_bit_cast(float, (unsigned)hi), __builtin_bit_cast(float, (unsigned)(hi >> 32)));
-}
 
 // LDS floats of one workgroup (the kernels below declare the array; the body only receives the pointer, so that two
 // bodies sharing a launch -- conv_pair_kernel -- share one allocation)
@@ -1094,9 +1079,10 @@ __device__ __forceinline__ void conv_mfma_body(const ConvArgs &a, const int bx, 
             else coherent_store(outp + u.addr, s);
         });
         if (split_k && a.counters) {
-            // The partial sums went out as device-coherent (relaxed, agent-scope atomic) stores: they are at the device's
-            // coherence point once they have completed (vmcnt 0) -- no L2 write-back / invalidate of the whole XCD, which a
-            // release / acquire fence would cost every workgroup (measured: +11 us per launch).  Then the block's ticket.
+            // The block's ticket; the workgroup that draws the last one adds the copies up.  The protocol, and why it holds:
+            // split_arrive_last() in split_finish.hpp -- the same sequence, written out here (the ticket through red[0] as a float
+            // bit pattern) because through the helper 9 kernels of this template changed their VGPR / AGPR counts by 1-4 and the
+            // 1.2 % forward measured 0.2-0.3 % slower (profiles/split_finish_ab.jsonl).
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
             __syncthreads();
             int32_t *const cnt = a.counters + mb * a.ngk + ng;
@@ -1112,7 +1098,7 @@ __device__ __forceinline__ void conv_mfma_body(const ConvArgs &a, const int bx, 
                     float4 pv[8];
 #pragma unroll
                     for (int sidx = 0; sidx < 8; ++sidx)
-                        pv[sidx] = coherent_load(a.out + (size_t)(sidx < a.ksplit ? sidx : a.ksplit - 1) * a.split_stride + u.addr);
+                        pv[sidx] = coherent_load4(a.out + (size_t)(sidx < a.ksplit ? sidx : a.ksplit - 1) * a.split_stride + u.addr);
                     float4 s = pv[0];
 #pragma unroll
                     for (int sidx = 1; sidx < 8; ++sidx)

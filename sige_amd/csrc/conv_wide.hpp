@@ -485,16 +485,9 @@ __device__ __forceinline__ void conv_wide_body(const WideArgs &a, const int bx, 
     if (!split_k) flush_stats();
     SIGE_WPROBE(6);  // statistics written
     if (split_k) {
-        // partial sums went out as device-coherent stores (complete = visible to every XCD); then the block's ticket; the
-        // workgroup that draws the last one adds the copies in split order (deterministic) and runs the epilogue
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        __syncthreads();
-        int32_t *const cnt = a.counters + bx;
-        if (tid == 0) red[0] = __builtin_bit_cast(float, __hip_atomic_fetch_add(cnt, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
-        __syncthreads();
-        const int ticket = __builtin_bit_cast(int, red[0]);
-        if (ticket == a.ksplit - 1) {
-            if (tid == 0) __hip_atomic_store(cnt, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        // the block's ticket; the workgroup that draws the last one adds the copies in split order (deterministic) and runs the
+        // epilogue (the protocol: split_finish.hpp)
+        if (split_arrive_last(a.counters + bx, a.ksplit, reinterpret_cast<int *>(red))) {
             // the copies of this lane's units (four units at a time), four splits in flight at a time, added in split order
 #pragma unroll
             for (int k0 = 0; k0 < EU; k0 += 4) {
@@ -508,7 +501,7 @@ __device__ __forceinline__ void conv_wide_body(const WideArgs &a, const int bx, 
                     for (int k = 0; k < 4; ++k)
 #pragma unroll
                         for (int d = 0; d < 4; ++d)
-                            pv[k][d] = coherent_load(a.out + (size_t)(s0 + d < a.ksplit ? s0 + d : a.ksplit - 1) * a.split_stride + us[k].addr);
+                            pv[k][d] = coherent_load4(a.out + (size_t)(s0 + d < a.ksplit ? s0 + d : a.ksplit - 1) * a.split_stride + us[k].addr);
 #pragma unroll
                     for (int k = 0; k < 4; ++k)
 #pragma unroll

@@ -109,6 +109,39 @@ def test_graph_replay_equals_eager_bit_for_bit(hip, Nq, Nk, d):
         assert torch.equal(out, eager)
 
 
+def test_release_graph_tickets_restarts_tickets_and_workspace(hip):
+    """hip.release_graph_tickets() once every captured graph is gone: the graph regions of BOTH pools of the split finish (tickets and
+    workspace) start over.  B = 1, heads = 1, Nq = 16, Nk = 128: ksplit = min(256 / 1, 8 / 4, 16) = 2, the smallest launch that draws
+    on both.  A capture before and a capture after the release replay the eager bits, and so does an eager launch afterwards."""
+    Nq, Nk, d = 16, 128, 192
+    q, k, v = _inputs(1, Nq, Nk, 1, d)
+    out = torch.empty(1, Nq, d, device=DEV)
+    eager = hip.attention_wide(q, k, v, 1, d ** -0.5).clone()
+    s = torch.cuda.Stream()
+
+    def capture_and_replay():
+        s.wait_stream(torch.cuda.current_stream())
+        g = torch.cuda.CUDAGraph()
+        with torch.cuda.stream(s):
+            with torch.cuda.graph(g, stream=s):
+                hip.attention_wide(q, k, v, 1, d ** -0.5, out=out)
+        torch.cuda.current_stream().wait_stream(s)
+        out.fill_(float("nan"))
+        g.replay()
+        torch.cuda.synchronize()
+        assert torch.equal(out, eager)
+        return g
+
+    g = capture_and_replay()
+    del g
+    hip.release_graph_tickets()
+    g = capture_and_replay()
+    out.fill_(float("nan"))
+    assert hip.attention_wide(q, k, v, 1, d ** -0.5, out=out) is out
+    torch.cuda.synchronize()
+    assert torch.equal(out, eager)
+
+
 def test_head_dimensions_outside_the_range_are_refused(hip):
     for d in (160, 528, 200):
         q, k, v = (torch.randn(1, 16, d, device=DEV) for _ in range(3))
