@@ -9,6 +9,7 @@
 #include <deque>
 
 #include "conv_mfma.hpp"
+#include "conv_call.hpp"
 #include "conv_tile3.hpp"  // (tile_conv3_launch: the routing in sige_hip_gather_conv_nhwc / sige_hip_scatter_gather_conv_scatter_nhwc)
 
 namespace sige {
@@ -584,154 +585,183 @@ bool take_held_shortcut(ConvArgs *b, int *mt) {
 
 int flush_held_conv() { return flush_held(); }
 
+// ---- one launch of a geometry: four steps, run by KindSteps::launch in this order ----
+constexpr int STEP_GO = 1;  // a step's answer "go on"; anything else is the status the call returns
+
+template <typename G> struct GeoTag { using type = G; };
+template <int NB> using NBTag = std::integral_constant<int, NB>;
+
 template <int KH, int STR, int R, int SRC, int DST, int LAY, int PREC = 0>
-static int launch_kind(ConvArgs a, int mode, hipStream_t st) {
+struct KindSteps {
     using G32 = GeoOf<PREC, KH, STR, R, 32>;
     using G16 = GeoOf<PREC, KH, STR, R, 16>;
-    constexpr bool kHasNB2 = STR == 1 && PREC != 2;
-    if constexpr (PREC == 2)  // 2^-S sits in the header behind the two packed tile shapes (pack_weights_x_kernel)
-        a.wscale_ptr = a.packed + packed_units_x(a.Cout, a.Cin, KH * KH, 32) + packed_units_x(a.Cout, a.Cin, KH * KH, 16) + 1;
-    constexpr bool kPairLayout = SRC == SRC_GATHER && LAY == LAYOUT_NHWC && STR == 1;
-    constexpr bool kPairFirst = kPairLayout && KH == 3, kPairSecond = kPairLayout && KH == 1;
-    const bool may_pair = kPairFirst && g_held.active && (mode == MODE_AFFINE_SWISH || mode == MODE_RAW) && g_held.st == st && g_held.dst == DST && g_held.prec == PREC;
-    if (g_held.active && !may_pair) {
-        const int rc = flush_held();
-        if (rc != SIGE_HIP_OK) return rc;
+    static constexpr bool kHasNB2 = STR == 1 && PREC != 2;
+    static constexpr bool kPairLayout = SRC == SRC_GATHER && LAY == LAYOUT_NHWC && STR == 1;
+    static constexpr bool kPairFirst = kPairLayout && KH == 3, kPairSecond = kPairLayout && KH == 1;
+    static constexpr bool kSideGeo = KH == 3 && STR == 1 && SRC == SRC_GATHER && DST == DST_NCHW && LAY == LAYOUT_NHWC && PREC == 0;
+    static constexpr bool kHasC16 = SRC == SRC_SCATTER_GATHER && LAY == LAYOUT_NHWC && KH == 3 && STR == 1;
+    static constexpr bool kHasW8 = LAY == LAYOUT_NHWC && STR == 1 && PREC == 0;
+
+    // the ladder of template instances: f(GeoTag<G32 | G16>, NBTag<1 | 2>) for the planned output block
+    template <typename F>
+    static void with_block(const ConvPlan &p, F &&f) {
+        if constexpr (kHasNB2) {
+            if (p.nb == 2) {
+                if (p.mt == 32) f(GeoTag<G32>{}, NBTag<2>{}); else f(GeoTag<G16>{}, NBTag<2>{});
+                return;
+            }
+        }
+        if (p.mt == 32) f(GeoTag<G32>{}, NBTag<1>{}); else f(GeoTag<G16>{}, NBTag<1>{});
     }
-    if (kPairSecond && g_pairing && !g_held.active && mode == MODE_RAW && !tuning(SIGE_HIP_TUNE_CONV_TILE_MT)) {
-        g_held.active = true; g_held.a = a; g_held.mode = mode; g_held.dst = DST; g_held.st = st; g_held.prec = PREC;
-        g_held.launch = &launch_kind<KH, STR, R, SRC, DST, LAY, PREC>;
-        note_launches(-1);  // (the caller counts one launch per call: this one happens later, or inside its partner's)
-        return SIGE_HIP_OK;
+
+    // 1. the shortcut: what is held and cannot ride along with this launch goes first; an eligible 1x1 is held back itself
+    static int hold_or_pair(const ConvArgs &a, int mode, hipStream_t st, bool *may_pair) {
+        *may_pair = kPairFirst && g_held.active && (mode == MODE_AFFINE_SWISH || mode == MODE_RAW) && g_held.st == st && g_held.dst == DST && g_held.prec == PREC;
+        if (g_held.active && !*may_pair) {
+            const int rc = flush_held();
+            if (rc != SIGE_HIP_OK) return rc;
+        }
+        if (kPairSecond && g_pairing && !g_held.active && mode == MODE_RAW && !tuning(SIGE_HIP_TUNE_CONV_TILE_MT)) {
+            g_held.active = true; g_held.a = a; g_held.mode = mode; g_held.dst = DST; g_held.st = st; g_held.prec = PREC;
+            g_held.launch = &launch;
+            note_launches(-1);  // (the caller counts one launch per call: this one happens later, or inside its partner's)
+            return SIGE_HIP_OK;
+        }
+        return STEP_GO;
     }
-    const int cap = (LAY == LAYOUT_NHWC && a.ws) ? a.ksplit_max : 1;
-    // side convs (above): what this launch must not overtake goes first; an armed sige_hip_conv_side_begin takes this call if eligible
-    constexpr bool kSideGeo = KH == 3 && STR == 1 && SRC == SRC_GATHER && DST == DST_NCHW && LAY == LAYOUT_NHWC && PREC == 0;
-    if (!g_side.empty() && (g_side.front().st != st || side_hazard(a))) {
-        const int rc = flush_side();
-        if (rc != SIGE_HIP_OK) return rc;
-    }
-    if constexpr (kSideGeo) {
-        if (g_side_armed > 0 && !g_held.active && mode == MODE_RAW && !a.twin0 && !a.twin1 && !a.up && !a.x1 && !a.hp_shift) {
-            ConvArgs q = a;
-            ConvPlan pq;
-            // (eligible only if a launch of its own would not split K: the sum order, hence the bits, stay what they were)
-            if (plan_conv<KH, STR, R, SRC, LAY, PREC>(q, cap, 0, false, pq) == SIGE_HIP_OK && q.ksplit == 1) {
-                q = a;
-                // block shape: a side workgroup should not outlast a host workgroup -- the hosts this library has are 16 x 16
-                // blocks over K = 4608 (the dense 8x8 level of the U-Net), which a 16 x 32 block matches at half that K
-                const int want_nb = 9 * a.Cin <= kSideNB2MaxK ? 2 : 1;
-                if (plan_conv<KH, STR, R, SRC, LAY, PREC>(q, 1, 0, false, pq, want_nb) == SIGE_HIP_OK && pq.mt == 16 && pq.waves == 4 && q.ksplit == 1) {
-                    q.ng_fast = 0;  // all tiles of an output-channel block are consecutive workgroups: a slice streams its weights once
-                    SideConv sc;
-                    sc.a = q; sc.nb = pq.nb; sc.total = q.mbk * q.ngk; sc.budget = g_side_armed; sc.st = st;
-                    g_side.push_back(sc);
-                    g_side_armed = 0;
-                    note_launches(-1);  // (as for a held shortcut: hosted blocks ride in other launches, a flushed rest counts there)
-                    return SIGE_HIP_OK;
+
+    // 2. side convs (above): what this launch must not overtake goes first; an armed sige_hip_conv_side_begin takes this call if eligible
+    static int queue_side(const ConvArgs &a, int mode, int cap, hipStream_t st) {
+        if (!g_side.empty() && (g_side.front().st != st || side_hazard(a))) {
+            const int rc = flush_side();
+            if (rc != SIGE_HIP_OK) return rc;
+        }
+        if constexpr (kSideGeo) {
+            if (g_side_armed > 0 && !g_held.active && mode == MODE_RAW && !a.twin0 && !a.twin1 && !a.up && !a.x1 && !a.hp_shift) {
+                ConvArgs q = a;
+                ConvPlan pq;
+                // (eligible only if a launch of its own would not split K: the sum order, hence the bits, stay what they were)
+                if (plan_conv<KH, STR, R, SRC, LAY, PREC>(q, cap, 0, false, pq) == SIGE_HIP_OK && q.ksplit == 1) {
+                    q = a;
+                    // block shape: a side workgroup should not outlast a host workgroup -- the hosts this library has are 16 x 16
+                    // blocks over K = 4608 (the dense 8x8 level of the U-Net), which a 16 x 32 block matches at half that K
+                    const int want_nb = 9 * a.Cin <= kSideNB2MaxK ? 2 : 1;
+                    if (plan_conv<KH, STR, R, SRC, LAY, PREC>(q, 1, 0, false, pq, want_nb) == SIGE_HIP_OK && pq.mt == 16 && pq.waves == 4 && q.ksplit == 1) {
+                        q.ng_fast = 0;  // all tiles of an output-channel block are consecutive workgroups: a slice streams its weights once
+                        SideConv sc;
+                        sc.a = q; sc.nb = pq.nb; sc.total = q.mbk * q.ngk; sc.budget = g_side_armed; sc.st = st;
+                        g_side.push_back(sc);
+                        g_side_armed = 0;
+                        note_launches(-1);  // (as for a held shortcut: hosted blocks ride in other launches, a flushed rest counts there)
+                        return SIGE_HIP_OK;
+                    }
                 }
             }
         }
+        return STEP_GO;
     }
-    ConvPlan p;
-    const ConvArgs a0 = a;  // (as handed in: plan_conv rewrites the packed-weight pointer and the grid fields)
-    const int prc = plan_conv<KH, STR, R, SRC, LAY, PREC>(a, cap, 0, false, p);
-    if (prc != SIGE_HIP_OK) {
-        const int rc = flush_held();
-        return rc != SIGE_HIP_OK ? rc : prc;
-    }
-    float *final_out = a.out;
-    if (a.ksplit > 1) {
-        a.counters = split_tickets(st, (long)a.mbk * a.ngk);
-        if (!a.counters && (a.twin0 || a.twin1)) {
-            // (the second-pass kernel does not write twins: without tickets such a launch runs unsplit)
-            a = a0;
-            const int rc1 = plan_conv<KH, STR, R, SRC, LAY, PREC>(a, 1, 0, false, p);
-            if (rc1 != SIGE_HIP_OK) {
-                // no unsplit plan either: a split launch finished by the second pass would leave the twins unwritten while the
-                // caller reports them as written -- refuse, the caller falls back and its consumers activate for themselves
-                const int rc = flush_held();
-                return rc != SIGE_HIP_OK ? rc : SIGE_HIP_EUNSUPPORTED;
+
+    // 3. the plan: output block, waves, K split.  A split needs tickets (its finish inside the launch) or, without twins, the
+    //    second-pass kernel; a split launch writes its partial sums to the workspace, *final_out is where the result goes
+    static int plan(ConvArgs &a, int cap, hipStream_t st, ConvPlan &p, float **final_out) {
+        const ConvArgs a0 = a;  // (as handed in: plan_conv rewrites the packed-weight pointer and the grid fields)
+        const int prc = plan_conv<KH, STR, R, SRC, LAY, PREC>(a, cap, 0, false, p);
+        if (prc != SIGE_HIP_OK) {
+            const int rc = flush_held();
+            return rc != SIGE_HIP_OK ? rc : prc;
+        }
+        *final_out = a.out;
+        if (a.ksplit > 1) {
+            a.counters = split_tickets(st, (long)a.mbk * a.ngk);
+            if (!a.counters && (a.twin0 || a.twin1)) {
+                // (the second-pass kernel does not write twins: without tickets such a launch runs unsplit)
+                a = a0;
+                const int rc1 = plan_conv<KH, STR, R, SRC, LAY, PREC>(a, 1, 0, false, p);
+                if (rc1 != SIGE_HIP_OK) {
+                    // no unsplit plan either: a split launch finished by the second pass would leave the twins unwritten while the
+                    // caller reports them as written -- refuse, the caller falls back and its consumers activate for themselves
+                    const int rc = flush_held();
+                    return rc != SIGE_HIP_OK ? rc : SIGE_HIP_EUNSUPPORTED;
+                }
             }
         }
+        if (a.ksplit > 1) {
+            a.out = a.ws;
+            a.fout = *final_out;
+        }
+        return STEP_GO;
     }
-    if (a.ksplit > 1) {
-        a.out = a.ws;
-        a.fout = final_out;
-    }
-    const int mt = p.mt, nb = p.nb, waves = p.waves;
-    bool done = false;
-    if constexpr (kPairFirst) {
-        if (may_pair) {
-            done = launch_pair<DST, PREC>(a, p, mode, g_held.a, st);
-            if (done) g_held.active = false;
-            else {
-                const int rc = flush_held();
-                if (rc != SIGE_HIP_OK) return rc;
+
+    // 4. the launch: with the held shortcut, as the host of queued side blocks, or alone in the form the plan and the cache dtype ask for
+    static int dispatch(const ConvArgs &a, const ConvPlan &p, int mode, bool may_pair, float *final_out, hipStream_t st) {
+        bool done = false;
+        if constexpr (kPairFirst) {
+            if (may_pair) {
+                done = launch_pair<DST, PREC>(a, p, mode, g_held.a, st);
+                if (done) g_held.active = false;
+                else {
+                    const int rc = flush_held();
+                    if (rc != SIGE_HIP_OK) return rc;
+                }
             }
         }
-    }
-    if constexpr (kSideGeo) {
-        // an eligible host: its idle CUs run the next blocks of the queue's head
-        if (!done && !g_side.empty() && mt == 16 && nb == 1 && waves == 4 && a.ksplit == 1 && (mode == MODE_RAW || mode == MODE_AFFINE_SWISH)) {
-            SideConv &sc = g_side.front();
-            const int na = conv_grid_x(a);
-            int take = sc.total - sc.next;
-            take = take < sc.budget ? take : sc.budget;
-            take = take < kSideChipWorkgroups - na ? take : kSideChipWorkgroups - na;
-            if (take > 0) {
-                if (sc.nb == 2) launch_conv_side<K31_16, 1, K31_16, 2, DST_NCHW, 4>(a, sc.a, mode, na, sc.next, take, st);
-                else launch_conv_side<K31_16, 1, K31_16, 1, DST_NCHW, 4>(a, sc.a, mode, na, sc.next, take, st);
-                sc.next += take;
-                g_side_hosted.fetch_add(take, std::memory_order_relaxed);
-                if (sc.next >= sc.total) g_side.pop_front();
+        if constexpr (kSideGeo) {
+            // an eligible host: its idle CUs run the next blocks of the queue's head
+            if (!done && !g_side.empty() && p.mt == 16 && p.nb == 1 && p.waves == 4 && a.ksplit == 1 && (mode == MODE_RAW || mode == MODE_AFFINE_SWISH)) {
+                SideConv &sc = g_side.front();
+                const int na = conv_grid_x(a);
+                int take = sc.total - sc.next;
+                take = take < sc.budget ? take : sc.budget;
+                take = take < kSideChipWorkgroups - na ? take : kSideChipWorkgroups - na;
+                if (take > 0) {
+                    if (sc.nb == 2) launch_conv_side<K31_16, 1, K31_16, 2, DST_NCHW, 4>(a, sc.a, mode, na, sc.next, take, st);
+                    else launch_conv_side<K31_16, 1, K31_16, 1, DST_NCHW, 4>(a, sc.a, mode, na, sc.next, take, st);
+                    sc.next += take;
+                    g_side_hosted.fetch_add(take, std::memory_order_relaxed);
+                    if (sc.next >= sc.total) g_side.pop_front();
+                    done = true;
+                }
+            }
+        }
+        if constexpr (kHasC16) {
+            if (!done && a.y_f16) {  // the cached tensor is stored as fp16: the Y16 form of the kernel (4 waves)
+                if (p.waves != 4) return SIGE_HIP_EUNSUPPORTED;
+                with_block(p, [&](auto g, auto nb) { launch_conv_c16<typename decltype(g)::type, decltype(nb)::value, DST>(a, mode, st); });
+                done = true;
+            }
+        } else {
+            if (a.y_f16) return SIGE_HIP_EUNSUPPORTED;
+        }
+        if constexpr (kHasW8) {
+            if (!done && p.waves == 8) {
+                with_block(p, [&](auto g, auto nb) { launch_conv_geo<typename decltype(g)::type, decltype(nb)::value, SRC, DST, LAY, 8>(a, mode, st); });
                 done = true;
             }
         }
-    }
-    if constexpr (SRC == SRC_SCATTER_GATHER && LAY == LAYOUT_NHWC && KH == 3 && STR == 1) {
-        if (!done && a.y_f16) {  // the cached tensor is stored as fp16: the Y16 form of the kernel (4 waves)
-            if (waves != 4) return SIGE_HIP_EUNSUPPORTED;
-            if constexpr (kHasNB2) {
-                if (mt == 32 && nb == 2) { launch_conv_c16<G32, 2, DST>(a, mode, st); done = true; }
-                else if (nb == 2) { launch_conv_c16<G16, 2, DST>(a, mode, st); done = true; }
-            }
-            if (!done) {
-                if (mt == 32) launch_conv_c16<G32, 1, DST>(a, mode, st);
-                else launch_conv_c16<G16, 1, DST>(a, mode, st);
-                done = true;
-            }
+        if (!done) with_block(p, [&](auto g, auto nb) { launch_conv_geo<typename decltype(g)::type, decltype(nb)::value, SRC, DST, LAY, 4>(a, mode, st); });
+        if (a.ksplit > 1 && !a.counters) {
+            const size_t n4 = a.split_stride / 4;
+            const int grid = (int)((n4 + 255) / 256 < 2048 ? (n4 + 255) / 256 : 2048);
+            splitk_reduce_nhwc_kernel<<<grid, 256, 0, st>>>(a.ws, a.ksplit, a.split_stride, n4, a.Cout, a.bias, a.residual,
+                                                           a.oscale, a.oshift, a.oact, final_out);
+            note_launches(1);
         }
-    } else {
-        if (a.y_f16) return SIGE_HIP_EUNSUPPORTED;
+        return SIGE_HIP_OK;
     }
-    constexpr bool kHasW8 = LAY == LAYOUT_NHWC && STR == 1 && PREC == 0;
-    if constexpr (kHasW8) {
-        if (!done && waves == 8) {
-            if (mt == 32 && nb == 2) launch_conv_geo<G32, 2, SRC, DST, LAY, 8>(a, mode, st);
-            else if (mt == 32) launch_conv_geo<G32, 1, SRC, DST, LAY, 8>(a, mode, st);
-            else if (nb == 2) launch_conv_geo<G16, 2, SRC, DST, LAY, 8>(a, mode, st);
-            else launch_conv_geo<G16, 1, SRC, DST, LAY, 8>(a, mode, st);
-            done = true;
-        }
+
+    static int launch(ConvArgs a, int mode, hipStream_t st) {
+        if constexpr (PREC == 2)  // 2^-S sits in the header behind the two packed tile shapes (pack_weights_x_kernel)
+            a.wscale_ptr = a.packed + packed_units_x(a.Cout, a.Cin, KH * KH, 32) + packed_units_x(a.Cout, a.Cin, KH * KH, 16) + 1;
+        bool may_pair;
+        ConvPlan p;
+        float *final_out;
+        const int cap = (LAY == LAYOUT_NHWC && a.ws) ? a.ksplit_max : 1;
+        int rc = hold_or_pair(a, mode, st, &may_pair);
+        if (rc == STEP_GO) rc = queue_side(a, mode, cap, st);
+        if (rc == STEP_GO) rc = plan(a, cap, st, p, &final_out);
+        return rc == STEP_GO ? dispatch(a, p, mode, may_pair, final_out, st) : rc;
     }
-    if constexpr (kHasNB2) {
-        if (!done && mt == 32 && nb == 2) { launch_conv_geo<G32, 2, SRC, DST, LAY, 4>(a, mode, st); done = true; }
-        else if (!done && nb == 2) { launch_conv_geo<G16, 2, SRC, DST, LAY, 4>(a, mode, st); done = true; }
-    }
-    if (!done) {
-        if (mt == 32) launch_conv_geo<G32, 1, SRC, DST, LAY, 4>(a, mode, st);
-        else launch_conv_geo<G16, 1, SRC, DST, LAY, 4>(a, mode, st);
-    }
-    if (a.ksplit > 1 && !a.counters) {
-        const size_t n4 = a.split_stride / 4;
-        const int grid = (int)((n4 + 255) / 256 < 2048 ? (n4 + 255) / 256 : 2048);
-        splitk_reduce_nhwc_kernel<<<grid, 256, 0, st>>>(a.ws, a.ksplit, a.split_stride, n4, a.Cout, a.bias, a.residual,
-                                                       a.oscale, a.oshift, a.oact, final_out);
-        note_launches(1);
-    }
-    return SIGE_HIP_OK;
-}
+};
 
 // ---- nearest-x2 Upsample conv in the phase form (upsample2x = 2 of sige_hip_gather_conv_nhwc) ----
 // `a` as for the 9-tap launch of the same call (up = 1, full-tensor destination), a.packed = the phase pack
@@ -772,37 +802,31 @@ static int launch_phase_up(ConvArgs a, hipStream_t st) {
 }
 
 template <int SRC, int DST = DST_TILES, int LAY = LAYOUT_NCHW, int PREC = 0>
-static int launch_conv(const ConvArgs &a, int mode, int kH, int kW, int R, int S, int strH, int strW, hipStream_t st) {
+static int launch_conv(const ConvArgs &a, int mode, int kind, hipStream_t st) {  // kind: mfma_kind of the call
     int rc;
-    switch (mfma_kind(kH, kW, R, S, strH, strW, 1)) {
-        case 1: rc = launch_kind<3, 1, 6, SRC, DST, LAY, PREC>(a, mode, st); break;
-        case 2: rc = launch_kind<1, 1, 4, SRC, DST, LAY, PREC>(a, mode, st); break;
+    switch (kind) {
+        case 1: rc = KindSteps<3, 1, 6, SRC, DST, LAY, PREC>::launch(a, mode, st); break;
+        case 2: rc = KindSteps<1, 1, 4, SRC, DST, LAY, PREC>::launch(a, mode, st); break;
         case 3:
             if constexpr (PREC != 0) return SIGE_HIP_EUNSUPPORTED;  // (see the f16-compute declarations above)
-            else rc = launch_kind<3, 2, 5, SRC, DST, LAY, PREC>(a, mode, st);
+            else rc = KindSteps<3, 2, 5, SRC, DST, LAY, PREC>::launch(a, mode, st);
             break;
         default: return SIGE_HIP_EUNSUPPORTED;
     }
     return rc != SIGE_HIP_OK ? rc : launch_status();
 }
 
-// (scale, shift, activation) -> staging mode of the fused kernels; -1: not expressible
-// (the caller then uses gather / scatter_gather + block_conv).  scale and shift must be
-// both present with one broadcast shape [1|B, 1|C, 1, 1], or both absent.
-static int staging_mode(const float *scale, int sB, int sC, const float *shift, int tB, int tC, int activation,
-                        int B, int C, int *aff_sb, int *aff_sc) {
+// staging affine -> staging mode of the fused kernels; -1: not expressible (the caller then uses gather / scatter_gather +
+// block_conv).  The rules are conv_call.hpp's: scale and shift both present with one broadcast shape [1|B, 1|C, 1, 1], or both absent.
+static int staging_mode(const StagingAffine &f, int B, int C, int *aff_sb, int *aff_sc) {
     *aff_sb = *aff_sc = 0;
-    if (!scale && !shift) return activation == SIGE_HIP_ACT_IDENTITY ? MODE_RAW : -1;
-    if (!scale || !shift || sB != tB || sC != tC) return -1;
-    if (!((sB == 1 || sB == B) && (sC == 1 || sC == C))) return -1;
-    *aff_sb = sB > 1 ? sC : 0;
-    *aff_sc = sC > 1 ? 1 : 0;
-    return activation == SIGE_HIP_ACT_SWISH ? MODE_AFFINE_SWISH : MODE_AFFINE;
+    if (staging_affine_status(f, B, C, SIGE_HIP_EUNSUPPORTED, SIGE_HIP_EUNSUPPORTED) != SIGE_HIP_OK) return -1;
+    if (!f.scale) return MODE_RAW;
+    *aff_sb = f.scaleB > 1 ? f.scaleC : 0;
+    *aff_sc = f.scaleC > 1 ? 1 : 0;
+    return f.act == SIGE_HIP_ACT_SWISH ? MODE_AFFINE_SWISH : MODE_AFFINE;
 }
 
-}  // namespace sige
-
-namespace sige {
 // (conv_tile3.hip: the 10x10-window form neither joins nor overtakes work held or queued on the stacked-block kernels)
 bool conv_hold_pending() { return g_held.active || g_side_armed > 0 || !g_side.empty(); }
 }  // namespace sige
@@ -953,25 +977,25 @@ extern "C" int sige_hip_block_conv_f32(const float *x, int T, int Cin, int R, in
     if (T < 0 || Cin <= 0 || Cout <= 0) return SIGE_HIP_EINVAL;
     if (T == 0) return SIGE_HIP_OK;
     if (!x || !packed || !out) return SIGE_HIP_EINVAL;
-    if (reinterpret_cast<uintptr_t>(out) & 15 || reinterpret_cast<uintptr_t>(packed) & 15) return SIGE_HIP_EINVAL;
-    if ((long)T * Cin * R * S >= (1L << 29)) return SIGE_HIP_EUNSUPPORTED;  // 32-bit byte offsets in the kernel
+    if (!aligned16({out, packed})) return SIGE_HIP_EINVAL;
+    if (!offsets_fit((long)T * Cin * R * S)) return SIGE_HIP_EUNSUPPORTED;
     ConvArgs a{};
     a.x = x; a.packed = packed; a.bias = bias; a.out = out;
     a.T = T; a.Cin = Cin; a.Cout = Cout;
-    if (reinterpret_cast<uintptr_t>(x) & 15 || ((long)Cin * R * S) % 4) {
+    if (!aligned16({x}) || ((long)Cin * R * S) % 4) {
         // The tile slab cannot be staged with 16-byte loads: run it as a gather of ONE tile at
         // (0, 0) from each of T "images" [Cin, R, S] (element-wise staging, same MFMA order).
         void *zero_idx = nullptr;
         if (hipGetSymbolAddress(&zero_idx, HIP_SYMBOL(g_zero_idx)) != hipSuccess) return SIGE_HIP_ELAUNCH;
         a.x2 = x; a.Csplit = Cin; a.idx = static_cast<const int32_t *>(zero_idx);
         a.B = T; a.N = 1; a.H = R; a.W = S;
-        return launch_conv<SRC_GATHER>(a, MODE_RAW, kH, kW, R, S, strideH, strideW, as_stream(stream));
+        return launch_conv<SRC_GATHER>(a, MODE_RAW, mfma_kind(kH, kW, R, S, strideH, strideW, 1), as_stream(stream));
     }
-    return launch_conv<SRC_TILES>(a, 0, kH, kW, R, S, strideH, strideW, as_stream(stream));
+    return launch_conv<SRC_TILES>(a, 0, mfma_kind(kH, kW, R, S, strideH, strideW, 1), as_stream(stream));
 }
 
 static bool channel_affine(const float *p, int b, int c, int h, int w, int B, int C) {
-    return !p || ((b == 1 || b == B) && (c == 1 || c == C) && h == 1 && w == 1);
+    return !p || (affine_extent_ok(p, b, c, B, C) && h == 1 && w == 1);
 }
 
 extern "C" int sige_hip_gather_conv_f32(const float *x, int B, int Cin, int H, int W, int bH, int bW,
@@ -983,14 +1007,14 @@ extern "C" int sige_hip_gather_conv_f32(const float *x, int B, int Cin, int H, i
                                         int strideH, int strideW, float *out, void *stream) {
     SIGE_PLAN_HOOK_FIXED(sige_hip_gather_conv_f32, x, B, Cin, H, W, bH, bW, active_indices, N, scale, scaleB, scaleC, scaleH, scaleW, shift, shiftB, shiftC, shiftH, shiftW, activation, packed, bias, Cout, kH, kW, strideH, strideW, out, stream);
     if (B < 0 || Cin <= 0 || Cout <= 0 || H <= 0 || W <= 0 || N < 0) return SIGE_HIP_EINVAL;
-    if (activation != SIGE_HIP_ACT_IDENTITY && activation != SIGE_HIP_ACT_SWISH) return SIGE_HIP_EUNSUPPORTED;
+    if (!act_known(activation)) return SIGE_HIP_EUNSUPPORTED;
     if (!channel_affine(scale, scaleB, scaleC, scaleH, scaleW, B, Cin) ||
         !channel_affine(shift, shiftB, shiftC, shiftH, shiftW, B, Cin))
         return SIGE_HIP_EUNSUPPORTED;  // spatially varying affine: use gather + block_conv
-    if ((long)B * Cin * H * W >= (1L << 29)) return SIGE_HIP_EUNSUPPORTED;  // 32-bit element offsets in the kernel
+    if (!offsets_fit((long)B * Cin * H * W)) return SIGE_HIP_EUNSUPPORTED;
     if ((long)B * N == 0) return SIGE_HIP_OK;
     if (!x || !packed || !out || !active_indices) return SIGE_HIP_EINVAL;
-    if (reinterpret_cast<uintptr_t>(out) & 15 || reinterpret_cast<uintptr_t>(packed) & 15) return SIGE_HIP_EINVAL;
+    if (!aligned16({out, packed})) return SIGE_HIP_EINVAL;
     ConvArgs a{};
     a.x = x; a.idx = active_indices; a.packed = packed; a.bias = bias; a.out = out;
     a.T = B * N; a.Cin = Cin; a.Cout = Cout; a.B = B; a.N = N; a.H = H; a.W = W;
@@ -998,9 +1022,9 @@ extern "C" int sige_hip_gather_conv_f32(const float *x, int B, int Cin, int H, i
     a.Csplit = Cin;
     a.x2 = x;
     a.scale = scale; a.shift = shift;
-    const int mode = staging_mode(scale, scaleB, scaleC, shift, shiftB, shiftC, activation, B, Cin, &a.aff_sb, &a.aff_sc);
+    const int mode = staging_mode({scale, shift, scaleB, scaleC, shiftB, shiftC, activation}, B, Cin, &a.aff_sb, &a.aff_sc);
     if (mode < 0) return SIGE_HIP_EUNSUPPORTED;
-    return launch_conv<SRC_GATHER>(a, mode, kH, kW, bH, bW, strideH, strideW, as_stream(stream));
+    return launch_conv<SRC_GATHER>(a, mode, mfma_kind(kH, kW, bH, bW, strideH, strideW, 1), as_stream(stream));
 }
 
 extern "C" int sige_hip_gather_conv_nchw_f32(const float *x, const float *x2, int B, int C1, int C2, int H, int W,
@@ -1014,14 +1038,12 @@ extern "C" int sige_hip_gather_conv_nchw_f32(const float *x, const float *x2, in
     SIGE_PLAN_HOOK_FIXED(sige_hip_gather_conv_nchw_f32, x, x2, B, C1, C2, H, W, bH, bW, active_indices, N, scale, scaleB, scaleC, shift, shiftB, shiftC, activation, packed, bias, Cout, kH, kW, strideH, strideW, offsetH, offsetW, residual, Ho, Wo, out, stream);
     const int Cin = C1 + C2;
     if (B < 0 || C1 <= 0 || C2 < 0 || Cout <= 0 || H <= 0 || W <= 0 || N < 0 || Ho <= 0 || Wo <= 0) return SIGE_HIP_EINVAL;
-    if (activation != SIGE_HIP_ACT_IDENTITY && activation != SIGE_HIP_ACT_SWISH) return SIGE_HIP_EUNSUPPORTED;
-    if ((scale && !((scaleB == 1 || scaleB == B) && (scaleC == 1 || scaleC == Cin))) ||
-        (shift && !((shiftB == 1 || shiftB == B) && (shiftC == 1 || shiftC == Cin))))
-        return SIGE_HIP_EINVAL;
-    if ((long)B * Cin * H * W >= (1L << 29)) return SIGE_HIP_EUNSUPPORTED;  // 32-bit element offsets in the kernel
+    if (!act_known(activation)) return SIGE_HIP_EUNSUPPORTED;
+    if (!affine_extent_ok(scale, scaleB, scaleC, B, Cin) || !affine_extent_ok(shift, shiftB, shiftC, B, Cin)) return SIGE_HIP_EINVAL;
+    if (!offsets_fit((long)B * Cin * H * W)) return SIGE_HIP_EUNSUPPORTED;
     if ((long)B * N == 0) return SIGE_HIP_OK;
     if (!x || (C2 && !x2) || !packed || !out || !active_indices) return SIGE_HIP_EINVAL;
-    if (reinterpret_cast<uintptr_t>(packed) & 15) return SIGE_HIP_EINVAL;
+    if (!aligned16({packed})) return SIGE_HIP_EINVAL;
     ConvArgs a{};
     a.x = x; a.x2 = x2; a.Csplit = C1; a.idx = active_indices; a.packed = packed; a.bias = bias; a.out = out;
     a.T = B * N; a.Cin = Cin; a.Cout = Cout; a.B = B; a.N = N; a.H = H; a.W = W;
@@ -1029,10 +1051,10 @@ extern "C" int sige_hip_gather_conv_nchw_f32(const float *x, const float *x2, in
     if (C2 && B != 1) return SIGE_HIP_EUNSUPPORTED;  // the two-tensor input is per image (conv_mfma.hpp)
     if (!x2) a.x2 = x;
     a.scale = scale; a.shift = shift;
-    const int mode = staging_mode(scale, scaleB, scaleC, shift, shiftB, shiftC, activation, B, Cin, &a.aff_sb, &a.aff_sc);
+    const int mode = staging_mode({scale, shift, scaleB, scaleC, shiftB, shiftC, activation}, B, Cin, &a.aff_sb, &a.aff_sc);
     if (mode < 0) return SIGE_HIP_EUNSUPPORTED;
     a.residual = residual; a.Ho = Ho; a.Wo = Wo; a.offH = offsetH; a.offW = offsetW; a.strH = strideH; a.strW = strideW;
-    return launch_conv<SRC_GATHER, DST_NCHW>(a, mode, kH, kW, bH, bW, strideH, strideW, as_stream(stream));
+    return launch_conv<SRC_GATHER, DST_NCHW>(a, mode, mfma_kind(kH, kW, bH, bW, strideH, strideW, 1), as_stream(stream));
 }
 
 extern "C" int sige_hip_scatter_gather_conv_f32(const float *x, const float *y, int B, int Cin, int H, int W,
@@ -1045,29 +1067,31 @@ extern "C" int sige_hip_scatter_gather_conv_f32(const float *x, const float *y, 
                                                 int strideH, int strideW, float *out, void *stream) {
     SIGE_PLAN_HOOK_FIXED(sige_hip_scatter_gather_conv_f32, x, y, B, Cin, H, W, Rx, Sx, bH, bW, active_indices, N, scatter_map, scale, scaleB, scaleC, scaleH, scaleW, shift, shiftB, shiftC, shiftH, shiftW, activation, packed, bias, Cout, kH, kW, strideH, strideW, out, stream);
     if (B < 0 || Cin <= 0 || Cout <= 0 || H <= 0 || W <= 0 || N < 0 || Rx <= 0 || Sx <= 0) return SIGE_HIP_EINVAL;
-    if (activation != SIGE_HIP_ACT_IDENTITY && activation != SIGE_HIP_ACT_SWISH) return SIGE_HIP_EUNSUPPORTED;
+    if (!act_known(activation)) return SIGE_HIP_EUNSUPPORTED;
     if (!channel_affine(scale, scaleB, scaleC, scaleH, scaleW, B, Cin) ||
         !channel_affine(shift, shiftB, shiftC, shiftH, shiftW, B, Cin))
         return SIGE_HIP_EUNSUPPORTED;
-    if ((long)B * Cin * H * W >= (1L << 29) || (long)B * N * Cin * Rx * Sx >= (1L << 29)) return SIGE_HIP_EUNSUPPORTED;
+    if (!offsets_fit((long)B * Cin * H * W) || !offsets_fit((long)B * N * Cin * Rx * Sx)) return SIGE_HIP_EUNSUPPORTED;
     if ((long)B * N == 0) return SIGE_HIP_OK;
     if (!x || !y || !packed || !out || !active_indices || !scatter_map) return SIGE_HIP_EINVAL;
-    if (reinterpret_cast<uintptr_t>(out) & 15 || reinterpret_cast<uintptr_t>(packed) & 15) return SIGE_HIP_EINVAL;
+    if (!aligned16({out, packed})) return SIGE_HIP_EINVAL;
     ConvArgs a{};
     a.x = x; a.y = y; a.idx = active_indices; a.map = scatter_map; a.packed = packed; a.bias = bias; a.out = out;
     a.T = B * N; a.Cin = Cin; a.Cout = Cout; a.B = B; a.N = N; a.H = H; a.W = W;
     if (stacked_shift(H) != 0) return SIGE_HIP_EUNSUPPORTED;  // (stacked edits: channels-last fused kernels only)
     a.RxSx = Rx * Sx; a.Sx = Sx;
     a.scale = scale; a.shift = shift;
-    const int mode = staging_mode(scale, scaleB, scaleC, shift, shiftB, shiftC, activation, B, Cin, &a.aff_sb, &a.aff_sc);
+    const int mode = staging_mode({scale, shift, scaleB, scaleC, shiftB, shiftC, activation}, B, Cin, &a.aff_sb, &a.aff_sc);
     if (mode < 0) return SIGE_HIP_EUNSUPPORTED;
-    return launch_conv<SRC_SCATTER_GATHER>(a, mode, kH, kW, bH, bW, strideH, strideW, as_stream(stream));
+    return launch_conv<SRC_SCATTER_GATHER>(a, mode, mfma_kind(kH, kW, bH, bW, strideH, strideW, 1), as_stream(stream));
 }
 
 // ---- channels-last (NHWC) forms: the same kernels, tensors laid out [B,H,W,C] / [T,R,S,C] ----
-static bool nhwc_ok(int Cin, int C1, int Cout, const void *p0, const void *p1, const void *p2, const void *p3) {
-    auto al = [](const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; };
-    return Cin % 4 == 0 && C1 % 4 == 0 && Cout % 4 == 0 && al(p0) && al(p1) && al(p2) && al(p3);
+// Every entry point fills one TileConvCall (conv_call.hpp) behind its plan hook; the checks and everything below take the record.
+static bool channels_x4(const TileConvCall &c) { return c.Cin() % 4 == 0 && c.C1 % 4 == 0 && c.Cout % 4 == 0; }
+static int conv_kind(const TileConvCall &c) { return mfma_kind(c.kH, c.kW, c.bH, c.bW, c.strH, c.strW, 1); }
+static bool source_offsets_fit(const TileConvCall &c) {  // the full tensor and, under a scatter map, the tile slab scattered over it
+    return offsets_fit((long)c.B * c.Cin() * c.H * c.W) && (c.source != CALL_SCATTER_GATHER || offsets_fit(c.tiles() * c.Cin() * c.Rx * c.Sx));
 }
 
 extern "C" int sige_hip_conv_ksplit_hint(int T, int Cin, int Cout, int kH, int kW, int strideH, int strideW) {
@@ -1080,32 +1104,65 @@ extern "C" int sige_hip_conv_ksplit_hint(int T, int Cin, int Cout, int kH, int k
 
 // `compute` selects the arithmetic of a channels-last tile conv, i.e. which packing `packed` has: 0 exact fp32 | 1 fp16 operands |
 // 2 split fp16 operands; anything else is SIGE_HIP_EINVAL.  The one place where it becomes the implementations' PREC.
-#define SIGE_BY_COMPUTE(compute, impl, ...)         \
-    ((compute) == 0   ? impl<0>(__VA_ARGS__)        \
-     : (compute) == 1 ? impl<1>(__VA_ARGS__)        \
-     : (compute) == 2 ? impl<2>(__VA_ARGS__)        \
+#define SIGE_BY_COMPUTE(compute, impl, call)  \
+    ((compute) == 0   ? impl<0>(call)         \
+     : (compute) == 1 ? impl<1>(call)         \
+     : (compute) == 2 ? impl<2>(call)         \
                       : SIGE_HIP_EINVAL)
 
+// source, staging affine (*mode: its staging mode), weights and `out` of a gather-type call, as the kernels read them
+static int source_args(const TileConvCall &c, ConvArgs &a, int *mode) {
+    a.x = c.x; a.idx = c.idx; a.map = c.map; a.packed = c.packed; a.bias = c.bias; a.out = c.out;
+    if (c.source == CALL_GATHER) {
+        a.x2 = c.C2 ? static_cast<const float *>(c.x2) : c.x; a.Csplit = c.C1;
+    } else {
+        a.y = static_cast<const float *>(c.x2); a.y_f16 = c.x2_f16 ? 1 : 0; a.RxSx = c.Rx * c.Sx; a.Sx = c.Sx;
+    }
+    a.T = c.B * c.N; a.Cin = c.Cin(); a.Cout = c.Cout; a.B = c.B; a.N = c.N; a.H = c.H; a.W = c.W;
+    if (edit_shift_status(c.H, c.B, &a.hp_shift) != SIGE_HIP_OK) return SIGE_HIP_EUNSUPPORTED;  // (stacked edits: sige_hip_set_edit_batch)
+    a.scale = c.aff.scale; a.shift = c.aff.shift;
+    *mode = staging_mode(c.aff, c.B, a.Cin, &a.aff_sb, &a.aff_sc);
+    return *mode < 0 ? SIGE_HIP_EUNSUPPORTED : SIGE_HIP_OK;
+}
+
+// full-tensor destination (+ block residual) and twins
+static int full_args(const TileConvCall &c, ConvArgs &a) {
+    if (int rc = twins_status(c.twin)) return rc;
+    if (!twins_aligned(c.twin)) return SIGE_HIP_EUNSUPPORTED;
+    a.twin0 = c.twin[0].out; a.tscale0 = c.twin[0].scale; a.tshift0 = c.twin[0].shift;
+    a.twin1 = c.twin[1].out; a.tscale1 = c.twin[1].scale; a.tshift1 = c.twin[1].shift;
+    if (!c.to_full) return SIGE_HIP_OK;
+    a.residual = static_cast<const float *>(c.residual); a.res_f16 = c.res_f16 ? 1 : 0;
+    a.Ho = c.Ho; a.Wo = c.Wo; a.offH = c.offH; a.offW = c.offW; a.strH = c.strH; a.strW = c.strW;
+    if (c.source == CALL_SCATTER_GATHER) {
+        a.x1 = c.x1; a.table1 = c.table1; a.gW1 = c.gW1; a.N1 = c.N1; a.R1 = c.R1 > 0 ? c.R1 : 1; a.S1 = c.S1 > 0 ? c.S1 : 1;
+    }
+    return SIGE_HIP_OK;
+}
+
+// a conv over a tile slab: T = B * N tiles [R = bH, S = bW, Cin]
 template <int PREC>
-static int block_conv_nhwc_impl(const float *x, int T, int Cin, int R, int S,
-                                const float *packed, const float *bias, int Cout, int kH, int kW,
-                                int strideH, int strideW, float *out, void *stream) {
-    if (T < 0 || Cin <= 0 || Cout <= 0) return SIGE_HIP_EINVAL;
+static int block_conv_nhwc_impl(const TileConvCall &c) {
+    const long T = c.tiles();
+    if (T < 0 || c.C1 <= 0 || c.Cout <= 0) return SIGE_HIP_EINVAL;
     if (T == 0) return SIGE_HIP_OK;
-    if (!x || !packed || !out) return SIGE_HIP_EINVAL;
-    if (!nhwc_ok(Cin, Cin, Cout, x, packed, out, bias)) return SIGE_HIP_EUNSUPPORTED;
-    if ((long)T * Cin * R * S >= (1L << 29)) return SIGE_HIP_EUNSUPPORTED;
+    if (!c.x || !c.packed || !c.out) return SIGE_HIP_EINVAL;
+    if (!channels_x4(c) || !aligned16({c.x, c.packed, c.out, c.bias})) return SIGE_HIP_EUNSUPPORTED;
+    if (!offsets_fit(T * c.C1 * c.bH * c.bW)) return SIGE_HIP_EUNSUPPORTED;
     ConvArgs a{};
-    a.x = x; a.packed = packed; a.bias = bias; a.out = out;
-    a.T = T; a.Cin = Cin; a.Cout = Cout;
-    return launch_conv<SRC_TILES, DST_TILES, LAYOUT_NHWC, PREC>(a, 0, kH, kW, R, S, strideH, strideW, as_stream(stream));
+    a.x = c.x; a.packed = c.packed; a.bias = c.bias; a.out = c.out;
+    a.T = (int)T; a.Cin = c.C1; a.Cout = c.Cout;
+    return launch_conv<SRC_TILES, DST_TILES, LAYOUT_NHWC, PREC>(a, 0, conv_kind(c), as_stream(c.stream));
 }
 
 extern "C" int sige_hip_block_conv_nhwc(int compute, const float *x, int T, int Cin, int R, int S,
                                         const float *packed, const float *bias, int Cout, int kH, int kW,
                                         int strideH, int strideW, float *out, void *stream) {
     SIGE_PLAN_HOOK_FIXED(sige_hip_block_conv_nhwc, compute, x, T, Cin, R, S, packed, bias, Cout, kH, kW, strideH, strideW, out, stream);
-    return SIGE_BY_COMPUTE(compute, block_conv_nhwc_impl, x, T, Cin, R, S, packed, bias, Cout, kH, kW, strideH, strideW, out, stream);
+    TileConvCall c{};
+    c.source = CALL_TILES; c.x = x; c.B = 1; c.N = T; c.C1 = Cin; c.bH = R; c.bW = S; c.packed = packed; c.bias = bias; c.Cout = Cout;
+    c.kH = kH; c.kW = kW; c.strH = strideH; c.strW = strideW; c.out = out; c.stream = stream;
+    return SIGE_BY_COMPUTE(compute, block_conv_nhwc_impl, c);
 }
 
 // ... over the tiles of an index list: T = B * N.  `count_key` is the index list the N tiles belong to; it is not read -- a launch
@@ -1116,79 +1173,48 @@ extern "C" int sige_hip_block_conv_nhwc_keyed(int compute, const float *x, const
                                               int strideH, int strideW, float *out, void *stream) {
     SIGE_PLAN_HOOK_N(sige_hip_block_conv_nhwc_keyed, (sige::CountOf<2, 4>), compute, x, count_key, B, N, Cin, R, S, packed, bias, Cout, kH, kW, strideH, strideW, out, stream);
     if (B < 0 || N < 0 || !count_key || (long)B * N > 0x7fffffffL) return SIGE_HIP_EINVAL;
-    const int T = B * N;
-    return SIGE_BY_COMPUTE(compute, block_conv_nhwc_impl, x, T, Cin, R, S, packed, bias, Cout, kH, kW, strideH, strideW, out, stream);
+    TileConvCall c{};
+    c.source = CALL_TILES; c.x = x; c.B = B; c.N = N; c.C1 = Cin; c.bH = R; c.bW = S; c.packed = packed; c.bias = bias; c.Cout = Cout;
+    c.kH = kH; c.kW = kW; c.strH = strideH; c.strW = strideW; c.out = out; c.stream = stream;
+    return SIGE_BY_COMPUTE(compute, block_conv_nhwc_impl, c);
 }
 
 template <int PREC>
-static int gather_conv_nhwc_impl(const float *x, const float *x2, int B, int C1, int C2, int H, int W,
-                                             int bH, int bW, const int32_t *active_indices, int N,
-                                             const float *scale, int scaleB, int scaleC,
-                                             const float *shift, int shiftB, int shiftC,
-                                             int activation,
-                                             const float *packed, const float *bias, int Cout, int kH, int kW,
-                                             int strideH, int strideW,
-                                             int to_full, int offsetH, int offsetW, const float *residual, int Ho, int Wo,
-                                             float *workspace, size_t workspace_floats,
-                                             const float *out_scale, const float *out_shift, int out_activation,
-                                             int upsample2x,
-                                             float *twin0, const float *twin0_scale, const float *twin0_shift,
-                                             float *twin1, const float *twin1_scale, const float *twin1_shift,
-                                             float *out, void *stream) {
-    const int Cin = C1 + C2;
-    if (upsample2x < 0 || upsample2x > 2) return SIGE_HIP_EINVAL;
-    if (upsample2x && ((H | W) & 1)) return SIGE_HIP_EINVAL;  // (H, W) = the upsampled size
-    if (upsample2x == 2 && PREC != 0) return SIGE_HIP_EUNSUPPORTED;  // (the entry point has checked what else the phase form needs)
-    if (B < 0 || C1 <= 0 || C2 < 0 || Cout <= 0 || H <= 0 || W <= 0 || N < 0) return SIGE_HIP_EINVAL;
-    if (to_full && (Ho <= 0 || Wo <= 0)) return SIGE_HIP_EINVAL;
-    if (activation != SIGE_HIP_ACT_IDENTITY && activation != SIGE_HIP_ACT_SWISH) return SIGE_HIP_EUNSUPPORTED;
-    if ((long)B * Cin * H * W >= (1L << 29)) return SIGE_HIP_EUNSUPPORTED;
-    if ((long)B * N == 0) return SIGE_HIP_OK;
-    if (!x || (C2 && !x2) || !packed || !out || !active_indices) return SIGE_HIP_EINVAL;
-    if (C2 && B != 1) return SIGE_HIP_EUNSUPPORTED;
-    if (!nhwc_ok(Cin, C1, Cout, x, C2 ? x2 : x, out, bias) || (reinterpret_cast<uintptr_t>(packed) & 15) ||
-        (reinterpret_cast<uintptr_t>(residual) & 15))
-        return SIGE_HIP_EUNSUPPORTED;
+static int gather_conv_nhwc_impl(const TileConvCall &c) {
+    if (c.up < 0 || c.up > 2) return SIGE_HIP_EINVAL;
+    if (c.up && ((c.H | c.W) & 1)) return SIGE_HIP_EINVAL;  // (H, W) = the upsampled size
+    if (c.up == 2 && PREC != 0) return SIGE_HIP_EUNSUPPORTED;  // (the entry point has checked what else the phase form needs)
+    if (c.B < 0 || c.C1 <= 0 || c.C2 < 0 || c.Cout <= 0 || c.H <= 0 || c.W <= 0 || c.N < 0) return SIGE_HIP_EINVAL;
+    if (c.to_full && (c.Ho <= 0 || c.Wo <= 0)) return SIGE_HIP_EINVAL;
+    if (!act_known(c.aff.act)) return SIGE_HIP_EUNSUPPORTED;
+    if (!source_offsets_fit(c)) return SIGE_HIP_EUNSUPPORTED;
+    if (c.tiles() == 0) return SIGE_HIP_OK;
+    if (!c.x || (c.C2 && !c.x2) || !c.packed || !c.out || !c.idx) return SIGE_HIP_EINVAL;
+    if (c.C2 && c.B != 1) return SIGE_HIP_EUNSUPPORTED;
+    if (!channels_x4(c) || !aligned16({c.x, c.C2 ? c.x2 : c.x, c.out, c.bias, c.packed, c.residual})) return SIGE_HIP_EUNSUPPORTED;
     ConvArgs a{};
-    a.x = x; a.x2 = C2 ? x2 : x; a.Csplit = C1; a.idx = active_indices; a.packed = packed; a.bias = bias; a.out = out;
-    a.T = B * N; a.Cin = Cin; a.Cout = Cout; a.B = B; a.N = N; a.H = H; a.W = W;
-    a.hp_shift = stacked_shift(H);  // (stacked edits: sige_hip_set_edit_batch)
-    if (a.hp_shift < 0 || (a.hp_shift && B != 1)) return SIGE_HIP_EUNSUPPORTED;
-    a.scale = scale; a.shift = shift;
-    const int mode = staging_mode(scale, scaleB, scaleC, shift, shiftB, shiftC, activation, B, Cin, &a.aff_sb, &a.aff_sc);
-    if (mode < 0) return SIGE_HIP_EUNSUPPORTED;
-    if ((out_scale == nullptr) != (out_shift == nullptr)) return SIGE_HIP_EINVAL;
-    if (out_activation != SIGE_HIP_ACT_IDENTITY && out_activation != SIGE_HIP_ACT_SWISH) return SIGE_HIP_EUNSUPPORTED;
-    if ((reinterpret_cast<uintptr_t>(out_scale) | reinterpret_cast<uintptr_t>(out_shift)) & 15) return SIGE_HIP_EUNSUPPORTED;
-    a.oscale = out_scale; a.oshift = out_shift; a.oact = out_activation;
-    a.up = upsample2x ? 1 : 0;
-    {   // optional K split: `workspace` holds whole copies of the output
-        const int Ro = (bH - kH) / strideH + 1, So = (bW - kW) / strideW + 1;
-        a.split_stride = to_full ? (size_t)B * Ho * Wo * Cout : (size_t)B * N * Ro * So * Cout;
-        a.ws = workspace;
-        a.ksplit_max = (workspace && a.split_stride && !(reinterpret_cast<uintptr_t>(workspace) & 15))
-                           ? (int)(workspace_floats / a.split_stride < 8 ? workspace_floats / a.split_stride : 8) : 1;
+    int mode;
+    if (int rc = source_args(c, a, &mode)) return rc;
+    if (int rc = out_affine_status(c.oscale, c.oshift)) return rc;
+    if (!act_known(c.oact) || !aligned16({c.oscale, c.oshift})) return SIGE_HIP_EUNSUPPORTED;
+    a.oscale = c.oscale; a.oshift = c.oshift; a.oact = c.oact;
+    a.up = c.up ? 1 : 0;
+    {   // optional K split: the workspace holds whole copies of the output
+        const int Ro = (c.bH - c.kH) / c.strH + 1, So = (c.bW - c.kW) / c.strW + 1;
+        a.split_stride = c.to_full ? (size_t)c.B * c.Ho * c.Wo * c.Cout : (size_t)c.B * c.N * Ro * So * c.Cout;
+        a.ws = c.ws;
+        a.ksplit_max = (c.ws && a.split_stride && aligned16({c.ws})) ? (int)(c.ws_floats / a.split_stride < 8 ? c.ws_floats / a.split_stride : 8) : 1;
         // (the second pass reads whole output copies: every pixel must be written by some tile)
-        if (to_full && (long)N * Ro * So < (long)Ho * Wo) a.ksplit_max = 1;
+        if (c.to_full && (long)c.N * Ro * So < (long)c.Ho * c.Wo) a.ksplit_max = 1;
     }
-    if ((twin0 || twin1) && !to_full) return SIGE_HIP_EINVAL;  // twins share the addressing of a full-tensor destination
-    if ((twin0 && (!twin0_scale || !twin0_shift)) || (twin1 && (!twin1_scale || !twin1_shift))) return SIGE_HIP_EINVAL;
-    if ((reinterpret_cast<uintptr_t>(twin0) | reinterpret_cast<uintptr_t>(twin1) | reinterpret_cast<uintptr_t>(twin0_scale) |
-         reinterpret_cast<uintptr_t>(twin0_shift) | reinterpret_cast<uintptr_t>(twin1_scale) | reinterpret_cast<uintptr_t>(twin1_shift)) & 15)
-        return SIGE_HIP_EUNSUPPORTED;
-    a.twin0 = twin0; a.tscale0 = twin0_scale; a.tshift0 = twin0_shift;
-    a.twin1 = twin1; a.tscale1 = twin1_scale; a.tshift1 = twin1_shift;
-    if (to_full) {
-        a.residual = residual; a.Ho = Ho; a.Wo = Wo; a.offH = offsetH; a.offW = offsetW; a.strH = strideH; a.strW = strideW;
-        if constexpr (PREC == 0) {
-            if (upsample2x == 2) return launch_phase_up(a, as_stream(stream));
-        }
-        return launch_conv<SRC_GATHER, DST_NCHW, LAYOUT_NHWC, PREC>(a, mode, kH, kW, bH, bW, strideH, strideW, as_stream(stream));
+    if ((c.twin[0].out || c.twin[1].out) && !c.to_full) return SIGE_HIP_EINVAL;  // twins share the addressing of a full-tensor destination
+    if (int rc = full_args(c, a)) return rc;
+    if (!c.to_full) return launch_conv<SRC_GATHER, DST_TILES, LAYOUT_NHWC, PREC>(a, mode, conv_kind(c), as_stream(c.stream));
+    if constexpr (PREC == 0) {
+        if (c.up == 2) return launch_phase_up(a, as_stream(c.stream));
     }
-    return launch_conv<SRC_GATHER, DST_TILES, LAYOUT_NHWC, PREC>(a, mode, kH, kW, bH, bW, strideH, strideW, as_stream(stream));
+    return launch_conv<SRC_GATHER, DST_NCHW, LAYOUT_NHWC, PREC>(a, mode, conv_kind(c), as_stream(c.stream));
 }
-
-extern "C" size_t sige_hip_upsample_phase_packed_size(int Cout, int Cin);
 
 // ---- routing: conv_mfma.hpp or the tile conv v3 (conv_tile3.hpp), decided HERE from the tile count ----
 // sige_hip_gather_conv_nhwc and sige_hip_scatter_gather_conv_scatter_nhwc take the weights in the v3 layout beside `packed` and a
@@ -1206,20 +1232,22 @@ constexpr int kTile3F16PairMin = 256;  // (profiles/r6j_tile3_f16_pairs_bench.js
 // SIGE_HIP_TUNE_TILE3_F16_SPARSE_MIN = -1: this value, 0 = no separate rule
 constexpr int kTile3F16SparseMin = 128;  // (profiles/r6o_tile3_f16_sparse_min.json: -1 % at 10 - 20 % edits, nothing lost at 1.2 / 5 %; 32 - 96 lose at 1.2 %)
 
-// Block size 10 (10x10 windows of a 3x3 / stride-1 conv): the v3 kernel's one-window form is the ONLY matrix form of this geometry,
-// so with v3 weights the call runs there whatever `min_blocks` says; without them it is refused below as ever.
-static bool tile3_block10(const float *packed_tile3, int kH, int kW, int bH, int bW, int strideH, int strideW) {
-    return packed_tile3 && kH == 3 && kW == 3 && bH == 10 && bW == 10 && strideH == 1 && strideW == 1;
+static bool geometry_3x3_s1(const TileConvCall &c, int block) {
+    return c.kH == 3 && c.kW == 3 && c.bH == block && c.bW == block && c.strH == 1 && c.strW == 1;
 }
 
-static bool tile3_takes(const float *packed_tile3, int min_blocks, int B, int N, int C1, int C2, int Cout, int kH, int kW, int bH, int bW,
-                        int strideH, int strideW, hipStream_t st, bool f16 = false, int H = 0, int W = 0) {
-    if (!packed_tile3 || min_blocks <= 0) return false;
-    if (kH != 3 || kW != 3 || bH != 6 || bW != 6 || strideH != 1 || strideW != 1) return false;
-    if (!sige_hip_tile_conv3_supported(C1, C2, Cout)) return false;
-    const long blocks = (long)((B * (long)N + 1) / 2) * (Cout / 64);
-    int need = min_blocks;
-    if (f16 && H > 0 && (long)N * 16 < (long)H * W) {  // a sparse tile list
+// Block size 10 (10x10 windows of a 3x3 / stride-1 conv): the v3 kernel's one-window form is the ONLY matrix form of this geometry,
+// so with v3 weights the call runs there whatever `min_blocks` says; without them it is refused below as ever.
+static bool tile3_block10(const TileConvCall &c) { return c.packed_tile3 && geometry_3x3_s1(c, 10); }
+
+// `f16`: the fp16-operand form and its rules (a sparse tile list, a held shortcut)
+static bool tile3_takes(const TileConvCall &c, bool f16) {
+    if (!c.packed_tile3 || c.min_blocks <= 0) return false;
+    if (!geometry_3x3_s1(c, 6)) return false;
+    if (!sige_hip_tile_conv3_supported(c.C1, c.C2, c.Cout)) return false;
+    const long blocks = (long)((c.tiles() + 1) / 2) * (c.Cout / 64);
+    int need = c.min_blocks;
+    if (f16 && c.H > 0 && (long)c.N * 16 < (long)c.H * c.W) {  // a sparse tile list
         int sm = tuning(SIGE_HIP_TUNE_TILE3_F16_SPARSE_MIN);
         if (sm < 0) sm = kTile3F16SparseMin;
         if (sm > 0 && sm < need) need = sm;
@@ -1227,13 +1255,20 @@ static bool tile3_takes(const float *packed_tile3, int min_blocks, int B, int N,
     if (blocks < need) return false;
     // a 1x1 shortcut held by conv_pair_begin() shares the conv_mfma.hpp launch of this conv1: keeping the pair beats the v3 kernel
     // plus a launch of its own for the shortcut (46.7 vs 39.5 + 8.7 us at a 15 % edit: profiles/r5j_sequence_15pct_*.csv)
-    if (g_held.active && g_held.st == st) {
+    if (g_held.active && g_held.st == as_stream(c.stream)) {
         if (!f16) return false;
         int pm = tuning(SIGE_HIP_TUNE_TILE3_F16_PAIR_MIN);
         if (pm < 0) pm = kTile3F16PairMin;
         if (pm == 0 || blocks < pm) return false;
     }
     return true;
+}
+
+// the affine the v3 kernel stages: none (`raw_act`: with any activation, which tile_conv3_launch then judges), or one entry per input channel
+static bool tile3_affine_ok(const TileConvCall &c, bool raw_act) {
+    const StagingAffine &f = c.aff;
+    if (!f.scale && !f.shift) return raw_act || f.act == SIGE_HIP_ACT_IDENTITY;
+    return f.scale && f.shift && f.scaleC == c.Cin() && f.shiftC == c.Cin() && f.scaleB == f.shiftB && (f.scaleB == 1 || f.scaleB == c.B);
 }
 
 extern "C" int sige_hip_gather_conv_nhwc(int compute, const float *x, const float *x2, int B, int C1, int C2, int H, int W,
@@ -1252,80 +1287,74 @@ extern "C" int sige_hip_gather_conv_nhwc(int compute, const float *x, const floa
                                          const float *packed_tile3, int min_blocks,
                                          float *out, void *stream) {
     SIGE_PLAN_HOOK_N(sige_hip_gather_conv_nhwc, (sige::CountOf<10, 11>), compute, x, x2, B, C1, C2, H, W, bH, bW, active_indices, N, scale, scaleB, scaleC, shift, shiftB, shiftC, activation, packed, bias, Cout, kH, kW, strideH, strideW, to_full, offsetH, offsetW, residual, Ho, Wo, workspace, workspace_floats, out_scale, out_shift, out_activation, upsample2x, twin0, twin0_scale, twin0_shift, twin1, twin1_scale, twin1_shift, packed_tile3, min_blocks, out, stream);
-    const int Cin = C1 + C2;
+    TileConvCall c{};
+    c.source = CALL_GATHER; c.x = x; c.x2 = x2; c.B = B; c.C1 = C1; c.C2 = C2; c.H = H; c.W = W; c.up = upsample2x; c.bH = bH; c.bW = bW;
+    c.idx = active_indices; c.N = N;
+    c.aff = {scale, shift, scaleB, scaleC, shiftB, shiftC, activation};
+    c.packed = packed; c.bias = bias; c.Cout = Cout; c.kH = kH; c.kW = kW; c.strH = strideH; c.strW = strideW;
+    c.packed_tile3 = packed_tile3; c.min_blocks = min_blocks;
+    c.to_full = to_full; c.offH = offsetH; c.offW = offsetW; c.Ho = Ho; c.Wo = Wo; c.residual = residual;
+    c.oscale = out_scale; c.oshift = out_shift; c.oact = out_activation;
+    c.twin[0] = {twin0, twin0_scale, twin0_shift}; c.twin[1] = {twin1, twin1_scale, twin1_shift};
+    c.ws = workspace; c.ws_floats = workspace_floats; c.out = out; c.stream = stream;
     const bool f16 = compute == 1;
-    const bool aff_ok = (!scale && !shift) || (scale && shift && scaleC == Cin && shiftC == Cin && scaleB == shiftB && (scaleB == 1 || scaleB == B));
-    if (tile3_block10(packed_tile3, kH, kW, bH, bW, strideH, strideW)) {
-        if (compute != 0 || !aff_ok || upsample2x == 2) return SIGE_HIP_EUNSUPPORTED;
-        return tile_conv3_launch(T3_GATHER, x, x2, B, C1, C2, H, W, upsample2x, active_indices, N, nullptr, 0, 0, scale, shift,
-                                 scale ? scaleB : 0, activation, packed_tile3, bias, Cout, to_full, offsetH, offsetW, Ho, Wo,
-                                 to_full ? residual : nullptr, nullptr, nullptr, 0, 0, 0, 0, 0, out_scale, out_shift, out_activation,
-                                 twin0, twin0_scale, twin0_shift, twin1, twin1_scale, twin1_shift, out, stream, WIDE_F32, 0, 0, 10);
+    const bool aff_ok = tile3_affine_ok(c, true);
+    // (the v3 kernel refuses a residual beside a tiles destination; conv_mfma.hpp does not look at it)
+    auto for_tile3 = [&c] { TileConvCall t = c; if (!t.to_full) t.residual = nullptr; return t; };
+    if (tile3_block10(c)) {
+        if (compute != 0 || !aff_ok || c.up == 2) return SIGE_HIP_EUNSUPPORTED;
+        return tile_conv3_launch(for_tile3(), WIDE_F32, 10);
     }
-    if (upsample2x == 2) {
+    if (c.up == 2) {
         // `packed` = the phase pack (sige_hip_upsample_phase_pack_f32) directly followed by the 9-tap pack of the same conv
         // (sige_hip_block_conv_pack_f32).  What the phase form does not cover is refused: the caller repeats the call with
         // upsample2x = 1.  What it covers but another form runs faster is routed HERE, from the tile count, so that a launch plan
         // replayed under another mask takes the form the module forward takes under that mask.
-        if (compute != 0 || C2 || kH != 3 || kW != 3 || bH != 6 || bW != 6 || strideH != 1 || strideW != 1 || !to_full || scale || shift ||
+        if (compute != 0 || C2 || !geometry_3x3_s1(c, 6) || !to_full || scale || shift ||
             activation != SIGE_HIP_ACT_IDENTITY || stacked_shift(H) != 0 || g_side_armed > 0)
             return SIGE_HIP_EUNSUPPORTED;
         // (measured inside the DDPM-256 forward, DESIGN.md 5.19: all five Upsample launches are faster in the phase form, the two
         //  512-channel ones with 6 and 9 tiles included, so the only rule is the v3 tile conv's own: from the tile count at which it
         //  takes the 9-tap call it keeps it)
-        const bool nine_tap = B > 0 && N > 0 &&
-                              tile3_takes(packed_tile3, min_blocks, B, N, C1, C2, Cout, kH, kW, bH, bW, strideH, strideW, as_stream(stream));
-        if (nine_tap) {
-            upsample2x = 1;
-            packed += sige_hip_upsample_phase_packed_size(Cout, Cin);
+        if (B > 0 && N > 0 && tile3_takes(c, false)) {
+            c.up = 1;
+            c.packed += sige_hip_upsample_phase_packed_size(Cout, c.Cin());
         }
     }
     // (a conv that sige_hip_conv_side_begin waits for stays on the stacked-block kernels, where it can be queued)
-    if (upsample2x != 2 && (compute == 0 || f16) && B > 0 && N > 0 && aff_ok && !(g_side_armed > 0 && compute == 0 && to_full) &&
-        tile3_takes(packed_tile3, min_blocks, B, N, C1, C2, Cout, kH, kW, bH, bW, strideH, strideW, as_stream(stream), f16, f16 ? H : 0, f16 ? W : 0)) {
-        const int rc = tile_conv3_launch(T3_GATHER, x, x2, B, C1, C2, H, W, upsample2x, active_indices, N, nullptr, 0, 0, scale, shift,
-                                         scale ? scaleB : 0, activation, packed_tile3, bias, Cout, to_full, offsetH, offsetW, Ho, Wo,
-                                         to_full ? residual : nullptr, nullptr, nullptr, 0, 0, 0, 0, 0, out_scale, out_shift, out_activation,
-                                         twin0, twin0_scale, twin0_shift, twin1, twin1_scale, twin1_shift, out, stream, f16 ? WIDE_F16 : WIDE_F32, 0, 0);
+    if (c.up != 2 && (compute == 0 || f16) && B > 0 && N > 0 && aff_ok && !(g_side_armed > 0 && compute == 0 && to_full) && tile3_takes(c, f16)) {
+        const int rc = tile_conv3_launch(for_tile3(), f16 ? WIDE_F16 : WIDE_F32, 6);
         if (rc != SIGE_HIP_EUNSUPPORTED) { g_side_armed = 0; return rc; }
     }
-    const int rc = SIGE_BY_COMPUTE(compute, gather_conv_nhwc_impl, x, x2, B, C1, C2, H, W, bH, bW, active_indices, N, scale, scaleB, scaleC, shift, shiftB,
-                                   shiftC, activation, packed, bias, Cout, kH, kW, strideH, strideW, to_full, offsetH, offsetW, residual, Ho, Wo,
-                                   workspace, workspace_floats, out_scale, out_shift, out_activation, upsample2x, twin0, twin0_scale, twin0_shift,
-                                   twin1, twin1_scale, twin1_shift, out, stream);
+    const int rc = SIGE_BY_COMPUTE(compute, gather_conv_nhwc_impl, c);
     g_side_armed = 0;  // (sige_hip_conv_side_begin is spent on THIS call, queued or not: it never waits for a later, unrelated conv)
     return rc;
 }
 
-// `y` -- the cached tensor of the ScatterGather, or its activated copy -- holds halves when y_f16 != 0 (fp16-STORED caches:
-// SURVEY.md 8b export list "_f16", 8f row 4; 3x3 / stride 1 only), floats otherwise; every `compute` reads either.
+// scatter_gather -> conv, tiles out (to_full = 0), or -> Scatter / ScatterWithBlockResidual in ONE launch (to_full): the conv's
+// output tiles go straight into `out` [B,H,W,Cout], a buffer that already holds the cached tensor outside this mask's tiles
+// (in-place scatter).  x2_f16 / res_f16: the cached tensor / `residual` (with x1 != NULL the cached shortcut tensor) hold halves
+// (fp16-STORED caches: SURVEY.md 8b export list "_f16", 8f row 4; 3x3 / stride 1 only); every `compute` reads either.
 template <int PREC>
-static int scatter_gather_conv_nhwc_impl(const float *x, const void *y, int y_f16, int B, int Cin, int H, int W,
-                                                     int Rx, int Sx, int bH, int bW,
-                                                     const int32_t *active_indices, int N, const int32_t *scatter_map,
-                                                     const float *scale, int scaleB, int scaleC,
-                                                     const float *shift, int shiftB, int shiftC,
-                                                     int activation,
-                                                     const float *packed, const float *bias, int Cout, int kH, int kW,
-                                                     int strideH, int strideW, float *out, void *stream) {
-    if (B < 0 || Cin <= 0 || Cout <= 0 || H <= 0 || W <= 0 || N < 0 || Rx <= 0 || Sx <= 0) return SIGE_HIP_EINVAL;
-    if (activation != SIGE_HIP_ACT_IDENTITY && activation != SIGE_HIP_ACT_SWISH) return SIGE_HIP_EUNSUPPORTED;
-    if ((long)B * Cin * H * W >= (1L << 29) || (long)B * N * Cin * Rx * Sx >= (1L << 29)) return SIGE_HIP_EUNSUPPORTED;
-    if ((long)B * N == 0) return SIGE_HIP_OK;
-    if (!x || !y || !packed || !out || !active_indices || !scatter_map) return SIGE_HIP_EINVAL;
-    if (!nhwc_ok(Cin, Cin, Cout, x, y, out, bias) || (reinterpret_cast<uintptr_t>(packed) & 15)) return SIGE_HIP_EUNSUPPORTED;
-    if (y_f16 && (kH != 3 || kW != 3 || strideH != 1 || strideW != 1)) return SIGE_HIP_EUNSUPPORTED;
+static int scatter_gather_conv_nhwc_impl(const TileConvCall &c) {
+    if (c.B < 0 || c.C1 <= 0 || c.Cout <= 0 || c.H <= 0 || c.W <= 0 || c.N < 0 || c.Rx <= 0 || c.Sx <= 0) return SIGE_HIP_EINVAL;
+    if (c.to_full && !geometry_3x3_s1(c, 6)) return SIGE_HIP_EUNSUPPORTED;  // the stride-1 3x3 geometry of a ResBlock's conv2
+    if (!act_known(c.aff.act)) return SIGE_HIP_EUNSUPPORTED;
+    if (!source_offsets_fit(c)) return SIGE_HIP_EUNSUPPORTED;
+    if (c.tiles() == 0) return SIGE_HIP_OK;
+    if (!c.x || !c.x2 || !c.packed || !c.out || !c.idx || !c.map) return SIGE_HIP_EINVAL;
+    if (c.x1 && (!c.residual || !c.table1 || c.R1 <= 0 || c.S1 <= 0 || c.gH1 < (c.H + c.R1 - 1) / c.R1 || c.gW1 < (c.W + c.S1 - 1) / c.S1))
+        return SIGE_HIP_EINVAL;
+    if (!channels_x4(c) || !aligned16({c.x, c.x2, c.out, c.bias, c.packed, c.residual, c.x1})) return SIGE_HIP_EUNSUPPORTED;
+    if (c.res_f16 && !c.residual) return SIGE_HIP_EINVAL;
+    if (c.x2_f16 && (c.kH != 3 || c.kW != 3 || c.strH != 1 || c.strW != 1)) return SIGE_HIP_EUNSUPPORTED;
     ConvArgs a{};
-    a.y_f16 = y_f16 ? 1 : 0;
-    a.x = x; a.y = static_cast<const float *>(y); a.idx = active_indices; a.map = scatter_map; a.packed = packed; a.bias = bias; a.out = out;
-    a.T = B * N; a.Cin = Cin; a.Cout = Cout; a.B = B; a.N = N; a.H = H; a.W = W;
-    a.hp_shift = stacked_shift(H);  // (stacked edits: sige_hip_set_edit_batch)
-    if (a.hp_shift < 0 || (a.hp_shift && B != 1)) return SIGE_HIP_EUNSUPPORTED;
-    a.RxSx = Rx * Sx; a.Sx = Sx;
-    a.scale = scale; a.shift = shift;
-    const int mode = staging_mode(scale, scaleB, scaleC, shift, shiftB, shiftC, activation, B, Cin, &a.aff_sb, &a.aff_sc);
-    if (mode < 0) return SIGE_HIP_EUNSUPPORTED;
-    return launch_conv<SRC_SCATTER_GATHER, DST_TILES, LAYOUT_NHWC, PREC>(a, mode, kH, kW, bH, bW, strideH, strideW, as_stream(stream));
+    int mode;
+    if (int rc = source_args(c, a, &mode)) return rc;
+    if (int rc = full_args(c, a)) return rc;
+    if (!c.to_full) return launch_conv<SRC_SCATTER_GATHER, DST_TILES, LAYOUT_NHWC, PREC>(a, mode, conv_kind(c), as_stream(c.stream));
+    return KindSteps<3, 1, 6, SRC_SCATTER_GATHER, DST_NCHW, LAYOUT_NHWC, PREC>::launch(a, mode, as_stream(c.stream)) != SIGE_HIP_OK
+               ? SIGE_HIP_EUNSUPPORTED : launch_status();
 }
 
 extern "C" int sige_hip_scatter_gather_conv_nhwc(int compute, const float *x, const void *y, int y_f16, int B, int Cin, int H, int W,
@@ -1337,55 +1366,13 @@ extern "C" int sige_hip_scatter_gather_conv_nhwc(int compute, const float *x, co
                                                  const float *packed, const float *bias, int Cout, int kH, int kW,
                                                  int strideH, int strideW, float *out, void *stream) {
     SIGE_PLAN_HOOK_N(sige_hip_scatter_gather_conv_nhwc, (sige::CountOf<12, 13>), compute, x, y, y_f16, B, Cin, H, W, Rx, Sx, bH, bW, active_indices, N, scatter_map, scale, scaleB, scaleC, shift, shiftB, shiftC, activation, packed, bias, Cout, kH, kW, strideH, strideW, out, stream);
-    return SIGE_BY_COMPUTE(compute, scatter_gather_conv_nhwc_impl, x, y, y_f16, B, Cin, H, W, Rx, Sx, bH, bW, active_indices, N, scatter_map, scale, scaleB,
-                           scaleC, shift, shiftB, shiftC, activation, packed, bias, Cout, kH, kW, strideH, strideW, out, stream);
-}
-
-// scatter_gather -> conv -> Scatter / ScatterWithBlockResidual in ONE launch: the conv's output tiles go straight
-// into `out` [B,H,W,Cout], a buffer that already holds the cached tensor outside this mask's tiles (in-place scatter).
-// y_f16 / residual_f16: `y` / `residual` (with x1 != NULL the cached shortcut tensor) hold halves -- the fp16-stored caches again.
-template <int PREC>
-static int scatter_gather_conv_scatter_nhwc_impl(
-        const float *x, const void *y, int y_f16, int B, int Cin, int H, int W, int Rx, int Sx, int bH, int bW,
-        const int32_t *active_indices, int N, const int32_t *scatter_map,
-        const float *scale, int scaleB, int scaleC, const float *shift, int shiftB, int shiftC, int activation,
-        const float *packed, const float *bias, int Cout, int kH, int kW,
-        int offsetH, int offsetW, const void *residual, int residual_f16,
-        const float *x1, const int32_t *table1, int gH1, int gW1, int N1, int R1, int S1,
-        float *twin0, const float *twin0_scale, const float *twin0_shift,
-        float *twin1, const float *twin1_scale, const float *twin1_shift,
-        float *out, void *stream) {
-    if (B < 0 || Cin <= 0 || Cout <= 0 || H <= 0 || W <= 0 || N < 0 || Rx <= 0 || Sx <= 0) return SIGE_HIP_EINVAL;
-    if (kH != 3 || kW != 3 || bH != 6 || bW != 6) return SIGE_HIP_EUNSUPPORTED;  // the stride-1 3x3 geometry of a ResBlock's conv2
-    if (activation != SIGE_HIP_ACT_IDENTITY && activation != SIGE_HIP_ACT_SWISH) return SIGE_HIP_EUNSUPPORTED;
-    if ((long)B * Cin * H * W >= (1L << 29) || (long)B * N * Cin * Rx * Sx >= (1L << 29)) return SIGE_HIP_EUNSUPPORTED;
-    if ((long)B * N == 0) return SIGE_HIP_OK;
-    if (!x || !y || !packed || !out || !active_indices || !scatter_map) return SIGE_HIP_EINVAL;
-    if (x1 && (!residual || !table1 || R1 <= 0 || S1 <= 0 || gH1 < (H + R1 - 1) / R1 || gW1 < (W + S1 - 1) / S1)) return SIGE_HIP_EINVAL;
-    if (!nhwc_ok(Cin, Cin, Cout, x, y, out, bias) || (reinterpret_cast<uintptr_t>(packed) & 15) ||
-        (reinterpret_cast<uintptr_t>(residual) & 15) || (reinterpret_cast<uintptr_t>(x1) & 15))
-        return SIGE_HIP_EUNSUPPORTED;
-    if (residual_f16 && !residual) return SIGE_HIP_EINVAL;
-    ConvArgs a{};
-    a.y_f16 = y_f16 ? 1 : 0; a.res_f16 = residual_f16 ? 1 : 0;
-    a.x = x; a.y = static_cast<const float *>(y); a.idx = active_indices; a.map = scatter_map; a.packed = packed; a.bias = bias; a.out = out;
-    a.T = B * N; a.Cin = Cin; a.Cout = Cout; a.B = B; a.N = N; a.H = H; a.W = W;
-    a.hp_shift = stacked_shift(H);  // (stacked edits: sige_hip_set_edit_batch)
-    if (a.hp_shift < 0 || (a.hp_shift && B != 1)) return SIGE_HIP_EUNSUPPORTED;
-    a.RxSx = Rx * Sx; a.Sx = Sx;
-    a.scale = scale; a.shift = shift;
-    const int mode = staging_mode(scale, scaleB, scaleC, shift, shiftB, shiftC, activation, B, Cin, &a.aff_sb, &a.aff_sc);
-    if (mode < 0) return SIGE_HIP_EUNSUPPORTED;
-    a.residual = static_cast<const float *>(residual); a.Ho = H; a.Wo = W; a.offH = offsetH; a.offW = offsetW; a.strH = 1; a.strW = 1;
-    a.x1 = x1; a.table1 = table1; a.gW1 = gW1; a.N1 = N1; a.R1 = R1 > 0 ? R1 : 1; a.S1 = S1 > 0 ? S1 : 1;
-    if ((twin0 && (!twin0_scale || !twin0_shift)) || (twin1 && (!twin1_scale || !twin1_shift))) return SIGE_HIP_EINVAL;
-    if ((reinterpret_cast<uintptr_t>(twin0) | reinterpret_cast<uintptr_t>(twin1) | reinterpret_cast<uintptr_t>(twin0_scale) |
-         reinterpret_cast<uintptr_t>(twin0_shift) | reinterpret_cast<uintptr_t>(twin1_scale) | reinterpret_cast<uintptr_t>(twin1_shift)) & 15)
-        return SIGE_HIP_EUNSUPPORTED;
-    a.twin0 = twin0; a.tscale0 = twin0_scale; a.tshift0 = twin0_shift;
-    a.twin1 = twin1; a.tscale1 = twin1_scale; a.tshift1 = twin1_shift;
-    return launch_kind<3, 1, 6, SRC_SCATTER_GATHER, DST_NCHW, LAYOUT_NHWC, PREC>(a, mode, as_stream(stream)) != SIGE_HIP_OK
-               ? SIGE_HIP_EUNSUPPORTED : launch_status();
+    TileConvCall c{};
+    c.source = CALL_SCATTER_GATHER; c.x = x; c.x2 = y; c.x2_f16 = y_f16; c.B = B; c.C1 = Cin; c.H = H; c.W = W; c.bH = bH; c.bW = bW;
+    c.idx = active_indices; c.N = N; c.map = scatter_map; c.Rx = Rx; c.Sx = Sx;
+    c.aff = {scale, shift, scaleB, scaleC, shiftB, shiftC, activation};
+    c.packed = packed; c.bias = bias; c.Cout = Cout; c.kH = kH; c.kW = kW; c.strH = strideH; c.strW = strideW;
+    c.out = out; c.stream = stream;
+    return SIGE_BY_COMPUTE(compute, scatter_gather_conv_nhwc_impl, c);
 }
 
 extern "C" int sige_hip_scatter_gather_conv_scatter_nhwc(
@@ -1400,31 +1387,28 @@ extern "C" int sige_hip_scatter_gather_conv_scatter_nhwc(
         const float *packed_tile3, int min_blocks,
         float *out, void *stream) {
     SIGE_PLAN_HOOK_N(sige_hip_scatter_gather_conv_scatter_nhwc, (sige::CountOf<12, 13>, sige::CountOf<32, 35>), compute, x, y, y_f16, B, Cin, H, W, Rx, Sx, bH, bW, active_indices, N, scatter_map, scale, scaleB, scaleC, shift, shiftB, shiftC, activation, packed, bias, Cout, kH, kW, offsetH, offsetW, residual, residual_f16, x1, table1, gH1, gW1, N1, R1, S1, twin0, twin0_scale, twin0_shift, twin1, twin1_scale, twin1_shift, packed_tile3, min_blocks, out, stream);
+    TileConvCall c{};
+    c.source = CALL_SCATTER_GATHER; c.x = x; c.x2 = y; c.x2_f16 = y_f16; c.B = B; c.C1 = Cin; c.H = H; c.W = W; c.bH = bH; c.bW = bW;
+    c.idx = active_indices; c.N = N; c.map = scatter_map; c.Rx = Rx; c.Sx = Sx;
+    c.aff = {scale, shift, scaleB, scaleC, shiftB, shiftC, activation};
+    c.packed = packed; c.bias = bias; c.Cout = Cout; c.kH = kH; c.kW = kW; c.strH = 1; c.strW = 1;
+    c.packed_tile3 = packed_tile3; c.min_blocks = min_blocks;
+    c.to_full = 1; c.offH = offsetH; c.offW = offsetW; c.Ho = H; c.Wo = W; c.residual = residual; c.res_f16 = residual_f16;
+    c.x1 = x1; c.table1 = table1; c.gH1 = gH1; c.gW1 = gW1; c.N1 = N1; c.R1 = R1; c.S1 = S1;
+    c.twin[0] = {twin0, twin0_scale, twin0_shift}; c.twin[1] = {twin1, twin1_scale, twin1_shift};
+    c.out = out; c.stream = stream;
     const bool f16 = compute == 1;
-    const bool aff_ok = (!scale && !shift && activation == SIGE_HIP_ACT_IDENTITY) ||
-                        (scale && shift && scaleC == Cin && shiftC == Cin && scaleB == shiftB && (scaleB == 1 || scaleB == B));
-    if (tile3_block10(packed_tile3, kH, kW, bH, bW, 1, 1)) {
+    if (tile3_block10(c)) {
         if (compute != 0 || y_f16 || residual_f16 || scale || shift || activation != SIGE_HIP_ACT_IDENTITY || Rx != 8 || Sx != 8)
             return SIGE_HIP_EUNSUPPORTED;
-        return tile_conv3_launch(T3_SCATTER_GATHER, x, static_cast<const float *>(y), B, Cin, 0, H, W, 0, active_indices, N, scatter_map, Rx, Sx,
-                                 nullptr, nullptr, 0, activation, packed_tile3, bias, Cout, 1, offsetH, offsetW, H, W,
-                                 static_cast<const float *>(residual), x1, table1, gH1, gW1, N1, R1, S1, nullptr, nullptr, 0,
-                                 twin0, twin0_scale, twin0_shift, twin1, twin1_scale, twin1_shift, out, stream, WIDE_F32, 0, 0, 10);
+        return tile_conv3_launch(c, WIDE_F32, 10);
     }
     // (the exact-fp32 v3 kernel reads fp32-stored caches only)
-    if ((f16 || (compute == 0 && !y_f16 && !residual_f16)) && B > 0 && N > 0 && aff_ok &&
-        tile3_takes(packed_tile3, min_blocks, B, N, Cin, 0, Cout, kH, kW, bH, bW, 1, 1, as_stream(stream), f16, f16 ? H : 0, f16 ? W : 0)) {
-        const int rc = tile_conv3_launch(T3_SCATTER_GATHER, x, static_cast<const float *>(y), B, Cin, 0, H, W, 0, active_indices, N, scatter_map, Rx, Sx,
-                                         scale, shift, scale ? scaleB : 0, activation, packed_tile3, bias, Cout, 1, offsetH, offsetW, H, W,
-                                         static_cast<const float *>(residual), x1, table1, gH1, gW1, N1, R1, S1, nullptr, nullptr, 0,
-                                         twin0, twin0_scale, twin0_shift, twin1, twin1_scale, twin1_shift, out, stream,
-                                         f16 ? WIDE_F16 : WIDE_F32, y_f16, residual_f16);
+    if ((f16 || (compute == 0 && !y_f16 && !residual_f16)) && B > 0 && N > 0 && tile3_affine_ok(c, false) && tile3_takes(c, f16)) {
+        const int rc = tile_conv3_launch(c, f16 ? WIDE_F16 : WIDE_F32, 6);
         if (rc != SIGE_HIP_EUNSUPPORTED) return rc;
     }
-    return SIGE_BY_COMPUTE(compute, scatter_gather_conv_scatter_nhwc_impl, x, y, y_f16, B, Cin, H, W, Rx, Sx, bH, bW, active_indices, N, scatter_map,
-                           scale, scaleB, scaleC, shift, shiftB, shiftC, activation, packed, bias, Cout, kH, kW, offsetH, offsetW,
-                           residual, residual_f16, x1, table1, gH1, gW1, N1, R1, S1, twin0, twin0_scale, twin0_shift, twin1, twin1_scale,
-                           twin1_shift, out, stream);
+    return SIGE_BY_COMPUTE(compute, scatter_gather_conv_nhwc_impl, c);
 }
 #undef SIGE_BY_COMPUTE
 

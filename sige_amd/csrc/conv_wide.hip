@@ -3,6 +3,7 @@
 // Reference: the layers a SIGE network runs densely -- below `sparse_resolution_threshold` in the sparse pass
 // (diffusion/models/ddpm_arch/sige_fused_unet.py:112-123) and every conv of the full pass (sige/nn/base.py:85-86) --
 // go through F.conv2d (cuDNN / MIOpen) after separate elementwise kernels for the cached affine, SiLU, cat and skip add.
+#include "conv_call.hpp"
 #include "conv_wide.hpp"
 
 namespace sige {
@@ -182,33 +183,32 @@ extern "C" int sige_hip_wide_conv_nhwc(const float *x, const float *x2, int B, i
     if (B <= 0 || H <= 0 || W <= 0 || C1 <= 0 || C2 < 0 || Cout <= 0 || prec < WIDE_F16 || prec > WIDE_F32) return SIGE_HIP_EINVAL;
     if (!x || (C2 && !x2) || !packed || !out) return SIGE_HIP_EINVAL;
     if (!wide_shape_ok(C1, C2, Cout, kH, kW)) return SIGE_HIP_EUNSUPPORTED;
-    if ((scale == nullptr) != (shift == nullptr)) return SIGE_HIP_EINVAL;
-    if (scale && affineB != 1 && affineB != B) return SIGE_HIP_EINVAL;
-    if (!scale && activation != SIGE_HIP_ACT_IDENTITY) return SIGE_HIP_EUNSUPPORTED;  // (an activation comes with the cached affine)
-    if (activation != SIGE_HIP_ACT_IDENTITY && activation != SIGE_HIP_ACT_SWISH) return SIGE_HIP_EUNSUPPORTED;
-    if (out_scale && out_activation != SIGE_HIP_ACT_IDENTITY && out_activation != SIGE_HIP_ACT_SWISH) return SIGE_HIP_EUNSUPPORTED;
-    if ((out_scale == nullptr) != (out_shift == nullptr)) return SIGE_HIP_EINVAL;
+    // (one affine entry per input channel, for affineB images)
+    if (int rc = staging_affine_status({scale, shift, affineB, C1 + C2, affineB, C1 + C2, activation}, B, C1 + C2, SIGE_HIP_EINVAL, SIGE_HIP_EINVAL)) return rc;
+    if (!act_known(activation)) return SIGE_HIP_EUNSUPPORTED;
+    if (out_scale && !act_known(out_activation)) return SIGE_HIP_EUNSUPPORTED;
+    if (int rc = out_affine_status(out_scale, out_shift)) return rc;
     if (upsample2x && ((H | W) & 1)) return SIGE_HIP_EINVAL;
     const long src_px = (long)B * (H >> (upsample2x ? 1 : 0)) * (W >> (upsample2x ? 1 : 0));
-    if (src_px * (C1 > C2 ? C1 : C2) >= (1L << 29)) return SIGE_HIP_EUNSUPPORTED;  // 32-bit byte offsets in the kernel
-    auto al = [](const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; };
-    if (!al(x) || !al(x2) || !al(packed) || !al(out) || !al(bias) || !al(scale) || !al(shift) || !al(residual) || !al(out_scale) ||
-        !al(out_shift) || !al(twin0) || !al(twin1) || !al(workspace) || (reinterpret_cast<uintptr_t>(stats) & 7))
+    if (!offsets_fit(src_px * (C1 > C2 ? C1 : C2))) return SIGE_HIP_EUNSUPPORTED;
+    if (!aligned16({x, x2, packed, out, bias, scale, shift, residual, out_scale, out_shift, twin0, twin1, workspace}) ||
+        (reinterpret_cast<uintptr_t>(stats) & 7))
         return SIGE_HIP_EUNSUPPORTED;
     WideArgs a{};
     a.x = x; a.x2 = x2 ? x2 : x; a.packed = packed; a.bias = bias; a.scale = scale; a.shift = shift; a.residual = residual;
     a.oscale = out_scale; a.oshift = out_shift; a.oact = out_activation; a.out = out; a.fout = out;
     a.twin0 = twin0; a.tscale0 = twin_scale0; a.tshift0 = twin_shift0;
     a.twin1 = twin1; a.tscale1 = twin_scale1; a.tshift1 = twin_shift1;
-    if ((twin0 && !(twin_scale0 && twin_shift0)) || (twin1 && !(twin_scale1 && twin_shift1))) return SIGE_HIP_EINVAL;
+    const TwinOut twins[2] = {{twin0, twin_scale0, twin_shift0}, {twin1, twin_scale1, twin_shift1}};
+    if (int rc = twins_status(twins)) return rc;
     a.wscale = ldexpf(1.0f, -wshift);
     a.stats = reinterpret_cast<float2 *>(stats);
 #ifdef SIGE_WIDE_PROBE
     a.probe = g_wprobe_buf;
 #endif
     a.B = B; a.H = H; a.W = W; a.C1 = C1; a.C2 = C2; a.Cout = Cout; a.up = upsample2x ? 1 : 0; a.act = activation;
-    a.hp_shift = stacked_shift(H);
-    if (a.hp_shift < 0 || (a.hp_shift && (B != 1 || (1 << a.hp_shift) % 8 || stats))) return SIGE_HIP_EUNSUPPORTED;  // (8-row patches must not straddle a seam)
+    if (edit_shift_status(H, B, &a.hp_shift) != SIGE_HIP_OK) return SIGE_HIP_EUNSUPPORTED;
+    if (a.hp_shift && ((1 << a.hp_shift) % 8 || stats)) return SIGE_HIP_EUNSUPPORTED;  // (8-row patches must not straddle a seam)
     a.aff_sb = (scale && affineB > 1) ? C1 + C2 : 0;
     const int pwo = wide_patch(W);
     a.th = ceil_div(H, 8); a.tw = ceil_div(W, pwo); a.ntn = Cout / 64;

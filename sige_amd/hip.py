@@ -1101,15 +1101,7 @@ def wide_conv_cl(x, x2, scale, shift, activationName: str, packed, bias, Cout: i
         r = _req_cl(residual, "residual")
         if tuple(r.shape) != tuple(out.shape):
             raise RuntimeError("wide_conv_cl: residual %s != output %s" % (tuple(r.shape), tuple(out.shape)))
-    if out_affine is not None:
-        os_, oh_, oact = out_affine
-        os_, oh_ = _req(os_.reshape(-1), torch.float32, "out_scale", 1), _req(oh_.reshape(-1), torch.float32, "out_shift", 1)
-        if os_.numel() != Cout or oh_.numel() != Cout:
-            raise RuntimeError("wide_conv_cl: out_affine must have one entry per output channel")
-        oargs = (os_.data_ptr(), oh_.data_ptr(), _act(oact))
-    else:
-        os_ = oh_ = None
-        oargs = (None, None, 0)
+    oargs, o_keep = _out_affine_args(out_affine, Cout, "wide_conv_cl")
     targs, twin_keep = _twin_args(twins if twins else None, out, Cout, "wide_conv_cl")
     ws, ws_n = None, int(lib().sige_hip_wide_conv_workspace(B, H, W, C1, C2, Cout, kernel[0], kernel[1])) if KSPLIT else 0
     if ws_n:
@@ -1621,6 +1613,24 @@ def _p(t: Optional[torch.Tensor]):
     return None if t is None else t.data_ptr()
 
 
+# the optional argument groups of the tile-conv entry points (include/sige_hip.h) when a call has none of them
+_NO_OUT_AFFINE = (None, None, 0)
+_NO_BLOCK_RESIDUAL = (None, None, 0, 0, 0, 0, 0)
+_NO_TWINS = (None,) * 6
+
+
+def _out_affine_args(out_affine, Cout: int, name: str):
+    """(out_scale, out_shift, out_activation) of a conv launch from `out_affine` = (scale [*,Cout,1,1], shift, activation name) or
+    None: the consumer's affine + activation in the epilogue.  Returns (args, keep-alive list)."""
+    if out_affine is None:
+        return _NO_OUT_AFFINE, []
+    os_, oh_, oact = out_affine
+    os_, oh_ = _req(os_.reshape(-1), torch.float32, "out_scale", 1), _req(oh_.reshape(-1), torch.float32, "out_shift", 1)
+    if os_.numel() != Cout or oh_.numel() != Cout:
+        raise RuntimeError("%s: out_affine must have one entry per output channel" % name)
+    return (os_.data_ptr(), oh_.data_ptr(), _act(oact)), [os_, oh_]
+
+
 def _twin_args(twins, like: torch.Tensor, Cout: int, name: str):
     """The six twin pointers of a full-tensor conv launch (include/sige_hip.h) from `twins` = up to two (buffer, scale,
     shift): buffer = channels-last tensor shaped like the launch's output, scale / shift = [Cout] (or [1,Cout,1,1]) fp32.
@@ -1696,7 +1706,7 @@ def _block_conv_cl_geometry(geo: str, x, key, packed, bias, Cout: int):
         # "b10": a slab of 10x10 tiles is a batch of T images of 10x10 with one window at the origin each
         origin = torch.zeros((1, 2), dtype=torch.int32, device=x.device)
         out = tile_conv3_cl(1, x, None, T, Cin, 0, 10, 10, False, origin, None, (0, 0), None, None, "identity", packed, bias, Cout,
-                            None, None, (None, None, 0, 0, 0, 0, 0), None, (None,) * 6, _empty_cl((T, Cout, 8, 8), x.device), block=10)
+                            None, None, _NO_BLOCK_RESIDUAL, None, _NO_TWINS, _empty_cl((T, Cout, 8, 8), x.device), block=10)
         if out is None:
             return None
     return tag_tiles(out, *key) if key is not None and key[0].shape[0] * key[1] == T else out
@@ -1774,14 +1784,7 @@ def tile_conv3_cl(source: int, x, x2, B, C1, C2, H, W, up, idx, smap, rx_sx, sca
         if sa[2] != C1 + C2 or ta[2] != C1 + C2 or sa[1] != ta[1]:
             return None
         sc, sh, affB = sa[0], ta[0], sa[1]
-    if out_affine is not None:
-        os_, oh_, oact = out_affine
-        os_, oh_ = _req(os_.reshape(-1), torch.float32, "out_scale", 1), _req(oh_.reshape(-1), torch.float32, "out_shift", 1)
-        if os_.numel() != Cout or oh_.numel() != Cout:
-            raise RuntimeError("tile_conv3_cl: out_affine must have one entry per output channel")
-        oargs = (os_.data_ptr(), oh_.data_ptr(), _act(oact))
-    else:
-        oargs = (None, None, 0)
+    oargs, o_keep = _out_affine_args(out_affine, Cout, "tile_conv3_cl")
     fargs = (0, 0, 0, 0, 0) if full is None else (1, *full)
     y16 = int(x2 is not None and x2.dtype == torch.float16)
     r16 = int(residual is not None and residual.dtype == torch.float16)
@@ -1847,17 +1850,17 @@ def gather_conv_cl(x, x2, block: Tuple[int, int], activeIndices, scale, shift, a
             if tuple(r.shape) != tuple(out.shape):
                 raise RuntimeError("gather_conv_cl: residual %s != output %s" % (tuple(r.shape), tuple(out.shape)))
         fargs = (1, full["offset"][0], full["offset"][1], None if r is None else r.data_ptr(), Ho, Wo)
+    if twins and full is None:
+        raise RuntimeError("gather_conv_cl: twins need a full-tensor destination")
+    targs, twin_keep = _twin_args(twins if twins else None, out, Cout, "gather_conv_cl")
     compute = _compute_id(packed)
     t3 = _tile3_route(packed, B * N, C1, C2, Cout, kernel, stride, block)  # (TILE3 = True: the v3 kernel, forced)
     if getattr(_side_state, "armed", False):
         t3 = None  # (conv_side_begin() waits for THIS call: it stays on the kernels that can queue it)
     if t3 is not None and N > 0:
-        if twins and full is None:
-            raise RuntimeError("gather_conv_cl: twins need a full-tensor destination")
-        targs3, twin_keep3 = _twin_args(twins if twins else None, out, Cout, "gather_conv_cl")
         got = tile_conv3_cl(1, x, x2, B, C1, C2, H, W, upsample2x, idx, None, (0, 0), scale, shift, activationName, t3, bias, Cout,
                             None if full is None else (full["offset"][0], full["offset"][1], Ho, Wo),
-                            None if full is None else r, (None, None, 0, 0, 0, 0, 0), out_affine, targs3, out, compute=compute)
+                            None if full is None else r, _NO_BLOCK_RESIDUAL, out_affine, targs, out, compute=compute)
         if got is not None:
             return got if full is not None else tag_tiles(got, idx, B)
     # deep-K convs over a handful of tiles: workspace for the cross-workgroup K split
@@ -1880,19 +1883,8 @@ def gather_conv_cl(x, x2, block: Tuple[int, int], activeIndices, scale, shift, a
         ws_n = ks * out.numel()
         ws = torch.empty(ws_n, dtype=torch.float32, device=x.device)
     fargs = fargs + (None if ws is None else ws.data_ptr(), ws_n)
-    # epilogue affine + activation of the consumer: (scale [*,Cout,1,1], shift, activation name)
-    if out_affine is not None:
-        os_, oh_, oact = out_affine
-        os_, oh_ = _req(os_.reshape(-1), torch.float32, "out_scale", 1), _req(oh_.reshape(-1), torch.float32, "out_shift", 1)
-        if os_.numel() != Cout or oh_.numel() != Cout:
-            raise RuntimeError("gather_conv_cl: out_affine must have one entry per output channel")
-        fargs = fargs + (os_.data_ptr(), oh_.data_ptr(), _act(oact))
-    else:
-        fargs = fargs + (None, None, 0)
-    if twins and full is None:
-        raise RuntimeError("gather_conv_cl: twins need a full-tensor destination")
-    targs, twin_keep = _twin_args(twins if twins else None, out, Cout, "gather_conv_cl")
-    fargs = fargs + (int(bool(upsample2x)), *targs)
+    oargs, o_keep = _out_affine_args(out_affine, Cout, "gather_conv_cl")  # (the consumer's affine + activation in the epilogue)
+    fargs = fargs + (*oargs, int(bool(upsample2x)), *targs)
     # with v3 weights beside `packed` the entry point routes: conv_mfma.hpp or the v3 kernel, decided in C from N
     t3r = _tile3_packed(packed) if (TILE3 is None and compute in (0, 1)) else None
     t3args = (packed.data_ptr(), 0) if b10 else _tile3_args(packed, t3r)
@@ -1945,26 +1937,22 @@ def scatter_gather_conv_cl(x, y, block: Tuple[int, int], activeIndices, scatterM
     geo, usable = _geometry_of(block, kernel, stride, packed)
     if not usable:
         return None
+    if geo is not None and (geo != "b10" or scale is not None or shift is not None or activationName != "identity"):
+        return None
+    x, y = _req_cl(x, "x"), _req_cl_cache(y, "y")
+    idx = _req(activeIndices, torch.int32, "activeIndices", 2)
+    smap = _req(scatterMap, torch.int32, "scatterMap", 3)
+    B, C, H, W = y.shape
     if geo is not None:
-        if geo != "b10" or scale is not None or shift is not None or activationName != "identity":
-            return None
-        x, y = _req_cl(x, "x"), _req_cl_cache(y, "y")
-        idx = _req(activeIndices, torch.int32, "activeIndices", 2)
-        smap = _req(scatterMap, torch.int32, "scatterMap", 3)
-        B, C, H, W = y.shape
         if y.dtype != torch.float32:
             return None
         if idx.shape[0] == 0:
             return tag_tiles(_empty_tiles_cl(B, idx, Cout, 8, 8, y.device), idx, B)
         out = tile_conv3_cl(2, x, y, B, C, 0, H, W, False, idx, smap, (x.shape[2], x.shape[3]), None, None, "identity", packed, bias, Cout,
-                            None, None, (None, None, 0, 0, 0, 0, 0), None, (None,) * 6, _empty_tiles_cl(B, idx, Cout, 8, 8, y.device), block=10)
+                            None, None, _NO_BLOCK_RESIDUAL, None, _NO_TWINS, _empty_tiles_cl(B, idx, Cout, 8, 8, y.device), block=10)
         return None if out is None else tag_tiles(out, idx, B)
     bias_keep = _vec(bias, "bias")
-    x, y = _req_cl(x, "x"), _req_cl_cache(y, "y")
-    idx = _req(activeIndices, torch.int32, "activeIndices", 2)
-    smap = _req(scatterMap, torch.int32, "scatterMap", 3)
     (sa, s_keep), (ta, t_keep) = _cvec(scale, "scale"), _cvec(shift, "shift")
-    B, C, H, W = y.shape
     N = idx.shape[0]
     Ro, So = (block[0] - kernel[0]) // stride[0] + 1, (block[1] - kernel[1]) // stride[1] + 1
     out = _empty_tiles_cl(B, idx, Cout, Ro, So, y.device)
@@ -2009,7 +1997,7 @@ def scatter_gather_conv_scatter_cl(x, y, block, activeIndices, scatterMap, scale
         t1 = _req(table1, torch.int32, "table1", 2)
         bargs = (x1.data_ptr(), t1.data_ptr(), t1.shape[0], t1.shape[1], x1.shape[0] // B, x1.shape[2], x1.shape[3])
     else:
-        bargs = (None, None, 0, 0, 0, 0, 0)
+        bargs = _NO_BLOCK_RESIDUAL
     targs, twin_keep = _twin_args(twins if twins else None, out, Cout, "scatter_gather_conv_scatter_cl")
     compute = _compute_id(packed)
     t3 = _tile3_route(packed, B * idx.shape[0], C, 0, Cout, kernel, (1, 1), block)
