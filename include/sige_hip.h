@@ -667,6 +667,25 @@ int sige_hip_spade_separable_nhwc_f32(const float *actv, int tiled, int T, int H
                                       const float *dw_weight, const float *dw_bias, const float *in_scale, const float *in_shift,
                                       const float *pw_weight, const float *pw_bias, int oc, float *out, void *stream);
 
+/* ... the InstanceNorm of a DENSE layer, recomputed per image (mobile_modules.py:116: the blocks below num_sparse_layers run the
+ * whole module on the edited label features): actv [H,W,Ch] is E images of h = H / E rows under sige_hip_set_edit_batch(E) (E = 1:
+ * one image, any H and W); out_scale / out_shift [E,2,Ch].  For image e, branch b, channel c over the image's h * W pixels, with
+ * d = dw_bias[b][c] + sum_tap dw_weight[b][c][tap] * actv[p + tap][c] and zero padding at THAT image's border (seam rows included):
+ *   out_scale = 1 / sqrt(var(d) + eps) (biased variance), out_shift = -mean(d) * out_scale.
+ * ONE launch, two passes inside it (the mean, then sum (d - mean)^2 with d recomputed in the tap order of the launch above), fixed
+ * summation order, no atomics and no workspace: the statistics of image e are bit-identical to a single-image call on that image and
+ * from run to run.  Ch as above, all pointers 16-byte aligned, h a power of two >= 4 when E > 1; anything else is
+ * SIGE_HIP_EUNSUPPORTED without a launch. */
+int sige_hip_spade_separable_stats_nhwc_f32(const float *actv, int H, int W, int Ch, const float *dw_weight, const float *dw_bias,
+                                            float eps, float *out_scale, float *out_shift, void *stream);
+
+/* ... and the dense form (tiled == 0) over those E images with ONE AFFINE PER IMAGE, in_scale / in_shift [E,2,Ch]: a pixel of row y
+ * belongs to image e = y / h, its taps are zero outside rows [e*h, (e+1)*h) and its affine is image e's; out [H,W,2*oc].  The same
+ * kernel and the same arithmetic in the same order: at E = 1 equal to sige_hip_spade_separable_nhwc_f32(tiled = 0) bit for bit. */
+int sige_hip_spade_separable_images_nhwc_f32(const float *actv, int H, int W, int Ch, const float *dw_weight, const float *dw_bias,
+                                             const float *in_scale, const float *in_shift, const float *pw_weight,
+                                             const float *pw_bias, int oc, float *out, void *stream);
+
 /* ---- channels-last helpers of the GauGAN SPADE generator's sparse forward (csrc/spade_ops.hip): what was left to torch kernels
  * in round 4, so that the whole forward goes through this library and a launch plan can record it.
  * resize_nearest: F.interpolate(mode="nearest") by an INTEGER factor up or down, x [B,H,W,C] -> out [B,Ho,Wo,C]

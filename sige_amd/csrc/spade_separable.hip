@@ -22,6 +22,17 @@
 // A column block lies inside one branch (the branch is blockIdx.z); a ragged last block and the channels between Ch and the next
 // multiple of 16 are masked by value: every load has a clamped, valid address and none sits behind a lane-dependent branch.
 // No atomics, no workspace: bit-identical from run to run.
+//
+// Stacked edits (sige_hip_set_edit_batch): the dense form over E images of h = 2^s rows each, [E h][W][Ch] (..._images_nhwc_f32).
+// Pixel (y, x) belongs to image e = y >> s: its taps are zero outside rows [e h, (e + 1) h) and its affine is row e of [E][2][Ch].
+// Only the tap mask and the affine's address change; E = 1 is s = 0 with affine stride 0 and is the plain dense form bit for bit.
+//
+// The affine of a DENSE layer is the InstanceNorm of d_b over ONE image, recomputed for every edit (mobile_modules.py:116):
+// spade_separable_stats_kernel, one workgroup per (16-channel group, branch, image), 4 channel quads x 64 pixel slots.  Two passes
+// inside the launch, d_b recomputed in the tap order of step 1: mean_b[c] first, then sum (d - mean)^2 -- E[d^2] - E[d]^2 loses
+// the variance to cancellation once |mean| / sigma reaches 100.  A slot adds its pixels p = slot, slot + 64, ... in that order, the 64
+// slots of a channel are added through LDS as 4 x 16 in slot order, then 4: the order depends on (h, W) alone, so image e of a
+// stacked call has the bits of a single-image call on it.
 #include "common.hpp"
 
 namespace sige {
@@ -37,6 +48,8 @@ struct SepArgs {
     long npb;          // pixel blocks of the launch
     int H, W, Ch, oc;  // (tiled: H = W = 6)
     int mb_shift;      // MB = 1 << mb_shift pixel blocks per workgroup; CB = 4 >> mb_shift column blocks
+    int img_shift;     // dense: log2 of the rows of ONE image when several are stacked along H; 0 = one image of H rows
+    int aff_stride;    // dense: floats from one image's sc / sh to the next one's (0 = one affine for every row)
     int pad;
 };
 static_assert(sizeof(SepArgs) >= 96, "kernarg_touch<96>");
@@ -81,6 +94,7 @@ __global__ __launch_bounds__(256) void spade_separable_kernel(SepArgs g) {
         const int p = pl & 15;
         float4 av[9];
         bool live;
+        size_t aoff = 0;  // this pixel's affine within sc / sh (dense form over stacked images)
         if (TILED) {
             live = blk < npb;
             const float *base = g.a + (size_t)(blk < npb ? blk : npb - 1) * 36 * Ch + (size_t)((p >> 2) * 6 + (p & 3)) * Ch + cc;
@@ -91,10 +105,13 @@ __global__ __launch_bounds__(256) void spade_separable_kernel(SepArgs g) {
             live = q < npix;
             const unsigned qc = (unsigned)(q < npix ? q : npix - 1);  // (H * W < 2^31: checked by the entry point)
             const int y = (int)(qc / (unsigned)W), x = (int)(qc - (unsigned)y * (unsigned)W);
+            // the rows of this pixel's image: [0, H), or [e h, (e + 1) h) of image e = y >> s when images are stacked
+            const int s = g.img_shift, e = s ? y >> s : 0, y0 = e << s, y1 = s ? y0 + (1 << s) : H;
+            aoff = (size_t)e * (size_t)g.aff_stride;
 #pragma unroll
             for (int tap = 0; tap < 9; ++tap) {
                 const int yy = y + tap / 3 - 1, xx = x + tap % 3 - 1;
-                const bool in = yy >= 0 && yy < H && xx >= 0 && xx < W;
+                const bool in = yy >= y0 && yy < y1 && xx >= 0 && xx < W;
                 const float *ptr = g.a + ((size_t)min(max(yy, 0), H - 1) * W + min(max(xx, 0), W - 1)) * Ch + cc;
                 av[tap] = sel4(in, *reinterpret_cast<const float4 *>(ptr));  // (clamped address, zero padding by value)
             }
@@ -110,8 +127,8 @@ __global__ __launch_bounds__(256) void spade_separable_kernel(SepArgs g) {
             }
         }
         const float4 b4 = *reinterpret_cast<const float4 *>(g.dw_b + (size_t)br * Ch + cc);
-        const float4 s4 = *reinterpret_cast<const float4 *>(g.sc + (size_t)br * Ch + cc);
-        const float4 t4 = *reinterpret_cast<const float4 *>(g.sh + (size_t)br * Ch + cc);
+        const float4 s4 = *reinterpret_cast<const float4 *>(g.sc + aoff + (size_t)br * Ch + cc);
+        const float4 t4 = *reinterpret_cast<const float4 *>(g.sh + aoff + (size_t)br * Ch + cc);
         float d[4] = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
         for (int tap = 0; tap < 9; ++tap) {
@@ -167,21 +184,140 @@ static int sep_launch(const SepArgs &a, dim3 grid, hipStream_t st) {
     return launch_status();
 }
 
+// ---- InstanceNorm statistics of the depthwise output, per (image, branch, channel) ---------------------------------------------
+struct SepStatsArgs {
+    const float *a, *dw_w, *dw_b;
+    float *out_sc, *out_sh;
+    int h, W, Ch;  // ONE image: h rows; image e starts at row e h (blockIdx.z = e)
+    float eps;
+};
+static_assert(sizeof(SepStatsArgs) >= 56, "kernarg_touch<56>");
+
+constexpr int kStatSlots = 64;                 // pixel slots of a workgroup
+constexpr int kStatPitch = 16 * 16 + 16;       // floats between the 16-slot parts in LDS: part k starts at bank 16 k
+
+// sum over the 64 slots of this thread's channel quad, the same bits in every thread of the quad: 4 parts of 16 slots in slot
+// order, then the 4 parts in order.  `L` [4 parts][16 slots][16 channels], `P` [4 parts][16 channels].
+__device__ __forceinline__ float4 stat_sum(float4 v, float *L, float *P, int tid) {
+    const int slot = tid >> 2, qd = tid & 3;
+    *reinterpret_cast<float4 *>(L + (slot >> 4) * kStatPitch + (slot & 15) * 16 + 4 * qd) = v;
+    __syncthreads();
+    if (tid < 64) {  // (wave 0, whole: a scalar branch)
+        const int c = tid & 15, part = tid >> 4;
+        const float *src = L + part * kStatPitch + c;
+        float acc = src[0];
+#pragma unroll
+        for (int k = 1; k < 16; ++k) acc += src[16 * k];
+        P[16 * part + c] = acc;
+    }
+    __syncthreads();
+    float4 r = *reinterpret_cast<const float4 *>(P + 4 * qd);
+#pragma unroll
+    for (int part = 1; part < 4; ++part) {
+        const float4 q = *reinterpret_cast<const float4 *>(P + 16 * part + 4 * qd);
+        r.x += q.x; r.y += q.y; r.z += q.z; r.w += q.w;
+    }
+    return r;
+}
+
+__global__ __launch_bounds__(256) void spade_separable_stats_kernel(SepStatsArgs g) {
+    kernarg_touch<56>();
+    __shared__ __attribute__((aligned(16))) float L[2][4 * kStatPitch];  // (one buffer per pass: no barrier between the passes)
+    __shared__ __attribute__((aligned(16))) float P[2][64];
+
+    const int tid = threadIdx.x, slot = tid >> 2, qd = tid & 3;
+    const int h = g.h, W = g.W, Ch = g.Ch, br = blockIdx.y, img = blockIdx.z;
+    const int c0 = 16 * (int)blockIdx.x + 4 * qd, cc = min(c0, Ch - 4);
+    const unsigned n = (unsigned)h * (unsigned)W;  // pixels of one image (< 2^30: checked by the entry point)
+    const float *a = g.a + (size_t)img * n * Ch + cc;
+
+    // the depthwise weights of the quad: dw_b[cc .. cc+3][0..8] are 36 contiguous floats
+    float wf[36];
+    {
+        const float *wp = g.dw_w + ((size_t)br * Ch + cc) * 9;
+#pragma unroll
+        for (int k = 0; k < 9; ++k) {
+            const float4 v = *reinterpret_cast<const float4 *>(wp + 4 * k);
+            wf[4 * k] = v.x; wf[4 * k + 1] = v.y; wf[4 * k + 2] = v.z; wf[4 * k + 3] = v.w;
+        }
+    }
+    const float4 b4 = *reinterpret_cast<const float4 *>(g.dw_b + (size_t)br * Ch + cc);
+
+    // d_b + bias of pixel p of the image for the quad, in the tap order of spade_separable_kernel's step 1
+    auto depthwise = [&](unsigned p, float (&d)[4]) {
+        const int y = (int)(p / (unsigned)W), x = (int)(p - (unsigned)y * (unsigned)W);
+        float4 av[9];
+#pragma unroll
+        for (int tap = 0; tap < 9; ++tap) {
+            const int yy = y + tap / 3 - 1, xx = x + tap % 3 - 1;
+            const bool in = yy >= 0 && yy < h && xx >= 0 && xx < W;  // (the image's own border: a seam row is padding)
+            const float *ptr = a + ((size_t)min(max(yy, 0), h - 1) * W + min(max(xx, 0), W - 1)) * Ch;
+            av[tap] = sel4(in, *reinterpret_cast<const float4 *>(ptr));  // (clamped address, zero padding by value)
+        }
+        d[0] = d[1] = d[2] = d[3] = 0.f;
+#pragma unroll
+        for (int tap = 0; tap < 9; ++tap) {
+            const float x4[4] = {av[tap].x, av[tap].y, av[tap].z, av[tap].w};
+#pragma unroll
+            for (int e = 0; e < 4; ++e) d[e] += wf[9 * e + tap] * x4[e];
+        }
+        d[0] += b4.x; d[1] += b4.y; d[2] += b4.z; d[3] += b4.w;
+    };
+
+    const float inv_n = 1.0f / (float)n;
+    // ---- pass 1: the mean ----
+    float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
+    for (unsigned p0 = 0; p0 < n; p0 += kStatSlots) {  // (workgroup-uniform trip count; the pixel is clamped, its value masked)
+        const unsigned p = p0 + slot;
+        float d[4];
+        depthwise(min(p, n - 1), d);
+        const bool live = p < n;
+        acc.x += live ? d[0] : 0.f; acc.y += live ? d[1] : 0.f; acc.z += live ? d[2] : 0.f; acc.w += live ? d[3] : 0.f;
+    }
+    float4 mean = stat_sum(acc, L[0], P[0], tid);
+    mean.x *= inv_n; mean.y *= inv_n; mean.z *= inv_n; mean.w *= inv_n;
+
+    // ---- pass 2: the sum of squared deviations, d recomputed ----
+    acc = make_float4(0.f, 0.f, 0.f, 0.f);
+    for (unsigned p0 = 0; p0 < n; p0 += kStatSlots) {
+        const unsigned p = p0 + slot;
+        float d[4];
+        depthwise(min(p, n - 1), d);
+        const bool live = p < n;
+        const float ex = d[0] - mean.x, ey = d[1] - mean.y, ez = d[2] - mean.z, ew = d[3] - mean.w;
+        acc.x += live ? ex * ex : 0.f; acc.y += live ? ey * ey : 0.f; acc.z += live ? ez * ez : 0.f; acc.w += live ? ew * ew : 0.f;
+    }
+    const float4 ss = stat_sum(acc, L[1], P[1], tid);
+
+    if (slot == 0 && c0 < Ch) {
+        float4 sc, sh;
+        sc.x = 1.0f / sqrtf(ss.x * inv_n + g.eps);
+        sc.y = 1.0f / sqrtf(ss.y * inv_n + g.eps);
+        sc.z = 1.0f / sqrtf(ss.z * inv_n + g.eps);
+        sc.w = 1.0f / sqrtf(ss.w * inv_n + g.eps);
+        sh.x = -mean.x * sc.x; sh.y = -mean.y * sc.y; sh.z = -mean.z * sc.z; sh.w = -mean.w * sc.w;
+        const size_t o = ((size_t)img * 2 + br) * Ch + c0;
+        store_out4(g.out_sc + o, sc);
+        store_out4(g.out_sh + o, sh);
+    }
+}
+
 }  // namespace sige
 
 using namespace sige;
 
-extern "C" int sige_hip_spade_separable_nhwc_f32(const float *actv, int tiled, int T, int H, int W, int Ch,
-                                                 const float *dw_weight, const float *dw_bias,
-                                                 const float *in_scale, const float *in_shift,
-                                                 const float *pw_weight, const float *pw_bias, int oc, float *out, void *stream) {
-    SIGE_PLAN_HOOK_FIXED(sige_hip_spade_separable_nhwc_f32, actv, tiled, T, H, W, Ch, dw_weight, dw_bias, in_scale, in_shift, pw_weight, pw_bias,
-                   oc, out, stream);
+// the two separable entry points behind one set of checks; `images`: the dense form over the images of the current edit batch,
+// in_scale / in_shift [E][2][Ch]
+static int sep_entry(const float *actv, int tiled, int T, int H, int W, int Ch, const float *dw_weight, const float *dw_bias,
+                     const float *in_scale, const float *in_shift, const float *pw_weight, const float *pw_bias, int oc, float *out,
+                     void *stream, bool images) {
     if (T < 0 || H <= 0 || W <= 0 || Ch <= 0 || oc <= 0) return SIGE_HIP_EINVAL;
     if (!dw_weight || !dw_bias || !in_scale || !in_shift || !pw_weight || !pw_bias) return SIGE_HIP_EINVAL;
     if (Ch % 4 || Ch < kSepMinCh || Ch > kSepMaxCh || oc % 4 || oc < kSepMinOc || oc > kSepMaxOc) return SIGE_HIP_EUNSUPPORTED;
     if (tiled ? (H != 6 || W != 6) : T != 1) return SIGE_HIP_EUNSUPPORTED;
-    if (!tiled && stacked_shift(H) != 0) return SIGE_HIP_EUNSUPPORTED;  // (the dense form pads at the image border only)
+    const int img_shift = tiled ? 0 : stacked_shift(H);
+    // (the plain dense form pads at the border of the whole tensor only; the per-image form needs stacked_shift's power-of-two height)
+    if (images ? img_shift < 0 : img_shift != 0) return SIGE_HIP_EUNSUPPORTED;
     auto al = [](const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; };
     if (!al(actv) || !al(dw_weight) || !al(dw_bias) || !al(in_scale) || !al(in_shift) || !al(pw_weight) || !al(pw_bias) || !al(out))
         return SIGE_HIP_EUNSUPPORTED;
@@ -198,7 +334,47 @@ extern "C" int sige_hip_spade_separable_nhwc_f32(const float *actv, int tiled, i
     SepArgs a = {};
     a.a = actv; a.dw_w = dw_weight; a.dw_b = dw_bias; a.sc = in_scale; a.sh = in_shift; a.pw_w = pw_weight; a.pw_b = pw_bias;
     a.out = out; a.npb = npb; a.H = H; a.W = W; a.Ch = Ch; a.oc = oc; a.mb_shift = mb_shift;
+    a.img_shift = img_shift; a.aff_stride = img_shift ? 2 * Ch : 0;  // (one image: shift 0, one affine)
     const dim3 grid((unsigned)gx, (unsigned)gy, 2);
     hipStream_t st = as_stream(stream);
     return tiled ? sep_launch<true>(a, grid, st) : sep_launch<false>(a, grid, st);
+}
+
+extern "C" int sige_hip_spade_separable_nhwc_f32(const float *actv, int tiled, int T, int H, int W, int Ch,
+                                                 const float *dw_weight, const float *dw_bias,
+                                                 const float *in_scale, const float *in_shift,
+                                                 const float *pw_weight, const float *pw_bias, int oc, float *out, void *stream) {
+    SIGE_PLAN_HOOK_FIXED(sige_hip_spade_separable_nhwc_f32, actv, tiled, T, H, W, Ch, dw_weight, dw_bias, in_scale, in_shift, pw_weight, pw_bias,
+                   oc, out, stream);
+    return sep_entry(actv, tiled, T, H, W, Ch, dw_weight, dw_bias, in_scale, in_shift, pw_weight, pw_bias, oc, out, stream, false);
+}
+
+extern "C" int sige_hip_spade_separable_images_nhwc_f32(const float *actv, int H, int W, int Ch,
+                                                        const float *dw_weight, const float *dw_bias,
+                                                        const float *in_scale, const float *in_shift,
+                                                        const float *pw_weight, const float *pw_bias, int oc, float *out, void *stream) {
+    SIGE_PLAN_HOOK(sige_hip_spade_separable_images_nhwc_f32, actv, H, W, Ch, dw_weight, dw_bias, in_scale, in_shift, pw_weight, pw_bias, oc, out,
+                   stream);
+    return sep_entry(actv, 0, 1, H, W, Ch, dw_weight, dw_bias, in_scale, in_shift, pw_weight, pw_bias, oc, out, stream, true);
+}
+
+extern "C" int sige_hip_spade_separable_stats_nhwc_f32(const float *actv, int H, int W, int Ch, const float *dw_weight,
+                                                       const float *dw_bias, float eps, float *out_scale, float *out_shift,
+                                                       void *stream) {
+    SIGE_PLAN_HOOK(sige_hip_spade_separable_stats_nhwc_f32, actv, H, W, Ch, dw_weight, dw_bias, eps, out_scale, out_shift, stream);
+    if (H <= 0 || W <= 0 || Ch <= 0 || !(eps >= 0.f)) return SIGE_HIP_EINVAL;
+    if (!dw_weight || !dw_bias) return SIGE_HIP_EINVAL;
+    if (Ch % 4 || Ch < kSepMinCh || Ch > kSepMaxCh) return SIGE_HIP_EUNSUPPORTED;
+    const int s = stacked_shift(H);
+    if (s < 0) return SIGE_HIP_EUNSUPPORTED;
+    auto al = [](const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; };
+    if (!al(actv) || !al(dw_weight) || !al(dw_bias) || !al(out_scale) || !al(out_shift)) return SIGE_HIP_EUNSUPPORTED;
+    if (!actv || !out_scale || !out_shift) return SIGE_HIP_EINVAL;  // (the tensors last, as in the launch above)
+    const int h = s ? 1 << s : H, E = s ? H >> s : 1;
+    if ((long)h * W > 0x7fffffffL / 2 || E > 65535) return SIGE_HIP_EUNSUPPORTED;
+    SepStatsArgs a = {};
+    a.a = actv; a.dw_w = dw_weight; a.dw_b = dw_bias; a.out_sc = out_scale; a.out_sh = out_shift;
+    a.h = h; a.W = W; a.Ch = Ch; a.eps = eps;
+    spade_separable_stats_kernel<<<dim3((unsigned)ceil_div(Ch, 16), 2, (unsigned)E), 256, 0, as_stream(stream)>>>(a);
+    return launch_status();
 }

@@ -173,6 +173,8 @@ _SIGNATURES = {
     "sige_hip_conv3x3_latent_head_nhwc_f32": (
         _c_int, [_c_vp] + [_c_int] * 4 + [_c_vp, _c_int, _c_int] * 2 + [_c_int, _c_vp, _c_vp, _c_int, _c_vp, _c_vp, ctypes.c_float, _c_vp, _c_vp]),
     "sige_hip_spade_separable_nhwc_f32": (_c_int, [_c_vp] + [_c_int] * 5 + [_c_vp] * 6 + [_c_int, _c_vp, _c_vp]),
+    "sige_hip_spade_separable_stats_nhwc_f32": (_c_int, [_c_vp] + [_c_int] * 3 + [_c_vp, _c_vp, ctypes.c_float, _c_vp, _c_vp, _c_vp]),
+    "sige_hip_spade_separable_images_nhwc_f32": (_c_int, [_c_vp] + [_c_int] * 3 + [_c_vp] * 6 + [_c_int, _c_vp, _c_vp]),
     "sige_hip_resize_nearest_nhwc_f32": (_c_int, [_c_vp] + [_c_int] * 6 + [_c_vp, _c_vp]),
     "sige_hip_act_split_nhwc_f32": (_c_int, [_c_vp, ctypes.c_int64, _c_int, _c_int, ctypes.c_int64, _c_int, ctypes.c_float, _c_vp, _c_vp]),
     "sige_hip_scatter_gather_split_nhwc_f32": (
@@ -2283,15 +2285,20 @@ def spade_separable_cl(actv, dw_w, dw_b, in_scale, in_shift, pw_w, pw_b, out=Non
     dw_w [2,Ch,3,3], dw_b / in_scale / in_shift [2,Ch], pw_w [2,oc,Ch] (or [2,oc,Ch,1,1]), pw_b [2,oc], contiguous fp32 -- the
     caller builds them once per weight version.  `actv` channels-last fp32: tile slabs [T,Ch,6,6] that carry their halo ->
     [T,2*oc,4,4], or a full tensor [1,Ch,H,W] -> [1,2*oc,H,W] (zero padding at the border).  `tiled` None: tile slabs are 6x6
-    tensors that carry a tile tag (tag_tiles).  None if unsupported (nothing is launched)."""
+    tensors that carry a tile tag (tag_tiles).  A full tensor also takes one affine per image of the edit batch, in_scale / in_shift
+    [E,2,Ch] with E = get_edit_batch() (spade_separable_stats_cl's results): [1,Ch,E*h,W], taps zero beyond a pixel's own image
+    (sige_hip_spade_separable_images_nhwc_f32).  None if unsupported (nothing is launched)."""
     key = getattr(actv, "_sige_count_key", None)
     actv = _req_cl(actv, "actv")
     N, Ch, H, W = actv.shape
     if tiled is None:
         tiled = (H, W) == (6, 6) and key is not None
+    images = in_scale.dim() == 3  # one affine per image of the edit batch
+    if images and (tiled or in_scale.shape[0] != get_edit_batch()):
+        raise ValueError("spade_separable_cl: [E, 2, Ch] affines go with a full tensor and E = the edit batch (%d)" % get_edit_batch())
+    aff = (in_scale.shape[0], 2, Ch) if images else (2, Ch)
     ops = []
-    for t, shape, name in ((dw_w, (2, Ch, 3, 3), "dw_w"), (dw_b, (2, Ch), "dw_b"), (in_scale, (2, Ch), "in_scale"),
-                           (in_shift, (2, Ch), "in_shift")):
+    for t, shape, name in ((dw_w, (2, Ch, 3, 3), "dw_w"), (dw_b, (2, Ch), "dw_b"), (in_scale, aff, "in_scale"), (in_shift, aff, "in_shift")):
         if tuple(t.shape) != shape:
             raise ValueError("spade_separable_cl: `%s` must be %s" % (name, list(shape)))
         ops.append(_req(t.detach(), torch.float32, name, None))
@@ -2317,14 +2324,40 @@ def spade_separable_cl(actv, dw_w, dw_b, in_scale, in_shift, pw_w, pw_b, out=Non
             out = _empty_cl(shape, actv.device)
     elif tuple(out.shape) != shape or out.dtype != torch.float32 or not out.is_cuda or not out.is_contiguous(memory_format=CL):
         raise ValueError("spade_separable_cl: `out` must be a channels-last fp32 %s GPU tensor" % list(shape))
-    status = lib().sige_hip_spade_separable_nhwc_f32(base_ptr(actv), int(bool(tiled)), N if tiled else 1, H, W, Ch,
-                                                     *(t.data_ptr() for t in ops), oc, base_ptr(out), _stream(actv))
+    if images:
+        status = lib().sige_hip_spade_separable_images_nhwc_f32(base_ptr(actv), H, W, Ch, *(t.data_ptr() for t in ops), oc, base_ptr(out),
+                                                                _stream(actv))
+    else:
+        status = lib().sige_hip_spade_separable_nhwc_f32(base_ptr(actv), int(bool(tiled)), N if tiled else 1, H, W, Ch,
+                                                         *(t.data_ptr() for t in ops), oc, base_ptr(out), _stream(actv))
     if status == UNSUPPORTED:
         return None
     _check(status, "spade_separable_cl")
     if tiled and key is not None and key[0].shape[0] * key[1] == N:
         tag_tiles(out, key[0], key[1])
     return out
+
+
+def spade_separable_stats_cl(actv, dw_w, dw_b, eps: float):
+    """(scale, shift), each [E,2,Ch], of the InstanceNorm of a dense sub-mobile SPADE layer's two depthwise convs (include/sige_hip.h:
+    sige_hip_spade_separable_stats_nhwc_f32) in one launch: `actv` a full channels-last tensor [1,Ch,E*h,W] holding the E =
+    get_edit_batch() images one below the other, dw_w [2,Ch,3,3], dw_b [2,Ch] as for spade_separable_cl.  Per image, branch and channel
+    scale = 1 / sqrt(var + eps) (biased, two-pass) and shift = -mean * scale of the depthwise output, zero padding at the image's own
+    border.  None if unsupported (nothing is launched)."""
+    actv = _req_cl(actv, "actv")
+    N, Ch, H, W = actv.shape
+    if tuple(dw_w.shape) != (2, Ch, 3, 3) or tuple(dw_b.shape) != (2, Ch):
+        raise ValueError("spade_separable_stats_cl: `dw_w` must be [2, Ch, 3, 3] and `dw_b` [2, Ch]")
+    if N != 1:
+        return None
+    w, b = _req(dw_w.detach(), torch.float32, "dw_w", None), _req(dw_b.detach(), torch.float32, "dw_b", None)
+    out = torch.empty((2, get_edit_batch(), 2, Ch), dtype=torch.float32, device=actv.device)
+    status = lib().sige_hip_spade_separable_stats_nhwc_f32(base_ptr(actv), H, W, Ch, w.data_ptr(), b.data_ptr(), float(eps),
+                                                           out[0].data_ptr(), out[1].data_ptr(), _stream(actv))
+    if status == UNSUPPORTED:
+        return None
+    _check(status, "spade_separable_stats_cl")
+    return out[0], out[1]
 
 
 def conv3x3_small_cout_act_cl(x, weight, bias, activationName: str = "identity", slope: float = 0.0, outActivationName: str = "identity"):

@@ -17,7 +17,8 @@ gaugan_spade.py's code: gamma | beta are concatenated and go through ONE Scatter
 
 Sparse mode computes gamma | beta of a layer in one of two forms with the same arithmetic:
   * SEPARABLE_NATIVE: ONE launch of hip.spade_separable_cl (csrc/spade_separable.hip) on channels-last GPU tensors -- tile slabs for
-    the tiled layers, the full tensor (behind a torch prologue for the InstanceNorm statistics) for the dense ones;
+    the tiled layers, the full tensor for the dense ones, behind its InstanceNorm statistics: a torch prologue, or ONE more launch
+    (hip.spade_separable_stats_cl; SEPARABLE_STATS_NATIVE, and always in a stacked forward, where every edit has its own affine);
   * the reference's chain: depthwise SIGEConv2d(groups=Ch), affine, 1x1 SIGEConv2d, per branch, then torch.cat.  Whatever the
     kernel refuses takes the chain.
 """
@@ -35,6 +36,10 @@ from .gaugan_spade import SPADEConfig, SpadeGenerator, SpadeNorm, SpadeResBlock,
 # One hip.spade_separable_cl launch per SPADE layer in sparse mode.  False: the reference's module chain.  The default follows the
 # measurement in DESIGN.md 5.18 (tools/sub_mobile_bench.py).
 SEPARABLE_NATIVE = True
+# The InstanceNorm statistics of a dense SPADE layer from ONE hip.spade_separable_stats_cl launch in a single-edit forward too (a
+# stacked forward always takes it).  False: the torch prologue -- a grouped conv, var_mean and four elementwise kernels per layer.
+# The default follows the A/B in DESIGN.md 5.23 (tools/sub_mobile_bench.py --stacked): on, 0.24 - 0.26 ms of a 0.79 - 1.09 ms forward.
+SEPARABLE_STATS_NATIVE = True
 
 
 @dataclass
@@ -133,13 +138,25 @@ class SubMobileSpadeNorm(SpadeNorm):
                 return None
             sc, sh = self._sep_affine
         else:
-            # the reference recomputes a dense layer's InstanceNorm on the edited label features: its statistics from ONE grouped conv
-            # (output channel 2 c + b = branch b of channel c), then the launch applies them as the affine
-            _refuse_in_stacked_mode(actv, "the InstanceNorm statistics of a dense separable conv")
-            Ch = self.nhidden
-            d = F.conv2d(actv, dw_w.transpose(0, 1).reshape(2 * Ch, 1, 3, 3), dw_b.t().reshape(-1), padding=1, groups=Ch)
-            sc, sh = _instance_norm_affine(d, self.mlp_gamma.conv[1].eps)
-            sc, sh = sc.view(Ch, 2).t().contiguous(), sh.view(Ch, 2).t().contiguous()
+            # the reference recomputes a dense layer's InstanceNorm on the edited label features, so in a stacked forward every edit
+            # has its own: one statistics launch ([E,2,Ch], hip.spade_separable_stats_cl), then the launch applies them per image
+            stacked = hip.get_edit_batch() > 1
+            stats = None
+            if stacked or SEPARABLE_STATS_NATIVE:
+                stats = hip.spade_separable_stats_cl(actv, dw_w, dw_b, self.mlp_gamma.conv[1].eps)
+            if stats is not None:
+                sc, sh = stats
+            else:
+                # ... or its statistics from ONE grouped conv (output channel 2 c + b = branch b of channel c) and torch kernels
+                _refuse_in_stacked_mode(actv, "the InstanceNorm statistics of a dense separable conv")
+                Ch = self.nhidden
+                d = F.conv2d(actv, dw_w.transpose(0, 1).reshape(2 * Ch, 1, 3, 3), dw_b.t().reshape(-1), padding=1, groups=Ch)
+                sc, sh = _instance_norm_affine(d, self.mlp_gamma.conv[1].eps)
+                sc, sh = sc.view(Ch, 2).t().contiguous(), sh.view(Ch, 2).t().contiguous()
+            out = hip.spade_separable_cl(actv, dw_w, dw_b, sc, sh, pw_w, pw_b, tiled=False)
+            if out is None:
+                _refuse_in_stacked_mode(actv, "a dense separable conv")  # (the module chain is torch: no seam-aware form)
+            return out
         return hip.spade_separable_cl(actv, dw_w, dw_b, sc, sh, pw_w, pw_b, tiled=self.tiled)
 
     def mlp_gamma_beta(self, actv: torch.Tensor) -> torch.Tensor:
@@ -195,7 +212,12 @@ class SubMobileSpadeGenerator(SpadeGenerator):
 
     def _forward(self, seg: torch.Tensor) -> torch.Tensor:
         if self.edit_batch > 1:
-            raise RuntimeError("SubMobileSpadeGenerator: stacked edits are not supported (the separable convs have no seam-aware form)")
+            # stacked edits (sige_amd/stacked.py) are SpadeGenerator's path: E label maps, one per edit, on the tall tensor; the dense
+            # SPADE layers take one InstanceNorm affine per edit (SubMobileSpadeNorm._native).  The library finds the seams by a shift
+            if self.sh < 4 or self.sh & (self.sh - 1):
+                raise RuntimeError("SubMobileSpadeGenerator: stacked edits need a power-of-two height of at least 4 rows at the smallest "
+                                   "level (this configuration has %d x %d)" % (self.sh, self.sw))
+            return super()._forward(seg)
         _refuse_in_stacked_mode(seg, "the sub-mobile generator")
         if seg.shape[0] != 1:
             raise RuntimeError("SubMobileSpadeGenerator: batch 1 only -- the InstanceNorm of the separable convs is cached as ONE "

@@ -18,6 +18,19 @@ and -- once, in a child of its own -- one hip.spade_separable_cl launch ALONE at
 `default_on`: at 5 % the native forward's median is not above the chain's by more than the chain's own min-max spread over the
 batches -- the rule SEPARABLE_NATIVE's default follows.
 
+    python tools/sub_mobile_bench.py --stacked  -> profiles/gaugan_sub_mobile_stacked_bench.json
+
+--stacked: stacked edits (sige_amd/stacked.py) and the statistics switch, per ratio in ONE child process with the same protocol.  Two
+models with the same weights: one stays on single edits, the other is stacked for E = 2, 4, 8 in turn, so that every graph's caches and
+index lists stay alive while it is replayed.
+  * E = 1, the switch A/B: the native forward with gaugan_sub_mobile.SEPARABLE_STATS_NATIVE off (the torch prologue) and on (one
+    hip.spade_separable_stats_cl launch per dense SPADE layer), alternating batch by batch.  `stats_native_default_on`: at ALL ratios
+    the switch-on median is below the switch-off median by more than the larger of the two min-max spreads of that run.
+  * E = 2, 4, 8: ONE stacked forward of E relabellings of the same rectangle (each edit its own label map, mask and InstanceNorm
+    statistics), alternating with the single-edit forward (the switch at the module's default: `single_edit_form`); ms per edit =
+    forward / E, `speedup` = single-edit median over ms per edit (`speedup_vs_stats_torch`: over the switch-off median of the A/B),
+    and max |stacked - single| per edit after both graphs replayed on the same label maps.
+
 The parent process never touches the GPU: it starts one child per measurement under `timeout -k 10` and stops at the first that
 fails."""
 import argparse
@@ -178,6 +191,139 @@ def child(a):
     print(TAG + json.dumps(row), flush=True)
 
 
+def child_stacked(a):
+    import torch
+
+    from benchlib.common import capture_fn
+    from sige_amd import hip, stacked
+    from sige_amd.utils import compute_difference_mask, dilate_mask, downsample_mask
+    from sige_amd.workloads import gaugan_sub_mobile as gsm
+    from tests.golden.model_init import gaugan_labels
+
+    hip.lib()
+    torch.backends.cudnn.benchmark = True
+    dev = torch.device("cuda")
+
+    def make_model():
+        torch.manual_seed(0)
+        m = gsm.SubMobileSpadeGenerator(gsm.SubMobileSPADEConfig()).eval().to(dev).to(memory_format=torch.channels_last)
+        m.set_scatter_inplace(True)
+        return m
+
+    x0 = gaugan_labels(H, W)[0]
+    lab0 = x0[0].argmax(0).numpy()
+    onehot = lambda l: torch.nn.functional.one_hot(torch.from_numpy(l), NC).permute(2, 0, 1)[None].float()  # noqa: E731
+    cl = lambda t: t.to(dev).contiguous(memory_format=torch.channels_last)  # noqa: E731
+    edits = [cl(onehot(relabelled(lab0, a.ratio, s))) for s in (5, 11, 17, 23, 29, 31, 7, 13)]
+    x0 = cl(x0)
+    row = {"ratio": a.ratio}
+    stat = lambda v: (round(statistics.median(v), 4), [round(min(v), 4), round(max(v), 4)])  # noqa: E731
+    with torch.no_grad():
+        single, tall_model = make_model(), make_model()
+        pyramid = None
+        for m in (single, tall_model):
+            m.set_mode("full")
+            m(x0)
+            diff = compute_difference_mask(x0, edits[0])
+            pyramid = downsample_mask(dilate_mask(diff, 1), (m.sh, m.sw), dilation=2)
+            m.set_masks(pyramid)
+            m.set_mode("sparse")
+        row["edit_ratio"] = float(diff.float().mean())
+        row["up_3_tiles"] = int(single.up_3.main_gather.active_indices.shape[0])
+        # ---- E = 1: the statistics switch off / on, alternating ----
+        x1 = edits[0].clone()
+        graphs, outs = {}, {}
+        keep = gsm.SEPARABLE_STATS_NATIVE
+        try:
+            for name, on in (("stats_torch", False), ("stats_native", True)):
+                gsm.SEPARABLE_STATS_NATIVE = on
+                single(x1)
+                n0 = hip.launch_count()
+                single(x1)
+                row[name + "_library_launches"] = hip.launch_count() - n0
+                graphs[name], outs[name] = capture_fn(lambda: single(x1))
+        finally:
+            gsm.SEPARABLE_STATS_NATIVE = keep
+        ms = {k: [] for k in graphs}
+        for batch in range(a.batches):
+            x1.copy_(edits[batch % len(edits)])
+            for name in (list(graphs) if batch % 2 == 0 else list(graphs)[::-1]):
+                ms[name].append(events_ms(graphs[name], a.steps, 5))
+        for name, v in ms.items():
+            row[name + "_ms"], row[name + "_ms_min_max"] = stat(v)
+        row["stats_native_minus_torch_max_abs"] = float((outs["stats_native"] - outs["stats_torch"]).abs().max())
+        spread = max(row[n + "_ms_min_max"][1] - row[n + "_ms_min_max"][0] for n in ms)
+        row["switch_spread_ms"] = round(spread, 4)
+        row["stats_native_faster_beyond_spread"] = bool(row["stats_native_ms"] < row["stats_torch_ms"] - spread)
+        base = "stats_native" if gsm.SEPARABLE_STATS_NATIVE else "stats_torch"  # (the single-edit forward as the module ships it)
+        row["single_edit_form"] = base
+        g1, out1 = graphs[base], outs[base]
+        del graphs
+        # ---- E = 2, 4, 8: one stacked forward against the single-edit forward, alternating ----
+        row["E"] = {}
+        for E in (2, 4, 8):
+            xs = torch.cat(edits[:E], 0).contiguous(memory_format=torch.channels_last)
+            stacked.stack_caches(tall_model, E)
+            try:
+                stacked.set_masks(tall_model, [pyramid] * E)
+                with stacked.edit_batch(tall_model, E):
+                    tall_model(xs)
+                    n0 = hip.launch_count()
+                    tall_model(xs)
+                    launches = hip.launch_count() - n0
+                    gE, outE = capture_fn(lambda: tall_model(xs))
+                tE, t1 = [], []
+                for batch in range(a.batches):
+                    for e in range(E):
+                        xs[e].copy_(edits[(batch + e) % len(edits)][0])
+                    x1.copy_(edits[batch % len(edits)])
+                    for name in (("E", "1") if batch % 2 == 0 else ("1", "E")):
+                        (tE if name == "E" else t1).append(events_ms(gE if name == "E" else g1, a.steps, 5))
+                worst = 0.0
+                for e in range(E):
+                    xs[e].copy_(edits[e][0])
+                gE.replay()
+                for e in range(E):
+                    x1.copy_(edits[e])
+                    g1.replay()
+                    worst = max(worst, float((outE[e] - out1[0]).abs().max()))
+                del gE
+            finally:
+                stacked.unstack_caches(tall_model)
+            mE, mmE = stat(tE)
+            m1, mm1 = stat(t1)
+            row["E"][str(E)] = {"forward_ms": mE, "forward_ms_min_max": mmE, "ms_per_edit": round(mE / E, 4), "single_edit_ms": m1,
+                                "single_edit_ms_min_max": mm1, "speedup": round(m1 * E / mE, 3),
+                                "speedup_vs_stats_torch": round(row["stats_torch_ms"] * E / mE, 3), "library_launches": launches,
+                                "max_abs_stacked_minus_single": worst}
+    print(TAG + json.dumps(row), flush=True)
+
+
+def main_stacked(a, build):
+    res = {"workload": "GAN-Compression GauGAN generator (sub-mobile SPADE, 32_32_32_48_32_24_24_32, num_sparse_layers 4), label map "
+                       "[1,36,256,512], exact fp32, channels-last, hipGraph replay, default-initialised weights (seed 0); stacked edits: E "
+                       "relabellings of one rectangle, one label map, mask and InstanceNorm affine per edit",
+           "source_hash": build.source_hash(), "steps": a.steps, "batches": a.batches, "rows": []}
+    for r in a.ratios.split(","):
+        cmd = ["timeout", "-k", "10", str(a.limit), sys.executable, os.path.abspath(__file__), "--stacked", "--ratio", r,
+               "--steps", str(a.steps), "--batches", str(a.batches)]
+        p = subprocess.run(cmd, cwd=REPO, capture_output=True, text=True)
+        line = next((l for l in p.stdout.splitlines() if l.startswith(TAG)), None)
+        if p.returncode != 0 or line is None:
+            # (a fault, an abort or a time limit: nothing more is started on the GPU)
+            res["failed"] = {"job": r, "returncode": p.returncode, "stderr_tail": p.stderr[-2000:]}
+            break
+        res["rows"].append(json.loads(line[len(TAG):]))
+        print("sub_mobile_bench --stacked: %s done" % r, file=sys.stderr, flush=True)
+    if "failed" not in res and res["rows"]:
+        res["stats_native_default_on"] = all(r["stats_native_faster_beyond_spread"] for r in res["rows"])
+    with open(a.out, "w") as f:
+        json.dump(res, f, indent=1)
+        f.write("\n")
+    print(json.dumps(res))
+    return 1 if "failed" in res else 0
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--ratios", default="0.012,0.05,0.15")
@@ -188,14 +334,19 @@ def main():
     ap.add_argument("--batches", type=int, default=10)
     ap.add_argument("--reps", type=int, default=8)
     ap.add_argument("--limit", type=int, default=150, help="seconds per child")
-    ap.add_argument("--out", default=os.path.join(REPO, "profiles", "gaugan_sub_mobile_bench.json"))
+    ap.add_argument("--stacked", action="store_true", help="stacked edits E = 1, 2, 4, 8 and the statistics switch A/B")
+    ap.add_argument("--out", default=None)
     a = ap.parse_args()
+    if a.out is None:
+        a.out = os.path.join(REPO, "profiles", "gaugan_sub_mobile_stacked_bench.json" if a.stacked else "gaugan_sub_mobile_bench.json")
     if a.layer:
         return layer_alone(a)
     if a.ratio is not None:
-        return child(a)
+        return child_stacked(a) if a.stacked else child(a)
     from sige_amd import build
 
+    if a.stacked:
+        return main_stacked(a, build)
     res = {"workload": "GAN-Compression GauGAN generator (sub-mobile SPADE, 32_32_32_48_32_24_24_32, num_sparse_layers 4), label map "
                        "[1,36,256,512], exact fp32, channels-last, hipGraph replay, default-initialised weights (seed 0)",
            "source_hash": build.source_hash(), "steps": a.steps, "batches": a.batches, "rows": []}
