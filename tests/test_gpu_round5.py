@@ -415,7 +415,6 @@ def test_tile_conv3_gather_forms_vs_fp64(hip, c1, c2, cout, up):
     mask[10:40, 5:50] = True
     mask[0, 0] = mask[res - 1, res - 1] = True
     idx = reduce_mask(mask.to(DEV), 6, 4, 1)
-    assert idx.shape[0] % 2 == 0 or True
     x = _cl(torch.randn(B, c1, src, src, device=DEV))
     x2 = _cl(torch.randn(1, c2, src, src, device=DEV)) if c2 else None
     w = torch.randn(cout, C, 3, 3, device=DEV) / (3 * C ** 0.5)
@@ -445,9 +444,15 @@ def test_tile_conv3_gather_forms_vs_fp64(hip, c1, c2, cout, up):
                 hip.TILE3 = None
         return outs
 
+    # (this list has an odd tile count, and a per-batch affine needs whole tile pairs per image: at Bs = 2 the entry point refuses the
+    #  two affine cases and the old kernel would run -- they are counted as skipped here.  The per-batch affine, upsample2x behind an
+    #  affine, ragged images and the full destination against fp64 are pinned in tests/test_gpu_tile_conv3_block6.py.)
+    ran = skipped = 0
     for act, sc, sh in (("swish", scale, shift), ("identity", scale, shift), ("identity", None, None)):
         if Bs > 1 and sc is not None and idx.shape[0] % 2:
-            continue  # (a per-batch affine needs whole tile pairs per image: the entry point says unsupported and the old kernel runs)
+            skipped += 1
+            continue
+        ran += 1
         tiles = hip.gather_cl(full_in, 6, 6, idx, sc, sh, act)
         want = conv(tiles)
         new, old = run(sc=sc, sh=sh, act=act)
@@ -458,6 +463,7 @@ def test_tile_conv3_gather_forms_vs_fp64(hip, c1, c2, cout, up):
         new, old = run(sc=sc, sh=sh, act=act, oa=(os_, oh_, "swish"))
         torch.testing.assert_close(new, F.silu(want * os_.view(1, -1, 1, 1) + oh_.view(1, -1, 1, 1)), rtol=0, atol=2e-4)
         torch.testing.assert_close(new, old, rtol=0, atol=2e-4)
+    assert ran + skipped == 3 and ran >= 1 and (Bs > 1 or ran == 3), (Bs, ran, skipped)
     # into a full tensor: + residual, two activated twins
     residual = _cl(torch.randn(Bs, cout, res, res, device=DEV))
     ts0, tt0, ts1, tt1 = (torch.randn(cout, device=DEV) for _ in range(4))
