@@ -240,38 +240,65 @@ template <> void launch_conv_phase<P22_32, 1>(ConvArgs, hipStream_t);
 
 // ---- cross-workgroup K split: deterministic second pass ------------------------
 // out[i] = sum_s ws[s][i] + bias[channel(i)] + residual[i]   (channels-last: channel = i mod C)
+// (one float4 of the output: everything it needs is requested before the first value is used -- bias, residual and the out-affine
+//  entries do not depend on the partial sums; loaded after them, each was one more memory round trip)
+__device__ __forceinline__ void splitk_reduce_unit(const float *__restrict__ ws, int S, size_t stride, size_t at, int c,
+                                                   const float *__restrict__ bias, const float *__restrict__ residual,
+                                                   const float *__restrict__ oscale, const float *__restrict__ oshift, int oact,
+                                                   float *__restrict__ out) {
+    const float4 zero = make_float4(0.f, 0.f, 0.f, 0.f);
+    float4 b = zero, r = zero, os = zero, oh = zero;
+    if (bias) b = *reinterpret_cast<const float4 *>(bias + c);
+    if (residual) r = *reinterpret_cast<const float4 *>(residual + at);
+    if (oscale) {
+        os = *reinterpret_cast<const float4 *>(oscale + c);
+        oh = *reinterpret_cast<const float4 *>(oshift + c);
+    }
+    // all (<= 8) partials in flight at once, added in split order
+    float4 p[8];
+#pragma unroll
+    for (int s = 0; s < 8; ++s) p[s] = *reinterpret_cast<const float4 *>(ws + (size_t)(s < S ? s : S - 1) * stride + at);
+    float4 v = p[0];
+#pragma unroll
+    for (int s = 1; s < 8; ++s)
+        if (s < S) { v.x += p[s].x; v.y += p[s].y; v.z += p[s].z; v.w += p[s].w; }
+    if (bias) { v.x += b.x; v.y += b.y; v.z += b.z; v.w += b.w; }
+    if (residual) { v.x += r.x; v.y += r.y; v.z += r.z; v.w += r.w; }
+    if (oscale) {
+        v.x = os.x * v.x; v.y = os.y * v.y; v.z = os.z * v.z; v.w = os.w * v.w;
+        v.x = oh.x + v.x; v.y = oh.y + v.y; v.z = oh.z + v.z; v.w = oh.w + v.w;
+        if (oact == SIGE_HIP_ACT_SWISH) { v.x = swish(v.x); v.y = swish(v.y); v.z = swish(v.z); v.w = swish(v.w); }
+    }
+    *reinterpret_cast<float4 *>(out + at) = v;
+}
+
+// tiles destination: the output IS the tile slab, every element of a copy was written by the launch
 __global__ __launch_bounds__(256) void splitk_reduce_nhwc_kernel(const float *__restrict__ ws, int S, size_t stride, size_t n4, int C,
                                                                 const float *__restrict__ bias, const float *__restrict__ residual,
                                                                 const float *__restrict__ oscale, const float *__restrict__ oshift, int oact,
                                                                 float *__restrict__ out) {
-    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n4; i += (size_t)gridDim.x * 256) {
-        // everything this element needs is requested before the first value is used: bias, residual and the
-        // out-affine entries do not depend on the partial sums (loaded after them, each was one more memory round trip)
-        const float4 zero = make_float4(0.f, 0.f, 0.f, 0.f);
-        const int c = (int)((4 * i) % C);
-        float4 b = zero, r = zero, os = zero, oh = zero;
-        if (bias) b = *reinterpret_cast<const float4 *>(bias + c);
-        if (residual) r = *reinterpret_cast<const float4 *>(residual + 4 * i);
-        if (oscale) {
-            os = *reinterpret_cast<const float4 *>(oscale + c);
-            oh = *reinterpret_cast<const float4 *>(oshift + c);
-        }
-        // all (<= 8) partials in flight at once, added in split order
-        float4 p[8];
-#pragma unroll
-        for (int s = 0; s < 8; ++s) p[s] = *reinterpret_cast<const float4 *>(ws + (size_t)(s < S ? s : S - 1) * stride + 4 * i);
-        float4 v = p[0];
-#pragma unroll
-        for (int s = 1; s < 8; ++s)
-            if (s < S) { v.x += p[s].x; v.y += p[s].y; v.z += p[s].z; v.w += p[s].w; }
-        if (bias) { v.x += b.x; v.y += b.y; v.z += b.z; v.w += b.w; }
-        if (residual) { v.x += r.x; v.y += r.y; v.z += r.z; v.w += r.w; }
-        if (oscale) {
-            v.x = os.x * v.x; v.y = os.y * v.y; v.z = os.z * v.z; v.w = os.w * v.w;
-            v.x = oh.x + v.x; v.y = oh.y + v.y; v.z = oh.z + v.z; v.w = oh.w + v.w;
-            if (oact == SIGE_HIP_ACT_SWISH) { v.x = swish(v.x); v.y = swish(v.y); v.z = swish(v.z); v.w = swish(v.w); }
-        }
-        *reinterpret_cast<float4 *>(out + 4 * i) = v;
+    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n4; i += (size_t)gridDim.x * 256)
+        splitk_reduce_unit(ws, S, stride, 4 * i, (int)((4 * i) % C), bias, residual, oscale, oshift, oact, out);
+}
+
+// full-tensor destination: the launch wrote the pixels of ITS tiles into each copy and nothing else, so the second pass walks
+// the tile list like the kernel's own epilogue (conv_mfma.hpp: locate) -- a pixel no tile covers keeps what `out` held, whatever
+// the workspace holds there.  units = T * RO * RO * (C / 4); tile t = b * N + n, pixel pxo of its RO x RO outputs.
+__global__ __launch_bounds__(256) void splitk_reduce_full_nhwc_kernel(const float *__restrict__ ws, int S, size_t stride, size_t units, int C,
+                                                                     const int32_t *__restrict__ idx, int N, int RO, int offH, int offW,
+                                                                     int strH, int strW, int Ho, int Wo,
+                                                                     const float *__restrict__ bias, const float *__restrict__ residual,
+                                                                     const float *__restrict__ oscale, const float *__restrict__ oshift, int oact,
+                                                                     float *__restrict__ out) {
+    const int c4 = C / 4, px = RO * RO;
+    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < units; i += (size_t)gridDim.x * 256) {
+        const int c = 4 * (int)(i % c4);
+        const size_t m = i / c4;
+        const int pxo = (int)(m % px), t = (int)(m / px);
+        const int b = t / N, n = t - b * N;
+        const int h = (offH + idx[2 * n]) / strH + pxo / RO, w = (offW + idx[2 * n + 1]) / strW + pxo % RO;
+        if (h < 0 || h >= Ho || w < 0 || w >= Wo) continue;
+        splitk_reduce_unit(ws, S, stride, (((size_t)b * Ho + h) * Wo + w) * C + c, c, bias, residual, oscale, oshift, oact, out);
     }
 }
 
@@ -621,7 +648,13 @@ struct KindSteps {
             const int rc = flush_held();
             if (rc != SIGE_HIP_OK) return rc;
         }
-        if (kPairSecond && g_pairing && !g_held.active && mode == MODE_RAW && !tuning(SIGE_HIP_TUNE_CONV_TILE_MT)) {
+        // (only a conv that has a launch of its own is held: one no block shape can stage -- a fused cat off the 1x1 chunk size -- is
+        //  refused HERE, while its caller still listens; held, it would be refused when its partner launches, its output unwritten.
+        //  The plan asked for is the conv's OWN, 4 waves: a partner of 8 waves doubles the chunk and may still refuse the pair --
+        //  flush_held then launches the shortcut alone under exactly this plan, so what passes here is always written.  Costs
+        //  one more host-side plan_conv per held shortcut: integer arithmetic, no device call)
+        auto has_plan = [&] { ConvArgs q = a; ConvPlan pq; return plan_conv<KH, STR, R, SRC, LAY, PREC>(q, 1, 0, false, pq) == SIGE_HIP_OK; };
+        if (kPairSecond && g_pairing && !g_held.active && mode == MODE_RAW && !tuning(SIGE_HIP_TUNE_CONV_TILE_MT) && has_plan()) {
             g_held.active = true; g_held.a = a; g_held.mode = mode; g_held.dst = DST; g_held.st = st; g_held.prec = PREC;
             g_held.launch = &launch;
             note_launches(-1);  // (the caller counts one launch per call: this one happens later, or inside its partner's)
@@ -740,10 +773,16 @@ struct KindSteps {
         }
         if (!done) with_block(p, [&](auto g, auto nb) { launch_conv_geo<typename decltype(g)::type, decltype(nb)::value, SRC, DST, LAY, 4>(a, mode, st); });
         if (a.ksplit > 1 && !a.counters) {
-            const size_t n4 = a.split_stride / 4;
+            // (a full-tensor destination: over the tile list, not over whole copies -- the list need not cover the tensor)
+            const size_t n4 = DST == DST_TILES ? a.split_stride / 4 : (size_t)a.T * G16::PX * (a.Cout / 4);
             const int grid = (int)((n4 + 255) / 256 < 2048 ? (n4 + 255) / 256 : 2048);
-            splitk_reduce_nhwc_kernel<<<grid, 256, 0, st>>>(a.ws, a.ksplit, a.split_stride, n4, a.Cout, a.bias, a.residual,
-                                                           a.oscale, a.oshift, a.oact, final_out);
+            if constexpr (DST == DST_TILES)
+                splitk_reduce_nhwc_kernel<<<grid, 256, 0, st>>>(a.ws, a.ksplit, a.split_stride, n4, a.Cout, a.bias, a.residual,
+                                                               a.oscale, a.oshift, a.oact, final_out);
+            else
+                splitk_reduce_full_nhwc_kernel<<<grid, 256, 0, st>>>(a.ws, a.ksplit, a.split_stride, n4, a.Cout, a.idx, a.N, G16::RO,
+                                                                    a.offH, a.offW, a.strH, a.strW, a.Ho, a.Wo, a.bias, a.residual,
+                                                                    a.oscale, a.oshift, a.oact, final_out);
             note_launches(1);
         }
         return SIGE_HIP_OK;
@@ -1204,7 +1243,10 @@ static int gather_conv_nhwc_impl(const TileConvCall &c) {
         a.split_stride = c.to_full ? (size_t)c.B * c.Ho * c.Wo * c.Cout : (size_t)c.B * c.N * Ro * So * c.Cout;
         a.ws = c.ws;
         a.ksplit_max = (c.ws && a.split_stride && aligned16({c.ws})) ? (int)(c.ws_floats / a.split_stride < 8 ? c.ws_floats / a.split_stride : 8) : 1;
-        // (the second pass reads whole output copies: every pixel must be written by some tile)
+        // a full-tensor destination splits only as a DENSE level: tile pixels >= image pixels (hip.py: gather_conv_cl sizes the
+        // workspace by the same rule).  The count is a routing rule, not a coverage proof -- on an image whose sides are no
+        // multiples of the tile step a list with tiles missing passes it -- so neither finish relies on it: both walk the tile list
+        // (conv_mfma.hpp: locate; splitk_reduce_full_nhwc_kernel) and leave the pixels no tile covers alone
         if (c.to_full && (long)c.N * Ro * So < (long)c.Ho * c.Wo) a.ksplit_max = 1;
     }
     if ((c.twin[0].out || c.twin[1].out) && !c.to_full) return SIGE_HIP_EINVAL;  // twins share the addressing of a full-tensor destination

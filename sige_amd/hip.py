@@ -1869,7 +1869,10 @@ def gather_conv_cl(x, x2, block: Tuple[int, int], activeIndices, scale, shift, a
     ws, ws_n = None, 0
     ks = lib().sige_hip_conv_ksplit_hint(B * N, C1 + C2, Cout, kernel[0], kernel[1], stride[0], stride[1])
     if full is not None and N * ((block[0] - kernel[0]) // stride[0] + 1) * ((block[1] - kernel[1]) // stride[1] + 1) < Ho * Wo:
-        ks = 1  # tiles written into a larger tensor: the second pass would need whole output copies
+        # a full-tensor destination splits only as a DENSE level: tile pixels >= image pixels (block_conv.hip:
+        # gather_conv_nhwc_impl applies the same rule to the workspace it is handed).  A routing rule, not a coverage proof: both
+        # finishes of a split walk the tile list and leave the pixels no tile covers alone
+        ks = 1
     if b10:
         ks = 1  # (the v3 kernel splits K inside the workgroup)
     cap = _tile_capacity(idx)

@@ -10,7 +10,8 @@ ROW_TESTS = {
     "a2 mask pyramid": ["test_gpu_round2.py::test_device_mask_helpers_bit_exact"],
     "a3 gather": ["test_gpu_parity.py::test_golden_cases", "test_gpu_parity.py::test_against_oracle_mid_size",
                   "test_gpu_round2.py::test_grouped_nchw_gather_bit_exact"],
-    "a4 block conv": ["test_gpu_parity.py::test_block_conv_vs_torch_and_oracle", "test_gpu_parity.py::test_golden_cases"],
+    "a4 block conv": ["test_gpu_parity.py::test_block_conv_vs_torch_and_oracle", "test_gpu_parity.py::test_golden_cases",
+                      "test_gpu_tile_conv_default.py::test_k31_gather_forms_to_tiles_and_full"],
     "a5 scatter": ["test_gpu_parity.py::test_golden_cases", "test_gpu_parity.py::test_against_oracle_mid_size"],
     "a6 scatter with block residual": ["test_gpu_parity.py::test_golden_cases", "test_gpu_parity.py::test_resblock_gpu_vs_oracle_backend"],
     "a7 scatter_gather + map": ["test_gpu_parity.py::test_golden_cases", "test_gpu_round3.py::test_scatter_gather_row_form_bit_exact"],
