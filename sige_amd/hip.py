@@ -22,6 +22,8 @@ from typing import Optional, Tuple
 
 import torch
 
+from .nn.twins import LaunchSet
+
 _PKG = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("SIGE_HIP_LIB", os.path.join(_PKG, "lib", "libsige_hip.so"))
 
@@ -2531,15 +2533,15 @@ def attention_residual_cl(qkv: torch.Tensor, scale: float, bias: Optional[torch.
         residual = _req_cl(residual, "residual")
         if tuple(residual.shape) != tuple(out.shape):
             raise RuntimeError("attention_residual_cl: residual must be shaped like the output")
-    tw = [(key, _empty_cl((B, C, H, W), qkv.device), sc, sh) for key, (sc, sh) in list((twins or {}).items())[:2]]
-    targs, twin_keep = _twin_args([(b, sc, sh) for _, b, sc, sh in tw] or None, out, C, "attention_residual_cl")
+    tw = LaunchSet.fresh(twins, (B, C, H, W), qkv.device)
+    targs, twin_keep = _twin_args(tw.args(), out, C, "attention_residual_cl")
     ws = torch.empty(B * HW * HW, dtype=torch.float32, device=qkv.device)
     status = lib().sige_hip_attention_residual_nhwc_f32(qkv.data_ptr(), B, C, HW, float(scale), ws.data_ptr(), _p(bias_keep),
                                                         _p(residual), *targs, out.data_ptr(), _stream(qkv))
     if status == UNSUPPORTED:
         return None
     _check(status, "attention_residual_cl")
-    return out, {key: b for key, b, _, _ in tw}
+    return out, tw.written()
 
 
 def attention_residual_qv_cl(qv: torch.Tensor, keys: torch.Tensor, scale: float, bias: Optional[torch.Tensor] = None,
@@ -2562,8 +2564,8 @@ def attention_residual_qv_cl(qv: torch.Tensor, keys: torch.Tensor, scale: float,
         residual = _req_cl(residual, "residual")
         if tuple(residual.shape) != tuple(out.shape):
             raise RuntimeError("attention_residual_qv_cl: residual must be shaped like the output")
-    tw = [(key, _empty_cl((B, C, H, W), qv.device), sc, sh) for key, (sc, sh) in list((twins or {}).items())[:2]]
-    targs, twin_keep = _twin_args([(b, sc, sh) for _, b, sc, sh in tw] or None, out, C, "attention_residual_qv_cl")
+    tw = LaunchSet.fresh(twins, (B, C, H, W), qv.device)
+    targs, twin_keep = _twin_args(tw.args(), out, C, "attention_residual_qv_cl")
     (qa, q_keep) = _cvec(qscale, "qscale")
     if q_keep is not None and (qa[2] != C or qa[1] not in (1, B)):
         raise RuntimeError("attention_residual_qv_cl: qscale must be [1|B, C, 1, 1]")
@@ -2573,7 +2575,7 @@ def attention_residual_qv_cl(qv: torch.Tensor, keys: torch.Tensor, scale: float,
     if status == UNSUPPORTED:
         return None
     _check(status, "attention_residual_qv_cl")
-    return out, {key: b for key, b, _, _ in tw}
+    return out, tw.written()
 
 
 def attention_tokens(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, heads: int, scale: float,

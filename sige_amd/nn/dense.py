@@ -20,6 +20,8 @@ import torch
 from torch import nn
 from torch.nn import functional as F
 
+from . import twins as _twins
+
 _GEOMETRY = {
     # (kernel, stride, padding) -> (tile block, out tile, gather offset)
     ((3, 3), (1, 1), (1, 1)): ((6, 6), (4, 4), (1, 1)),
@@ -114,16 +116,11 @@ def _wide_conv(conv: nn.Conv2d, x, x2, scale, shift, activation_name, residual, 
         return None
     B = x.shape[0]
     H, W = (2 * x.shape[2], 2 * x.shape[3]) if upsample2x else (x.shape[2], x.shape[3])
-    tw = []
-    if twins and out_affine is None:
-        for key, (sc, sh) in list(twins.items())[:2]:
-            tw.append((key, torch.empty((B, conv.out_channels, H, W), dtype=torch.float32, device=x.device,
-                                        memory_format=torch.channels_last), sc, sh))
+    tw = _twins.LaunchSet.fresh(twins, (B, conv.out_channels, H, W), x.device, out_affine)
     out = hip.wide_conv_cl(x, x2, scale, shift, activation_name, packed, conv.bias, conv.out_channels, k, residual=residual,
-                           out_affine=out_affine, twins=[(b, sc, sh) for _, b, sc, sh in tw] or None, upsample2x=upsample2x,
-                           stats=stats)
+                           out_affine=out_affine, twins=tw.args(), upsample2x=upsample2x, stats=stats)
     if out is not None and made is not None:
-        made.update({k_: b for k_, b, _, _ in tw})
+        made.update(tw.written())
     return out
 
 
@@ -226,7 +223,7 @@ def fused_conv2d(conv: nn.Conv2d, x: torch.Tensor, scale: Optional[torch.Tensor]
     epilogue (one launch, once per element): act(out * scale + shift).
     `twins` = {key: (scale [Cout], shift [Cout])} (at most two): where the launch can, it also writes
     SiLU(scale * result + shift) -- the activated input of a consumer's conv1 -- and returns them as
-    `out._sige_twins[key]` (scatter.tag_twins); a consumer that finds no entry activates for itself.
+    `twins.twin_of(out, key)`; a consumer that finds no entry activates for itself.
     `tiles` = an index list in this conv's tile geometry (hip.DemandTiles: `main` for a 3x3, `flat` for a 1x1) with `out` a
     persistent channels-last buffer (demand_buffer): the conv is evaluated on those output cells only, in place -- `out` and the
     twins (persistent too, one set per conv) keep whatever they held outside the list, which nobody may read; ignored where the
@@ -237,13 +234,9 @@ def fused_conv2d(conv: nn.Conv2d, x: torch.Tensor, scale: Optional[torch.Tensor]
     if isinstance(out, tuple):  # (tensor, epilogue still to apply)
         out, (os_, oh_, oact) = out
         out = _act(out * os_.reshape(1, -1, 1, 1) + oh_.reshape(1, -1, 1, 1), oact)
-    if not made and twins and out_affine is None:
-        from . import scatter
-
-        if scatter.EMULATE_TWINS:  # (tests only: see scatter.EMULATE_TWINS)
-            made = scatter.emulated_twins(out, twins)
-    out._sige_twins = made
-    return out
+    if not made and twins and out_affine is None and _twins.EMULATE_TWINS:  # (tests only)
+        made = _twins.emulated_twins(out, twins)
+    return _twins.tag(out, made)
 
 
 def demand_buffer(conv: nn.Conv2d, name, shape, device) -> torch.Tensor:
@@ -257,17 +250,17 @@ def demand_buffer(conv: nn.Conv2d, name, shape, device) -> torch.Tensor:
     return buf
 
 
-def _demand_twin_buffers(conv: nn.Conv2d, keys, shape, device):
-    """One persistent twin buffer per registered consumer key (registrations of an affine that is gone are dropped)."""
-    from .scatter import twin_key_cache_id
-
+def _demand_twins(conv: nn.Conv2d, served, shape, device, out_affine) -> _twins.LaunchSet:
+    """One persistent twin buffer per served consumer key (registrations of an affine that is gone are dropped)."""
+    tw = _twins.LaunchSet(served, lambda key, *_: demand_buffer(conv, _twins.BufferName(key), shape, device), out_affine)
+    keys = tw.written()
     bufs = conv.__dict__.setdefault("_sige_demand_bufs", {})
-    cids = {twin_key_cache_id(k) for k in keys}
+    cids = {_twins.cache_id_of(k) for k in keys}
     # (a launch serves the registrations of ONE cache id: those of another id keep their buffers until that id runs again)
-    for name in [n for n in bufs if isinstance(n, tuple) and n[0] == "twin" and n[1] not in keys
-                 and (twin_key_cache_id(n[1]) is None or twin_key_cache_id(n[1]) in cids)]:
+    for name in [n for n in bufs if isinstance(n, _twins.BufferName) and n.key not in keys
+                 and _twins.cache_id_of(n.key) in cids | {None}]:
         del bufs[name]
-    return [demand_buffer(conv, ("twin", k), shape, device) for k in keys]
+    return tw
 
 
 def _fused_conv2d(conv, x, scale, shift, activation_name, x2, residual, pad_bottom_right, out_affine, twins=None, made=None,
@@ -283,17 +276,15 @@ def _fused_conv2d(conv, x, scale, shift, activation_name, x2, residual, pad_bott
             # the tile kernel over a partial list, into the persistent buffers: the dispatcher sizes output block, channel
             # blocks and workgroup order from the tile count, as for a SIGE layer of that size (csrc/block_conv.hip plan_conv)
             B, _, H, W = x.shape
-            keys = list(twins)[:2] if twins and out_affine is None else []
-            tbufs = _demand_twin_buffers(conv, keys, (B, conv.out_channels, H, W), x.device)
-            tw = [(k, b, *twins[k]) for k, b in zip(keys, tbufs)]
+            tw = _demand_twins(conv, twins, (B, conv.out_channels, H, W), x.device, out_affine)
             out = hip.gather_conv_cl(x, x2, block, tiles, scale, shift, activation_name, _packed(conv, block), conv.bias,
                                      conv.out_channels, conv.kernel_size, conv.stride,
                                      full=dict(offset=offset, out_res=(H, W), residual=residual), out_affine=out_affine,
-                                     out=out_buf, twins=[(b, sc, sh) for _, b, sc, sh in tw] or None)
+                                     out=out_buf, twins=tw.args())
             if out is None:
                 raise RuntimeError("fused_conv2d: no tile kernel for this conv over a partial tile list")
             if made is not None:
-                made.update({k: b for k, b, _, _ in tw})
+                made.update(tw.written())
             return out
         if not pad_bottom_right:
             out = _wide_conv(conv, x, x2, scale, shift, activation_name, residual, out_affine, twins, made)
@@ -315,18 +306,14 @@ def _fused_conv2d(conv, x, scale, shift, activation_name, x2, residual, pad_bott
                 return out
         idx = hip.all_tiles(H, W, out_tile, conv.stride, offset, x.device)
         if hip.is_cl(x) and hip.cl_supported(x.shape[1], 0 if x2 is None else x2.shape[1], conv.out_channels):
-            tw = []
-            if twins and out_affine is None:  # (a twin is a function of the RAW result: the primary output must be it)
-                for key, (sc, sh) in list(twins.items())[:2]:
-                    tw.append((key, torch.empty((B, conv.out_channels, Ho, Wo), dtype=torch.float32, device=x.device,
-                                                memory_format=torch.channels_last), sc, sh))
+            tw = _twins.LaunchSet.fresh(twins, (B, conv.out_channels, Ho, Wo), x.device, out_affine)
             out = hip.gather_conv_cl(x, x2, block, idx, scale, shift, activation_name, _packed(conv, block), conv.bias,
                                      conv.out_channels, conv.kernel_size, conv.stride,
                                      full=dict(offset=offset, out_res=(Ho, Wo), residual=residual), out_affine=out_affine,
-                                     twins=[(b, sc, sh) for _, b, sc, sh in tw] or None)
+                                     twins=tw.args())
             if out is not None:
                 if made is not None:
-                    made.update({k: b for k, b, _, _ in tw})
+                    made.update(tw.written())
                 return out
         out = hip.gather_conv_nchw(x.contiguous(), None if x2 is None else x2.contiguous(), block, idx,
                                     scale, shift, activation_name, _packed(conv, block, False), conv.bias,

@@ -13,7 +13,7 @@ from typing import Optional
 
 import torch
 
-from . import deferred
+from . import deferred, twins
 from .base import SIGEModule, SIGEModuleWrapper
 from .gather import Gather
 
@@ -124,51 +124,30 @@ class _OutputBuffers:
         self.bufs = {}
 
 
-def twin_key_cache_id(key):
-    """Consumers key their registration (consumer id, input part, affine generation, cache id): the registered (scale,
-    shift) is the consumer's cached affine of THAT cache id (one cache per denoising step, sige/nn/scatter.py:59-60).  Keys of
-    any other shape apply to every cache id."""
-    return key[3] if isinstance(key, tuple) and len(key) >= 4 else None
+class _TwinBuffers(twins.Registry):
+    """Activated twins of a Scatter module's persistent output (not in the reference; the protocol: sige_amd/nn/twins.py).
 
-
-def twins_for(regs: dict, cache_id) -> dict:
-    """The registrations a launch under `cache_id` serves."""
-    return {k: v for k, v in regs.items() if twin_key_cache_id(k) in (None, cache_id)}
-
-
-class _TwinBuffers:
-    """Activated twins of a Scatter module's persistent output (not in the reference).
-
-    A CONSUMER whose conv1 applies a cached GroupNorm affine + SiLU to this module's output can register (scale, shift)
-    under a key; the fused conv -> scatter launch then also writes SiLU(scale * value + shift) for every pixel it writes
-    into a second persistent buffer that equals SiLU(scale * cache + shift) elsewhere -- the consumer stages raw values
-    (the activation is computed once per element by the producer instead of once per output-channel block).  At most two
-    registrations (a skip tensor has two consumers); further ones are refused and those consumers keep activating."""
-
-    MAX = 2
+    For every registration the fused conv -> scatter launch also writes SiLU(scale * value + shift) for every pixel it writes
+    into a second persistent buffer that equals SiLU(scale * cache + shift) elsewhere."""
 
     def __init__(self):
-        self.regs = {}   # key -> (scale [C], shift [C])
-        self.bufs = {}   # key -> _OutputBuffers
+        super().__init__()   # regs: key -> (scale [C], shift [C])
+        self.bufs = {}       # key -> _OutputBuffers
 
     def register(self, key, scale: torch.Tensor, shift: torch.Tensor) -> bool:
-        if key not in self.regs and len(twins_for(self.regs, twin_key_cache_id(key))) >= self.MAX:
-            return False
-        self.regs[key] = (scale, shift)
-        self.bufs.pop(key, None)
-        return True
+        ok = super().register(key, scale, shift)
+        if ok:
+            self.bufs.pop(key, None)
+        return ok
 
     def unregister(self, key):
-        self.regs.pop(key, None)
+        super().unregister(key)
         self.bufs.pop(key, None)
 
-    def launch_args(self, cache_id, cached: torch.Tensor, stamp):
+    def launch_args(self, cache_id, cached: torch.Tensor, stamp) -> twins.LaunchSet:
         """[(key, buffer, scale, shift)] for the fused launch; buffers are (re)built from the cache when stale."""
-        out = []
-        for key, (sc, sh) in twins_for(self.regs, cache_id).items():
-            buf = self.bufs.setdefault(key, _OutputBuffers()).get(cache_id, cached, stamp, build=(sc, sh))
-            out.append((key, buf, sc, sh))
-        return out
+        return twins.LaunchSet(self.serving(cache_id), lambda key, sc, sh: self.bufs.setdefault(key, _OutputBuffers()).get(
+            cache_id, cached, stamp, build=(sc, sh)))
 
     def invalidate(self, cache_id=None):
         for b in self.bufs.values():
@@ -181,24 +160,9 @@ class _TwinBuffers:
     def clear(self):
         self.bufs = {}
 
-
-# Tests only (tests/test_host_logic.py): where a launch cannot write twins itself (no GPU: the CPU path goes through the
-# plain Scatter kernels), compute them from the finished output with torch -- the registration / invalidation logic of the
-# twins can then be exercised end to end on the oracle backend.  Never set in the product.
-EMULATE_TWINS = False
-
-
-def emulated_twins(out: torch.Tensor, regs: dict) -> dict:
-    return {k: torch.nn.functional.silu(out * sc.view(1, -1, 1, 1) + sh.view(1, -1, 1, 1)) for k, (sc, sh) in list(regs.items())[:2]}
-
-
-def tag_twins(out: torch.Tensor, twins: dict, producer=None) -> torch.Tensor:
-    """Attach {consumer key: activated twin} (possibly empty: persistent outputs keep their Python object, a stale
-    entry must not survive a launch that did not write it) and the producing module to an output tensor."""
-    out._sige_twins = twins
-    if producer is not None:
-        out._sige_producer = producer
-    return out
+    def unwritten(self, output: torch.Tensor, cache_id) -> torch.Tensor:
+        """Tag the output of a launch that wrote no twin: consumers activate for themselves (tests: twins.EMULATE_TWINS)."""
+        return twins.tag(output, twins.emulated_twins(output, self.serving(cache_id)) if twins.EMULATE_TWINS else {})
 
 
 class Scatter(SIGEModule):
@@ -242,9 +206,9 @@ class Scatter(SIGEModule):
             if _cl_ok(cached, residual) and isinstance(tiles, deferred.DeferredTiles) and tiles.spec is not None:
                 out = self._out_bufs.get(self.cache_id, cached, g.timestamp)
                 tw = self.twins.launch_args(self.cache_id, cached, g.timestamp)
-                done = _fused_conv_into(conv, tiles, out, g, residual=residual, twins=[(b, sc, sh) for _, b, sc, sh in tw])
+                done = _fused_conv_into(conv, tiles, out, g, residual=residual, twins=tw.args())
                 if done is not None:
-                    return tag_twins(done, {k: b for k, b, _, _ in tw})
+                    return twins.tag(done, tw.written())
         return self.forward(conv(tiles), residual)
 
     def forward(self, x: torch.Tensor, residual: Optional[torch.Tensor] = None) -> torch.Tensor:
@@ -275,8 +239,7 @@ class Scatter(SIGEModule):
                 cached.copy_(output)
                 self._out_bufs.invalidate(self.cache_id)
                 self.twins.invalidate(self.cache_id)
-            # (this launch wrote no twin: consumers activate for themselves)
-            return tag_twins(output, emulated_twins(output, twins_for(self.twins.regs, self.cache_id)) if EMULATE_TWINS else {})
+            return self.twins.unwritten(output, self.cache_id)
         if self.mode == "full":
             output = x if residual is None else x + residual
             self.output_res = output.shape[2:]
@@ -379,9 +342,9 @@ class ScatterWithBlockResidual(SIGEModule):
                 x1 = deferred.resolve(residual)
                 tw = self.twins.launch_args(self.cache_id, y0, (mg.timestamp, sg.timestamp))
                 done = _fused_conv_into(conv, tiles, out, mg, residual=y1, x1=x1, table1=sg.tile_table(y0.shape[2:], y0.device),
-                                        twins=[(b, sc, sh) for _, b, sc, sh in tw])
+                                        twins=tw.args())
                 if done is not None:
-                    return tag_twins(done, {k: b for k, b, _, _ in tw})
+                    return twins.tag(done, tw.written())
         return self.forward(conv(tiles), residual)
 
     def forward(self, x: torch.Tensor, residual: torch.Tensor, x_is_sum: bool = False) -> torch.Tensor:
@@ -431,7 +394,7 @@ class ScatterWithBlockResidual(SIGEModule):
                     fn = self.native(self.scatter_runtime, x)
                     y1.copy_(fn(residual.contiguous(), deferred.from_cache(y1).contiguous(), sg.offset[0], sg.offset[1],
                                 sg.model_stride[0], sg.model_stride[1], sg.indices_on(x.device), None))
-            return tag_twins(output, emulated_twins(output, twins_for(self.twins.regs, self.cache_id)) if EMULATE_TWINS else {})  # (no twin written)
+            return self.twins.unwritten(output, self.cache_id)
         if self.mode == "full":
             # (x_is_sum: the caller's conv already added the residual in its epilogue -- one launch less, one pass less)
             output = x if x_is_sum else x + residual

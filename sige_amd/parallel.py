@@ -22,6 +22,8 @@ from typing import Callable, Dict, List, Optional, Sequence, Tuple
 import torch
 import torch.distributed as dist
 
+from .nn import twins
+
 _ALIGN = 64  # floats; keeps every view 256-byte aligned for 16-byte vector access
 _PAD = 64 * 48  # floats: world sizes 1, 2, 3, 4, 6, 8, 12, 16 divide the padded buffer into 256-byte aligned chunks
 
@@ -134,17 +136,7 @@ def pack_caches(model: torch.nn.Module) -> torch.Tensor:
         _set(s, view)
         layout.append((s[4], off, off + size, t.numel() * k))
         off += size
-    for m in model.modules():  # the cache tensors moved: persistent outputs are rebuilt on next use
-        bufs = getattr(m, "_out_bufs", None)
-        if bufs is not None:
-            bufs.invalidate()
-        # ... and so did the cached affines: activated twins were registered with VIEWS of the old affine tensors (a consumer's
-        # conv1 affine, held by its producers).  Drop the registrations; the consumers register again, with the views of the
-        # flat buffer, on their next sparse forward (sparse -> pack -> broadcast otherwise serves twins of the OLD
-        # affine -- 0.18 max error on the oracle backend).
-        drop = getattr(m, "_drop_twin_links", None)
-        if drop is not None:
-            drop()
+    twins.invalidate(model)  # (the cache tensors moved, the cached affines with them)
     model.__dict__["_sige_cache_layout"] = (flat.data_ptr(), layout)
     return flat
 
@@ -288,7 +280,7 @@ def _refresh_schedule(model: torch.nn.Module, layout, total: int, world: int, n_
     for m in by_id.values():
         regs = getattr(getattr(m, "twins", None), "regs", None)
         for key in (regs or ()):
-            consumer = by_id.get(key[0]) if isinstance(key, tuple) and key else None
+            consumer = by_id.get(getattr(key, "consumer", None))  # (twins.TwinKey)
             if consumer is not None:
                 needs[m] = max(needs.get(m, 0), own.get(consumer, 0))
     end = {}

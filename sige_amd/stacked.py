@@ -21,6 +21,7 @@ from typing import Dict, List
 import torch
 
 from . import hip
+from .nn import twins
 
 
 def tall(x: torch.Tensor) -> torch.Tensor:
@@ -91,15 +92,7 @@ def stack_caches(model: torch.nn.Module, E: int) -> None:
             if r is not None and len(r) == 2:
                 res.append((m, name, r))
                 setattr(m, name, torch.Size((E * r[0], r[1])))
-        bufs = getattr(m, "_out_bufs", None)
-        if bufs is not None:
-            bufs.invalidate()
-        tw = getattr(m, "twins", None)
-        if tw is not None and hasattr(tw, "invalidate"):
-            tw.invalidate()
-        drop = getattr(m, "_drop_twin_links", None)
-        if drop is not None:
-            drop()
+    twins.invalidate(model)
     model.__dict__["_sige_stacked"] = (E, saved, res)
 
 
@@ -112,16 +105,7 @@ def unstack_caches(model: torch.nn.Module) -> None:
         d[k] = t
     for m, name, r in res:
         setattr(m, name, r)
-    for m in model.modules():
-        bufs = getattr(m, "_out_bufs", None)
-        if bufs is not None:
-            bufs.invalidate()
-        tw = getattr(m, "twins", None)
-        if tw is not None and hasattr(tw, "invalidate"):
-            tw.invalidate()
-        drop = getattr(m, "_drop_twin_links", None)
-        if drop is not None:
-            drop()
+    twins.invalidate(model)
 
 
 class edit_batch:

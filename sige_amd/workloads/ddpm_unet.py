@@ -28,6 +28,7 @@ from torch.nn import functional as F
 from ..nn import Gather, Scatter, ScatterGather, ScatterWithBlockResidual, SIGEConv2d, SIGEModel, SIGEModule, paired_convs
 from ..nn.deferred import lazy_cat
 from ..nn.dense import demand_buffer, fast_full_pass, full_conv2d, fused_conv2d, group_norm_affine, input_conv2d
+from ..nn.twins import BufferName, TwinConsumer, TwinProducer, cache_id_of, tag, twin_of
 
 
 @dataclass
@@ -55,11 +56,9 @@ class DDPMConfig:
     # launch the shortcut 1x1 of a ResBlock inside the kernel of its conv1 (sige_amd.hip.conv_pair: horizontal fusion)
     pair_shortcut: bool = True
     # conv1 inputs activated by their PRODUCERS: every module whose output feeds a ResBlock's conv1 also writes
-    # SiLU(scale1 * out + shift1) (an "activated twin", sige_amd.nn.scatter._TwinBuffers / dense.fused_conv2d(twins=...)), so
-    # conv1 stages raw values -- the cached affine + SiLU is computed once per element instead of once per
-    # output-channel block (8-16 per layer).  Consumers register on their first sparse forward and activate for
-    # themselves until the twin exists.  (WIP: written without GPU time left in round 2 -- validate first:
-    # tests/test_gpu_round2.py::test_ddpm_forward_twins_vs_no_twins, then bench.py; measured upper bound -76 us / forward.)
+    # SiLU(scale1 * out + shift1) (an "activated twin"), so conv1 stages raw values -- the cached affine + SiLU is computed once
+    # per element instead of once per output-channel block (8-16 per layer).  Consumers register on their first sparse
+    # forward and activate for themselves until the twin exists.  The protocol: sige_amd/nn/twins.py.
     conv1_twins: bool = True
     # run the shortcut branch of a ResBlock (1x1 conv on the block input) on a second stream (it is independent of
     # conv1 -> conv2).  Measured on MI355X / ROCm 7.2: the cross-stream graph edges cost more than the overlap gains
@@ -156,52 +155,7 @@ def fold_keys_into_query(w_qkv: torch.Tensor, b_qkv: Optional[torch.Tensor]):
     return M.to(wq.dtype).contiguous(), m.to(wq.dtype)
 
 
-class _TwinProducer:
-    """Mixin of the modules whose output is written by a full-tensor conv epilogue and can therefore carry activated twins
-    for the conv1 of a consumer (cfg.conv1_twins).  `_twin_scatter()`: the Scatter module that owns the persistent in-place
-    output (SIGE layers: persistent twins live next to it), or None (dense layers: a fresh twin per forward)."""
-
-    def _twin_scatter(self):
-        return None
-
-    def _twins_ok(self) -> bool:
-        return True
-
-    def register_twin(self, key, scale: torch.Tensor, shift: torch.Tensor) -> bool:
-        if not self._twins_ok():
-            return False
-        sct = self._twin_scatter()
-        if sct is not None:
-            return sct.twins.register(key, scale, shift)
-        from ..nn.scatter import twin_key_cache_id, twins_for
-
-        regs = self.__dict__.setdefault("twin_regs", {})
-        if key not in regs and len(twins_for(regs, twin_key_cache_id(key))) >= 2:
-            return False
-        regs[key] = (scale, shift)
-        return True
-
-    def unregister_twin(self, key):
-        sct = self._twin_scatter()
-        if sct is not None:
-            sct.twins.unregister(key)
-        self.__dict__.setdefault("twin_regs", {}).pop(key, None)
-
-    def _my_twins(self) -> dict:
-        """(dense producers) the registrations this forward serves: those of the current cache id."""
-        from ..nn.scatter import twins_for
-
-        return twins_for(self.__dict__.get("twin_regs") or {}, getattr(self, "cache_id", 0))
-
-    def _produced(self, out: torch.Tensor) -> torch.Tensor:
-        """Mark `out` as this module's output of the current sparse forward (consumers find their producer through it)."""
-        out._sige_producer = self
-        if not hasattr(out, "_sige_twins"):
-            out._sige_twins = {}
-        return out
-
-
-class ResBlock(SIGEModule, _TwinProducer):
+class ResBlock(SIGEModule, TwinProducer, TwinConsumer):
     def __init__(self, cfg: DDPMConfig, cin: int, cout: int, sparse: bool):
         super().__init__()
         self.cin, self.cout = cin, cout
@@ -228,10 +182,7 @@ class ResBlock(SIGEModule, _TwinProducer):
         self.preactivate = cfg.preactivate
         self.overlap = cfg.overlap_shortcut
         self.pair = cfg.pair_shortcut
-        self.use_twins = cfg.conv1_twins
-        self.twin_regs = {}     # as a producer (dense blocks): consumer key -> (scale, shift)
-        self._twin_links = {}   # as a consumer: key -> the producer it registered with
-        self._aff_gen = 0       # bumped when the cached affine is recomputed: old twins are for the old affine
+        self._init_twin_consumer(cfg.conv1_twins)
         self._side = None
 
     def clear_cache(self):
@@ -288,10 +239,9 @@ class ResBlock(SIGEModule, _TwinProducer):
 
         for conv in self.split_conv1(ch):
             _packed(conv, (6, 6))
-        key_h, key_s = ((id(self), i, self._aff_gen, self.cache_id) for i in (0, 1))
-        if key_h not in self._twin_links:
+        if self._twin_key(0) not in self._twin_links:
             return None
-        return getattr(skip, "_sige_twins", {}).get(key_s)
+        return twin_of(skip, self._twin_key(1))
 
     def submit_side_product(self, skip: torch.Tensor) -> bool:
         """Queue W[:, ch:] * act(skip) as a side conv (hip.conv_side_begin) into a persistent buffer; _sparse_dense picks it up."""
@@ -309,49 +259,9 @@ class ResBlock(SIGEModule, _TwinProducer):
         self.__dict__["_side_product"] = (buf, tw)
         return True
 
-    # ---- activated twins (cfg.conv1_twins) ----
+    # ---- activated twins (cfg.conv1_twins): producer and consumer, sige_amd/nn/twins.py ----
     def _twin_scatter(self):
         return self.scatter if self.sparse_main else None
-
-    def _drop_twin_links(self):
-        for key, (prod, _) in self._twin_links.items():
-            prod.unregister_twin(key)
-        self._twin_links = {}
-        self._aff_gen += 1
-
-    def _twin_inputs(self, parts, s1, t1):
-        """The activated twins of this block's conv1 inputs, one per part of the (possibly concatenated) input -- or None
-        (then conv1 activates in its staging path, as without twins).  A missing twin is requested from the module that
-        produced the part; it exists from the next forward on."""
-        from ..nn import scatter as _scatter
-
-        if not (self.use_twins and self.preactivate and self.mode == "sparse" and (parts[0].is_cuda or _scatter.EMULATE_TWINS)):
-            return None
-        if s1.shape[0] != 1:
-            return None  # (per-sample affine: the epilogue's twin vectors are per channel)
-        # A registration holds VIEWS of the affine tensors it was made with.  If the cached affine has been re-pointed since
-        # (sige_amd.parallel.pack_caches moves every cache tensor into one flat buffer; anything that assigns `affine[cid]`
-        # without going through _full), the producers would keep activating with the old tensors: drop every link and start
-        # over with the current ones (ADVICE r3: sparse -> pack_caches -> broadcast gave stale twins, max error 0.18).
-        anchor = (s1.data_ptr(), t1.data_ptr())
-        if any(a != anchor for k, (_, a) in self._twin_links.items() if k[3] == self.cache_id):
-            self._drop_twin_links()
-        twins, off, complete = [], 0, True
-        for i, p in enumerate(parts):
-            c = p.shape[1]
-            key = (id(self), i, self._aff_gen, self.cache_id)  # (the registered affine is this cache id's)
-            t = getattr(p, "_sige_twins", {}).get(key)
-            if t is None:
-                complete = False
-                prod = getattr(p, "_sige_producer", None)
-                if prod is not None and key not in self._twin_links:
-                    sc = s1.reshape(-1)[off:off + c].contiguous()
-                    sh = t1.reshape(-1)[off:off + c].contiguous()
-                    if prod.register_twin(key, sc, sh):
-                        self._twin_links[key] = (prod, anchor)
-            twins.append(t)
-            off += c
-        return twins if complete else None
 
     def rebuild_derived_caches(self):
         """(sige_amd.parallel) the cache tensors were rewritten in place: recompute the activated ScatterGather copy."""
@@ -555,12 +465,11 @@ class ResBlock(SIGEModule, _TwinProducer):
         return fused_conv2d(self.conv2, h, s2, t2, "swish", residual=skip)
 
 
-class AttnBlock(SIGEModule, _TwinProducer):
+class AttnBlock(SIGEModule, TwinProducer):
     def __init__(self, cfg: DDPMConfig, ch: int, sparse: bool):
         super().__init__()
         self.ch = ch
         self.edit_batch = 1  # (sige_amd.stacked: E images stacked along H; attention is per image)
-        self.twin_regs = {}
         self.quirk = cfg.reference_attn_quirk
         self.sparse = sparse and cfg.shortcut_block is not None
         Conv = SIGEConv2d if self.sparse else nn.Conv2d
@@ -732,8 +641,7 @@ class AttnBlock(SIGEModule, _TwinProducer):
                     else:
                         res = hip.attention_residual_qv_cl(qv, x, self.ch ** -0.5, bp, residual=x, twins=self._my_twins(), qscale=qs)
                     if res is not None:
-                        res[0]._sige_twins = res[1]
-                        return self._produced(res[0])
+                        return tag(res[0], res[1], self)
             conv, bp = self.folded_proj()
             qkv = fused_conv2d(conv, x, s, t, "identity")
             if hip.is_cl(qkv):
@@ -749,14 +657,13 @@ class AttnBlock(SIGEModule, _TwinProducer):
                 else:
                     res = hip.attention_residual_cl(qkv, self.ch ** -0.5, bp, residual=x, twins=self._my_twins())
                 if res is not None:
-                    res[0]._sige_twins = res[1]
-                    return self._produced(res[0])
+                    return tag(res[0], res[1], self)
             refused.add(tuple(x.shape))
         qkv = fused_conv2d(self.qkv, x, s, t, "identity")
         return self._produced(fused_conv2d(self.proj_out, self._attention(qkv), residual=x, twins=self._my_twins()))
 
 
-class Upsample(SIGEModule, _TwinProducer):
+class Upsample(SIGEModule, TwinProducer):
     """nearest x2 then a tiled 3x3 conv (always tiled, as in the reference)."""
 
     def _twin_scatter(self):
@@ -788,7 +695,7 @@ class Upsample(SIGEModule, _TwinProducer):
         return self.scatter(self.conv(self.gather(x)))
 
 
-class Downsample(SIGEModule, _TwinProducer):
+class Downsample(SIGEModule, TwinProducer):
     """3x3 stride-2 conv with (0,1,0,1) zero padding; tiled when `sparse` (the
     gather's zero fill past the bottom/right border IS the padding then)."""
 
@@ -1097,13 +1004,11 @@ class DDPMSparseUNet(SIGEModel):
     def _change_buffers(stage, cid):
         """The persistent outputs and twins of the level's convs for cache id `cid`, by name and address: a buffer that is new
         (or gone) holds nothing outside the lists yet."""
-        from ..nn.scatter import twin_key_cache_id
-
         out = []
         for b in stage.block:
             for conv in (b.conv1, b.conv2, getattr(b, "nin_shortcut", None)):
                 for name, buf in (conv.__dict__.get("_sige_demand_bufs", {}) if conv is not None else {}).items():
-                    if name == ("out", cid) or (isinstance(name, tuple) and name[0] == "twin" and twin_key_cache_id(name[1]) == cid):
+                    if name == ("out", cid) or (isinstance(name, BufferName) and cache_id_of(name.key) == cid):
                         out.append((id(conv), repr(name), buf.data_ptr()))
         return tuple(out)
 

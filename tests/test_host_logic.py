@@ -468,11 +468,11 @@ def test_paired_convs_is_a_noop_off_the_gpu():
 def test_conv1_twins_host_logic_on_the_oracle_backend():
     """Producer-side activation of the conv1 inputs (DDPMConfig.conv1_twins): registration on the first sparse forward,
     persistent twins across mask changes, invalidation by a new full pass -- with the twins EMULATED in torch where the CPU
-    path cannot write them from a launch (scatter.EMULATE_TWINS), so that the whole state machine runs without a GPU.  The
+    path cannot write them from a launch (twins.EMULATE_TWINS), so that the whole state machine runs without a GPU.  The
     network with twins must equal the network without to fp32 rounding in every situation."""
     from oracle import oracle
     from sige_amd import runtime
-    from sige_amd.nn import scatter
+    from sige_amd.nn import twins
     from sige_amd.utils import dilate_mask, downsample_mask
     from sige_amd.workloads.ddpm_unet import DDPMConfig, DDPMSparseUNet, ResBlock
 
@@ -497,7 +497,7 @@ def test_conv1_twins_host_logic_on_the_oracle_backend():
         return out.clone()
 
     runtime.register_backend("cpu", oracle)
-    scatter.EMULATE_TWINS = True
+    twins.EMULATE_TWINS = True
     try:
         with torch.no_grad():
             model.set_mode("full")
@@ -544,7 +544,7 @@ def test_conv1_twins_host_logic_on_the_oracle_backend():
             assert any(k[3] == 0 for b in blocks for k in b._twin_links) and any(k[3] == 1 for b in blocks for k in b._twin_links)
             model.set_cache_id(0)
     finally:
-        scatter.EMULATE_TWINS = False
+        twins.EMULATE_TWINS = False
         runtime.unregister_backend("cpu")
 
 
@@ -555,7 +555,7 @@ def test_twins_survive_sparse_then_pack_then_new_cache():
     SiLU(old_scale * x + old_shift).  Order under test: full(A) -> sparse x3 -> pack -> flat <- caches of B -> refresh -> sparse."""
     from oracle import oracle
     from sige_amd import parallel, runtime
-    from sige_amd.nn import scatter
+    from sige_amd.nn import twins
     from sige_amd.utils import dilate_mask, downsample_mask
     from sige_amd.workloads.ddpm_unet import DDPMConfig, DDPMSparseUNet, ResBlock
 
@@ -574,7 +574,7 @@ def test_twins_survive_sparse_then_pack_then_new_cache():
         return net
 
     runtime.register_backend("cpu", oracle)
-    scatter.EMULATE_TWINS = True
+    twins.EMULATE_TWINS = True
     try:
         with torch.no_grad():
             # what rank 0 would send: the packed cache of image B
@@ -621,7 +621,7 @@ def test_twins_survive_sparse_then_pack_then_new_cache():
             for _ in range(3):
                 assert (net(xb + noise * m, t) - ref2).abs().max() < 1e-4
     finally:
-        scatter.EMULATE_TWINS = False
+        twins.EMULATE_TWINS = False
         runtime.unregister_backend("cpu")
 
 
@@ -631,7 +631,7 @@ def test_pipelined_refresh_waits_for_the_consumers_affine():
     refresh schedule must place such a module no earlier than the chunk holding that affine."""
     from oracle import oracle
     from sige_amd import parallel, runtime
-    from sige_amd.nn import scatter
+    from sige_amd.nn import twins
     from sige_amd.utils import dilate_mask, downsample_mask
     from sige_amd.workloads.ddpm_unet import DDPMConfig, DDPMSparseUNet
 
@@ -644,7 +644,7 @@ def test_pipelined_refresh_waits_for_the_consumers_affine():
     m = torch.zeros(64, 64, dtype=torch.bool)
     m[18:34, 12:30] = True
     runtime.register_backend("cpu", oracle)
-    scatter.EMULATE_TWINS = True
+    twins.EMULATE_TWINS = True
     try:
         with torch.no_grad():
             net.set_mode("full")
@@ -654,7 +654,7 @@ def test_pipelined_refresh_waits_for_the_consumers_affine():
             net.set_mode("sparse")
             net(x, t)  # (consumers register with their producers, against the packed affines)
     finally:
-        scatter.EMULATE_TWINS = False
+        twins.EMULATE_TWINS = False
         runtime.unregister_backend("cpu")
     _, layout = net.__dict__["_sige_cache_layout"]
     bounds, ready = parallel._refresh_schedule(net, layout, flat.numel(), 2, 8)

@@ -36,4 +36,8 @@ for nchw_first in (True, False):
             d = float((recs[3][0] - recs[1][0]).abs().max())
             first = next(((n, float((recs[3][1][n] - recs[1][1][n]).abs().max())) for n, _ in mods if float((recs[3][1][n] - recs[1][1][n]).abs().max()) > 0), None)
             links = sum(len(b._twin_links) for _, b in mods if isinstance(b, ResBlock))
+            names = {id(b): n for n, b in model.named_modules()}
+            # the census of links: (producer, consumer, part, cache id)
+            for row in sorted((names[id(prod)], n, key[1], key[3]) for n, b in mods if isinstance(b, ResBlock) for key, (prod, _) in b._twin_links.items()):
+                print("link %s -> %s part %d cache %d" % row, flush=True)
             print("nchw_first=%s layout=%s: forward 4 vs forward 2 (same input): %.3e, first module that differs %s, links %d" % (nchw_first, layout, d, first, links), flush=True)
