@@ -619,7 +619,8 @@ static int scatter_nhwc_impl(const float *x, const CT *y, int B, int C, int H, i
     hipStream_t st = as_stream(stream);
     if (in_place) {
         const long units = (long)B * N * R * S * (C / 4);
-        if (units) scatter_tiles_nhwc_kernel<false, CT><<<grid_for(units), kT, 0, st>>>(a, units, units);
+        if (!units) return SIGE_HIP_OK;  // (no tile: nothing is launched, and no launch is counted)
+        scatter_tiles_nhwc_kernel<false, CT><<<grid_for(units), kT, 0, st>>>(a, units, units);
     } else {
         const long units = (long)B * H * W * (C / 4);
         scatter_full_nhwc_kernel<false, CT><<<grid_for(units), kT, 0, st>>>(a, units);
@@ -667,7 +668,8 @@ static int scatter_with_block_residual_nhwc_impl(
     hipStream_t st = as_stream(stream);
     if (in_place) {
         const long units0 = (long)B * N0 * R0 * S0 * (C / 4), units = units0 + (long)B * N1 * R1 * S1 * (C / 4);
-        if (units) scatter_tiles_nhwc_kernel<true, CT><<<grid_for(units), kT, 0, st>>>(a, units0, units);
+        if (!units) return SIGE_HIP_OK;  // (no tile: nothing is launched, and no launch is counted)
+        scatter_tiles_nhwc_kernel<true, CT><<<grid_for(units), kT, 0, st>>>(a, units0, units);
     } else {
         const long units = (long)B * H * W * (C / 4);
         scatter_full_nhwc_kernel<true, CT><<<grid_for(units), kT, 0, st>>>(a, units);
