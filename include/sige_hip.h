@@ -916,6 +916,22 @@ int sige_hip_attention_wide_supported(int Nq, int Nk, int C, int heads);
 int sige_hip_attention_wide_f32(const float *q, int ldq, const float *k, int ldk, const float *v, int ldv,
                                 int B, int Nq, int Nk, int C, int heads, float scale, float *out, int ldo, void *stream);
 
+/* ---- ... with the keys of a query tile's OWN image (stacked edits, sige_hip_set_edit_batch) ---------------------------------
+ * The queries are the tokens of T active 4x4 tiles of the tall image [1,C,H,W] = E images of H / E rows (E = the calling
+ * thread's edit batch): q, out [16 T, ld*], tile t = rows 16 t .. 16 t + 15; k, v [H W, ld*], the rows of the tall image (the two
+ * halves of one [H W, 2C] tensor, as above); active_indices = the Gather's device int32 [T,2] list, row origin first.  B = 1.
+ * Tile t belongs to image e = origin_row >> log2(H / E), clamped into [0, E - 1] (a bad list cannot move an address outside
+ * k / v), and attends to rows [e (H / E) W, (e + 1) (H / E) W) only: the kernel of the entry above with both buffer descriptors
+ * moved to the image's first row and spanning ONE image's keys, so tail masking, key split and the 2 GiB limit are per image
+ * (Nk = (H / E) W).  One launch for the tiles of all E edits; no per-edit count ever reaches the host, so the call can be
+ * captured in a graph and replayed under new index lists of the same T.  E = 1: the results of the entry above, bit for bit.
+ * SIGE_HIP_EINVAL: T < 0, non-positive H / W / C / heads, a row stride below C, null pointers (the index list among them)
+ * with work to do.  SIGE_HIP_EUNSUPPORTED: H / E not a power of two >= 4 (or E does not divide H), and everything the entry
+ * above refuses with Nq = 16 T, Nk = (H / E) W.  T == 0: SIGE_HIP_OK, nothing launched.                                     */
+int sige_hip_attention_wide_tiles_f32(const float *q, int ldq, const float *k, int ldk, const float *v, int ldv,
+                                      const int32_t *active_indices, int T, int H, int W, int C, int heads, float scale,
+                                      float *out, int ldo, void *stream);
+
 /* ---- fp16-STORED caches: the "_f16" forms of SURVEY.md 8b's export list (8f row 4: fp16 cache) ---------------------
  * The reference is fp32-only (sige/nn/base.py:15,55-63).  Here the CACHED tensors of a SIGE model -- Scatter /
  * ScatterGather `original_outputs`, ScatterWithBlockResidual `original_outputs` / `original_residuals`, and the activated
@@ -969,7 +985,8 @@ int sige_hip_convert_f32_f16(const float *src, void *dst, size_t n, void *stream
  * 10 % edit has, and a launch leaves the launch-bound regime.  sige_hip_set_edit_batch(E) tells the library where the seams are:
  * a halo row beyond a tile's own image is zero padding (not the neighbour image's pixels) in the channels-last fused gather /
  * scatter_gather -> conv kernels, the dense-layer conv, the standalone channels-last gather / scatter_gather, the SPADE
- * modulation and sige_hip_scatter_gather_split_nhwc_f32; entry points whose kernels have no seam test (the NCHW forms) return
+ * modulation and sige_hip_scatter_gather_split_nhwc_f32, and a query tile of sige_hip_attention_wide_tiles_f32 attends to its
+ * own image's keys; entry points whose kernels have no seam test (the NCHW forms) return
  * SIGE_HIP_EUNSUPPORTED while E > 1; per-pixel helpers (nearest resize by an integer factor, act_split, the dense SPADE
  * modulation) need none.  One image's height must be a power of two at every resolution.  Per host thread; 1 = off (default).  Whole-image ops (conv_in / conv_out, attention, GroupNorm) are simply
  * called with B = E on the same memory (sige_amd/stacked.py).  The mask pipeline follows: sige_hip_reduce_mask_i32 lets a

@@ -24,6 +24,12 @@
 // finish (split_finish.hpp), no second launch.  Without tickets or workspace (first use inside a capture, regions exhausted) ksplit = 1.
 //
 // q [B,Nq,ldq], k [B,Nk,ldk], v [B,Nk,ldv], out [B,Nq,ldo]: row strides in elements, head h at channels [h*d, (h+1)*d) of a row.
+//
+// Stacked edits (sige_hip_attention_wide_tiles_f32): a workgroup IS one 4x4 tile x one key split, so it can read its
+// keys from the tile's own image -- the tile's origin row from the Gather's index list (one wave-uniform load), e = row >> log2(rows
+// of an image), clamped, and both buffer descriptors start at image e's first key row and span ONE image's Nk keys.  Everything
+// else -- the split arithmetic, tail masking, clamped key rows, the range check -- is per image without knowing it.  Without an
+// index list e = 0: the batched entry's launch, bit for bit.
 #include <algorithm>
 
 #include "attention_rows.hpp"  // (max_over_rows, merge_weight: shared with attention_tokens.hip)
@@ -42,6 +48,10 @@ struct WideAttnArgs {
     int Nq, Nk, C, heads, d;
     int q_tiles, ksplit, split_blocks;  // split s takes key blocks [s * split_blocks, (s + 1) * split_blocks)
     float scale_log2e;
+    // per-image keys (sige_hip_attention_wide_tiles_f32; stacked edits): query tile t is the 4x4 tile with origin row tiles[2t] of
+    // the tall image, its keys are the Nk rows of image tiles[2t] >> img_shift.  nullptr: every tile reads the keys of image 0.
+    const int32_t *tiles;
+    int img_shift, images;
 };
 
 // ring depth: the largest divisor of the 2G chunks of a key block that is <= 8 (slots stay compile-time across blocks)
@@ -66,6 +76,10 @@ void attention_wide_kernel(WideAttnArgs a) {
     const unsigned b = pair / (unsigned)a.heads, head = pair - b * (unsigned)a.heads;
     const int q0 = (int)qtile * 16, d = a.d;
     const size_t hoff = (size_t)head * d;
+    // the tile's origin row: ONE wave-uniform load per workgroup (the address is the same in every lane; the branch is the same for
+    // the whole launch), issued in front of the Q stage and first used behind it
+    int tile_row = 0;
+    if (a.tiles) tile_row = a.tiles[2 * qtile];
 
     // ---- Q stage: 16 rows x 64 G channels, zeros beyond d (clamped address, load, select) ----
     {
@@ -92,11 +106,15 @@ void attention_wide_kernel(WideAttnArgs a) {
         for (int e = 0; e < 4; ++e) o[g][e] = f32x4{0.f, 0.f, 0.f, 0.f};
     }
 
-    // K / V of batch b, head `head`: valid bytes from the head's first channel of key 0 to the end of the last key's C channels
+    // K / V of batch b (of image `image`: B = 1 there), head `head`: valid bytes from the head's first channel of key 0 to the end of
+    // the last key's C channels -- ONE image's keys, a read outside them returns the descriptor's zeros
+    // (clamped: no index list can move the descriptors outside k / v; without `tiles`: shift 0, one image -- 0)
+    const int image = min(max(__builtin_amdgcn_readfirstlane(tile_row) >> a.img_shift, 0), a.images - 1);
+    const size_t krow0 = ((size_t)b + (size_t)image) * a.Nk;
     const unsigned k_bytes = (unsigned)((((size_t)a.Nk - 1) * a.ldk + a.C - hoff) * sizeof(float));
     const unsigned v_bytes = (unsigned)((((size_t)a.Nk - 1) * a.ldv + a.C - hoff) * sizeof(float));
-    const __amdgpu_buffer_rsrc_t r_k = __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(a.k + (size_t)b * a.Nk * a.ldk + hoff), 0, k_bytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t r_v = __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(a.v + (size_t)b * a.Nk * a.ldv + hoff), 0, v_bytes, 0x00020000);
+    const __amdgpu_buffer_rsrc_t r_k = __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(a.k + krow0 * a.ldk + hoff), 0, k_bytes, 0x00020000);
+    const __amdgpu_buffer_rsrc_t r_v = __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(a.v + krow0 * a.ldv + hoff), 0, v_bytes, 0x00020000);
     const int k_row = a.ldk * (int)sizeof(float), v_row = a.ldv * (int)sizeof(float);
 
     float4 ring[NB][4];
@@ -316,17 +334,15 @@ extern "C" int sige_hip_attention_wide_supported(int Nq, int Nk, int C, int head
     return (Nq % 16 == 0 && d % 16 == 0 && d > 160 && d <= 512) ? 1 : 0;
 }
 
-extern "C" int sige_hip_attention_wide_f32(const float *q, int ldq, const float *k, int ldk, const float *v, int ldv,
-                                           int B, int Nq, int Nk, int C, int heads, float scale, float *out, int ldo, void *stream) {
-    SIGE_PLAN_HOOK(sige_hip_attention_wide_f32, q, ldq, k, ldk, v, ldv, B, Nq, Nk, C, heads, scale, out, ldo, stream);
-    if (B < 0 || Nq < 0 || Nk <= 0 || C <= 0 || heads <= 0) return SIGE_HIP_EINVAL;
-    if (ldq < C || ldk < C || ldv < C || ldo < C) return SIGE_HIP_EINVAL;
-    if ((long)B * Nq == 0) return SIGE_HIP_OK;
-    if (!q || !k || !v || !out) return SIGE_HIP_EINVAL;
+namespace sige {
+
+// Both entry points: q [B,Nq,ldq] against k / v of Nk keys per batch -- or, with `tiles` (B = 1), per image of 2^img_shift rows.
+static int launch_attention_wide(const float *q, int ldq, const float *k, int ldk, const float *v, int ldv, int B, int Nq, int Nk, int C,
+                                 int heads, float scale, float *out, int ldo, const int32_t *tiles, int img_shift, int images, void *stream) {
     if (!sige_hip_attention_wide_supported(Nq, Nk, C, heads)) return SIGE_HIP_EUNSUPPORTED;
     auto al = [](const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; };
     if (!al(q) || !al(k) || !al(v) || !al(out) || ((ldq | ldk | ldv | ldo) & 3)) return SIGE_HIP_EUNSUPPORTED;
-    // (32-bit byte offsets into one batch's K / V)
+    // (32-bit byte offsets into one batch's -- one image's -- K / V)
     if ((size_t)Nk * ldk * sizeof(float) >= 0x7fffffffu || (size_t)Nk * ldv * sizeof(float) >= 0x7fffffffu) return SIGE_HIP_EUNSUPPORTED;
     const int d = C / heads, G = (d + 63) / 64;
     const long units = (long)B * heads * (Nq / 16);
@@ -351,6 +367,7 @@ extern "C" int sige_hip_attention_wide_f32(const float *q, int ldq, const float 
     a.Nq = Nq; a.Nk = Nk; a.C = C; a.heads = heads; a.d = d;
     a.q_tiles = Nq / 16; a.ksplit = ksplit;
     a.scale_log2e = scale * 1.44269504088896341f;
+    a.tiles = tiles; a.img_shift = img_shift; a.images = images;
     const dim3 grid((unsigned)ksplit, (unsigned)(Nq / 16), (unsigned)(B * heads));
     switch (G) {
         case 3: attention_wide_kernel<3><<<grid, 256, 0, st>>>(a); break;
@@ -362,4 +379,34 @@ extern "C" int sige_hip_attention_wide_f32(const float *q, int ldq, const float 
         default: return SIGE_HIP_EUNSUPPORTED;
     }
     return launch_status();
+}
+
+}  // namespace sige
+
+extern "C" int sige_hip_attention_wide_f32(const float *q, int ldq, const float *k, int ldk, const float *v, int ldv,
+                                           int B, int Nq, int Nk, int C, int heads, float scale, float *out, int ldo, void *stream) {
+    SIGE_PLAN_HOOK(sige_hip_attention_wide_f32, q, ldq, k, ldk, v, ldv, B, Nq, Nk, C, heads, scale, out, ldo, stream);
+    if (B < 0 || Nq < 0 || Nk <= 0 || C <= 0 || heads <= 0) return SIGE_HIP_EINVAL;
+    if (ldq < C || ldk < C || ldv < C || ldo < C) return SIGE_HIP_EINVAL;
+    if ((long)B * Nq == 0) return SIGE_HIP_OK;
+    if (!q || !k || !v || !out) return SIGE_HIP_EINVAL;
+    return launch_attention_wide(q, ldq, k, ldk, v, ldv, B, Nq, Nk, C, heads, scale, out, ldo, nullptr, 0, 1, stream);
+}
+
+// Stacked edits (sige_hip_set_edit_batch): the queries are the tokens of T active 4x4 tiles of the tall image [1,C,H,W] = E images
+// of H / E rows, and tile t attends to the (H / E) W keys of ITS image only -- one launch for the tiles of all E edits, the
+// per-edit tile counts never on the host.
+extern "C" int sige_hip_attention_wide_tiles_f32(const float *q, int ldq, const float *k, int ldk, const float *v, int ldv,
+                                                 const int32_t *active_indices, int T, int H, int W, int C, int heads, float scale,
+                                                 float *out, int ldo, void *stream) {
+    SIGE_PLAN_HOOK(sige_hip_attention_wide_tiles_f32, q, ldq, k, ldk, v, ldv, active_indices, T, H, W, C, heads, scale, out, ldo, stream);
+    if (T < 0 || H <= 0 || W <= 0 || C <= 0 || heads <= 0) return SIGE_HIP_EINVAL;
+    if (ldq < C || ldk < C || ldv < C || ldo < C) return SIGE_HIP_EINVAL;
+    if (T == 0) return SIGE_HIP_OK;
+    if (!q || !k || !v || !out || !active_indices) return SIGE_HIP_EINVAL;
+    const int s = stacked_shift(H);
+    if (s < 0) return SIGE_HIP_EUNSUPPORTED;  // (one image's height: a power of two >= 4)
+    const int E = s > 0 ? H >> s : 1;         // (shift 0 = no edit batch: one image, base 0 -- the other entry's launch)
+    if ((long)T * 16 > 0x7fffffffL || (long)(H / E) * W > 0x7fffffffL) return SIGE_HIP_EUNSUPPORTED;
+    return launch_attention_wide(q, ldq, k, ldk, v, ldv, 1, 16 * T, (H / E) * W, C, heads, scale, out, ldo, active_indices, s, E, stream);
 }

@@ -159,6 +159,7 @@ _SIGNATURES = {
     "sige_hip_attention_tokens_f16c": (_c_int, [_c_vp] * 3 + [_c_int] * 5 + [ctypes.c_float, _c_vp, _c_vp]),
     "sige_hip_attention_wide_supported": (_c_int, [_c_int] * 4),
     "sige_hip_attention_wide_f32": (_c_int, [_c_vp, _c_int] * 3 + [_c_int] * 5 + [ctypes.c_float, _c_vp, _c_int, _c_vp]),
+    "sige_hip_attention_wide_tiles_f32": (_c_int, [_c_vp, _c_int] * 3 + [_c_vp] + [_c_int] * 5 + [ctypes.c_float, _c_vp, _c_int, _c_vp]),
     # fp16-stored caches
     "sige_hip_gather_nhwc_f16": (
         _c_int, [_c_vp] + [_c_int] * 6 + [_c_vp, _c_int] + [_c_vp, _c_int, _c_int] * 2 + [_c_int, _c_vp, _c_vp]),
@@ -2615,26 +2616,42 @@ def _token_rows(t: torch.Tensor):
 
 
 def attention_wide(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, heads: int, scale: float,
-                   out: Optional[torch.Tensor] = None) -> Optional[torch.Tensor]:
+                   out: Optional[torch.Tensor] = None, tiles=None) -> Optional[torch.Tensor]:
     """attention_tokens for WIDE heads (160 < d <= 512, d % 16 == 0; include/sige_hip.h: sige_hip_attention_wide_f32): ONE launch.
     q [B,Nq,C], k / v [B,Nk,C] may be strided views whose last dimension is contiguous (the two halves of a [B,Nk,2C] tensor,
     a column slice): they are read in place.  `out`: a [B,Nq,C] destination of the same kind (default: a fresh tensor).  None if
-    unsupported (the caller runs the bmm / softmax / bmm chain)."""
+    unsupported (the caller runs the bmm / softmax / bmm chain).
+
+    `tiles` = (active_indices, H, W): the keys of a query tile's OWN image (stacked edits, set_edit_batch;
+    sige_hip_attention_wide_tiles_f32).  q [1,16T,C] are the tokens of the T 4x4 tiles of the Gather's device int32 [T,2] list,
+    k / v [1,H*W,C] the rows of the tall image of get_edit_batch() images; tile t reads the (H/E)*W keys of image
+    origin_row // (H/E).  T = 0: `out` without a launch."""
     if not (q.is_cuda and q.dtype == k.dtype == v.dtype == torch.float32 and q.dim() == k.dim() == v.dim() == 3):
         return None
     B, Nq, C = q.shape
     if tuple(k.shape) != tuple(v.shape) or k.shape[0] != B or k.shape[2] != C:
         return None
     Nk = k.shape[1]
-    if not lib().sige_hip_attention_wide_supported(Nq, Nk, C, heads):
+    if tiles is not None:
+        idx, H, W = tiles
+        if not (idx.is_cuda and idx.dtype == torch.int32 and idx.dim() == 2 and idx.shape[1] == 2 and idx.is_contiguous()):
+            raise ValueError("attention_wide: tiles = (device int32 [T,2] index list, H, W)")
+        if B != 1 or Nq != 16 * idx.shape[0] or Nk != int(H) * int(W):
+            raise ValueError("attention_wide: with tiles, q is [1,16T,C] and k / v are [1,H*W,C]")
+    elif not lib().sige_hip_attention_wide_supported(Nq, Nk, C, heads):
         return None
     (q, ldq), (k, ldk), (v, ldv) = _token_rows(q), _token_rows(k), _token_rows(v)
     if out is None:
         out = torch.empty((B, Nq, C), dtype=torch.float32, device=q.device)
     elif tuple(out.shape) != (B, Nq, C) or out.dtype != torch.float32 or _token_rows(out)[0] is not out:
         raise ValueError("attention_wide: `out` must be a [B,Nq,C] fp32 tensor with contiguous rows")
-    status = lib().sige_hip_attention_wide_f32(q.data_ptr(), ldq, k.data_ptr(), ldk, v.data_ptr(), ldv, B, Nq, Nk, C, heads,
-                                               float(scale), out.data_ptr(), out.stride(1), _stream(q))
+    if tiles is not None:
+        status = lib().sige_hip_attention_wide_tiles_f32(q.data_ptr(), ldq, k.data_ptr(), ldk, v.data_ptr(), ldv, idx.data_ptr(),
+                                                         Nq // 16, int(H), int(W), C, heads, float(scale), out.data_ptr(),
+                                                         max(out.stride(1), C), _stream(q))
+    else:
+        status = lib().sige_hip_attention_wide_f32(q.data_ptr(), ldq, k.data_ptr(), ldk, v.data_ptr(), ldv, B, Nq, Nk, C, heads,
+                                                   float(scale), out.data_ptr(), out.stride(1), _stream(q))
     if status == UNSUPPORTED:
         return None
     _check(status, "attention_wide")

@@ -20,6 +20,12 @@ over a [B,Nq,HW] score tensor, bmm, with its reshapes and copies); a shape the a
 fused q and K | V.  With in-place scatters (SIGEModel.set_scatter_inplace) the persistent K | V tensor and the attention's output rows
 are allocated by set_masks() / set_mode(), never inside a forward; without, every Scatter returns a fresh tensor as the reference's does.  Batch 1 (the reference's sparse mode calls scale.view(1, -1, 1, 1): one cached original).
 
+Stacked edits (sige_amd/stacked.py): under `stacked.edit_batch(model, E)` both models take [E, ...] inputs in sparse
+mode -- the first conv at batch E, every block on the tall image [1,C,E*H,W], the tail per image at batch E again -- and the
+attention is hip.attention_wide(tiles=...): the queries of an edit's tiles against THAT edit's H * W keys, one launch for all E
+edits.  What has no per-image form (C <= 160, NATIVE_ATTENTION off, NCHW, CPU, sparse_update, a shape the entry refuses) raises a
+RuntimeError that names stacked edits: the chain would softmax over the keys of all E images.
+
 The encoder (SIGEEncoder, sige_model.py:177) is built from the same blocks: SparseVAEEncoder, at the end of the file."""
 from dataclasses import dataclass
 from typing import Tuple
@@ -130,6 +136,7 @@ class VAEAttnBlock(SIGEModule):
         self.affine = {}      # cache_id -> (scale, shift) as [1,C,1,1]
         self._attn_out = None  # [1, 16 * active tiles, C]: the attention launch's output rows (alloc_buffers)
         self.plain = False
+        self.edit_batch = 1    # stacked edits (sige_amd/stacked.py: `with stacked.edit_batch(model, E)`)
 
     def clear_cache(self):
         self.affine = {}
@@ -219,8 +226,12 @@ class VAEAttnBlock(SIGEModule):
         if self.mode not in ("sparse", "profile"):
             raise NotImplementedError("Unknown mode [%s]!!!" % self.mode)
         s, t = self.affine[self.cache_id]
+        stacked = self._stacked(x)
+        if stacked and not (self.mode == "sparse" and NATIVE_ATTENTION and _fused_layout(x) and x.shape[0] == 1):
+            # (the chain below would softmax over the keys of all E images: a wrong answer, not an error)
+            self._refuse_stacked("sparse mode with NATIVE_ATTENTION on the channels-last fp32 GPU tall tensor [1,C,E*H,W]")
         if self.mode == "sparse" and NATIVE_ATTENTION and _fused_layout(x) and x.shape[0] == 1:
-            out = self._sparse_fused(x, s, t)
+            out = self._sparse_fused(x, s, t, stacked)
             if out is not None:
                 return out
         # the reference's module chain: CPU, NCHW, NATIVE_ATTENTION off
@@ -233,20 +244,42 @@ class VAEAttnBlock(SIGEModule):
         h = h.reshape(b, c, -1, bs, bs).permute(0, 2, 1, 3, 4).reshape(-1, c, bs, bs)
         return self.out_scatter(self.proj_out(h), x)
 
-    def _sparse_fused(self, x, s, t):
-        """None: no fused form as things stand (the caller runs the module chain)."""
+    # ---- stacked edits (sige_amd/stacked.py) ---------------------------------------------------------------------------------------
+    def _stacked(self, x) -> bool:
+        if self.edit_batch > 1:
+            return True
+        if not x.is_cuda:
+            return False
+        from .. import hip
+
+        return hip.get_edit_batch() > 1
+
+    def _refuse_stacked(self, needs: str):
+        raise RuntimeError("VAEAttnBlock: stacked edits attend per image -- the queries of an edit's tiles against that edit's own "
+                           "keys --, which only hip.attention_wide(tiles=...) does: %s (this block has %d channels)" % (needs, self.ch))
+
+    def _sparse_fused(self, x, s, t, stacked=False):
+        """None: no fused form as things stand (the caller runs the module chain).  `stacked`: x is the tall image of E edits
+        (hip.set_edit_batch) and there is no chain to fall back to -- whatever has no per-image form raises."""
         from .. import hip
 
         kv_cache = self._fused_cache()
         C, g = self.ch, self.gather
+        if stacked:
+            if C <= 160:
+                self._refuse_stacked("more than 160 channels (hip.attention_tokens has no per-image form)")
+            if kv_cache is None or C % 4 or self.sparse_update:
+                self._refuse_stacked("a channels-last K | V cache of the full pass, channels a multiple of 4, no sparse_update")
         if kv_cache is None or C % 4 or self.sparse_update:
             return None
         T = int(g.active_indices.shape[0])
         if T == 0:
-            return None
+            return None  # (no query: the chain has nothing to attend with, under stacked edits too)
         q = self.q(self.gather(x, s, t))  # [T,C,4,4] channels-last tiles = the token matrix [16 T, C]
         kv = self.kv_scatter.forward_fused(self.folded_kv(), self.gather(x, s, t))  # persistent [1,2C,H,W]: new K | V on the tiles
         if not (hip.is_cl(q) and hip.is_cl(kv)):
+            if stacked:
+                self._refuse_stacked("channels-last tiles and K | V")
             return None
         _, _, H, W = kv.shape
         qt = q.permute(0, 2, 3, 1).reshape(1, 16 * T, C)            # (views: no copy on either side)
@@ -259,7 +292,12 @@ class VAEAttnBlock(SIGEModule):
             if buf is None or buf.shape[1] != 16 * T or buf.device != x.device:
                 # (not reached after set_masks() / set_mode(): only a block driven module by module allocates here)
                 buf = self._attn_out = torch.empty((1, 16 * T, C), dtype=torch.float32, device=x.device)
-            o = hip.attention_wide(qt, tok[:, :, :C], tok[:, :, C:], 1, scale, out=buf)
+            # stacked edits: kv is the tall image; tile t's keys are the rows of the image its origin row lies in, found inside the launch
+            o = hip.attention_wide(qt, tok[:, :, :C], tok[:, :, C:], 1, scale, out=buf,
+                                   tiles=(g.active_indices, H, W) if stacked else None)
+        if o is None and stacked:
+            self._refuse_stacked("a shape sige_hip_attention_wide_tiles_f32 takes (one image's height a power of two >= 4; K | V is "
+                                 "%d x %d for the whole edit batch)" % (H, W))
         if o is None:
             # a shape the entry does not take: the reference's bmm chain on the fused q and K | V
             o = self._chain(qt, kv[:, :C], kv[:, C:]).permute(0, 2, 1)
@@ -267,10 +305,31 @@ class VAEAttnBlock(SIGEModule):
         return self.out_scatter(self.proj_out(h), x)
 
 
+def _enter_stacked(model, x, h, E: int):
+    """Stacked edits (sige_amd/stacked.py): x is [E,c,H,W], h = conv_in(x) a whole-image op at batch E; from here to the output norm
+    every tensor is the tall image [1,C,E*H,W] -- the same bytes -- and every sparse module works on it unchanged."""
+    if model.mode != "sparse" or x.shape[0] != E:
+        raise RuntimeError("stacked edits: sparse mode, one input image per edit (edit batch %d, mode %r, input batch %d)"
+                           % (E, model.mode, x.shape[0]))
+    if not _fused_layout(h):
+        raise RuntimeError("stacked edits: channels-last fp32 GPU tensors only")
+    from ..stacked import tall
+
+    return tall(h)
+
+
+def _leave_stacked(h, E: int):
+    """The tall image back as [E,C,H,W] (the same bytes) for the per-image tail."""
+    from ..stacked import untall
+
+    return untall(h, E)
+
+
 class SparseVAEDecoder(SIGEModel):
     def __init__(self, cfg: VAEDecoderConfig = VAEDecoderConfig()):
         super().__init__()
         self.cfg = cfg
+        self.edit_batch = 1  # stacked edits (sige_amd/stacked.py: `with stacked.edit_batch(model, E)`)
         ch, mult = cfg.ch, tuple(cfg.ch_mult)
         self.num_resolutions, self.num_res_blocks = len(mult), cfg.num_res_blocks
         cur = ch * mult[-1]
@@ -350,6 +409,9 @@ class SparseVAEDecoder(SIGEModel):
         h = self.conv_in(z)
         if z.is_contiguous(memory_format=torch.channels_last) and not z.is_contiguous():
             h = h.contiguous(memory_format=torch.channels_last)  # (MIOpen may hand back NCHW for 4 input channels)
+        E = self.edit_batch
+        if E > 1:
+            h = _enter_stacked(self, z, h, E)
         h = self.mid.block_1(h)
         h = self.mid.attn_1(h)
         h = self.mid.block_2(h)
@@ -361,6 +423,8 @@ class SparseVAEDecoder(SIGEModel):
                     h = stage.attn[i](h)
             if lvl != 0:
                 h = stage.upsample(h)
+        if E > 1:
+            h = _leave_stacked(h, E)  # (norm_out and conv_out are per image: [E,C,1,1] affines at B = E)
         return self._head(h)
 
 
@@ -426,6 +490,7 @@ class SparseVAEEncoder(SIGEModel):
         self.norm_out = nn.GroupNorm(cfg.groups, cur, eps=cfg.eps)
         self.conv_out = nn.Conv2d(cur, 2 * cfg.z_channels if cfg.double_z else cfg.z_channels, 3, 1, 1)
         self._h0_buf = None  # conv_in's output on the active windows (alloc_buffers)
+        self.edit_batch = 1  # stacked edits (sige_amd/stacked.py: `with stacked.edit_batch(model, E)`)
 
     # ---- bookkeeping: as SparseVAEDecoder ----------------------------------------------------------------------------------------
     def _attn_blocks(self):
@@ -449,6 +514,8 @@ class SparseVAEEncoder(SIGEModel):
         for m in self._attn_blocks():
             m.alloc_buffers()
         g = self._conv_in_windows()
+        if self.__dict__.get("_sige_stacked"):
+            g = None  # (stacked caches: conv_in is a whole-image op at batch E, the window form is for single edits)
         if g is not None and g.active_indices.is_cuda:
             shape = (1, self.conv_in.out_channels) + tuple(g.input_res)
             buf = self._h0_buf
@@ -525,6 +592,9 @@ class SparseVAEEncoder(SIGEModel):
 
     def _body(self, x):
         h = self._conv_in(x)
+        E = self.edit_batch
+        if E > 1:
+            h = _enter_stacked(self, x, h, E)
         for lvl in range(self.num_resolutions):
             stage = self.down[lvl]
             for i, block in enumerate(stage.block):
@@ -535,7 +605,8 @@ class SparseVAEEncoder(SIGEModel):
                 h = stage.downsample(h)
         h = self.mid.block_1(h)
         h = self.mid.attn_1(h)
-        return self.mid.block_2(h)
+        h = self.mid.block_2(h)
+        return _leave_stacked(h, E) if E > 1 else h  # (the tail is per image: [E,C,1,1] affines, [E,z,h,w] noise, at B = E)
 
     def _tail(self, h, quant_conv=None, posterior=False, noise=None, scale_factor=1.0):
         """norm_out (a TRUE GroupNorm of the edited activation, sige_model.py:272-275) -> SiLU -> conv_out [-> quant_conv [-> the

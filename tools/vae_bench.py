@@ -2,6 +2,7 @@
 """The SD VAE decoder (configs/sige.yaml's ddconfig, latent 64 x 64 -> 512 x 512) on the MI355X: fp32, channels-last, hipGraph replay.
 
     python tools/vae_bench.py            -> profiles/sd_vae_decoder_bench.json
+    python tools/vae_bench.py --stacked  -> profiles/sd_vae_stacked_bench.json ("decoder"): stacked edits, tools/vae_stacked.py
 
 Per square edit of 1.2 / 5 / 15 % of the 512 x 512 image, in ONE child process so that the comparison stays inside one session:
   (a) the sparse forward;
@@ -25,6 +26,8 @@ import sys
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, REPO)
+from tools import vae_stacked  # noqa: E402  (--stacked)
+
 PEAK_F32_MFMA = 157.3e12
 LATENT = 64
 
@@ -159,7 +162,10 @@ def main():
     ap.add_argument("--reps", type=int, default=4)
     ap.add_argument("--limit", type=int, default=240, help="seconds per child")
     ap.add_argument("--out", default=os.path.join(REPO, "profiles", "sd_vae_decoder_bench.json"))
+    vae_stacked.add_arguments(ap)
     a = ap.parse_args()
+    if a.stacked:
+        return vae_stacked.dispatch("decoder", a, __file__)
     if a.ratio is not None:
         return child(a)
     from sige_amd import build

@@ -3,6 +3,7 @@
 hipGraph replay.
 
     python tools/vae_encoder_bench.py            -> profiles/sd_vae_encoder_bench.json
+    python tools/vae_encoder_bench.py --stacked  -> profiles/sd_vae_stacked_bench.json ("encoder"): stacked edits, tools/vae_stacked.py
 
 Per square edit of 1.2 / 5 / 15 % of the image, in ONE child process so that the comparison stays inside one session:
   (a) the sparse forward through moments(): the tail is group_norm_affine + ONE launch of hip.conv3x3_latent_head_cl with quant_conv
@@ -29,6 +30,8 @@ import sys
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, REPO)
+from tools import vae_stacked  # noqa: E402  (--stacked)
+
 PEAK_F32_MFMA = 157.3e12  # 256 CUs x 4 SIMDs x 64 FLOP / clk x 2.4 GHz
 PEAK_HBM = 8.0e12         # bytes / s
 IMAGE, LATENT = 512, 64
@@ -182,7 +185,10 @@ def main():
     ap.add_argument("--reps", type=int, default=8)
     ap.add_argument("--limit", type=int, default=240, help="seconds per child")
     ap.add_argument("--out", default=os.path.join(REPO, "profiles", "sd_vae_encoder_bench.json"))
+    vae_stacked.add_arguments(ap)
     a = ap.parse_args()
+    if a.stacked:
+        return vae_stacked.dispatch("encoder", a, __file__)
     if a.head:
         return head_alone(a)
     if a.ratio is not None:
