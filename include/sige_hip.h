@@ -531,7 +531,13 @@ int sige_hip_scatter_with_block_residual_nhwc_f32(
  *   active_indices == NULL (N = 0, tiles NULL): every cell of res -- the dense levels.
  * SIGE_HIP_EINVAL: null x with work to do, non-positive dims, a tile count without a list.  SIGE_HIP_EUNSUPPORTED: C % 4,
  * odd H or W in DOWN, tiles in UP (the fused gather reads the half-resolution tensor: upsample2x), one of scale / shift
- * alone, a scatter stride other than 1, pointers not 16-byte aligned, B * N or the rows of a launch > 65535, stacked edits.  B * N == 0: SIGE_HIP_OK, nothing launched. */
+ * alone, a scatter stride other than 1, pointers not 16-byte aligned, B * N or the rows of a launch > 65535.  B * N == 0:
+ * SIGE_HIP_OK, nothing launched (answered before the checks below).
+ * Stacked edits (sige_hip_set_edit_batch(E)): x is the tall image [B,E*hp,W,C], the list holds the tiles of all E edits at the
+ * resampled resolution.  A tile belongs to the image its window's third row lies in (the rule of sige_hip_reduce_mask_i32 and
+ * of the conv staging): a window row of `tiles` beyond that image is exactly 0, never the neighbour's pooled pixels, and the
+ * rows of its `res` cells are clipped to that image.  The forms without a list need no seam (an even hp).
+ * SIGE_HIP_EUNSUPPORTED: E does not divide H, hp is not a power of two or < 4; a list in DOWN with hp < 8. */
 enum { SIGE_HIP_RESAMPLE_DOWN = 0, SIGE_HIP_RESAMPLE_UP = 1 };
 int sige_hip_resample_tiles_nhwc_f32(const float *x, int B, int C, int H, int W, int mode,
                                      const int32_t *active_indices, int N, int bH, int bW,

@@ -99,6 +99,10 @@ __device__ __forceinline__ float affine_act(float z, const Bcast4 &scale, const 
 // log2 of the height of ONE image at a launch whose tensors are H rows tall; -1 = the launch cannot honour the mode.
 int stacked_shift(int H);
 
+// Stacked edits: a tile belongs to the image its window's THIRD row lies in (the rule of reduce_mask.hip and of the conv kernels'
+// staging).  First row of that image for a tile whose window starts at row h0 (0 when the mode is off).
+__device__ __forceinline__ int seam_lo(int h0, int hp_shift) { return hp_shift ? (((h0 + 2) >> hp_shift) << hp_shift) : 0; }
+
 // (api.hip) every entry point reports how many kernels it launched: sige_hip_launch_count()
 void note_launches(int kernels);
 

@@ -42,8 +42,7 @@ __device__ __forceinline__ float4 affine_act4(float4 z, const float *scale, cons
 
 // Stacked edits (sige_hip_set_edit_batch: E images stacked along H, hp_shift = log2 of one image's height): a tile belongs to the
 // image its window's THIRD row lies in (the rule of reduce_mask.hip and of the conv kernels' staging) and rows of its window
-// beyond that image are zero padding, not the neighbour's pixels.  First row of the tile's image (0 when the mode is off).
-__device__ __forceinline__ int seam_lo(int h0, int hp_shift) { return hp_shift ? (((h0 + 2) >> hp_shift) << hp_shift) : 0; }
+// beyond that image are zero padding, not the neighbour's pixels: seam_lo (common.hpp).
 
 // ------------------------------------------------------------------ gather ----
 // x [B,H,W,C] -> out [B*N, bH, bW, C]; scale/shift [1|B, C]

@@ -18,6 +18,13 @@
 // per item and z / N per workgroup.  A lane beyond its row reads the row's last item and an out-of-image position its clamped
 // neighbour, both dropped by a select: no load sits behind an exec-masked branch.  The scatter's stride is 1 (the
 // block's convs are 3x3 / stride 1): (offset + origin) / stride is a plain sum.
+//
+// Stacked edits (sige_hip_set_edit_batch: the tensors are E images stacked along H, the list holds the tiles of all of them): a
+// tile belongs to the image its window's third row lies in (common.hpp: seam_lo, at the RESAMPLED resolution).  The rows of that
+// image, [hlo, hhi), take the place of [0, Ho) in the test above: a window row beyond them is zero padding, a shortcut cell
+// beyond them is not written.  Both are derived from the scalar origin: two more wave-uniform integers, the loads stay clamped
+// to the tensor and selected.  The forms without a list pool or repeat whole images (an even per-image height: no 2x2 window
+// and no x2 repeat straddles a seam) and run as they are.
 #include <algorithm>
 
 #include "common.hpp"
@@ -37,6 +44,7 @@ struct ResampleArgs {
     int tile_rows;           // bH when tiles are written, else 0
     int offH, offW, strH, strW, rH, rW;
     float *res;              // [B,Ho,Wo,C] or nullptr
+    int hp_shift;            // stacked edits, tiled forms: log2 of one image's height at the resampled resolution (0 = off)
 };
 
 __device__ __forceinline__ float4 rt_ld4(const float *p) { return *reinterpret_cast<const float4 *>(p); }
@@ -79,7 +87,9 @@ __global__ __launch_bounds__(kRT) void resample_tiles_kernel(ResampleArgs a) {
     const unsigned s = ic / C4;
     const int c = (int)(ic - s * C4) * 4;
     const int ow = ow0 + (int)s;
-    const bool ok = oh >= 0 && oh < a.Ho && ow >= 0 && ow < a.Wo;
+    // (stacked edits: the rows of the tile's own image, from the scalar origin; [0, Ho) otherwise)
+    const int hlo = max(seam_lo(i0, a.hp_shift), 0), hhi = a.hp_shift ? min(hlo + (1 << a.hp_shift), a.Ho) : a.Ho;
+    const bool ok = oh >= hlo && oh < hhi && ow >= 0 && ow < a.Wo;
     const int ohc = min(max(oh, 0), a.Ho - 1), owc = min(max(ow, 0), a.Wo - 1);  // clamped address, load, select
     const size_t rowC = (size_t)a.W * a.C;  // one source row
     const float *p = a.x + ((size_t)b * a.H + (UP ? (ohc >> 1) : 2 * ohc)) * rowC + (size_t)(UP ? (owc >> 1) : 2 * owc) * a.C + c;
@@ -125,13 +135,15 @@ extern "C" int sige_hip_resample_tiles_nhwc_f32(const float *x, int B, int C, in
     if (res && active_indices && (strideH != 1 || strideW != 1)) return SIGE_HIP_EUNSUPPORTED;  // (3x3 / stride-1 blocks only)
     if (tiles && (up || !active_indices)) return SIGE_HIP_EUNSUPPORTED;  // (UP tiles: the fused gather's upsample2x read)
     if ((scale == nullptr) != (shift == nullptr)) return SIGE_HIP_EUNSUPPORTED;
-    if (stacked_shift(H) != 0) return SIGE_HIP_EUNSUPPORTED;               // (stacked edits: not built)
     if (!active_indices && N != 0) return SIGE_HIP_EINVAL;                   // (a tile count without a list)
     if (B == 0 || (active_indices && N == 0)) return SIGE_HIP_OK;
     if (!tiles && !res) return SIGE_HIP_OK;
     if (!x) return SIGE_HIP_EINVAL;
     if (!rt_al16(x) || !rt_al16(tiles) || !rt_al16(res) || !rt_al16(scale) || !rt_al16(shift)) return SIGE_HIP_EUNSUPPORTED;
-
+    // stacked edits: one image's height at the resampled resolution is a power of two >= 4 (the seam test is a shift)
+    const int src_shift = stacked_shift(H);
+    if (src_shift < 0) return SIGE_HIP_EUNSUPPORTED;
+    if (src_shift && !up && active_indices && src_shift < 3) return SIGE_HIP_EUNSUPPORTED;  // (a pooled image of < 4 rows)
 
     ResampleArgs a;
     a.x = x; a.B = B; a.C = C; a.H = H; a.W = W;
@@ -140,6 +152,7 @@ extern "C" int sige_hip_resample_tiles_nhwc_f32(const float *x, int B, int C, in
     a.scale = scale; a.shift = shift; a.tiles = tiles; a.tile_rows = tiles ? bH : 0;
     a.offH = offsetH; a.offW = offsetW; a.strH = strideH; a.strW = strideW; a.rH = rH; a.rW = rW;
     a.res = res;
+    a.hp_shift = (src_shift && active_indices) ? (up ? src_shift + 1 : src_shift - 1) : 0;
     const int res_rows = !res ? 0 : (active_indices ? rH : a.Ho);
     const long rows = (long)a.tile_rows + res_rows, zs = active_indices ? (long)B * N : (long)B;
     if (rows > 65535 || zs > 65535) return SIGE_HIP_EUNSUPPORTED;             // (grid y / z)

@@ -10,6 +10,10 @@ that sees the tiles of all E edits.  The kernels only need to know where one ima
 padding): hip.set_edit_batch(E).  Whole-image ops (first / last conv, attention, the output GroupNorm) run with batch E on the
 same memory.
 
+Models that take stacked edits (an `edit_batch` attribute, read by their forward): DDPMSparseUNet, SpadeGenerator and
+SubMobileSpadeGenerator (GauGAN), SparseVAEDecoder / SparseVAEEncoder (SD VAE), PDSparseUNet (Progressive Distillation).  What has no
+seam-aware launch raises a RuntimeError that names stacked edits; nothing falls back to a chain that would mix the images.
+
     stacked.stack_caches(model, E)              # after the full pass on the original (B = 1)
     stacked.set_masks(model, [pyramid_of_edit_0, ..., pyramid_of_edit_{E-1}])
     with stacked.edit_batch(model, E):

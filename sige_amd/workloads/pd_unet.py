@@ -19,7 +19,13 @@ stands.  What differs from the DDPM workload:
     hip.attention_tokens launch over the token view of the channels-last tensor, then proj_out with the residual.
 
 On the CPU, in NCHW and on any backend without the fused channels-last path every block runs the reference's expression order
-(affine -> swish -> avg_pool2d / interpolate -> gather)."""
+(affine -> swish -> avg_pool2d / interpolate -> gather).
+
+Stacked edits (sige_amd/stacked.py): under `stacked.edit_batch(model, E)` the model takes [E,3,H,W] in sparse mode.
+conv_in (image by image, see forward), norm_out and conv_out are whole-image ops on [E,C,H,W]; in between every tensor is the tall image [1,C,E*H,W] and every block runs its fused
+launches on it (hip.resample_tiles with the tiles of all E images; attention over the same bytes seen as [E, tokens, 3c], one launch).
+There is no chain to fall back to: NCHW, the CPU, FUSED_RESAMPLE = False, a block without a fused form and a shape the attention entry
+does not take raise a RuntimeError that names stacked edits."""
 import math
 from dataclasses import dataclass
 from typing import Optional, Tuple
@@ -76,6 +82,28 @@ def _fused_layout(*ts) -> bool:
     return all(t.is_cuda and t.dtype == torch.float32 and hip.is_cl(t) for t in ts)
 
 
+def _refuse_stacked(who: str, needs: str):
+    """Stacked edits (sige_amd/stacked.py) have no chain to fall back to: the torch ops would pool, pad and attend across the seams
+    of the tall image.  Whatever has no seam-aware launch raises."""
+    raise RuntimeError("%s: stacked edits run on the library's seam-aware launches only -- %s" % (who, needs))
+
+
+class _per_image:
+    """Around the whole-image ops at batch E (norm_out, conv_out): the library sees E separate images, no seams inside them."""
+
+    def __enter__(self):
+        from .. import hip
+
+        self.prev = hip.get_edit_batch()
+        hip.set_edit_batch(1)
+
+    def __exit__(self, *exc):
+        from .. import hip
+
+        hip.set_edit_batch(self.prev)
+        return False
+
+
 class PDResBlock(SIGEModule):
     def __init__(self, cfg: PDConfig, cin: int, cout: int, sparse: bool, resample: Optional[str] = None):
         super().__init__()
@@ -107,7 +135,8 @@ class PDResBlock(SIGEModule):
             self.scatter = Scatter(self.main_gather)
         self.affine = {}       # cache_id -> (scale1, shift1, scale2, shift2) as [1,C,1,1]
         self.plain = False
-        self._res_like = None  # (shape, device) of the shortcut buffer of a sparse resampling block, from the full pass
+        self.edit_batch = 1    # stacked edits (sige_amd/stacked.py: `with stacked.edit_batch(model, E)`)
+        self._res_like = None  # (shape of ONE image, device) of the shortcut buffer of a sparse resampling block, from the full pass
         self._res_buf = None
 
     def clear_cache(self):
@@ -116,10 +145,15 @@ class PDResBlock(SIGEModule):
     # ---- the persistent shortcut buffer of a sparse resampling block -----------------------------------------------------------
     def alloc_buffers(self):
         """(PDSparseUNet.set_masks / set_mode) the shortcut buffer of a sparse resampling block, allocated OUTSIDE any forward: a
-        forward may run under a graph capture.  Zero-filled once; afterwards stale outside the current mask's cells."""
+        forward may run under a graph capture.  Zero-filled once; afterwards stale outside the current mask's cells.  Under
+        stacked edits (stacked.set_masks: hip.get_edit_batch() is E) the buffer is the tall image, E times the rows."""
         if self._res_like is None:
             return
         shape, device = self._res_like
+        if device.type == "cuda":
+            from .. import hip
+
+            shape = (shape[0], shape[1], shape[2] * hip.get_edit_batch(), shape[3])
         buf = self._res_buf
         if buf is None or tuple(buf.shape) != tuple(shape) or buf.device != device:
             self._res_buf = torch.zeros(shape, dtype=torch.float32, device=device).contiguous(memory_format=torch.channels_last)
@@ -135,6 +169,8 @@ class PDResBlock(SIGEModule):
         """`x` may be a pair (h, skip): the up path's torch.cat."""
         pair = x if isinstance(x, (tuple, list)) else None
         if self.mode == "full":
+            if self.edit_batch > 1:
+                _refuse_stacked("PDResBlock", "sparse mode (the full pass is one original)")
             return self._full(torch.cat(pair, dim=1) if pair else x, temb)
         if self.mode in ("sparse", "profile"):
             parts = list(pair) if pair else [x]
@@ -142,6 +178,9 @@ class PDResBlock(SIGEModule):
                 out = self._sparse_fused(parts)
                 if out is not None:
                     return out
+            if self.edit_batch > 1:
+                _refuse_stacked("PDResBlock", "sparse mode on channels-last fp32 GPU tensors, and a fused form of this block "
+                                "(resample %r, %d -> %d channels, FUSED_RESAMPLE %s)" % (self.resample, self.cin, self.cout, FUSED_RESAMPLE))
             return self._sparse_chain(torch.cat(pair, dim=1) if pair else x)
         raise NotImplementedError("Unknown mode [%s]!!!" % self.mode)
 
@@ -228,7 +267,7 @@ class PDResBlock(SIGEModule):
                 return None
             if res is None or tuple(res.shape) != want or res.device != x.device:
                 # (not reached after set_masks() / set_mode(): only a model driven module by module allocates here)
-                self._res_like = (want, x.device)
+                self._res_like = ((want[0], want[1], want[2] // hip.get_edit_batch(), want[3]), x.device)
                 self.alloc_buffers()
                 res = self._res_buf
             idx = g.indices_on(x.device)
@@ -306,6 +345,7 @@ class PDAttnBlock(SIGEModule):
         self.proj_out = nn.Conv2d(heads * head_dim, ch, 1, 1, 0)
         self.affine = {}
         self.plain = False
+        self.edit_batch = 1  # stacked edits (sige_amd/stacked.py): E images stacked along H, attention is per image
 
     def clear_cache(self):
         self.affine = {}
@@ -333,21 +373,32 @@ class PDAttnBlock(SIGEModule):
         if self.mode not in ("sparse", "profile"):
             raise NotImplementedError("Unknown mode [%s]!!!" % self.mode)
         s, t = self.affine[self.cache_id]
+        E = self.edit_batch
         if self.mode == "sparse" and _fused_layout(x):
             from .. import hip
 
             qkv = fused_conv2d(self.qkv, x, s, t, "identity")
             b, _, hh, ww = qkv.shape
             c = self.heads * self.head_dim
+            if E > 1 and (b != 1 or hh % E):
+                _refuse_stacked("PDAttnBlock", "the tall image of %d edits, got %s" % (E, tuple(x.shape)))
+            # stacked edits: the tall image is E images -- tokens attend within their own image: the same bytes as [E, hp W, 3c],
+            # the one launch at batch E
+            tb, tn = (E, (hh // E) * ww) if E > 1 else (b, hh * ww)
             out = None
             if hip.is_cl(qkv):
-                tok = qkv.permute(0, 2, 3, 1).reshape(b, hh * ww, 3 * c)  # (a view: the channels-last tensor IS the token matrix)
+                tok = qkv.permute(0, 2, 3, 1).reshape(tb, tn, 3 * c)  # (a view: the channels-last tensor IS the token matrix)
                 out = hip.attention_tokens(tok[:, :, :c], tok[:, :, c:2 * c], tok[:, :, 2 * c:], self.heads, self.head_dim ** -0.5)
             if out is not None:
                 h = out.reshape(b, hh, ww, c).permute(0, 3, 1, 2)  # (channels-last again, no copy)
+            elif E > 1:
+                _refuse_stacked("PDAttnBlock", "a shape hip.attention_tokens takes (%d heads of %d, %d tokens per image): the chain "
+                                "would attend over the keys of all %d images" % (self.heads, self.head_dim, tn, E))
             else:
                 h = self._attention(qkv).contiguous(memory_format=torch.channels_last)
             return fused_conv2d(self.proj_out, h, residual=x)
+        if E > 1:
+            _refuse_stacked("PDAttnBlock", "sparse mode on channels-last fp32 GPU tensors")
         return self.proj_out(self._attention(self.qkv(x * s + t))) + x
 
 
@@ -355,6 +406,7 @@ class PDSparseUNet(SIGEModel):
     def __init__(self, cfg: PDConfig = PDConfig()):
         super().__init__()
         self.cfg = cfg
+        self.edit_batch = 1  # stacked edits (sige_amd/stacked.py: `with stacked.edit_batch(model, E)`)
         ch, mult = cfg.ch, tuple(cfg.ch_mult)
         self.ch, self.temb_ch = ch, cfg.temb_ch
         self.num_resolutions, self.num_res_blocks = len(mult), cfg.num_res_blocks
@@ -476,12 +528,38 @@ class PDSparseUNet(SIGEModel):
             return fused_conv2d(self._padded_conv_out(), h, so, to, "swish")[:, :co]
         return self.conv_out(F.silu(self.norm_out(h)))
 
+    def _enter_stacked(self, x, h0, E: int):
+        if self.mode != "sparse" or x.shape[0] != E:
+            raise RuntimeError("stacked edits: sparse mode, one input image per edit (edit batch %d, mode %r, input batch %d)"
+                               % (E, self.mode, x.shape[0]))
+        if not _fused_layout(x, h0):
+            raise RuntimeError("stacked edits: channels-last fp32 GPU tensors only")
+        low = self.resolution >> (self.num_resolutions - 1)
+        if self.resolution & (self.resolution - 1) or low < 4:
+            # (the seam test of every launch is a shift: sige_hip_set_edit_batch)
+            raise RuntimeError("stacked edits: every level's height must be a power of two of at least 4 rows (%d ... %d)"
+                               % (self.resolution, low))
+        from ..stacked import tall
+
+        return tall(h0)
+
     def forward(self, x: torch.Tensor, logsnr: torch.Tensor) -> torch.Tensor:
         assert x.shape[2] == x.shape[3] == self.resolution
         temb = self._temb(logsnr)
-        h0 = input_conv2d(self.conv_in, x) if self.mode == "sparse" else self.conv_in(x)
+        if self.mode == "sparse" and self.edit_batch > 1 and x.shape[0] > 1 and x.is_cuda:
+            # stacked edits: the first conv image by image.  ONE launch of the library's first conv at batch 8 (64 output channels,
+            # 128 x 128) returned wrong pixels in some images, differently from run to run, while its launches on one image each
+            # are right (found with tools/pd_bench.py --stacked, cause not found)
+            h0 = torch.cat([input_conv2d(self.conv_in, x[e:e + 1]) for e in range(x.shape[0])])
+        else:
+            h0 = input_conv2d(self.conv_in, x) if self.mode == "sparse" else self.conv_in(x)
         if x.is_contiguous(memory_format=torch.channels_last) and not x.is_contiguous():
             h0 = h0.contiguous(memory_format=torch.channels_last)  # (MIOpen may hand back NCHW for 3 input channels)
+        E = self.edit_batch
+        if E > 1:
+            # stacked edits (sige_amd/stacked.py): x is [E,3,H,W], conv_in a whole-image op at batch E; from here to the output norm
+            # every tensor is the tall image [1,C,E*H,W] -- the same bytes -- and every block works on it unchanged
+            h0 = self._enter_stacked(x, h0, E)
         hs = [h0]
         for lvl, stage in enumerate(self.down):
             for i, block in enumerate(stage.block):
@@ -504,4 +582,9 @@ class PDSparseUNet(SIGEModel):
                     h = stage.attn[i](h)
             if lvl != 0:
                 h = stage.upsample(h, temb)
+        if E > 1:
+            from ..stacked import untall
+
+            with _per_image():  # (norm_out and conv_out are per image: [E,C,1,1] affines at B = E)
+                return self._head(untall(h, E))
         return self._head(h)
