@@ -907,6 +907,27 @@ int sige_hip_attention_tokens_f32(const float *q, const float *k, const float *v
 int sige_hip_attention_tokens_f16c(const float *q, const float *k, const float *v, int B, int Nq, int Nk, int C,
                                    int heads, float scale, float *out, void *stream);
 
+/* ---- ... both with the keys of a query tile's OWN image (stacked edits, sige_hip_set_edit_batch) --------------------------------
+ * The queries are the tokens of T active 4x4 tiles of the tall image [1,C,H,W] = E images of H / E rows (E = the calling
+ * thread's edit batch): q, out [16 T, C], tile t = rows 16 t .. 16 t + 15; k, v [H W, C], the rows of the tall image;
+ * active_indices = the Gather's device int32 [T,2] list, row origin first.  B = 1.
+ * Tile t belongs to image e = origin_row >> log2(H / E), clamped into [0, E - 1] (a bad list cannot move an address outside
+ * k / v), and attends to rows [e (H / E) W, (e + 1) (H / E) W) only: the kernels of the two entries above -- a workgroup is one
+ * 16-query tile of one head -- with the K and V base pointers and both buffer descriptors moved to the image's first row and
+ * spanning ONE image's bytes, so tail masking, the key clamps, the zeros of an out-of-range load and the 2 GiB limit are per
+ * image (Nk = (H / E) W).  One launch for the tiles of all E edits; no per-edit count ever reaches the host.  The index list is
+ * the per-edit lists one after the other, so consecutive tiles of a head share an image's K / V.  E = 1: the results of
+ * sige_hip_attention_tokens_f32 / _f16c bit for bit (the same kernel, the list unread).  _f16c keeps the arithmetic contract
+ * stated at sige_hip_attention_tokens_f16c.
+ * Status, in this order: SIGE_HIP_EINVAL: T < 0, non-positive H / W / C / heads.  T == 0: SIGE_HIP_OK, nothing launched.
+ * SIGE_HIP_EINVAL: null pointers (the index list among them) with work to do.  SIGE_HIP_EUNSUPPORTED: H / E not a power of two
+ * >= 4 (or E does not divide H), and everything sige_hip_attention_tokens_f32 refuses with Nq = 16 T, Nk = (H / E) W: the shape
+ * predicate, pointers not 16-byte aligned, one image's K or V >= 2 GiB, heads * T past 2^31.                                    */
+int sige_hip_attention_tokens_tiles_f32(const float *q, const float *k, const float *v, const int32_t *active_indices,
+                                        int T, int H, int W, int C, int heads, float scale, float *out, void *stream);
+int sige_hip_attention_tokens_tiles_f16c(const float *q, const float *k, const float *v, const int32_t *active_indices,
+                                         int T, int H, int W, int C, int heads, float scale, float *out, void *stream);
+
 /* ---- the same attention for WIDE heads: 160 < d <= 512, d % 16 == 0 (the SD VAE decoder's single 512-channel head) -----
  * q [B,Nq,ldq], k [B,Nk,ldk], v [B,Nk,ldv], out [B,Nq,ldo]: every operand comes with its ROW STRIDE in elements (>= C, a
  * multiple of 4; batch stride = rows * row stride), so k and v may be the two halves of one [B,Nk,2C] tensor and q / out
@@ -991,8 +1012,8 @@ int sige_hip_convert_f32_f16(const float *src, void *dst, size_t n, void *stream
  * 10 % edit has, and a launch leaves the launch-bound regime.  sige_hip_set_edit_batch(E) tells the library where the seams are:
  * a halo row beyond a tile's own image is zero padding (not the neighbour image's pixels) in the channels-last fused gather /
  * scatter_gather -> conv kernels, the dense-layer conv, the standalone channels-last gather / scatter_gather, the SPADE
- * modulation and sige_hip_scatter_gather_split_nhwc_f32, and a query tile of sige_hip_attention_wide_tiles_f32 attends to its
- * own image's keys; entry points whose kernels have no seam test (the NCHW forms) return
+ * modulation and sige_hip_scatter_gather_split_nhwc_f32, and a query tile of sige_hip_attention_wide_tiles_f32,
+ * sige_hip_attention_tokens_tiles_f32 or sige_hip_attention_tokens_tiles_f16c attends to its own image's keys; entry points whose kernels have no seam test (the NCHW forms) return
  * SIGE_HIP_EUNSUPPORTED while E > 1; per-pixel helpers (nearest resize by an integer factor, act_split, the dense SPADE
  * modulation) need none.  One image's height must be a power of two at every resolution.  Per host thread; 1 = off (default).  Whole-image ops (conv_in / conv_out, attention, GroupNorm) are simply
  * called with B = E on the same memory (sige_amd/stacked.py).  The mask pipeline follows: sige_hip_reduce_mask_i32 lets a

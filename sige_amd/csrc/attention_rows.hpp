@@ -26,4 +26,19 @@ __device__ __forceinline__ float max_over_rows(float v) {
 // key (m = -inf, where M may be -inf too) weighs nothing.
 __device__ __forceinline__ float merge_weight(float m, float M) { return m == -INFINITY ? 0.f : __builtin_amdgcn_exp2f(m - M); }
 
+// Stacked edits in the token kernels (sige_hip_attention_tokens_tiles_f32 / _f16c): the image of query tile `qtile` -- its origin row
+// tiles[2 qtile] of the tall image >> log2 of one image's height, clamped into [0, images - 1] so that no index list can move the
+// K / V descriptors outside k / v (the rule of attention_wide.hip).  The index is the same in every lane and made uniform: ONE
+// scalar load per workgroup, a shift and two scalar min / max in front of the pointer arithmetic -- no branch, no division.
+// TILES = false is the constant 0: the kernels compile to what they were.
+template <bool TILES>
+__device__ __forceinline__ int tile_image(const int32_t *__restrict__ tiles, int qtile, int img_shift, int images) {
+    if constexpr (TILES) {
+        const int row = __builtin_amdgcn_readfirstlane(tiles[2 * __builtin_amdgcn_readfirstlane(qtile)]);
+        return min(max(row >> img_shift, 0), images - 1);
+    } else {
+        return 0;
+    }
+}
+
 }  // namespace sige

@@ -34,12 +34,17 @@ namespace sige {
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
-template <int UNITS, int QT>  // 16-channel units covering the head dimension (d <= 16 * UNITS); 16-query tiles per workgroup
+// TILES (stacked edits, sige_hip_attention_tokens_tiles_f32): B = 1, query tile t is the 4x4 tile with origin row tiles[2t] of the tall
+// image of `images` images of 2^img_shift rows, and k / v / Nk are those of ITS image.  false: the three arguments are not read and
+// the kernel is the one it was.
+template <int UNITS, int QT, bool TILES = false>  // 16-channel units covering the head dimension (d <= 16 * UNITS); 16-query tiles per workgroup
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(UNITS * QT <= 3 ? 4 : 1)))  // (SD's d = 40: 1 008 workgroups on 1 024 slots)
 void attention_tokens_kernel(const float *__restrict__ q, const float *__restrict__ k,
                                                                const float *__restrict__ v, float *__restrict__ out,
                                                                int Nq, int Nk, int C, int heads, int d, float scale_log2e,
-                                                               int q_tiles, int xcd_pairs) {
+                                                               int q_tiles, int xcd_pairs,
+                                                               const int32_t *__restrict__ tiles, int img_shift, int images) {
+    static_assert(!TILES || QT == 1, "two query tiles of a workgroup may belong to two images");
     constexpr int DT = UNITS;            // 16-column tiles of O
     constexpr int OS = UNITS * 16 + 4;   // padded row of the merge buffer
     constexpr int QR = 16 * QT;          // query rows of the workgroup
@@ -65,8 +70,9 @@ void attention_tokens_kernel(const float *__restrict__ q, const float *__restric
     const int head = pair % heads, b = pair / heads;
     const int q0 = qtile * QR;
     const size_t hoff = (size_t)head * d;
-    const float *kb = k + (size_t)b * Nk * C + hoff;
-    const float *vb = v + (size_t)b * Nk * C + hoff;
+    const size_t kv0 = ((size_t)b + tile_image<TILES>(tiles, qtile, img_shift, images)) * Nk * C + hoff;
+    const float *kb = k + kv0;
+    const float *vb = v + kv0;
 
     // Q of this lane: row j of every query tile, channels 16u + 4kq .. +3 of every unit (zeros beyond d; a tile past Nq -- the
     // last workgroup of an odd tile count -- reads the last tile's rows and is not stored)
@@ -101,6 +107,11 @@ void attention_tokens_kernel(const float *__restrict__ q, const float *__restric
     // unit) reads the next head's channels -- or, past the end of this batch's [Nk, C] matrix, the zeros a buffer load returns out of
     // range --, a lane whose key lies past Nk (the tail block) the last key's; what it reads meets a ZERO on the other side of the
     // product (Q is zero on padded channels, P is zero on masked keys) or lands in a padded column of O that is never stored
+    // TILES: base and size are those of the tile's IMAGE (kb / vb start at the image's first row, Nk is one image's key count), so the
+    // tail mask, the min(key, Nk - 1) clamps, the out-of-range zeros and the 2 GiB limit are per image.  Re-read for the last head of
+    // the last row of image e < E - 1: a lane past d points at the first channels of image e + 1's first row, which lie past
+    // kv_bytes of THIS descriptor -- it reads zeros, not the neighbour's keys; on every other row of the image it reads the next
+    // row's first channels (this image's), on every other head the next head's.  All finite, all against a zero: the argument holds.
     const unsigned kv_bytes = (unsigned)(((size_t)Nk * C - hoff) * sizeof(float));
     const __amdgpu_buffer_rsrc_t r_k = __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(kb), 0, kv_bytes, 0x00020000);
     const __amdgpu_buffer_rsrc_t r_v = __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(vb), 0, kv_bytes, 0x00020000);
@@ -233,11 +244,11 @@ void attention_tokens_kernel(const float *__restrict__ q, const float *__restric
 // wave cycles are issue stalls behind the matrix pipe -- what is left is the pipe itself, the padding, and 1 008 workgroups on
 // 1 024 slots.
 // (the row maximum over the 4 lane rows, max_over_rows: attention_rows.hpp -- shared with the fp16-operand form)
-template <int UNITS>
+template <int UNITS, bool TILES = false>  // (TILES: as in attention_tokens_kernel)
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(UNITS <= 3 ? 4 : 1)))
 void attention_tokens_t_kernel(const float *__restrict__ q, const float *__restrict__ k, const float *__restrict__ v,
                                float *__restrict__ out, int Nq, int Nk, int C, int heads, int d, float scale_log2e,
-                               int q_tiles, int xcd_pairs) {
+                               int q_tiles, int xcd_pairs, const int32_t *__restrict__ tiles, int img_shift, int images) {
     constexpr int DT = UNITS;           // 16-channel tiles of O
     constexpr int OS = UNITS * 16 + 4;  // padded row of the merge buffer (a multiple of 4 floats: 16-byte rows)
     __shared__ float m_lds[4][16], l_lds[4][4][16];
@@ -257,8 +268,9 @@ void attention_tokens_t_kernel(const float *__restrict__ q, const float *__restr
     const int head = pair % heads, b = pair / heads;
     const int q0 = qtile * 16;
     const size_t hoff = (size_t)head * d;
-    const float *kb = k + (size_t)b * Nk * C + hoff;
-    const float *vb = v + (size_t)b * Nk * C + hoff;
+    const size_t kv0 = ((size_t)b + tile_image<TILES>(tiles, qtile, img_shift, images)) * Nk * C + hoff;
+    const float *kb = k + kv0;
+    const float *vb = v + kv0;
 
     // Q of this lane = the B operand: query j, channels 16u + 4kq .. +3 of every unit (zeros beyond d)
     float4 qr[UNITS];
@@ -388,14 +400,14 @@ extern "C" int sige_hip_attention_tokens_supported(int Nq, int Nk, int C, int he
     return (Nq % 16 == 0 && d % 4 == 0 && d <= 160 && C % 4 == 0) ? 1 : 0;
 }
 
-extern "C" int sige_hip_attention_tokens_f32(const float *q, const float *k, const float *v, int B, int Nq, int Nk, int C,
-                                             int heads, float scale, float *out, void *stream) {
-    SIGE_PLAN_HOOK(sige_hip_attention_tokens_f32, q, k, v, B, Nq, Nk, C, heads, scale, out, stream);
-    if (B < 0 || Nq < 0 || Nk <= 0 || C <= 0 || heads <= 0) return SIGE_HIP_EINVAL;
-    if ((long)B * Nq == 0) return SIGE_HIP_OK;
-    if (!q || !k || !v || !out) return SIGE_HIP_EINVAL;
+namespace sige {
+
+// Both entry points: q [B,Nq,C] against k / v of Nk keys per batch -- or, with `tiles` (B = 1), per image of 2^img_shift rows.
+static int launch_attention_tokens(const float *q, const float *k, const float *v, int B, int Nq, int Nk, int C, int heads, float scale,
+                                   float *out, const int32_t *tiles, int img_shift, int images, void *stream) {
     if (!sige_hip_attention_tokens_supported(Nq, Nk, C, heads)) return SIGE_HIP_EUNSUPPORTED;
     auto al = [](const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; };
+    // (32-bit byte offsets into one batch's -- one image's -- K / V)
     if (!al(q) || !al(k) || !al(v) || !al(out) || (size_t)Nk * C * sizeof(float) >= 0x7fffffffu) return SIGE_HIP_EUNSUPPORTED;
     const int d = C / heads;
     const int units = (d + 15) / 16;
@@ -403,9 +415,10 @@ extern "C" int sige_hip_attention_tokens_f32(const float *q, const float *k, con
     hipStream_t st = as_stream(stream);
     // forms: 0 (automatic) = the transposed-score kernel (round 6); 1 = round 4's 16 queries per workgroup with P through LDS;
     // 2 = 32 queries per workgroup (two query tiles share every K / V fragment a wave loads; d <= 96) -- measured equal to form 1
-    // at SD's shapes (profiles/r4i_bench_sd.json).  1 and 2 are kept for the A/B in the measurement build.
+    // at SD's shapes (profiles/r4i_bench_sd.json).  1 and 2 are kept for the A/B in the measurement build.  With `tiles` the two
+    // tiles of form 2 may belong to two images: knob 2 is form 1 there.
     const int knob = tuning(SIGE_HIP_TUNE_ATTENTION_FORM);
-    const int form = (knob == 2 && units <= 6) ? 2 : (knob == 1 ? 1 : 0);
+    const int form = tiles ? (knob == 1 || knob == 2 ? 1 : 0) : (knob == 2 && units <= 6) ? 2 : (knob == 1 ? 1 : 0);
     const int pairs = B * heads, t16 = Nq / 16, t32 = (Nq + 31) / 32;
     if ((long)pairs * t16 > 0x7fffffffL) return SIGE_HIP_EUNSUPPORTED;
 #ifdef SIGE_ATTENTION_PLAIN_ORDER
@@ -413,11 +426,15 @@ extern "C" int sige_hip_attention_tokens_f32(const float *q, const float *k, con
 #else
     const int xp = pairs % 8 == 0 ? pairs / 8 : 0;
 #endif
+#define SIGE_ATT_ARGS(QT) q, k, v, out, Nq, Nk, C, heads, d, sl, QT, xp, tiles, img_shift, images
 #define SIGE_ATT_GO(U)                                                                                             \
     do {                                                                                                           \
-        if (form == 0) attention_tokens_t_kernel<U><<<dim3(t16 * pairs), 256, (size_t)4 * 16 * (U * 16 + 4) * sizeof(float), st>>>(q, k, v, out, Nq, Nk, C, heads, d, sl, t16, xp); \
-        else if (form == 2) attention_tokens_kernel<(U <= 6 ? U : 1), 2><<<dim3(t32 * pairs), 256, (size_t)4 * 32 * (U * 16 + 4) * sizeof(float), st>>>(q, k, v, out, Nq, Nk, C, heads, d, sl, t32, xp); \
-        else attention_tokens_kernel<U, 1><<<dim3(t16 * pairs), 256, (size_t)4 * 16 * (U * 16 + 4) * sizeof(float), st>>>(q, k, v, out, Nq, Nk, C, heads, d, sl, t16, xp); \
+        const size_t lds = (size_t)4 * 16 * (U * 16 + 4) * sizeof(float);                                          \
+        if (tiles && form == 0) attention_tokens_t_kernel<U, true><<<dim3(t16 * pairs), 256, lds, st>>>(SIGE_ATT_ARGS(t16)); \
+        else if (tiles) attention_tokens_kernel<U, 1, true><<<dim3(t16 * pairs), 256, lds, st>>>(SIGE_ATT_ARGS(t16)); \
+        else if (form == 0) attention_tokens_t_kernel<U><<<dim3(t16 * pairs), 256, lds, st>>>(SIGE_ATT_ARGS(t16)); \
+        else if (form == 2) attention_tokens_kernel<(U <= 6 ? U : 1), 2><<<dim3(t32 * pairs), 256, 2 * lds, st>>>(SIGE_ATT_ARGS(t32)); \
+        else attention_tokens_kernel<U, 1><<<dim3(t16 * pairs), 256, lds, st>>>(SIGE_ATT_ARGS(t16));               \
     } while (0)
     switch (units) {
         case 1: SIGE_ATT_GO(1); break;
@@ -431,5 +448,33 @@ extern "C" int sige_hip_attention_tokens_f32(const float *q, const float *k, con
         default: return SIGE_HIP_EUNSUPPORTED;
     }
 #undef SIGE_ATT_GO
+#undef SIGE_ATT_ARGS
     return launch_status();
+}
+
+}  // namespace sige
+
+extern "C" int sige_hip_attention_tokens_f32(const float *q, const float *k, const float *v, int B, int Nq, int Nk, int C,
+                                             int heads, float scale, float *out, void *stream) {
+    SIGE_PLAN_HOOK(sige_hip_attention_tokens_f32, q, k, v, B, Nq, Nk, C, heads, scale, out, stream);
+    if (B < 0 || Nq < 0 || Nk <= 0 || C <= 0 || heads <= 0) return SIGE_HIP_EINVAL;
+    if ((long)B * Nq == 0) return SIGE_HIP_OK;
+    if (!q || !k || !v || !out) return SIGE_HIP_EINVAL;
+    return launch_attention_tokens(q, k, v, B, Nq, Nk, C, heads, scale, out, nullptr, 0, 1, stream);
+}
+
+// Stacked edits (sige_hip_set_edit_batch): the queries are the tokens of T active 4x4 tiles of the tall image [1,C,H,W] = E images
+// of H / E rows, and tile t attends to the (H / E) W keys of ITS image only -- one launch for the tiles of all E edits, the
+// per-edit tile counts never on the host.  E = 1 (shift 0): the launch of sige_hip_attention_tokens_f32, the list unread.
+extern "C" int sige_hip_attention_tokens_tiles_f32(const float *q, const float *k, const float *v, const int32_t *active_indices,
+                                                   int T, int H, int W, int C, int heads, float scale, float *out, void *stream) {
+    SIGE_PLAN_HOOK(sige_hip_attention_tokens_tiles_f32, q, k, v, active_indices, T, H, W, C, heads, scale, out, stream);
+    if (T < 0 || H <= 0 || W <= 0 || C <= 0 || heads <= 0) return SIGE_HIP_EINVAL;
+    if (T == 0) return SIGE_HIP_OK;
+    if (!q || !k || !v || !out || !active_indices) return SIGE_HIP_EINVAL;
+    const int s = stacked_shift(H);
+    if (s < 0) return SIGE_HIP_EUNSUPPORTED;  // (one image's height: a power of two >= 4)
+    const int E = s > 0 ? H >> s : 1;
+    if ((long)T * 16 > 0x7fffffffL || (long)(H / E) * W > 0x7fffffffL) return SIGE_HIP_EUNSUPPORTED;
+    return launch_attention_tokens(q, k, v, 1, 16 * T, (H / E) * W, C, heads, scale, out, s > 0 ? active_indices : nullptr, s, E, stream);
 }

@@ -69,11 +69,12 @@ __device__ __forceinline__ void load_row(float (&dst)[N], __amdgpu_buffer_rsrc_t
     }
 }
 
-template <int U32, int DT>  // 32-channel units of the scores (d <= 32 * U32), 16-channel tiles of O (d <= 16 * DT)
+// TILES (stacked edits, sige_hip_attention_tokens_tiles_f16c): the keys of the query tile's own image, as in attention_tokens.hip
+template <int U32, int DT, bool TILES = false>  // 32-channel units of the scores (d <= 32 * U32), 16-channel tiles of O (d <= 16 * DT)
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(DT <= 3 ? 4 : 1)))
 void attention_tokens_f16_kernel(const float *__restrict__ q, const float *__restrict__ k, const float *__restrict__ v,
                                  float *__restrict__ out, int Nq, int Nk, int C, int heads, int d, float scale_log2e,
-                                 int q_tiles, int xcd_pairs) {
+                                 int q_tiles, int xcd_pairs, const int32_t *__restrict__ tiles, int img_shift, int images) {
     constexpr int OS = DT * 16 + 4;  // padded row of the merge buffer (a multiple of 4 floats: 16-byte rows)
     // V: a lane loads VC consecutive channels of a key in ONE load, so row i of O^T's tile n = VC g + c is channel 16 VC g + VC i + c
     // (the rows of an MFMA's A operand may be any channels; the merge puts them back)
@@ -97,8 +98,9 @@ void attention_tokens_f16_kernel(const float *__restrict__ q, const float *__res
     const int head = pair % heads, b = pair / heads;
     const int q0 = qtile * 16;
     const size_t hoff = (size_t)head * d;
-    const float *kb = k + (size_t)b * Nk * C + hoff;
-    const float *vb = v + (size_t)b * Nk * C + hoff;
+    const size_t kv0 = ((size_t)b + tile_image<TILES>(tiles, qtile, img_shift, images)) * Nk * C + hoff;
+    const float *kb = k + kv0;
+    const float *vb = v + kv0;
 
     // Q of this lane = the B operand of the scores: query j, slot e of unit u = channel 16 (2u + (e >> 2)) + 4kq + (e & 3) (zeros beyond d)
     f16x8 qh[U32];
@@ -126,6 +128,9 @@ void attention_tokens_f16_kernel(const float *__restrict__ q, const float *__res
     // row's, or the zeros a buffer load returns past the end of this batch's [Nk, C] matrix; a lane whose key lies past Nk the last
     // key's.  What it reads is a finite fp16 value (the contract) that meets a ZERO on the other side of the product or lands in a
     // padded column of O that is never stored.
+    // TILES: kb / vb and kv_bytes are those of the tile's IMAGE (Nk = one image's keys), so the tail mask, the clamps and the
+    // out-of-range zeros are per image; past the last head of the last row of image e < E - 1 lie image e + 1's first channels, which
+    // are past THIS descriptor's kv_bytes: zeros, as at the end of the tensor (attention_tokens.hip has the argument in full).
     const unsigned kv_bytes = (unsigned)(((size_t)Nk * C - hoff) * sizeof(float));
     const __amdgpu_buffer_rsrc_t r_k = __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(kb), 0, kv_bytes, 0x00020000);
     const __amdgpu_buffer_rsrc_t r_v = __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(vb), 0, kv_bytes, 0x00020000);
@@ -245,12 +250,11 @@ void attention_tokens_f16_kernel(const float *__restrict__ q, const float *__res
 
 using namespace sige;
 
-extern "C" int sige_hip_attention_tokens_f16c(const float *q, const float *k, const float *v, int B, int Nq, int Nk, int C,
-                                              int heads, float scale, float *out, void *stream) {
-    SIGE_PLAN_HOOK(sige_hip_attention_tokens_f16c, q, k, v, B, Nq, Nk, C, heads, scale, out, stream);
-    if (B < 0 || Nq < 0 || Nk <= 0 || C <= 0 || heads <= 0) return SIGE_HIP_EINVAL;
-    if ((long)B * Nq == 0) return SIGE_HIP_OK;
-    if (!q || !k || !v || !out) return SIGE_HIP_EINVAL;
+namespace sige {
+
+// Both entry points (as launch_attention_tokens of attention_tokens.hip): Nk keys per batch, or with `tiles` (B = 1) per image.
+static int launch_attention_tokens_f16(const float *q, const float *k, const float *v, int B, int Nq, int Nk, int C, int heads,
+                                       float scale, float *out, const int32_t *tiles, int img_shift, int images, void *stream) {
     if (!sige_hip_attention_tokens_supported(Nq, Nk, C, heads)) return SIGE_HIP_EUNSUPPORTED;
     auto al = [](const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; };
     if (!al(q) || !al(k) || !al(v) || !al(out) || (size_t)Nk * C * sizeof(float) >= 0x7fffffffu) return SIGE_HIP_EUNSUPPORTED;
@@ -261,8 +265,12 @@ extern "C" int sige_hip_attention_tokens_f16c(const float *q, const float *k, co
     const int pairs = B * heads, t16 = Nq / 16;
     if ((long)pairs * t16 > 0x7fffffffL) return SIGE_HIP_EUNSUPPORTED;
     const int xp = pairs % 8 == 0 ? pairs / 8 : 0;
-#define SIGE_ATT16_GO(U) \
-    attention_tokens_f16_kernel<(U + 1) / 2, U><<<dim3(t16 * pairs), 256, (size_t)4 * 16 * (U * 16 + 4) * sizeof(float), st>>>(q, k, v, out, Nq, Nk, C, heads, d, sl, t16, xp)
+#define SIGE_ATT16_GO(U)                                                                                                        \
+    do {                                                                                                                        \
+        const size_t lds = (size_t)4 * 16 * (U * 16 + 4) * sizeof(float);                                                       \
+        if (tiles) attention_tokens_f16_kernel<(U + 1) / 2, U, true><<<dim3(t16 * pairs), 256, lds, st>>>(q, k, v, out, Nq, Nk, C, heads, d, sl, t16, xp, tiles, img_shift, images); \
+        else attention_tokens_f16_kernel<(U + 1) / 2, U><<<dim3(t16 * pairs), 256, lds, st>>>(q, k, v, out, Nq, Nk, C, heads, d, sl, t16, xp, tiles, img_shift, images); \
+    } while (0)
     switch (units) {  // (the head sizes the fp32 entry takes)
         case 1: SIGE_ATT16_GO(1); break;
         case 2: SIGE_ATT16_GO(2); break;
@@ -276,4 +284,29 @@ extern "C" int sige_hip_attention_tokens_f16c(const float *q, const float *k, co
     }
 #undef SIGE_ATT16_GO
     return launch_status();
+}
+
+}  // namespace sige
+
+extern "C" int sige_hip_attention_tokens_f16c(const float *q, const float *k, const float *v, int B, int Nq, int Nk, int C,
+                                              int heads, float scale, float *out, void *stream) {
+    SIGE_PLAN_HOOK(sige_hip_attention_tokens_f16c, q, k, v, B, Nq, Nk, C, heads, scale, out, stream);
+    if (B < 0 || Nq < 0 || Nk <= 0 || C <= 0 || heads <= 0) return SIGE_HIP_EINVAL;
+    if ((long)B * Nq == 0) return SIGE_HIP_OK;
+    if (!q || !k || !v || !out) return SIGE_HIP_EINVAL;
+    return launch_attention_tokens_f16(q, k, v, B, Nq, Nk, C, heads, scale, out, nullptr, 0, 1, stream);
+}
+
+// Stacked edits: sige_hip_attention_tokens_tiles_f32 (attention_tokens.hip) with the arithmetic of the entry above.
+extern "C" int sige_hip_attention_tokens_tiles_f16c(const float *q, const float *k, const float *v, const int32_t *active_indices,
+                                                    int T, int H, int W, int C, int heads, float scale, float *out, void *stream) {
+    SIGE_PLAN_HOOK(sige_hip_attention_tokens_tiles_f16c, q, k, v, active_indices, T, H, W, C, heads, scale, out, stream);
+    if (T < 0 || H <= 0 || W <= 0 || C <= 0 || heads <= 0) return SIGE_HIP_EINVAL;
+    if (T == 0) return SIGE_HIP_OK;
+    if (!q || !k || !v || !out || !active_indices) return SIGE_HIP_EINVAL;
+    const int s = stacked_shift(H);
+    if (s < 0) return SIGE_HIP_EUNSUPPORTED;  // (one image's height: a power of two >= 4)
+    const int E = s > 0 ? H >> s : 1;
+    if ((long)T * 16 > 0x7fffffffL || (long)(H / E) * W > 0x7fffffffL) return SIGE_HIP_EUNSUPPORTED;
+    return launch_attention_tokens_f16(q, k, v, 1, 16 * T, (H / E) * W, C, heads, scale, out, s > 0 ? active_indices : nullptr, s, E, stream);
 }

@@ -157,6 +157,8 @@ _SIGNATURES = {
     "sige_hip_attention_tokens_supported": (_c_int, [_c_int] * 4),
     "sige_hip_attention_tokens_f32": (_c_int, [_c_vp] * 3 + [_c_int] * 5 + [ctypes.c_float, _c_vp, _c_vp]),
     "sige_hip_attention_tokens_f16c": (_c_int, [_c_vp] * 3 + [_c_int] * 5 + [ctypes.c_float, _c_vp, _c_vp]),
+    "sige_hip_attention_tokens_tiles_f32": (_c_int, [_c_vp] * 4 + [_c_int] * 5 + [ctypes.c_float, _c_vp, _c_vp]),
+    "sige_hip_attention_tokens_tiles_f16c": (_c_int, [_c_vp] * 4 + [_c_int] * 5 + [ctypes.c_float, _c_vp, _c_vp]),
     "sige_hip_attention_wide_supported": (_c_int, [_c_int] * 4),
     "sige_hip_attention_wide_f32": (_c_int, [_c_vp, _c_int] * 3 + [_c_int] * 5 + [ctypes.c_float, _c_vp, _c_int, _c_vp]),
     "sige_hip_attention_wide_tiles_f32": (_c_int, [_c_vp, _c_int] * 3 + [_c_vp] + [_c_int] * 5 + [ctypes.c_float, _c_vp, _c_int, _c_vp]),
@@ -2580,11 +2582,16 @@ def attention_residual_qv_cl(qv: torch.Tensor, keys: torch.Tensor, scale: float,
 
 
 def attention_tokens(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, heads: int, scale: float,
-                     compute: str = "f32") -> Optional[torch.Tensor]:
+                     compute: str = "f32", tiles=None) -> Optional[torch.Tensor]:
     """softmax(scale * q k^T) v per (batch, head) for token matrices q [B,Nq,C], k / v [B,Nk,C] (C = heads * d), in ONE launch
     with the heads as strides (include/sige_hip.h: sige_hip_attention_tokens_f32) -> [B,Nq,C].  None if unsupported (then the
     caller runs the reference's rearrange / bmm / softmax / bmm chain).  `compute`: "f32" exact fp32 products; "f16" fp16
-    operands with fp32 accumulation on the same fp32 tensors (sige_hip_attention_tokens_f16c states the contract)."""
+    operands with fp32 accumulation on the same fp32 tensors (sige_hip_attention_tokens_f16c states the contract).
+
+    `tiles` = (active_indices, H, W): the keys of a query tile's OWN image (stacked edits, set_edit_batch;
+    sige_hip_attention_tokens_tiles_f32 / _f16c), with the meaning it has in attention_wide: q [1,16T,C] are the tokens of the T
+    4x4 tiles of the Gather's device int32 [T,2] list, k / v [1,H*W,C] the rows of the tall image of get_edit_batch() images;
+    tile t reads the (H/E)*W keys of image origin_row // (H/E).  T = 0: an empty output without a launch."""
     if compute not in ("f32", "f16"):
         raise ValueError("attention_tokens: compute must be 'f32' or 'f16', got %r" % (compute,))
     if not (q.is_cuda and q.dtype == k.dtype == v.dtype == torch.float32 and q.dim() == k.dim() == v.dim() == 3):
@@ -2593,6 +2600,21 @@ def attention_tokens(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, heads: i
     if tuple(k.shape) != tuple(v.shape) or k.shape[0] != B or k.shape[2] != C:
         return None
     Nk = k.shape[1]
+    if tiles is not None:
+        idx, H, W = tiles
+        if not (idx.is_cuda and idx.dtype == torch.int32 and idx.dim() == 2 and idx.shape[1] == 2 and idx.is_contiguous()):
+            raise ValueError("attention_tokens: tiles = (device int32 [T,2] index list, H, W)")
+        if B != 1 or Nq != 16 * idx.shape[0] or Nk != int(H) * int(W):
+            raise ValueError("attention_tokens: with tiles, q is [1,16T,C] and k / v are [1,H*W,C]")
+        q, k, v = (t if t.is_contiguous() else t.contiguous() for t in (q, k, v))
+        out = torch.empty((B, Nq, C), dtype=torch.float32, device=q.device)
+        entry = lib().sige_hip_attention_tokens_tiles_f16c if compute == "f16" else lib().sige_hip_attention_tokens_tiles_f32
+        status = entry(q.data_ptr(), k.data_ptr(), v.data_ptr(), idx.data_ptr(), Nq // 16, int(H), int(W), C, heads, float(scale),
+                       out.data_ptr(), _stream(q))
+        if status == UNSUPPORTED:
+            return None
+        _check(status, "attention_tokens")
+        return out
     if not lib().sige_hip_attention_tokens_supported(Nq, Nk, C, heads):
         return None
     q, k, v = (t if t.is_contiguous() else t.contiguous() for t in (q, k, v))

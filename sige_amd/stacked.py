@@ -11,8 +11,13 @@ padding): hip.set_edit_batch(E).  Whole-image ops (first / last conv, attention,
 same memory.
 
 Models that take stacked edits (an `edit_batch` attribute, read by their forward): DDPMSparseUNet, SpadeGenerator and
-SubMobileSpadeGenerator (GauGAN), SparseVAEDecoder / SparseVAEEncoder (SD VAE), PDSparseUNet (Progressive Distillation).  What has no
-seam-aware launch raises a RuntimeError that names stacked edits; nothing falls back to a chain that would mix the images.
+SubMobileSpadeGenerator (GauGAN), SparseVAEDecoder / SparseVAEEncoder (SD VAE), PDSparseUNet (Progressive Distillation), SDUNet (Stable
+Diffusion).  What has no seam-aware launch raises a RuntimeError that names stacked edits; nothing falls back to a chain that would mix
+the images.
+
+SDUNet: a stacked forward is ONE sample times E edits -- the full pass runs at B = 1 (cached affines [1,C,1,1]) -- under ONE prompt (the
+cross-attention's cached text K / V are the original's) and one timestep.  The classifier-free-guidance pair in one batch (B = 2) is
+not stacked: guidance runs as two stacked forwards on two model instances that share weights.
 
     stacked.stack_caches(model, E)              # after the full pass on the original (B = 1)
     stacked.set_masks(model, [pyramid_of_edit_0, ..., pyramid_of_edit_{E-1}])

@@ -18,6 +18,12 @@ per-token maps, and the full feature map differs from the original image's only 
 K and V of every token, and a sparse pass projects ONLY the active tokens and scatters those rows into a persistent copy of
 the cached K / V (two Scatter launches per block) instead of re-projecting all HW tokens (sige_attention.py:78, attention.py:
 78-80).  The cross-attention's K / V depend on the text only and are cached as in the reference (sige_attention.py:35-42).
+
+Stacked edits (sige_amd/stacked.py): under hip.set_edit_batch(E) a tiled transformer's tensors are the tall image
+of E edits of one original, and the self-attention of a sparse block runs as hip.attention_tokens(tiles=...): a query tile reads
+the keys of ITS image only, found inside the launch from the Gather's index list.  The text K / V are the one prompt's.  Whatever
+has no per-image form (the switches listed at `_refuse_stacked`) raises a RuntimeError that names stacked edits; nothing falls
+back to a chain that would softmax over the keys of all E images.
 """
 from typing import Optional
 
@@ -82,6 +88,21 @@ def linear(lin: nn.Linear, x: torch.Tensor) -> torch.Tensor:
     return lin(x)
 
 
+def _edits(x: torch.Tensor) -> int:
+    """The library's edit batch (hip.set_edit_batch) where it can matter: GPU tensors."""
+    if not x.is_cuda:
+        return 1
+    from .. import hip
+
+    return hip.get_edit_batch()
+
+
+def _refuse_stacked(needs: str):
+    raise RuntimeError("SpatialTransformer: stacked edits attend per image -- the queries of an edit's tiles against that edit's own "
+                       "keys --, which only hip.attention_tokens(tiles=...) in a sparse-mode block with sparse_kv, NATIVE_ATTENTION and "
+                       "FUSED_TOKENS (or TOKEN_LINEAR), without NATIVE_LINEAR, does: %s" % needs)
+
+
 def _heads(t: torch.Tensor, h: int) -> torch.Tensor:
     b, n, c = t.shape
     return t.reshape(b, n, h, c // h).permute(0, 2, 1, 3).reshape(b * h, n, c // h)
@@ -120,16 +141,22 @@ class Attention(SIGEModule):
         out = torch.matmul(x.reshape(1, b * n, c), self._qkv_w)  # [3, B*n, inner]: one strided-batched GEMM
         return tuple(t.reshape(b, n, -1) for t in out.unbind(0))
 
-    def attend(self, q, k, v, bias: bool = True):
-        """`bias=False`: the output projection WITHOUT its bias (the caller's fused add + LayerNorm adds it)."""
+    def attend(self, q, k, v, bias: bool = True, tiles=None):
+        """`bias=False`: the output projection WITHOUT its bias (the caller's fused add + LayerNorm adds it).  `tiles`: stacked
+        edits -- (index list, H, W) of hip.attention_tokens; no chain stands in for a refusal there."""
         if NATIVE_ATTENTION and q.is_cuda and q.dtype == torch.float32:
             from .. import hip
 
-            out = hip.attention_tokens(q, k, v, self.heads, self.scale, compute=ATTENTION_COMPUTE)
+            out = hip.attention_tokens(q, k, v, self.heads, self.scale, compute=ATTENTION_COMPUTE, tiles=tiles)
+            if out is None and tiles is not None:
+                _refuse_stacked("the library refused the self-attention (K / V %d x %d for the whole edit batch, %d channels, %d heads)"
+                                % (tiles[1], tiles[2], q.shape[2], self.heads))
             if out is not None:
                 if not bias:
                     return F.linear(out, self.to_out[0].weight)
                 return self.to_out[1](linear(self.to_out[0], out))
+        if tiles is not None:
+            _refuse_stacked("NATIVE_ATTENTION on fp32 GPU tensors")
         if not bias:
             raise RuntimeError("attend(bias=False) needs the native attention path")
         q, k, v = _heads(q, self.heads), _heads(k, self.heads), _heads(v, self.heads)
@@ -144,7 +171,13 @@ class Attention(SIGEModule):
             k, v = linear(self.to_k, context), linear(self.to_v, context)
             if self.cache_context:
                 self.cached_k, self.cached_v = k, v
-        return self.attend(linear(self.to_q, x), k, v, bias=bias)
+        q = linear(self.to_q, x)
+        if self.cache_context and self.mode != "full" and k.shape[0] == 1 and q.shape[0] != 1:
+            # stacked edits in the untiled middle transformer: E images against the ONE prompt's cached K / V -- the attention is per
+            # query, so the E token matrices are one matrix of E n queries (a view)
+            b, n, c = q.shape
+            return self.attend(q.reshape(1, b * n, c), k, v, bias=bias).reshape(b, n, -1)
+        return self.attend(q, k, v, bias=bias)
 
 
 class GEGLU(nn.Module):
@@ -215,7 +248,8 @@ class TransformerBlock(SIGEModule):
 
         a1, a2, ff = self.attn1, self.attn2, self.ff
         (p_qkv, n_qkv), (p_o1, n_o1), (p_q2, n_q2), (p_o2, n_o2), (p_f0, n_f0), (p_f2, n_f2) = packs
-        sk, sv, (hh, ww) = kv_scatter
+        sk, sv, (hh, ww) = kv_scatter[:3]
+        tiles = _kv_tiles(kv_scatter)
         as_tiles = lambda t: t.reshape(-1, 4, 4, t.shape[2]).permute(0, 3, 1, 2)  # noqa: E731
         as_tokens = lambda t: t.permute(0, 2, 3, 1).reshape(t.shape[0], hh * ww, t.shape[1])  # noqa: E731
 
@@ -227,7 +261,10 @@ class TransformerBlock(SIGEModule):
         q_t, k_t, v_t = need(hip.token_linear(x, p_qkv, n_qkv, norm=self.norm1, parts=3), "the q | k | v projection")
         k = sk(as_tiles(k_t))
         v = sv(as_tiles(v_t))
-        o = need(hip.attention_tokens(q_t, as_tokens(k), as_tokens(v), a1.heads, a1.scale, compute=ATTENTION_COMPUTE), "the self-attention")
+        o = hip.attention_tokens(q_t, as_tokens(k), as_tokens(v), a1.heads, a1.scale, compute=ATTENTION_COMPUTE, tiles=tiles)
+        if o is None and tiles is not None:
+            _refuse_stacked("the library refused the self-attention (K / V %d x %d for the whole edit batch)" % (hh, ww))
+        need(o, "the self-attention")
         x1 = need(hip.token_linear(o, p_o1, n_o1, bias=a1.to_out[0].bias, residual=x), "attn1.to_out")
         q2 = need(hip.token_linear(x1, p_q2, n_q2, norm=self.norm2), "attn2.to_q")
         o = need(hip.attention_tokens(q2, a2.cached_k, a2.cached_v, a2.heads, a2.scale, compute=ATTENTION_COMPUTE), "the cross-attention")
@@ -244,13 +281,13 @@ class TransformerBlock(SIGEModule):
 
         a1, a2 = self.attn1, self.attn2
         _, xn = hip.add_layer_norm_tokens(x, None, None, self.norm1)
-        sk, sv, (hh, ww) = kv_scatter
+        sk, sv, (hh, ww) = kv_scatter[:3]
         as_tiles = lambda t: t.reshape(-1, 4, 4, t.shape[2]).permute(0, 3, 1, 2)  # noqa: E731
         q_t, k_t, v_t = a1.qkv(xn)
         k = sk(as_tiles(k_t))
         v = sv(as_tiles(v_t))
         as_tokens = lambda t: t.permute(0, 2, 3, 1).reshape(t.shape[0], hh * ww, t.shape[1])  # noqa: E731
-        d1 = a1.attend(q_t, as_tokens(k), as_tokens(v), bias=False)
+        d1 = a1.attend(q_t, as_tokens(k), as_tokens(v), bias=False, tiles=_kv_tiles(kv_scatter))
         x, xn = hip.add_layer_norm_tokens(x, d1, a1.to_out[0].bias, self.norm2)
         d2 = a2(xn, context=context, bias=False)
         x, xn = hip.add_layer_norm_tokens(x, d2, a2.to_out[0].bias, self.norm3)
@@ -260,7 +297,12 @@ class TransformerBlock(SIGEModule):
 
     def forward(self, x, full_x=None, context=None, kv_scatter=None):
         """x: query tokens [B,n,C]; full_x: all tokens [B,HW,C] (None: x itself); kv_scatter: (scatter_k, scatter_v, hw)
-        -- Scatter modules of the enclosing transformer for the sparse K / V refresh, or None for the reference's form."""
+        -- Scatter modules of the enclosing transformer for the sparse K / V refresh, or None for the reference's form.  A fourth
+        element is the Gather's device index list under stacked edits: hw is then the tall image's, and the self-attention reads
+        the keys of each query tile's own image."""
+        if _kv_tiles(kv_scatter) is not None and not (self.mode == "sparse" and self._fused_ok(x)):
+            _refuse_stacked("mode %r, NATIVE_ATTENTION %r, FUSED_TOKENS %r, NATIVE_LINEAR %r on contiguous fp32 GPU tokens"
+                            % (self.mode, NATIVE_ATTENTION, FUSED_TOKENS, NATIVE_LINEAR))
         if kv_scatter is not None and self.mode == "sparse" and self._fused_ok(x):
             packs = self._token_linear_packs(x) if TOKEN_LINEAR else None
             if packs is not None:
@@ -271,12 +313,12 @@ class TransformerBlock(SIGEModule):
         if kv_scatter is not None and self.mode == "full":
             ctx = xn if full_x is None else self.norm1(full_x)
             k, v = linear(a1.to_k, ctx), linear(a1.to_v, ctx)
-            sk, sv, (hh, ww) = kv_scatter
+            sk, sv, (hh, ww) = kv_scatter[:3]
             as_map = lambda t: t.reshape(t.shape[0], hh, ww, t.shape[2]).permute(0, 3, 1, 2)  # noqa: E731  [B,C,H,W] channels-last view
             sk(as_map(k)), sv(as_map(v))  # full mode: the Scatter modules remember K / V as their cached tensors
             x = a1.attend(linear(a1.to_q, xn), k, v) + x
         elif kv_scatter is not None and self.mode == "sparse":
-            sk, sv, (hh, ww) = kv_scatter
+            sk, sv, (hh, ww) = kv_scatter[:3]
             b, n, c = xn.shape
             as_tiles = lambda t: t.reshape(-1, 4, 4, t.shape[2]).permute(0, 3, 1, 2)  # noqa: E731  tokens -> [B*N,C,4,4] channels-last view
             q_t, k_t, v_t = a1.qkv(xn)
@@ -288,6 +330,13 @@ class TransformerBlock(SIGEModule):
             x = a1(xn, context=None if full_x is None else self.norm1(full_x)) + x
         x = self.attn2(self.norm2(x), context=context) + x
         return self.ff(self.norm3(x)) + x
+
+
+def _kv_tiles(kv_scatter):
+    """The `tiles` argument of hip.attention_tokens from a block's kv_scatter: (index list, H, W) under stacked edits, else None."""
+    if kv_scatter is None or len(kv_scatter) < 4 or kv_scatter[3] is None:
+        return None
+    return (kv_scatter[3], kv_scatter[2][0], kv_scatter[2][1])
 
 
 def group_norm_affine(x: torch.Tensor, norm: nn.GroupNorm):
@@ -334,6 +383,14 @@ class SpatialTransformer(SIGEModule):
     def forward(self, x: torch.Tensor, context=None) -> torch.Tensor:
         b, c, h, w = x.shape
         x_in = x
+        idx = None
+        if self.tiled and self.mode != "full" and _edits(x_in) > 1:
+            # stacked edits: x_in is the tall image of E edits; the blocks' self-attention needs the tiles' origins (the Gather's list)
+            if b != 1:
+                _refuse_stacked("E images stacked along H of ONE image (batch %d)" % b)
+            if not self.sparse_kv or self.mode != "sparse":
+                _refuse_stacked("sparse_kv in sparse mode (mode %r, sparse_kv %r)" % (self.mode, self.sparse_kv))
+            idx = self.gather.indices_on(x_in.device)
         if self.mode == "full":
             if self.tiled:
                 x = self.gather(x)
@@ -356,7 +413,7 @@ class SpatialTransformer(SIGEModule):
         else:
             full_x, q = None, tokens(x)
         for i, blk in enumerate(self.transformer_blocks):
-            kv = (self.kv_scatters[i][0], self.kv_scatters[i][1], (h, w)) if (self.sparse_kv and self.mode != "profile") else None
+            kv = (self.kv_scatters[i][0], self.kv_scatters[i][1], (h, w), idx) if (self.sparse_kv and self.mode != "profile") else None
             q = blk(q, full_x=full_x, context=context, kv_scatter=kv)
         if self.tiled and self.mode != "full":
             bs = self.gather.block_size

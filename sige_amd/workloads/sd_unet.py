@@ -10,6 +10,13 @@ Sparse mode: the timestep embedding is folded into the cached second shift (sige
 forward takes no embedding; a residual block is gather(+affine+SiLU) -> conv -> scatter_gather(+affine+SiLU) -> conv ->
 scatter with (block) residual, i.e. three fused launches on channels-last GPU tensors; the skip concatenation of the up path
 is a deferred cat read through two base pointers.
+
+Stacked edits (sige_amd/stacked.py): under `stacked.edit_batch(model, E)` the model takes [E,4,H,W] in sparse mode --
+E edits of ONE original (a full pass at B = 1) under ONE prompt.  conv_in runs at batch E, the tiled levels on the tall image
+[1,C,E*H,W], the dense middle block and the output norm / conv at batch E again; a tiled transformer's self-attention reads the keys
+of each query tile's own image (sd_transformer.py).  Classifier-free guidance in one batch (B = 2, per-sample affines) is not
+stacked: it runs as two stacked forwards on two model instances that share weights.  What has no per-image form raises a
+RuntimeError that names stacked edits.
 """
 import math
 from dataclasses import dataclass
@@ -171,6 +178,7 @@ class SDUNet(SIGEModel):
                     ds //= 2
                 self.output_blocks.append(nn.ModuleList(layers))
         self.out = nn.Sequential(GroupNorm32(32, ch), nn.SiLU(), nn.Conv2d(mc, cfg.out_channels, 3, padding=1))
+        self.edit_batch = 1  # stacked edits (sige_amd/stacked.py: `with stacked.edit_batch(model, E)`)
 
     @staticmethod
     def _run(layers, h, emb, context):
@@ -183,14 +191,47 @@ class SDUNet(SIGEModel):
                 h = layer(h)
         return h
 
+    def _check_stacked(self, x, timesteps, E: int):
+        """Stacked edits: what the tall image cannot carry is refused here, before a launch."""
+        if self.mode != "sparse" or x.dim() != 4 or x.shape[0] != E:
+            raise RuntimeError("stacked edits: sparse mode, one input image per edit (edit batch %d, mode %r, input %s)"
+                               % (E, self.mode, tuple(x.shape)))
+        if not (x.is_cuda and x.dtype == torch.float32 and x.is_contiguous(memory_format=torch.channels_last)):
+            raise RuntimeError("stacked edits: channels-last fp32 GPU tensors only")
+        levels = len(self.cfg.channel_mult) - 1
+        hp = x.shape[2] >> levels
+        if x.shape[2] != hp << levels or hp < 4 or hp & (hp - 1):
+            # (the seam test of every launch is a shift: sige_hip_set_edit_batch)
+            raise RuntimeError("stacked edits: every level's height must be a power of two of at least 4 rows (%d ... %d)"
+                               % (x.shape[2], hp))
+        if timesteps.numel() != 1 and (timesteps.numel() != E or bool((timesteps != timesteps.reshape(-1)[0]).any())):
+            raise RuntimeError("stacked edits: one timestep for all %d edits" % E)
+        for m in self.modules():
+            cached = m.affine if isinstance(m, ResBlock) and m.tiled else (m.scale, m.shift) if isinstance(m, SpatialTransformer) else None
+            if cached is not None and any(t is None or t.shape[0] != 1 for t in cached):
+                raise RuntimeError("stacked edits: E edits of ONE original -- the full pass runs at B = 1 (a cached affine of %s has %s "
+                                   "samples); classifier-free guidance runs as two stacked forwards on two model instances"
+                                   % (type(m).__name__, "no" if cached[0] is None else cached[0].shape[0]))
+
     def forward(self, x, timesteps=None, context=None):
+        E = self.edit_batch
+        if E > 1:
+            from ..stacked import tall, untall
+
+            self._check_stacked(x, timesteps, E)
+            timesteps = timesteps.reshape(-1)[:1]  # (one embedding row, broadcast over the E images of the middle block)
         emb = self.time_embed(timestep_embedding(timesteps, self.cfg.model_channels))
         hs = []
         h = x
-        for blk in self.input_blocks:
+        for i, blk in enumerate(self.input_blocks):
             h = self._run(blk, h, emb, context)
+            if E > 1 and i == 0:
+                h = tall(h)  # conv_in at batch E; from here every tiled level works on the tall image [1,C,E*H,W] (the same bytes)
             hs.append(h)
-        h = self._run(self.middle_block, h, emb, context)
+        if E > 1:  # the dense middle block at batch E: its GroupNorm statistics and its attention are per image
+            h = tall(self._run(self.middle_block, untall(h, E), emb, context))
+        else:
+            h = self._run(self.middle_block, h, emb, context)
         for blk in self.output_blocks:
             skip = hs.pop()
             first = blk[0]
@@ -199,4 +240,6 @@ class SDUNet(SIGEModel):
             else:
                 h = torch.cat([h, skip], dim=1)
             h = self._run(blk, h, emb, context)
+        if E > 1:
+            h = untall(h, E)  # (the output norm's statistics are per image)
         return self.out(h)
