@@ -518,6 +518,46 @@ int sige_hip_scatter_with_block_residual_nhwc_f32(
         const int32_t *active_indices1, const int32_t *table1, int gH1, int gW1, int N1,
         int in_place, float *out, void *stream);
 
+/* ---- committing an edit: the tiles of MANY cached tensors copied in one launch (csrc/commit_tiles.hip) ------------------------
+ * The reference accepts an edit by running the sparse forward with `sparse_update` set: every Scatter / ScatterGather then writes
+ * its result back into its cache (sige/nn/scatter.py:59-60,114-129, scatter_gather.py:65-77), a whole-tensor copy each.  Here the
+ * bytes that differ are the active tiles, and one launch executes a LIST of records, each of which says
+ *   over the tile list idx [N,2] (int32, row origin first, as sige_hip_reduce_mask_i32 gives it), write the pixels
+ *   (offset + idx) / stride + [0,r) x [0,s) of the channels-last destination dst [1,H,W,C] -- C division, clipped at the bottom
+ *   and right border (and never above or left of the image), exactly the pixels sige/cpu/scatter.cpp writes -- from
+ *     a FULL source (tile_source = 0): src is fp32 [1,H,W,C]; pixel (h,w) comes from pixel (h,w)  (a persistent Scatter output);
+ *     a TILE source (tile_source = 1): src is fp32 [N,r,s,C], the layout the tile convs write; pixel (i,j) of tile n goes to
+ *                                      (origin_n + (i,j))  (the reference's scatter without a residual).
+ *   scale / shift [C] (both or neither): the value written is SiLU(scale[c] * v + shift[c]) -- two separately rounded operations
+ *   and the SiLU of sige_hip_affine_act_nhwc_f32, bit for bit (the activated copy of a ScatterGather cache).
+ *   dst_f16 != 0: dst holds halves; the value is rounded to nearest even as sige_hip_convert_f32_f16 rounds it.
+ * The records are copied BY VALUE into the kernel arguments: no host-to-device copy, no memory of the caller is read after the call
+ * returns, and the launches can be captured.  SIGE_HIP_COMMIT_CAPACITY records fit one launch (the argument block is
+ * 8 + 76 * capacity = 3656 of the 4096 bytes a kernel may take); records with N == 0 are dropped first (idx may then be NULL), the
+ * rest run in ceil(n_nonempty / capacity) launches, in list order.  *launches (may be NULL) receives that number.
+ * Ordering: two tiles of ONE record that cover the same pixel are written in no defined order.  A full source writes the same
+ * value twice; for a tile source the reference lets the later tile win, but the lists sige_hip_reduce_mask_i32 builds do not
+ * overlap in output space, so the kernel has no ordering machinery.  Records of one call that write the same pixel of the same
+ * destination must write the same value (a ScatterWithBlockResidual's output over its main and its shortcut list).
+ * src and dst of a record must not overlap.
+ * Status, decided for the WHOLE list before anything is launched: SIGE_HIP_EINVAL: n < 0, a null list with n > 0, negative N,
+ * non-positive B / C / H / W / r / s / stride, a null src / dst / idx with N > 0, one of scale / shift without the other.
+ * SIGE_HIP_EUNSUPPORTED (no kernel for this shape; nothing is written): B != 1, C % 4, C > 16384, r or s > 16, a stride that
+ * is no power of two <= 128, |offset| > 127, H * W >= 2^31, more than 2^22 (tile, 64-channel chunk) units in one launch, src /
+ * scale / shift / an fp32 dst not 16-byte aligned, an fp16 dst not 8-byte aligned, stacked edits (sige_hip_set_edit_batch > 1:
+ * E edits of one original cannot all become the original). */
+#define SIGE_HIP_COMMIT_CAPACITY 48
+typedef struct sige_hip_commit_record {
+    const float *src;
+    void *dst;
+    const int32_t *idx;
+    const float *scale, *shift;
+    int N, B, C, H, W;
+    int r, s, offsetH, offsetW, strideH, strideW;
+    int tile_source, dst_f16;
+} sige_hip_commit_record;
+int sige_hip_commit_tiles(const sige_hip_commit_record *records, int n, int *launches, void *stream);
+
 /* ---- residual blocks that resample INSIDE the block (Progressive Distillation U-Net), on the active tiles, in ONE launch ----
  * x [B,H,W,C] channels-last; the resampled resolution Ho x Wo is H/2 x W/2 (mode DOWN: 2x2 mean) or 2H x 2W (mode UP:
  * nearest x2); active_indices [N,2]: tile origins AT THE RESAMPLED RESOLUTION, as sige_hip_reduce_mask_i32 gives them.

@@ -20,6 +20,17 @@ typedef float floatx16_in __attribute__((ext_vector_type(16)));
 //     per lane at a 108-byte lane stride);
 //   * the accumulators go through a wave-private LDS tile [32 pixels][Cout] and leave as 16-byte stores whose 64 lanes cover
 //     1 KB of consecutive addresses (before: 64 dword stores per lane).
+// The 16-byte store of a finished tile row.  128 output channels: the write-through store of common.hpp.  32 / 64 channels: a
+// plain store -- with the write-through form a launch of several hundred workgroups (1 x 3 x 256 x 256) left the first dword of
+// some lanes' last stores wrong in 7 of 8 launches (4 pixels per affected 32-pixel block, channels 16 / 20 / 24 / 28 of 32; errors
+// as large as the values), with plain stores in 0 of 8, and the 128-channel form in 0 of 4 either way
+// (profiles/conv_in_narrow_probe.txt).  Why the write-through form fails there is not known.
+template <int NBK>
+__device__ __forceinline__ void store_tile4(float *p, float4 v) {
+    if constexpr (NBK == 4) store_out4(p, v);
+    else *reinterpret_cast<float4 *>(p) = v;
+}
+
 template <int CIN, int NBK>
 __global__ __launch_bounds__(256) void conv_in_gemm_kernel(const float *__restrict__ x, long sb, long sc, long sh, long sw,
                                                           int B, int H, int W, const float *__restrict__ w,  // [Cout, CIN, 3, 3]
@@ -126,7 +137,7 @@ __global__ __launch_bounds__(256) void conv_in_gemm_kernel(const float *__restri
         for (int i = 0; i < 32 * COUT / 256; ++i) {
             const int o = (i * 64 + lane) * 4;
             const long px = opix[wave][o / COUT];
-            if (px >= 0) store_out4(out + px * COUT + o % COUT, *reinterpret_cast<const float4 *>(tl + o));
+            if (px >= 0) store_tile4<NBK>(out + px * COUT + o % COUT, *reinterpret_cast<const float4 *>(tl + o));
         }
         return;
     }
@@ -136,7 +147,7 @@ __global__ __launch_bounds__(256) void conv_in_gemm_kernel(const float *__restri
 #pragma unroll
     for (int i = 0; i < 32 * COUT / 256; ++i) {
         const int o = (i * 64 + lane) * 4;
-        if (o < left) store_out4(ob + o, *reinterpret_cast<const float4 *>(tl + o));
+        if (o < left) store_tile4<NBK>(ob + o, *reinterpret_cast<const float4 *>(tl + o));
     }
 }
 

@@ -123,6 +123,7 @@ _SIGNATURES = {
         _c_int, [_c_vp, _c_vp] + [_c_int] * 10 + [_c_vp, _c_vp, _c_int, _c_int, _c_int, _c_vp, _c_int, _c_vp, _c_vp]),
     "sige_hip_scatter_with_block_residual_nhwc_f32": (
         _c_int, [_c_vp] * 4 + [_c_int] * 12 + [_c_vp, _c_vp, _c_int, _c_int, _c_int] * 2 + [_c_int, _c_vp, _c_vp]),
+    "sige_hip_commit_tiles": (_c_int, [_c_vp, _c_int, _c_vp, _c_vp]),
     "sige_hip_group_norm_affine_nhwc_workspace": (_c_sz, [_c_int] * 5),
     "sige_hip_group_norm_affine_nhwc_f32": (_c_int, [_c_vp] + [_c_int] * 5 + [ctypes.c_float] + [_c_vp] * 6),
     "sige_hip_group_norm_affine_nhwc_bias_f32": (_c_int, [_c_vp] + [_c_int] * 5 + [ctypes.c_float] + [_c_vp] * 7),
@@ -2486,6 +2487,86 @@ def affine_act_cl(x: torch.Tensor, scale: torch.Tensor, shift: torch.Tensor, act
         return None
     _check(status, "affine_act_cl")
     return out
+
+
+class _CommitRecordC(ctypes.Structure):
+    """include/sige_hip.h: sige_hip_commit_record."""
+    _fields_ = ([(k, _c_vp) for k in ("src", "dst", "idx", "scale", "shift")]
+                + [(k, _c_int) for k in ("N", "B", "C", "H", "W", "r", "s", "offsetH", "offsetW", "strideH", "strideW", "tile_source", "dst_f16")])
+
+
+COMMIT_CAPACITY = 48  # SIGE_HIP_COMMIT_CAPACITY: records of one launch
+
+
+class CommitRecord:
+    """One record of commit_tiles: over the tile list `idx` [N,2] (int32, a Gather's active_indices), write the pixels
+    (offset + idx) / stride + [0,r) x [0,s), tile = (r, s), of the channels-last destination `dst` [1,C,H,W] (fp32, or an fp16-stored
+    cache) from `src`: a channels-last fp32 tensor of dst's shape (tile_source=False: pixel (h,w) from pixel (h,w)) or the
+    channels-last fp32 tiles [N,C,r,s] a tile conv wrote (tile_source=True).  scale / shift ([C] or [1,C,1,1], both or neither):
+    the value written is SiLU(scale[c] * v + shift[c]), bit for bit what affine_act_cl gives."""
+
+    __slots__ = ("src", "dst", "idx", "offset", "stride", "tile", "tile_source", "scale", "shift")
+
+    def __init__(self, src, dst, idx, offset=(0, 0), stride=(1, 1), tile=None, tile_source=False, scale=None, shift=None):
+        pair = lambda v: (int(v), int(v)) if isinstance(v, int) else (int(v[0]), int(v[1]))  # noqa: E731
+        self.src, self.dst, self.idx, self.tile_source, self.scale, self.shift = src, dst, idx, bool(tile_source), scale, shift
+        self.offset, self.stride = pair(offset), pair(stride)
+        if tile is None:
+            if not tile_source:
+                raise ValueError("CommitRecord: a full source needs the output tile (r, s)")
+            tile = (src.shape[2], src.shape[3])
+        self.tile = pair(tile)
+
+    def __repr__(self):
+        return "CommitRecord(%s %s -> %s %s, N=%d, offset=%s, stride=%s, tile=%s%s)" % (
+            "tiles" if self.tile_source else "full", tuple(self.src.shape), str(self.dst.dtype).replace("torch.", ""), tuple(self.dst.shape),
+            self.idx.shape[0], self.offset, self.stride, self.tile, ", affine" if self.scale is not None else "")
+
+
+def commit_tiles(records) -> Optional[int]:
+    """sige_hip_commit_tiles: execute a list of CommitRecord in ceil(records with a tile / COMMIT_CAPACITY) launches and return that
+    number.  None -- and nothing written -- if the library has no kernel for one of the records (C % 4, a batch, NCHW, ...)."""
+    records = list(records)
+    if not records:
+        return 0
+    arr = (_CommitRecordC * len(records))()
+    keep = []
+    for c, r in zip(arr, records):
+        src, dst, idx = r.src, r.dst, r.idx
+        if not (src.is_cuda and dst.is_cuda and idx.is_cuda and src.device == dst.device == idx.device):
+            raise RuntimeError("sige_amd.hip.commit_tiles: src, dst and idx must live on one GPU")
+        if src.dtype != torch.float32 or dst.dtype not in (torch.float32, torch.float16) or idx.dtype != torch.int32:
+            raise NotImplementedError("sige_amd.hip.commit_tiles: src fp32, dst fp32 / fp16, idx int32")
+        if src.dim() != 4 or dst.dim() != 4 or idx.dim() != 2 or idx.shape[1] != 2 or not idx.is_contiguous():
+            raise NotImplementedError("sige_amd.hip.commit_tiles: src, dst 4-D, idx a contiguous [N,2] list")
+        B, C, H, W = dst.shape
+        N = idx.shape[0]
+        want = (N, C, r.tile[0], r.tile[1]) if r.tile_source else (B, C, H, W)
+        if tuple(src.shape) != want:
+            raise RuntimeError("sige_amd.hip.commit_tiles: src is %s, the record needs %s" % (tuple(src.shape), want))
+        if not (dst.is_contiguous(memory_format=CL) and src.is_contiguous(memory_format=CL)):
+            return None  # (NCHW: no kernel)
+        aff = []
+        for v, name in ((r.scale, "scale"), (r.shift, "shift")):
+            if v is not None:
+                v = _req(v.reshape(-1), torch.float32, name, 1)
+                if v.numel() != C:
+                    return None  # (a per-batch affine: no kernel)
+                keep.append(v)
+            aff.append(v)
+        c.src, c.dst, c.idx, c.scale, c.shift = src.data_ptr(), dst.data_ptr(), (idx.data_ptr() if N else None), _p(aff[0]), _p(aff[1])
+        c.N, c.B, c.C, c.H, c.W = N, B, C, H, W
+        c.r, c.s = r.tile
+        c.offsetH, c.offsetW = r.offset
+        c.strideH, c.strideW = r.stride
+        c.tile_source, c.dst_f16 = int(r.tile_source), int(dst.dtype == torch.float16)
+    launches = ctypes.c_int(0)
+    status = lib().sige_hip_commit_tiles(ctypes.cast(arr, _c_vp), len(records), ctypes.cast(ctypes.pointer(launches), _c_vp),
+                                         _stream(records[0].dst))
+    if status == UNSUPPORTED:
+        return None
+    _check(status, "commit_tiles")
+    return launches.value
 
 
 # attention_cl: scores + softmax + values in ONE launch (csrc/attention_fused.hip) instead of two.  Off: measured on MI355X

@@ -53,6 +53,10 @@ class SIGEModule(nn.Module):
         self.sparse_update = False
         self.cache_dtype = "f32"  # SIGEModel.set_cache_dtype: how Scatter / ScatterGather modules STORE their caches
 
+    # the queue a `sparse_update` forward commits through (sige_amd/nn/commit.py) -- handed out by SIGEModel.set_sparse_update of a
+    # model class that opts in (SIGEModel.COMMIT_TILES); None: the reference's module-by-module refresh
+    commit_queue = None
+
     # -- mask / cache protocol driven by SIGEModel ---------------------------
     def set_mask(self, masks: Dict, cache: Dict, timestamp: int):
         self.timestamp = timestamp
@@ -290,16 +294,33 @@ class SIGEConv2d(nn.Conv2d, SIGEModule):
 
 
 class SIGEModel(nn.Module):
+    # (not in the reference) a `sparse_update` forward stays on the fused kernels and commits the active tiles of every cache in
+    # one launch at its end (sige_amd/nn/commit.py) instead of copying every cached tensor module by module.  Opt-in per model
+    # CLASS, whose `forward` must end with `self.flush_commit()`; False: exactly the reference's behaviour.
+    COMMIT_TILES = False
+
     def __init__(self, call_super: bool = True):
         if call_super:
             super(SIGEModel, self).__init__()
         self.mode = "full"
         self.timestamp = 0
 
+    # -- the commit queue of a sparse_update forward (COMMIT_TILES) ---------------
+    def _commit_idle(self, what: str):
+        q = self.__dict__.get("_commit_queue")
+        if q is not None:
+            q.require_empty(what)
+
+    def flush_commit(self) -> int:
+        """Execute what the modules queued in this forward (one launch per hip.COMMIT_CAPACITY records); returns the launches."""
+        q = self.__dict__.get("_commit_queue")
+        return q.flush() if q is not None else 0
+
     def _sige_modules(self):
         return (m for m in self.modules() if isinstance(m, SIGEModule))
 
     def set_masks(self, masks: Dict[Tuple[int, int], torch.Tensor]):
+        self._commit_idle("set_masks")
         self.timestamp += 1
         cache = {}  # shared by all modules: one reduce_mask / scatter_map per distinct geometry
         self._prebuild_indices(masks, cache)
@@ -379,11 +400,14 @@ class SIGEModel(nn.Module):
                         lists[k] = v
 
     def set_mode(self, mode: str):
+        if mode != "sparse":
+            self._commit_idle("leaving sparse mode")
         self.mode = mode
         for module in self._sige_modules():
             module.set_mode(mode)
 
     def clear_cache(self):
+        self._commit_idle("clear_cache")
         for module in self._sige_modules():
             module.clear_cache()
 
@@ -392,8 +416,18 @@ class SIGEModel(nn.Module):
             module.set_cache_id(cache_id)
 
     def set_sparse_update(self, sparse_update: bool):
+        self._commit_idle("set_sparse_update")
+        queue = None
+        if sparse_update and self.COMMIT_TILES:
+            if getattr(self, "edit_batch", 1) > 1:
+                raise RuntimeError("sige_amd: sparse_update under stacked edits -- E edits of one original cannot all become the original")
+            from .commit import CommitQueue
+
+            queue = CommitQueue()
+        self.__dict__["_commit_queue"] = queue
         for module in self._sige_modules():
             module.set_sparse_update(sparse_update)
+            module.commit_queue = queue
 
     def set_compute_dtype(self, dtype: str, keep=None, edit_ratio: Optional[float] = None):
         """MI355X-first option (not in the reference, which is fp32-only: sige/nn/base.py:15,55-63).

@@ -13,7 +13,7 @@ import torch
 from torch import nn
 
 from ..utils import reduce_mask
-from . import deferred
+from . import commit, deferred
 from .base import SIGEModule
 from .utils import activation
 
@@ -64,6 +64,11 @@ class Gather(SIGEModule):
         self.active_indices: Optional[torch.Tensor] = None
         self._tables: Dict = {}
 
+    def _no_deferral(self) -> bool:
+        """`sparse_update` keeps the tiles off the fused path (the reference's refresh needs them materialised) -- unless the model
+        commits through the queue (sige_amd/nn/commit.py)."""
+        return self.sparse_update and not commit.lifted(self)
+
     def note_full_input(self, res):
         """What a full-mode forward records (sige/nn/gather.py:51-57: the input resolution) -- for a full pass whose input tensor
         never exists as one tensor (a torch.cat / F.interpolate fused into the consuming conv)."""
@@ -101,7 +106,7 @@ class Gather(SIGEModule):
                 from .. import hip
 
                 if (hip.cat_fusable(a.shape[0], a.shape[1], self.kernel_size) and a.shape[1] % 4 == 0 and b.shape[1] % 4 == 0
-                        and deferred.defer_ok(a, scale, shift, self.activation_first, self.sparse_update, act_name)
+                        and deferred.defer_ok(a, scale, shift, self.activation_first, self._no_deferral(), act_name)
                         and hip.is_cl(a) and hip.is_cl(b)):
                     x, x2 = a, b
             fn = self.native(self.runtime, x)
@@ -126,7 +131,7 @@ class Gather(SIGEModule):
                     return hip.gather_cl(xx, bh, bw, idx, scale, shift, act)
                 return fn(xx, bh, bw, idx, scale, shift, act, first)
 
-            if deferred.defer_ok(x, scale, shift, first, self.sparse_update, act):
+            if deferred.defer_ok(x, scale, shift, first, self._no_deferral(), act):
                 # not computed yet: a SIGEConv2d consumer fuses it into its prologue,
                 # any other consumer materialises it through the gather kernel
                 channels = x.shape[1] + (0 if x2 is None else x2.shape[1])
@@ -172,7 +177,7 @@ class Gather(SIGEModule):
         """Can `forward(x, upsample2x=True)` be used for this input (see there)?"""
         return (self.mode == "sparse" and not isinstance(x, deferred.LazyCat)
                 and deferred.channels_last_ok(deferred.resolve(x), scale, shift, self.activation_first)
-                and deferred.defer_ok(deferred.resolve(x), scale, shift, self.activation_first, self.sparse_update,
+                and deferred.defer_ok(deferred.resolve(x), scale, shift, self.activation_first, self._no_deferral(),
                                       self.activation_name))
 
     def index_key(self, res) -> tuple:

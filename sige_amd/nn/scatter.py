@@ -13,7 +13,7 @@ from typing import Optional
 
 import torch
 
-from . import deferred, twins
+from . import commit, deferred, twins
 from .base import SIGEModule, SIGEModuleWrapper
 from .gather import Gather
 
@@ -200,7 +200,7 @@ class Scatter(SIGEModule):
         """(not in the reference) `self(conv(tiles), residual)` in ONE launch when the in-place mode is on and `tiles`
         are pending (deferred) channels-last tiles: the conv's epilogue writes into this module's persistent output.
         Falls back to the two-module form otherwise; values are identical."""
-        if self.mode == "sparse" and self.inplace and not self.sparse_update:
+        if self.mode == "sparse" and self.inplace and (not self.sparse_update or commit.active(self, self.original_outputs[self.cache_id])):
             g: Gather = self.gather.module
             cached = self.original_outputs[self.cache_id]
             if _cl_ok(cached, residual) and isinstance(tiles, deferred.DeferredTiles) and tiles.spec is not None:
@@ -208,8 +208,15 @@ class Scatter(SIGEModule):
                 tw = self.twins.launch_args(self.cache_id, cached, g.timestamp)
                 done = _fused_conv_into(conv, tiles, out, g, residual=residual, twins=tw.args())
                 if done is not None:
+                    if self.sparse_update:
+                        self._queue_commit(done, cached, g)
                     return twins.tag(done, tw.written())
         return self.forward(conv(tiles), residual)
+
+    def _queue_commit(self, out: torch.Tensor, cached: torch.Tensor, g: Gather):
+        """(commit.py) an accepted edit: the persistent output's pixels under this mask's tiles become the cache at the end of the
+        forward.  Nothing is invalidated -- output and twins then equal the new cache everywhere."""
+        self.commit_queue.add(out, cached, g.indices_on(out.device), g.offset, g.model_stride, g.out_tile)
 
     def forward(self, x: torch.Tensor, residual: Optional[torch.Tensor] = None) -> torch.Tensor:
         self.check_dtype(x, residual)
@@ -221,9 +228,13 @@ class Scatter(SIGEModule):
             if _cl_ok(cached, residual):
                 from .. import hip
 
-                out = self._out_bufs.get(self.cache_id, cached, g.timestamp) if (self.inplace and not self.sparse_update) else None
+                queue = self.inplace and commit.active(self, cached)
+                out = self._out_bufs.get(self.cache_id, cached, g.timestamp) if (self.inplace and (not self.sparse_update or queue)) else None
                 output = hip.scatter_cl(x, cached, g.offset, g.model_stride, g.indices_on(x.device),
                                         g.tile_table(cached.shape[2:], x.device), residual, out=out)
+                if queue:
+                    self._queue_commit(output, cached, g)
+                    return self.twins.unwritten(output, self.cache_id)
             elif _fused_ok(x):
                 from .. import hip
 
@@ -235,7 +246,11 @@ class Scatter(SIGEModule):
                 output = fn(x.contiguous(), deferred.from_cache(cached).contiguous(), g.offset[0], g.offset[1],
                             g.model_stride[0], g.model_stride[1], g.indices_on(x.device),
                             None if residual is None else residual.contiguous())
-            if self.sparse_update:
+            if self.sparse_update and self.inplace and commit.active(self, cached) and deferred.FORCE_ON_CPU:
+                # (tests: the protocol without a device -- the persistent output is the result, as the in-place kernels leave it)
+                output = self._out_bufs.get(self.cache_id, cached, g.timestamp).copy_(output)
+                self._queue_commit(output, cached, g)
+            elif self.sparse_update:
                 cached.copy_(output)
                 self._out_bufs.invalidate(self.cache_id)
                 self.twins.invalidate(self.cache_id)
@@ -331,7 +346,8 @@ class ScatterWithBlockResidual(SIGEModule):
     def forward_fused(self, conv, tiles: torch.Tensor, residual: torch.Tensor) -> torch.Tensor:
         """(not in the reference) `self(conv(tiles), residual)` in ONE launch (see Scatter.forward_fused): `residual` are
         the shortcut conv's tiles; the block-residual correction runs in the conv's epilogue."""
-        if self.mode == "sparse" and self.inplace and not self.sparse_update:
+        if self.mode == "sparse" and self.inplace and (not self.sparse_update or commit.active(
+                self, self.original_outputs[self.cache_id], self.original_residuals[self.cache_id])):
             mg: Gather = self.main_gather.module
             sg: Gather = self.shortcut_gather.module
             y0 = self.original_outputs[self.cache_id]
@@ -344,8 +360,21 @@ class ScatterWithBlockResidual(SIGEModule):
                 done = _fused_conv_into(conv, tiles, out, mg, residual=y1, x1=x1, table1=sg.tile_table(y0.shape[2:], y0.device),
                                         twins=tw.args())
                 if done is not None:
+                    if self.sparse_update:
+                        self._queue_commit(done, x1, y0, y1, mg, sg)
                     return twins.tag(done, tw.written())
         return self.forward(conv(tiles), residual)
+
+    def _queue_commit(self, out: torch.Tensor, x1: torch.Tensor, y0: torch.Tensor, y1: torch.Tensor, mg: Gather, sg: Gather):
+        """(commit.py) an accepted edit, at the end of the forward: the persistent output over the MAIN list and over the SHORTCUT list
+        (it differs from the cache on both: out += x1 - y1) becomes the output cache, the shortcut tiles go to the residual cache
+        (sige/nn/scatter.py:118-129).  Nothing is invalidated."""
+        q, dev = self.commit_queue, out.device
+        if x1.is_cuda:
+            x1 = x1.contiguous(memory_format=torch.channels_last)  # (what the tile convs write: no copy)
+        q.add(out, y0, mg.indices_on(dev), mg.offset, mg.model_stride, mg.out_tile)
+        q.add(out, y0, sg.indices_on(dev), sg.offset, sg.model_stride, sg.out_tile)
+        q.add(x1, y1, sg.indices_on(dev), sg.offset, sg.model_stride, tuple(x1.shape[2:]), tile_source=True)
 
     def forward(self, x: torch.Tensor, residual: torch.Tensor, x_is_sum: bool = False) -> torch.Tensor:
         """`x_is_sum` (full mode only, not in the reference): `x` already is main + residual."""
@@ -362,11 +391,15 @@ class ScatterWithBlockResidual(SIGEModule):
             if _cl_ok(y0, y1) and hip_is_cl(y1):
                 from .. import hip
 
+                queue = self.inplace and commit.active(self, y0, y1)
                 out = self._out_bufs.get(self.cache_id, y0, (mg.timestamp, sg.timestamp)) \
-                    if (self.inplace and not self.sparse_update) else None
+                    if (self.inplace and (not self.sparse_update or queue)) else None
                 output = hip.scatter_with_block_residual_cl(
                     x, y0, residual, y1, mg.offset, mg.model_stride, mg.indices_on(x.device), mg.tile_table(res, x.device),
                     sg.indices_on(x.device), sg.tile_table(res, x.device), out=out)
+                if queue:
+                    self._queue_commit(output, residual, y0, y1, mg, sg)
+                    return self.twins.unwritten(output, self.cache_id)
             elif _fused_ok(x):
                 from .. import hip
 
@@ -379,7 +412,11 @@ class ScatterWithBlockResidual(SIGEModule):
                 output = fn(x.contiguous(), deferred.from_cache(y0).contiguous(), residual.contiguous(), deferred.from_cache(y1).contiguous(),
                             mg.offset[0], mg.offset[1], mg.model_stride[0], mg.model_stride[1],
                             mg.indices_on(x.device), sg.indices_on(x.device))
-            if self.sparse_update:
+            if self.sparse_update and self.inplace and commit.active(self, y0, y1) and deferred.FORCE_ON_CPU:
+                # (tests: the protocol without a device -- the persistent output is the result, as the in-place kernels leave it)
+                output = self._out_bufs.get(self.cache_id, y0, (mg.timestamp, sg.timestamp)).copy_(output)
+                self._queue_commit(output, residual, y0, y1, mg, sg)
+            elif self.sparse_update:
                 if self.scatter_runtime is None:
                     self.scatter_runtime = self.load_runtime("scatter", {})
                 y0.copy_(output)

@@ -9,7 +9,7 @@ from typing import Dict, Optional
 
 import torch
 
-from . import deferred
+from . import commit, deferred
 from .base import SIGEModule, SIGEModuleWrapper
 from .gather import Gather
 from .utils import activation
@@ -132,13 +132,23 @@ class ScatterGather(SIGEModule):
                     return hip.scatter_gather_cl(x, cached, bh, bw, idx, smap, scale, shift, act)
                 return fn(x, deferred.from_cache(cached).contiguous(), bh, bw, idx, smap, scale, shift, act, first)
 
-            if deferred.defer_ok(x, scale, shift, first, self.sparse_update, act):
+            # an accepted edit on the fused path (commit.py): conv1's raw tiles go to the cache, and through (scale, shift) + SiLU to
+            # its activated copy, at the end of the forward -- both still hold the original while the consumer conv reads them
+            act_copy = self.activated_outputs.get(self.cache_id)
+            queue = commit.active(self, cached, act_copy) and (cl or deferred.FORCE_ON_CPU) and (act_copy is None or (
+                scale is not None and shift is not None and scale.shape[0] == 1 and act == "swish" and not first))
+            if queue:
+                geo = dict(idx=idx, offset=g.offset, stride=g.model_stride, tile=tuple(x.shape[2:]), tile_source=True)
+                self.commit_queue.add(x, cached, **geo)
+                if act_copy is not None:
+                    self.commit_queue.add(x, act_copy, scale=scale, shift=shift, **geo)
+            if deferred.defer_ok(x, scale, shift, first, self.sparse_update and not queue, act):
                 return deferred.DeferredTiles(
                     (cached.shape[0] * idx.shape[0], x.shape[1], bh, bw), x.dtype, x.device, run,
                     dict(kind="scatter_gather", x=x, y=cached, block=(bh, bw), idx=idx, map=smap, scale=scale,
                          shift=shift, act=act, cl=cl))
             output = run()
-            if self.sparse_update:
+            if self.sparse_update and not queue:
                 if x.is_cuda:
                     from .. import hip
 
@@ -148,6 +158,8 @@ class ScatterGather(SIGEModule):
                     sfn = self.native(self.scatter_runtime, x)
                     cached.copy_(sfn(x.contiguous(), deferred.from_cache(cached).contiguous(), g.offset[0], g.offset[1],
                                      g.model_stride[0], g.model_stride[1], g.indices_on(x.device), None))
+                if self.cache_id in self.activated_outputs and scale is not None and shift is not None:
+                    self.cache_activated(scale, shift)  # (the activated copy follows the cache it is derived from)
             return output
         if self.mode == "full":
             self.output_res = x.shape[2:]

@@ -386,15 +386,19 @@ class ResBlock(SIGEModule, TwinProducer, TwinConsumer):
             parts = list(x.parts) if hasattr(x, "parts") else [x]
             first = parts[0]
             tw = self._twin_inputs(parts, s1, t1)
+            # an accepted edit (`sparse_update`): conv1's RAW tiles are what the ScatterGather cache takes (SiLU cannot be inverted), so
+            # conv1 runs without its out-affine and conv2 stages SiLU(s2 * . + t2) itself -- the same launches, the activation moved
+            # to conv2's staging
+            oa = {} if self.sparse_update else dict(out_affine=(s2, t2, "swish"))
             with self._pairing(first):
                 skip, join = (self._shortcut_async(lambda: self._shortcut(x), first) if self.cin != self.cout
                               else (x, lambda: None))
                 if tw is not None:  # the producers wrote SiLU(s1 * x + t1): conv1 stages raw values
                     xa = tw[0] if len(tw) == 1 else lazy_cat(tw[0], tw[1])
-                    h = self.conv1(self.main_gather(xa, preactivated=True), out_affine=(s2, t2, "swish"))
+                    h = self.conv1(self.main_gather(xa, preactivated=True), **oa)
                 else:
-                    h = self.conv1(self.main_gather(x, s1, t1), out_affine=(s2, t2, "swish"))
-            tiles = self.scatter_gather(h, preactivated=True)
+                    h = self.conv1(self.main_gather(x, s1, t1), **oa)
+            tiles = self.scatter_gather(h, s2, t2) if self.sparse_update else self.scatter_gather(h, preactivated=True)
             join()
             return self._produced(self.scatter.forward_fused(self.conv2, tiles, skip))
         if not self.sparse_main:
@@ -733,6 +737,10 @@ class Downsample(SIGEModule, TwinProducer):
 
 
 class DDPMSparseUNet(SIGEModel):
+    # an accepted edit (`set_sparse_update(True)`) stays on the fused kernels and is committed by one tile-copy launch per
+    # hip.COMMIT_CAPACITY records at the end of the forward (sige_amd/nn/commit.py)
+    COMMIT_TILES = True
+
     # set_compute_dtype("f16"): the convs that stay at fp32-level precision (split fp16 operands, "f16x3") so that the f16
     # path meets sige_amd.tolerance.F16_CRITERION at every edit ratio of BASELINE.json configs[4] (1 ... 20 %).  From the
     # per-layer error trace (tests/f16_error_trace.py, profiles/r3a_f16_error_trace.json): fp16 rounding errors made on
@@ -1026,7 +1034,10 @@ class DDPMSparseUNet(SIGEModel):
         convs = [c for b in stage.block for c in (b.conv1, b.conv2, getattr(b, "nin_shortcut", None)) if c is not None]
         if not hip.is_cl(h) or h.dtype != torch.float32 or any(getattr(c, "compute_dtype", "f32") != "f32" for c in convs):
             return None
-        if any(b.sparse_update or b.mode != "sparse" for b in stage.block):
+        # (`sparse_update` on the reference's route rewrites the producer's cache mid-forward; where the model commits through the
+        #  queue -- nn/commit.py -- the level's buffers simply are the new base: original values outside the region, the accepted
+        #  edit's inside, and the signature below does not move)
+        if any((b.sparse_update and b.commit_queue is None) or b.mode != "sparse" for b in stage.block):
             return None
         g = self.down[lvl - 1].downsample.gather
         if tuple(g.input_res) != (2 * h.shape[2], 2 * h.shape[3]) or region.cells != -(-h.shape[2] // 4) * -(-h.shape[3] // 4):
@@ -1129,6 +1140,8 @@ class DDPMSparseUNet(SIGEModel):
             # [1,C,E*H,W] -- the same bytes -- and every sparse module works on it unchanged
             if self.mode != "sparse" or x.shape[0] != E:
                 raise RuntimeError("stacked edits: sparse mode, one input image per edit")
+            if self.__dict__.get("_commit_queue") is not None:
+                raise RuntimeError("stacked edits: sparse_update is not supported -- E edits of one original cannot all become the original")
             from ..stacked import tall, untall
 
             h0 = tall(h0)
@@ -1176,6 +1189,8 @@ class DDPMSparseUNet(SIGEModel):
                 h = untall(h, E)  # (the output norm and the last conv are per image)
             # the output norm is a TRUE GroupNorm of the edited activation (sige_fused_unet.py:430-432)
             so, to = group_norm_affine(h, self.norm_out)
-            return fused_conv2d(self.conv_out, h, so, to, "swish")
+            out = fused_conv2d(self.conv_out, h, so, to, "swish")
+            self.flush_commit()  # (an accepted edit: behind every reader of a cache in stream order)
+            return out
         return self.conv_out(F.silu(self.norm_out(h)))
 
