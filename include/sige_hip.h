@@ -999,6 +999,20 @@ int sige_hip_attention_wide_tiles_f32(const float *q, int ldq, const float *k, i
                                       const int32_t *active_indices, int T, int H, int W, int C, int heads, float scale,
                                       float *out, int ldo, void *stream);
 
+/* ---- ... both with fp16 OPERANDS (the f16 compute mode) ---------------------------------------------------------------------
+ * Arguments, layouts, shape predicate (sige_hip_attention_wide_supported), key split and status rules -- the same checks in the
+ * same order, nothing launched when refused or empty -- of sige_hip_attention_wide_f32 and sige_hip_attention_wide_tiles_f32;
+ * the arithmetic contract stated at sige_hip_attention_tokens_f16c (the split merge is one more fp32 merge of partial results).
+ * The key split is in 32-key steps.  E = 1 through the tiles entry: the results of the batched entry, bit for bit.               */
+/* how many workgroups share the keys of one query tile when tickets and workspace are available (1: no split; 0: a shape the
+ * predicate refuses) -- the launch's own formula, for tests and tools */
+int sige_hip_attention_wide_f16c_splits(int B, int Nq, int Nk, int C, int heads);
+int sige_hip_attention_wide_f16c(const float *q, int ldq, const float *k, int ldk, const float *v, int ldv,
+                                 int B, int Nq, int Nk, int C, int heads, float scale, float *out, int ldo, void *stream);
+int sige_hip_attention_wide_tiles_f16c(const float *q, int ldq, const float *k, int ldk, const float *v, int ldv,
+                                       const int32_t *active_indices, int T, int H, int W, int C, int heads, float scale,
+                                       float *out, int ldo, void *stream);
+
 /* ---- fp16-STORED caches: the "_f16" forms of SURVEY.md 8b's export list (8f row 4: fp16 cache) ---------------------
  * The reference is fp32-only (sige/nn/base.py:15,55-63).  Here the CACHED tensors of a SIGE model -- Scatter /
  * ScatterGather `original_outputs`, ScatterWithBlockResidual `original_outputs` / `original_residuals`, and the activated

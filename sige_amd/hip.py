@@ -163,6 +163,9 @@ _SIGNATURES = {
     "sige_hip_attention_wide_supported": (_c_int, [_c_int] * 4),
     "sige_hip_attention_wide_f32": (_c_int, [_c_vp, _c_int] * 3 + [_c_int] * 5 + [ctypes.c_float, _c_vp, _c_int, _c_vp]),
     "sige_hip_attention_wide_tiles_f32": (_c_int, [_c_vp, _c_int] * 3 + [_c_vp] + [_c_int] * 5 + [ctypes.c_float, _c_vp, _c_int, _c_vp]),
+    "sige_hip_attention_wide_f16c_splits": (_c_int, [_c_int] * 5),
+    "sige_hip_attention_wide_f16c": (_c_int, [_c_vp, _c_int] * 3 + [_c_int] * 5 + [ctypes.c_float, _c_vp, _c_int, _c_vp]),
+    "sige_hip_attention_wide_tiles_f16c": (_c_int, [_c_vp, _c_int] * 3 + [_c_vp] + [_c_int] * 5 + [ctypes.c_float, _c_vp, _c_int, _c_vp]),
     # fp16-stored caches
     "sige_hip_gather_nhwc_f16": (
         _c_int, [_c_vp] + [_c_int] * 6 + [_c_vp, _c_int] + [_c_vp, _c_int, _c_int] * 2 + [_c_int, _c_vp, _c_vp]),
@@ -2719,7 +2722,7 @@ def _token_rows(t: torch.Tensor):
 
 
 def attention_wide(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, heads: int, scale: float,
-                   out: Optional[torch.Tensor] = None, tiles=None) -> Optional[torch.Tensor]:
+                   out: Optional[torch.Tensor] = None, tiles=None, compute: str = "f32") -> Optional[torch.Tensor]:
     """attention_tokens for WIDE heads (160 < d <= 512, d % 16 == 0; include/sige_hip.h: sige_hip_attention_wide_f32): ONE launch.
     q [B,Nq,C], k / v [B,Nk,C] may be strided views whose last dimension is contiguous (the two halves of a [B,Nk,2C] tensor,
     a column slice): they are read in place.  `out`: a [B,Nq,C] destination of the same kind (default: a fresh tensor).  None if
@@ -2728,7 +2731,12 @@ def attention_wide(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, heads: int
     `tiles` = (active_indices, H, W): the keys of a query tile's OWN image (stacked edits, set_edit_batch;
     sige_hip_attention_wide_tiles_f32).  q [1,16T,C] are the tokens of the T 4x4 tiles of the Gather's device int32 [T,2] list,
     k / v [1,H*W,C] the rows of the tall image of get_edit_batch() images; tile t reads the (H/E)*W keys of image
-    origin_row // (H/E).  T = 0: `out` without a launch."""
+    origin_row // (H/E).  T = 0: `out` without a launch.
+
+    `compute`: "f32" exact fp32 products; "f16" fp16 operands with fp32 accumulation on the same fp32 tensors
+    (sige_hip_attention_wide_f16c / _tiles_f16c: the contract stated at sige_hip_attention_tokens_f16c)."""
+    if compute not in ("f32", "f16"):
+        raise ValueError("attention_wide: compute must be 'f32' or 'f16', got %r" % (compute,))
     if not (q.is_cuda and q.dtype == k.dtype == v.dtype == torch.float32 and q.dim() == k.dim() == v.dim() == 3):
         return None
     B, Nq, C = q.shape
@@ -2749,12 +2757,13 @@ def attention_wide(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, heads: int
     elif tuple(out.shape) != (B, Nq, C) or out.dtype != torch.float32 or _token_rows(out)[0] is not out:
         raise ValueError("attention_wide: `out` must be a [B,Nq,C] fp32 tensor with contiguous rows")
     if tiles is not None:
-        status = lib().sige_hip_attention_wide_tiles_f32(q.data_ptr(), ldq, k.data_ptr(), ldk, v.data_ptr(), ldv, idx.data_ptr(),
-                                                         Nq // 16, int(H), int(W), C, heads, float(scale), out.data_ptr(),
-                                                         max(out.stride(1), C), _stream(q))
+        entry = lib().sige_hip_attention_wide_tiles_f16c if compute == "f16" else lib().sige_hip_attention_wide_tiles_f32
+        status = entry(q.data_ptr(), ldq, k.data_ptr(), ldk, v.data_ptr(), ldv, idx.data_ptr(), Nq // 16, int(H), int(W), C, heads,
+                       float(scale), out.data_ptr(), max(out.stride(1), C), _stream(q))
     else:
-        status = lib().sige_hip_attention_wide_f32(q.data_ptr(), ldq, k.data_ptr(), ldk, v.data_ptr(), ldv, B, Nq, Nk, C, heads,
-                                                   float(scale), out.data_ptr(), out.stride(1), _stream(q))
+        entry = lib().sige_hip_attention_wide_f16c if compute == "f16" else lib().sige_hip_attention_wide_f32
+        status = entry(q.data_ptr(), ldq, k.data_ptr(), ldk, v.data_ptr(), ldv, B, Nq, Nk, C, heads, float(scale), out.data_ptr(),
+                       out.stride(1), _stream(q))
     if status == UNSUPPORTED:
         return None
     _check(status, "attention_wide")

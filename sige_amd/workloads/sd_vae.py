@@ -26,6 +26,15 @@ attention is hip.attention_wide(tiles=...): the queries of an edit's tiles again
 edits.  What has no per-image form (C <= 160, NATIVE_ATTENTION off, NCHW, CPU, sparse_update, a shape the entry refuses) raises a
 RuntimeError that names stacked edits: the chain would softmax over the keys of all E images.
 
+The f16 compute mode (SIGEModel.set_compute_dtype("f16")): both models run it on channels-last GPU tensors, sparse
+and full.  Every SIGEConv2d on tiles runs the fp16 tile kernels, the derived K | V conv takes its compute dtype from `k` and `v`
+(folded_kv()), and the attention launch follows `ATTENTION_COMPUTE` below (hip.attention_wide / attention_tokens, compute="f16").
+What has no fp16 form keeps its exact-fp32 kernel in that mode: `conv_in` / `conv_out` with the decoder's conv3x3_small_cout_cl
+head, the encoder's latent head (conv_latent_head.hip), the stride-2 Downsample conv (hip.conv_pack_weights packs that geometry for
+the exact-fp32 tile conv; the full pass runs it as the torch conv), the GroupNorm statistics, and the torch chain (`_chain`: CPU, NCHW, NATIVE_ATTENTION off,
+and the full-mode attention).  The Upsample conv runs as the 9-tap fp16 tile conv: SIGEConv2d.phase_kernels() is None outside f32.
+"f16x3" has no attention or tile form of its own: both run exact fp32.
+
 The encoder (SIGEEncoder, sige_model.py:177) is built from the same blocks: SparseVAEEncoder, at the end of the file."""
 from dataclasses import dataclass
 from typing import Tuple
@@ -45,6 +54,12 @@ NATIVE_ATTENTION = True
 # The latent-head launch of the library (hip.conv3x3_latent_head_cl) as the encoder's tail in sparse mode.  False: the reference's
 # chain, conv_out(silu(norm_out(h))) -> quant_conv -> the posterior in torch (A/B runs: tools/vae_encoder_bench.py; tests).
 NATIVE_HEAD = True
+# The arithmetic of the attention launch: "f32" exact fp32 products, "f16" fp16 operands with fp32 accumulation on the same fp32
+# tensors (sige_hip_attention_wide_f16c / sige_hip_attention_tokens_f16c), None: the model's compute policy -- "f16" where the block's
+# `q` conv has compute dtype "f16" (set_compute_dtype("f16") without a `keep` prefix naming it), "f32" otherwise ("f16x3" included).
+ATTENTION_COMPUTE = None
+# precision order of the compute dtypes: the derived K | V conv takes the higher one of `k` and `v`
+_PRECISION = {"f16": 0, "f16x3": 1, "f32": 2}
 
 
 @dataclass
@@ -151,7 +166,16 @@ class VAEAttnBlock(SIGEModule):
         clear_cache()."""
         params = (self.k.weight, self.k.bias, self.v.weight, self.v.bias)
         key = tuple(None if p is None else (p.data_ptr(), p._version, tuple(p.shape), p.device, p.dtype) for p in params)
+        # the compute dtype of `k` and `v` (set_compute_dtype never reaches the derived conv: it is no submodule); where a `keep`
+        # prefix names one of the two, the higher precision
+        dtype = max((getattr(c, "compute_dtype", "f32") for c in (self.k, self.v)), key=_PRECISION.__getitem__)
+        key += (dtype,)
         entry = self.__dict__.get("_kv_conv")
+        if entry is not None and entry[0] != key and entry[0][:-1] == key[:-1]:
+            # the same weights under another compute dtype: re-labelled (SIGEConv2d keeps one pack per compute form, each keyed
+            # on the weight, so no pack of the other form is ever read)
+            entry[1].compute_dtype = dtype
+            entry = self.__dict__["_kv_conv"] = (key, entry[1])
         if entry is None or entry[0] != key:
             C = self.ch
             with torch.device("meta"):
@@ -159,6 +183,7 @@ class VAEAttnBlock(SIGEModule):
             conv.weight = nn.Parameter(torch.cat([self.k.weight.detach(), self.v.weight.detach()]).contiguous(), requires_grad=False)
             conv.bias = nn.Parameter(torch.cat([self.k.bias.detach(), self.v.bias.detach()]).contiguous(), requires_grad=False)
             conv.set_mode("sparse")
+            conv.compute_dtype = dtype
             entry = (key, conv)
             self.__dict__["_kv_conv"] = entry  # (not through nn.Module.__setattr__: that would register the conv as a submodule)
         return entry[1]
@@ -222,6 +247,10 @@ class VAEAttnBlock(SIGEModule):
                 self.kv_scatter(torch.cat([k, v], dim=1).contiguous(memory_format=torch.channels_last))
             b, c, hh, ww = q.shape
             h = self._chain(q.reshape(b, c, hh * ww).permute(0, 2, 1), k, v).reshape(b, c, hh, ww)
+            if _fused_layout(x) and getattr(self.proj_out, "compute_dtype", "f32") != "f32":
+                # the chain's output is NCHW; the library's full-pass conv (f16 / f16x3) keeps its input's layout, and an NCHW
+                # cache behind out_scatter would send every later block down the exact-fp32 NCHW route, in both passes
+                h = h.contiguous(memory_format=torch.channels_last)
             return self.out_scatter(self.proj_out(h), x)
         if self.mode not in ("sparse", "profile"):
             raise NotImplementedError("Unknown mode [%s]!!!" % self.mode)
@@ -258,6 +287,15 @@ class VAEAttnBlock(SIGEModule):
         raise RuntimeError("VAEAttnBlock: stacked edits attend per image -- the queries of an edit's tiles against that edit's own "
                            "keys --, which only hip.attention_wide(tiles=...) does: %s (this block has %d channels)" % (needs, self.ch))
 
+    def attention_compute(self) -> str:
+        """ "f32" | "f16": `ATTENTION_COMPUTE`, or under None the compute policy as it reached `q`."""
+        compute = ATTENTION_COMPUTE
+        if compute is None:
+            compute = "f16" if getattr(self.q, "compute_dtype", "f32") == "f16" else "f32"
+        if compute not in ("f32", "f16"):
+            raise ValueError("sd_vae.ATTENTION_COMPUTE must be None, 'f32' or 'f16', got %r" % (compute,))
+        return compute
+
     def _sparse_fused(self, x, s, t, stacked=False):
         """None: no fused form as things stand (the caller runs the module chain).  `stacked`: x is the tall image of E edits
         (hip.set_edit_batch) and there is no chain to fall back to -- whatever has no per-image form raises."""
@@ -285,8 +323,9 @@ class VAEAttnBlock(SIGEModule):
         qt = q.permute(0, 2, 3, 1).reshape(1, 16 * T, C)            # (views: no copy on either side)
         tok = kv.permute(0, 2, 3, 1).reshape(1, H * W, 2 * C)
         scale = int(C) ** (-0.5)
+        compute = self.attention_compute()
         if C <= 160:
-            o = hip.attention_tokens(qt, tok[:, :, :C], tok[:, :, C:], 1, scale)
+            o = hip.attention_tokens(qt, tok[:, :, :C], tok[:, :, C:], 1, scale, compute=compute)
         else:
             buf = self._attn_out
             if buf is None or buf.shape[1] != 16 * T or buf.device != x.device:
@@ -294,12 +333,12 @@ class VAEAttnBlock(SIGEModule):
                 buf = self._attn_out = torch.empty((1, 16 * T, C), dtype=torch.float32, device=x.device)
             # stacked edits: kv is the tall image; tile t's keys are the rows of the image its origin row lies in, found inside the launch
             o = hip.attention_wide(qt, tok[:, :, :C], tok[:, :, C:], 1, scale, out=buf,
-                                   tiles=(g.active_indices, H, W) if stacked else None)
+                                   tiles=(g.active_indices, H, W) if stacked else None, compute=compute)
         if o is None and stacked:
-            self._refuse_stacked("a shape sige_hip_attention_wide_tiles_f32 takes (one image's height a power of two >= 4; K | V is "
+            self._refuse_stacked("a shape sige_hip_attention_wide_tiles_f32 / _f16c takes (one image's height a power of two >= 4; K | V is "
                                  "%d x %d for the whole edit batch)" % (H, W))
         if o is None:
-            # a shape the entry does not take: the reference's bmm chain on the fused q and K | V
+            # a shape the entry does not take: the reference's bmm chain on the fused q and K | V (fp32 in every compute mode)
             o = self._chain(qt, kv[:, :C], kv[:, C:]).permute(0, 2, 1)
         h = o.reshape(T, 4, 4, C).permute(0, 3, 1, 2)  # channels-last tiles again
         return self.out_scatter(self.proj_out(h), x)
@@ -326,6 +365,12 @@ def _leave_stacked(h, E: int):
 
 
 class SparseVAEDecoder(SIGEModel):
+    # set_compute_dtype("f16"): no conv stays at the higher precision, at any edit size.  tests/vae_f16.py's per-layer trace on
+    # name-initialised weights (profiles/sd_vae_f16_error_trace.json): the worst element is at 0.012 of the f16
+    # criterion's allowance with every conv and the attention in plain fp16 (1.2 - 15 % edits, both sizes).
+    F16_KEEP = ()
+    F16_KEEP_ABOVE = 0.0
+
     def __init__(self, cfg: VAEDecoderConfig = VAEDecoderConfig()):
         super().__init__()
         self.cfg = cfg
@@ -460,6 +505,12 @@ class SparseVAEEncoder(SIGEModel):
     launch of hip.conv3x3_latent_head_cl: quant_conv is folded into conv_out's weights (no nonlinearity between them) and the
     posterior sample rides in the launch's epilogue.  `NATIVE_HEAD = False`, CPU, NCHW and shapes the entry refuses run the
     reference's chain.  Batch 1 in sparse mode, as the decoder."""
+
+    # set_compute_dtype("f16"): no conv stays at the higher precision, at any edit size.  tests/vae_f16.py's per-layer trace on
+    # name-initialised weights (profiles/sd_vae_f16_error_trace.json; DESIGN.md 5.28): the worst element is at 0.005 of the f16
+    # criterion's allowance with every conv and the attention in plain fp16 (1.2 - 15 % edits, both sizes).
+    F16_KEEP = ()
+    F16_KEEP_ABOVE = 0.0
 
     def __init__(self, cfg: VAEEncoderConfig = VAEEncoderConfig()):
         super().__init__()

@@ -4,6 +4,7 @@ hipGraph replay.
 
     python tools/vae_encoder_bench.py            -> profiles/sd_vae_encoder_bench.json
     python tools/vae_encoder_bench.py --stacked  -> profiles/sd_vae_stacked_bench.json ("encoder"): stacked edits, tools/vae_stacked.py
+    python tools/vae_encoder_bench.py --dtype f16 -> profiles/sd_vae_f16_bench.json ("encoder"): the f16 compute mode, see child_f16()
 
 Per square edit of 1.2 / 5 / 15 % of the image, in ONE child process so that the comparison stays inside one session:
   (a) the sparse forward through moments(): the tail is group_norm_affine + ONE launch of hip.conv3x3_latent_head_cl with quant_conv
@@ -111,6 +112,73 @@ def head_alone(a):
     print("VAE_ENC_BENCH_ROW " + json.dumps(row), flush=True)
 
 
+def child_f16(a):
+    """--dtype f16, one ratio: the sparse forward through moments() in f16 mode (a), in f32 mode (b: a second model with its own
+    caches), in f16 mode with sd_vae.ATTENTION_COMPUTE = "f32" (c), as graphs that alternate batch by batch; the library launches of
+    each; the attention launch alone in both forms beside the torch chain (tools/vae_bench.attention_forms_alone: the middle block
+    is the decoder's -- 4 096 keys, one 512-wide head)."""
+    import torch
+
+    from benchlib.common import capture_fn
+    from sige_amd import hip
+    from sige_amd.utils import dilate_mask, downsample_mask
+    from sige_amd.workloads import sd_vae
+    from tests.golden import vae_inputs
+    from tools.vae_bench import attention_forms_alone
+
+    hip.lib()
+    dev = torch.device("cuda")
+    cfg = sd_vae.VAEEncoderConfig()
+    cl = lambda t: t.to(dev).contiguous(memory_format=torch.channels_last)  # noqa: E731
+    g = torch.Generator().manual_seed(1)
+    x0 = torch.randn(1, cfg.in_channels, IMAGE, IMAGE, generator=g)
+    noises = [torch.randn(1, cfg.in_channels, IMAGE, IMAGE, generator=g) for _ in range(4)]
+    mask = vae_inputs.square_mask(IMAGE, a.ratio)
+    row = {"ratio": a.ratio, "edit_ratio": float(mask.float().mean())}
+    models = {}
+    with torch.no_grad():
+        for dtype in ("f16", "f32"):
+            torch.manual_seed(0)
+            m = sd_vae.SparseVAEEncoder(cfg).eval().to(dev).to(memory_format=torch.channels_last)
+            quant = torch.nn.Conv2d(2 * cfg.z_channels, 2 * cfg.z_channels, 1).to(dev).to(memory_format=torch.channels_last)
+            m.set_scatter_inplace(True)
+            m.set_compute_dtype(dtype)
+            m.set_mode("full")
+            m(cl(x0))
+            m.set_masks(downsample_mask(dilate_mask(mask.to(dev), 2), LATENT))
+            m.set_mode("sparse")
+            models[dtype] = (m, quant)
+        edits = [cl(x0 + n * mask.float()) for n in noises]
+        x1 = edits[0].clone()
+        tiles = int(models["f16"][0].mid.attn_1.gather.active_indices.shape[0])
+        row["attention_tiles"] = tiles
+        graphs, outs = {}, {}
+        for name, dtype, attention in (("a_f16", "f16", "f16"), ("b_f32", "f32", "f32"), ("c_f16_attention_f32", "f16", "f32")):
+            sd_vae.ATTENTION_COMPUTE = attention
+            m, quant = models[dtype]
+            m.moments(x1, quant)
+            n0 = hip.launch_count()
+            m.moments(x1, quant)
+            row[name + "_library_launches"] = hip.launch_count() - n0
+            graphs[name], outs[name] = capture_fn(lambda m=m, quant=quant: m.moments(x1, quant))
+        sd_vae.ATTENTION_COMPUTE = None
+        ms = {k: [] for k in graphs}
+        names = list(graphs)
+        for batch in range(a.batches):
+            x1.copy_(edits[batch % len(edits)])
+            for name in names[batch % 3:] + names[:batch % 3]:
+                ms[name].append(events_ms(graphs[name], a.steps, 5))
+        row["a_minus_b_max_abs"] = float((outs["a_f16"] - outs["b_f32"]).abs().max())
+        row["a_minus_c_max_abs"] = float((outs["a_f16"] - outs["c_f16_attention_f32"]).abs().max())
+        for name, v in ms.items():
+            row[name + "_ms"] = round(statistics.median(v), 4)
+            row[name + "_ms_min_max"] = [round(min(v), 4), round(max(v), 4)]
+        row["f16_over_f32"] = round(row["a_f16_ms"] / row["b_f32_ms"], 3)
+        del graphs
+        row["attention_alone"] = attention_forms_alone(tiles, 4, a.steps)
+    print("VAE_ENC_BENCH_ROW " + json.dumps(row), flush=True)
+
+
 def child(a):
     import torch
 
@@ -184,7 +252,8 @@ def main():
     ap.add_argument("--batches", type=int, default=10)
     ap.add_argument("--reps", type=int, default=8)
     ap.add_argument("--limit", type=int, default=240, help="seconds per child")
-    ap.add_argument("--out", default=os.path.join(REPO, "profiles", "sd_vae_encoder_bench.json"))
+    ap.add_argument("--out", default=None, help="default: profiles/sd_vae_encoder_bench.json; --dtype f16: profiles/sd_vae_f16_bench.json")
+    ap.add_argument("--dtype", choices=("f32", "f16"), default="f32", help="f16: the f16 compute mode beside f32, child_f16()")
     vae_stacked.add_arguments(ap)
     a = ap.parse_args()
     if a.stacked:
@@ -192,7 +261,9 @@ def main():
     if a.head:
         return head_alone(a)
     if a.ratio is not None:
-        return child(a)
+        return child_f16(a) if a.dtype == "f16" else child(a)
+    if a.out is None:
+        a.out = os.path.join(REPO, "profiles", "sd_vae_f16_bench.json" if a.dtype == "f16" else "sd_vae_encoder_bench.json")
     from sige_amd import build
 
     res = {"workload": "SD VAE encoder (configs/sige.yaml ddconfig), image [1,3,512,512] -> moments [1,8,64,64] through quant_conv, "
@@ -200,6 +271,8 @@ def main():
            "source_hash": build.source_hash(), "steps": a.steps, "batches": a.batches, "rows": []}
     common = ["--steps", str(a.steps), "--batches", str(a.batches), "--reps", str(a.reps)]
     jobs = [("head", ["--head"])] + [(r, ["--ratio", r]) for r in a.ratios.split(",")]
+    if a.dtype == "f16":
+        jobs = [(r, ["--ratio", r, "--dtype", "f16"]) for r in a.ratios.split(",")]  # (the latent head has no fp16 form: not measured again)
     for tag, extra in jobs:
         cmd = ["timeout", "-k", "10", str(a.limit), sys.executable, os.path.abspath(__file__), *extra, *common]
         p = subprocess.run(cmd, cwd=REPO, capture_output=True, text=True)
@@ -213,11 +286,20 @@ def main():
             res["head_alone"] = row
         else:
             res["rows"].append(row)
+    if a.dtype == "f16":
+        # one file for both models: this tool owns its "encoder" key (tools/vae_bench.py: "decoder")
+        res["workload"] = res["workload"].replace("exact fp32, ", "f16 compute mode beside exact fp32, ")
+        whole = {}
+        if os.path.isfile(a.out):
+            with open(a.out) as f:
+                whole = json.load(f)
+        whole["encoder"] = res
+        res = whole
     with open(a.out, "w") as f:
         json.dump(res, f, indent=1)
         f.write("\n")
     print(json.dumps(res))
-    return 1 if "failed" in res else 0
+    return 1 if "failed" in res.get("encoder", res) else 0
 
 
 if __name__ == "__main__":

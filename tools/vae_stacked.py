@@ -28,6 +28,7 @@ sys.path.insert(0, REPO)
 IMAGE, LATENT = 512, 64
 TAG = "VAE_STACKED_ROW "
 OUT = os.path.join(REPO, "profiles", "sd_vae_stacked_bench.json")
+OUT_F16 = os.path.join(REPO, "profiles", "sd_vae_f16_bench.json")  # (--dtype f16: "decoder_stacked" / "encoder_stacked")
 SCALE_FACTOR = 0.18215
 
 
@@ -120,6 +121,8 @@ def child_stacked(kind, a):
         torch.manual_seed(0)
         m = (sd_vae.SparseVAEDecoder if decoder else sd_vae.SparseVAEEncoder)(cfg).eval().to(dev).to(memory_format=torch.channels_last)
         m.set_scatter_inplace(True)
+        if getattr(a, "dtype", "f32") == "f16":
+            m.set_compute_dtype("f16")  # (--dtype f16: both the single-edit and the stacked model, every launch in its fp16 form)
         return m
 
     torch.manual_seed(0)
@@ -208,8 +211,11 @@ def main_stacked(kind, a, script):
     res = {"workload": what + "; exact fp32, channels-last, hipGraph replay, default-initialised weights (seed 0); stacked edits: E "
                               "edited versions of one original under one square mask each, another noise per edit",
            "source_hash": build.source_hash(), "steps": a.steps, "batches": a.batches, "rows": []}
-    common = ["--stacked", "--steps", str(a.steps), "--batches", str(a.batches)]
-    jobs = ([("attention", ["--attention"])] if kind == "decoder" else []) + [(r, ["--ratio", r]) for r in a.ratios.split(",")]
+    f16 = getattr(a, "dtype", "f32") == "f16"
+    common = ["--stacked", "--steps", str(a.steps), "--batches", str(a.batches)] + (["--dtype", "f16"] if f16 else [])
+    jobs = ([("attention", ["--attention"])] if kind == "decoder" and not f16 else []) + [(r, ["--ratio", r]) for r in a.ratios.split(",")]
+    if f16:
+        res["workload"] = res["workload"].replace("exact fp32, ", "f16 compute mode (set_compute_dtype), ")
     for tag, extra in jobs:
         cmd = ["timeout", "-k", "10", str(a.limit), sys.executable, os.path.abspath(script), *extra, *common]
         p = subprocess.run(cmd, cwd=REPO, capture_output=True, text=True)
@@ -223,12 +229,12 @@ def main_stacked(kind, a, script):
         else:
             res["rows"].append(json.loads(line[len(TAG):]))
         print("%s --stacked: %s done" % (os.path.basename(script), tag), file=sys.stderr, flush=True)
-    out = a.stacked_out or OUT
+    out = a.stacked_out or (OUT_F16 if f16 else OUT)
     both = {}
     if os.path.isfile(out):
         with open(out) as f:
             both = json.load(f)
-    both[kind] = res
+    both[kind + "_stacked" if f16 else kind] = res
     with open(out, "w") as f:
         json.dump(both, f, indent=1)
         f.write("\n")
