@@ -636,6 +636,36 @@ int sige_hip_tile_conv3_block_nhwc(
         float *twin1, const float *twin_scale1, const float *twin_shift1,
         float *out, void *stream);
 
+/* ---- the nearest-x2 Upsample conv as four 2x2 phase convs ON THE TILE CONV V3 (csrc/conv_tile3.hpp: Tile3GeoP):
+ * what sige_hip_gather_conv_nhwc(upsample2x = 2) computes, on grids that fill the chip, in exact fp32 and on fp16 operands, under
+ * stacked edits too.  A workgroup is 8 tiles x one phase x 64 output channels; the grid is ceil(B N / 8) * (Cout / 64) x 4.
+ *   n = sige_hip_upsample_phase_tile3_packed_size(Cout, Cin, prec)   floats; prec 2: exact fp32, 0: fp16 (sige_hip_wide_conv_pack's)
+ *   sige_hip_upsample_phase_tile3_pack(w_phases, ..., prec, packed)  w_phases [4,Cout,Cin,2,2] fp32, phase 2a + b: the tap sums;
+ *       four sub-packs in the v3 stream order [ntile][wave][chunk][step], 4 steps per chunk, each with padding of its own;
+ *       prec 0 rounds the sums once more, to fp16 (RNE, saturated)
+ * sige_hip_upsample_phase_tile3_nhwc: x [B,H/2,W/2,C], (H, W) the upsampled size the 6x6 tile origins index, raw (no affine, one
+ * tensor), straight into out [B,Ho,Wo,Cout] at offset + origin (clipped) with bias, fp32 `residual`, out-affine and both twins as
+ * sige_hip_tile_conv3_nhwc; cells outside the list are untouched.  compute 0: exact fp32; 1: activations rounded to fp16 (RNE,
+ * saturated) in the staging path, fp32 accumulation, tensors fp32 in memory.  Stacked edits: a tile reads the rows of its own image.
+ * The call runs when its grid has at least `min_blocks` > 0 workgroups.  SIGE_HIP_EUNSUPPORTED -- nothing touched, never a wrong
+ * answer -- for a smaller grid, min_blocks <= 0, C or Cout not a multiple of 64, odd H or W, compute 2, a call
+ * sige_hip_conv_side_begin waits for, and while a launch plan records (no plan hook).  A shortcut held by sige_hip_conv_pair_begin
+ * is launched first; queued side convs are flushed on a hazard.  N = 0 or B = 0: SIGE_HIP_OK, no launch.
+ * PRECONDITION the library cannot check (the index list lives on the device): every tile origin is ODD in both coordinates, beside
+ * odd offsets (an even offset IS checked: SIGE_HIP_EUNSUPPORTED) -- the lists of a padding-1 3x3 conv, origins (4i - 1, 4j - 1) with offset (1, 1) -- so that a tile's 4x4 output
+ * block starts on an even hi-res pixel and splits into whole 2x2 phase blocks.  On any other list the phase decomposition is not the
+ * 9-tap conv; such callers keep upsample2x = 1.  (The same holds for sige_hip_gather_conv_nhwc with upsample2x = 2.) */
+int sige_hip_upsample_phase_tile3_supported(int C, int Cout);
+size_t sige_hip_upsample_phase_tile3_packed_size(int Cout, int Cin, int prec);
+int sige_hip_upsample_phase_tile3_pack(const float *w_phases, int Cout, int Cin, int prec, float *packed, void *stream);
+int sige_hip_upsample_phase_tile3_nhwc(
+        int compute, const float *x, int B, int C, int H, int W, const int32_t *active_indices, int N,
+        const float *packed_phase3, const float *bias, int Cout, int offsetH, int offsetW, const float *residual, int Ho, int Wo,
+        const float *out_scale, const float *out_shift, int out_activation,
+        float *twin0, const float *twin0_scale, const float *twin0_shift,
+        float *twin1, const float *twin1_scale, const float *twin1_shift,
+        int min_blocks, float *out, void *stream);
+
 /* ---- token-matrix helpers of Stable Diffusion's spatial transformer (csrc/token_ops.hip; sige_attention.py:86-185): tokens [T,C]
  * row-major fp32.  add_layer_norm: y = x (+ delta + bias[c] when delta != NULL; bias may be NULL); sum_out = y when not NULL;
  * out = LayerNorm(y) * gamma + beta (eps as nn.LayerNorm's).  geglu: out[t,d] = x[t,d] * gelu(x[t,D+d]), x [T,2D] (F.gelu's erf

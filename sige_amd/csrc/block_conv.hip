@@ -868,6 +868,19 @@ static int staging_mode(const StagingAffine &f, int B, int C, int *aff_sb, int *
 
 // (conv_tile3.hip: the 10x10-window form neither joins nor overtakes work held or queued on the stacked-block kernels)
 bool conv_hold_pending() { return g_held.active || g_side_armed > 0 || !g_side.empty(); }
+
+// (conv_tile3_phase.hip: the phase convs on the v3 kernel treat what is held or queued as launch_phase_up does -- a held shortcut is
+// launched first, queued side convs are flushed when they sit on another stream or `a` reads or writes one of their operands; a
+// call sige_hip_conv_side_begin waits for is not theirs to take)
+bool conv_side_armed() { return g_side_armed > 0; }
+int flush_for_phase_tile3(const float *x, const float *residual, float *out, float *twin0, float *twin1, hipStream_t st) {
+    int rc = flush_held();
+    if (rc != SIGE_HIP_OK) return rc;
+    ConvArgs a{};
+    a.x = x; a.residual = residual; a.out = out; a.twin0 = twin0; a.twin1 = twin1;
+    if (!g_side.empty() && (g_side.front().st != st || side_hazard(a))) rc = flush_side();
+    return rc;
+}
 }  // namespace sige
 
 using namespace sige;

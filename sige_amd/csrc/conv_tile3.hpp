@@ -37,6 +37,7 @@ struct Tile3Geo {
     static constexpr bool F32 = PREC_ == WIDE_F32;
     static_assert(PREC_ == WIDE_F32 || PREC_ == WIDE_F16, "tile conv v3: exact fp32 or fp16 operands");
     static constexpr int KK = 9;
+    static constexpr bool PHASE = false;
     // window geometry (Tile3GeoE10 below: the same kernel over 10x10 windows): edge, output edge = 1 << OSH, pixels of a window /
     // of its output, staged pixels between the M tiles of a wave
     static constexpr int EDGE = 6, OSH = 2, OE = 4, WPX = 36, OPX = 16, MT_STRIDE = 72;
@@ -78,6 +79,7 @@ struct Tile3GeoE10 {
     static constexpr int TPW = 1, PREC = WIDE_F32;
     static constexpr bool F32 = true;
     static constexpr int KK = 9;
+    static constexpr bool PHASE = false;
     static constexpr int EDGE = 10, OSH = 3, OE = 8, WPX = 100, OPX = 64, MT_STRIDE = 40;
     static constexpr int MTN = 2, BM = 64;
     static constexpr int NP = 2, CW = 16, CC = 64, STEPS = 9;
@@ -87,6 +89,42 @@ struct Tile3GeoE10 {
     static constexpr int LDS_BYTES = cmax(4 * 2 * ABUF, 4 * BM * 68 * 4);
     static_assert((2 * STEPS) % RB == 0, "the ring position of a step must not depend on the chunk");
     static_assert(NS == 7 && LDS_BYTES == 69632, "10x10 windows: 7 staging slots, the reduction buffer bounds the LDS");
+};
+
+// The same kernel over the four 2x2 PHASE convs of "nearest x2, then this 3x3 conv" (DESIGN.md 5.19 / 5.29): a workgroup is TPW tiles x
+// ONE phase (a, b) = (blockIdx.y >> 1, blockIdx.y & 1) x 64 output channels.  A tile's window is the 3x3 window of the HALF-resolution
+// tensor at ((h0 + 1) / 2 - 1 + a, (w0 + 1) / 2 - 1 + b), (h0, w0) the hi-res 6x6 origin of the unchanged index list; its output is
+// the tile's 2x2 phase block, pixel (y, x) at hi-res (h0 + 1 + 2y + a, w0 + 1 + 2x + b); tap (kh, kw) of output (y, x) reads staged
+// pixel (y + kh) * 3 + (x + kw), so the phase enters the staging coordinates (and the choice of the weight sub-pack) only.  A 32-pixel
+// M tile is 8 tiles x 4 pixels.  TPW = 8: 72 staged pixels, the footprint of Tile3Geo<2> (46 080 B of stages in fp32; fp16: the
+// 34 816 B of the reduction buffer).  Four k-steps per chunk: the ring is 2, 4 or 8 steps.
+// (workgroups per CU, ring) built: fp32 (3, 4) and fp16 (3, 4) -- the pairs DESIGN.md 5.29 lists with their registers; -D overrides
+// for A/B builds as for SIGE_T3H_RB.
+#ifndef SIGE_T3P_RB
+#define SIGE_T3P_RB 4
+#endif
+#ifndef SIGE_T3P_OCC
+#define SIGE_T3P_OCC 3
+#endif
+template <int TPW_, int PREC_ = WIDE_F32>
+struct Tile3GeoP {
+    static constexpr int TPW = TPW_, PREC = PREC_;
+    static constexpr bool F32 = PREC_ == WIDE_F32;
+    static_assert(PREC_ == WIDE_F32 || PREC_ == WIDE_F16, "tile conv v3: exact fp32 or fp16 operands");
+    static_assert(TPW_ % 8 == 0, "a 32-pixel M tile is 8 tiles x 4 pixels");
+    static constexpr int KK = 4;
+    static constexpr bool PHASE = true;
+    static constexpr int EDGE = 3, OSH = 1, OE = 2, WPX = 9, OPX = 4, MT_STRIDE = 72;
+    static constexpr int MTN = TPW_ / 8, BM = 4 * TPW_;
+    static constexpr int NP = F32 ? 2 : 1, CW = 16, CC = 64, STEPS = 4;
+    static constexpr int NPX = WPX * TPW_, QP = CW / 4, UNITS = NPX * QP, NS = (UNITS + 63) / 64;
+    static constexpr int KSB = 32 * NP, KQB = F32 ? 32 : 16, PLB = F32 ? 16 : 32, ROWB = KSB + 16, ABUF = NPX * ROWB, STEPB = 2 * NP * 1024;
+    static constexpr int RB = SIGE_T3P_RB, OCC = SIGE_T3P_OCC;
+    static constexpr int LDS_BYTES = cmax(4 * 2 * ABUF, 4 * BM * 68 * 4);
+    static_assert((2 * STEPS) % RB == 0, "the ring position of a step must not depend on the chunk");
+    static_assert(RB <= kWidePadSteps, "the read-ahead stays inside a sub-pack's padding");
+    // bytes of one phase's sub-pack: the v3 stream [ntile][wave][chunk][step] + its own padding (sige_hip_upsample_phase_tile3_pack)
+    static constexpr long sub_bytes(int ntn, int nchunks) { return (long)ntn * 4 * nchunks * STEPS * STEPB + (long)kWidePadSteps * STEPB; }
 };
 
 struct Tile3Args {
@@ -111,12 +149,16 @@ struct Tile3Args {
 
 // One workgroup: tiles [mtile * TPW, (mtile + 1) * TPW) x output channels [64 ntile, 64 ntile + 64).
 // Y16: SCATTER_GATHER only -- the cached tensor (x2) holds halves (SIGEModel.set_cache_dtype("f16"))
+// `ph`: the phase 2a + b of a Tile3GeoP launch (0 otherwise)
 template <typename G, int SRC, bool AFF, bool CAT, bool FULL, bool Y16 = false>
-__device__ __forceinline__ void conv_tile3_body(const Tile3Args &a, const int bx, unsigned char *const smem) {
+__device__ __forceinline__ void conv_tile3_body(const Tile3Args &a, const int bx, unsigned char *const smem, const int ph = 0) {
     constexpr int NS = G::NS, STEPS = G::STEPS, RB = G::RB, NP = G::NP, MTN = G::MTN;
     constexpr bool SG = SRC == T3_SCATTER_GATHER;
     constexpr bool F32 = G::F32;
+    constexpr bool PH = G::PHASE;
     static_assert(!Y16 || SG, "fp16-stored cache: the scatter_gather source");
+    static_assert(!PH || (SRC == T3_GATHER && !AFF && !CAT && FULL), "phase convs: a raw gather of one tensor into a full tensor");
+    const int ph_a = ph >> 1, ph_b = ph & 1;
     constexpr bool TWO = CAT || SG;  // a slot may come from the second tensor
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -142,14 +184,25 @@ __device__ __forceinline__ void conv_tile3_body(const Tile3Args &a, const int bx
         const int b = tt / a.N, n = tt - b * a.N;
         const int2 o = *reinterpret_cast<const int2 *>(a.idx + 2 * n);
         z_b[i] = b;
-        z_h[i] = o.x + q / G::EDGE;
-        z_w[i] = o.y + q % G::EDGE;
-        int hlo = 0, hhi = a.H;
-        if (a.hp_shift) {  // stacked edits: rows beyond the tile's own image are zero padding (its window's third row is inside it)
-            hlo = ((o.x + 2) >> a.hp_shift) << a.hp_shift;
-            hhi = hlo + (1 << a.hp_shift);
+        if constexpr (PH) {  // (low-res coordinates; stacked edits: the image of hi-res row o.x + 2, its low-res rows [img Hi/2, (img + 1) Hi/2))
+            z_h[i] = ((o.x + 1) >> 1) - 1 + ph_a + q / G::EDGE;
+            z_w[i] = ((o.y + 1) >> 1) - 1 + ph_b + q % G::EDGE;
+            int hlo = 0, hhi = Hs;
+            if (a.hp_shift) {
+                hlo = ((o.x + 2) >> a.hp_shift) << (a.hp_shift - 1);
+                hhi = hlo + (1 << (a.hp_shift - 1));
+            }
+            z_ok[i] = z_ok[i] && z_h[i] >= hlo && z_h[i] < hhi && z_w[i] >= 0 && z_w[i] < Ws;
+        } else {
+            z_h[i] = o.x + q / G::EDGE;
+            z_w[i] = o.y + q % G::EDGE;
+            int hlo = 0, hhi = a.H;
+            if (a.hp_shift) {  // stacked edits: rows beyond the tile's own image are zero padding (its window's third row is inside it)
+                hlo = ((o.x + 2) >> a.hp_shift) << a.hp_shift;
+                hhi = hlo + (1 << a.hp_shift);
+            }
+            z_ok[i] = z_ok[i] && z_h[i] >= hlo && z_h[i] < hhi && z_w[i] >= 0 && z_w[i] < a.W;
         }
-        z_ok[i] = z_ok[i] && z_h[i] >= hlo && z_h[i] < hhi && z_w[i] >= 0 && z_w[i] < a.W;
         ldsw[i] = p * G::ROWB + (v % G::QP) * 8;
     });
     int z_m0[SG ? NS : 1], z_m1[SG ? NS : 1], z_m2[SG ? NS : 1];
@@ -171,7 +224,9 @@ __device__ __forceinline__ void conv_tile3_body(const Tile3Args &a, const int bx
             voff[i] = (in && blk >= 0) ? (unsigned)((((z_b[i] * a.N + blk) * a.Rx + z_m1[i]) * a.Sx + z_m2[i]) * Cin + cb) * 4u : kOOB;
             voff2[i] = (in && blk < 0) ? (unsigned)(((z_b[i] * a.H + z_h[i]) * a.W + z_w[i]) * Cin + cb) * (Y16 ? 2u : 4u) : kOOB;
         } else {
-            const int spx = (z_b[i] * Hs + (z_h[i] >> a.up)) * Ws + (z_w[i] >> a.up);
+            int spx;
+            if constexpr (PH) spx = (z_b[i] * Hs + z_h[i]) * Ws + z_w[i];  // (low-res already)
+            else spx = (z_b[i] * Hs + (z_h[i] >> a.up)) * Ws + (z_w[i] >> a.up);
             voff[i] = in ? (unsigned)(spx * a.C1 + cb) * 4u : kOOB;
             if constexpr (CAT) voff2[i] = in ? (unsigned)(spx * a.C2 + cb) * 4u : kOOB;
         }
@@ -252,7 +307,9 @@ __device__ __forceinline__ void conv_tile3_body(const Tile3Args &a, const int bx
 
     // ---- B: this wave's stream of packed weights, contiguous over (chunk, k-step) ----
     const long stream_bytes = (long)a.nchunks * STEPS * G::STEPB;
-    const unsigned char *const bstream = reinterpret_cast<const unsigned char *>(a.packed) + ((long)(ntile * 4 + wave) * a.nchunks + first) * STEPS * G::STEPB;
+    long sub = 0;  // (phase convs: this phase's sub-pack, a v3 stream with padding of its own)
+    if constexpr (PH) sub = ph * G::sub_bytes(a.ntn, a.nchunks);
+    const unsigned char *const bstream = reinterpret_cast<const unsigned char *>(a.packed) + sub + ((long)(ntile * 4 + wave) * a.nchunks + first) * STEPS * G::STEPB;
     const long left = (long)a.ntn * 4 * stream_bytes - ((long)(ntile * 4 + wave) * a.nchunks + first) * STEPS * G::STEPB + (long)kWidePadSteps * G::STEPB;
     const rsrc_t r_b = __builtin_amdgcn_make_buffer_rsrc(const_cast<unsigned char *>(bstream), 0,
                                                          __builtin_amdgcn_readfirstlane((int)(left > 0x7fffffffL ? 0x7fffffffL : left)), 0x00020000);
@@ -269,12 +326,15 @@ __device__ __forceinline__ void conv_tile3_body(const Tile3Args &a, const int bx
     // ---- A operand of this lane: pixel i32 of M tile mt = tiles 2 mt, 2 mt + 1 of the workgroup; k-group kq ----
     const int i32 = lane & 31, kq = lane >> 5;
     // (10x10 windows: pixel i32 of M tile mt = output row 4 mt + (i32 >> 3), column i32 & 7 of the workgroup's window)
-    const int abase = (G::EDGE == 6 ? (i32 >> 4) * 36 + ((i32 & 15) >> 2) * 6 + (i32 & 3) : (i32 >> 3) * G::EDGE + (i32 & 7)) * G::ROWB +
+    // (phase convs: pixel i32 = tile i32 >> 2 of the M tile's eight, output (y, x) = ((i32 >> 1) & 1, i32 & 1) of its 2x2 block)
+    const int abase = (PH ? (i32 >> 2) * 9 + ((i32 >> 1) & 1) * 3 + (i32 & 1)
+                          : G::EDGE == 6 ? (i32 >> 4) * 36 + ((i32 & 15) >> 2) * 6 + (i32 & 3) : (i32 >> 3) * G::EDGE + (i32 & 7)) * G::ROWB +
                       kq * G::KQB;  // + mt * MT_STRIDE * ROWB
     struct AHalf { f16x8 v[MTN]; };
     auto a_read = [&](auto s_tag, const unsigned char *buf, int plane) -> AHalf {
         constexpr int tap = decltype(s_tag)::value;
-        constexpr int off = ((tap / 3) * G::EDGE + tap % 3) * G::ROWB;
+        constexpr int KW = PH ? 2 : 3;  // taps per kernel row
+        constexpr int off = ((tap / KW) * G::EDGE + tap % KW) * G::ROWB;
         AHalf r;
 #pragma unroll
         for (int mt = 0; mt < MTN; ++mt) r.v[mt] = *reinterpret_cast<const f16x8 *>(buf + abase + mt * G::MT_STRIDE * G::ROWB + off + plane * G::PLB);
@@ -409,7 +469,8 @@ __device__ __forceinline__ void conv_tile3_body(const Tile3Args &a, const int bx
         if constexpr (FULL) {
             const int b = t / a.N, n = t - b * a.N;
             const int2 og = *reinterpret_cast<const int2 *>(a.idx + 2 * n);
-            const int h = a.offH + og.x + (pix >> G::OSH), w = a.offW + og.y + (pix & (G::OE - 1));
+            constexpr int PS = PH ? 2 : 1;  // (phase convs: the 2x2 block's pixels are two hi-res pixels apart, from (a, b))
+            const int h = a.offH + og.x + PS * (pix >> G::OSH) + ph_a, w = a.offW + og.y + PS * (pix & (G::OE - 1)) + ph_b;
             if (h < 0 || h >= a.Ho || w < 0 || w >= a.Wo) continue;
             addr = (((size_t)b * a.Ho + h) * a.Wo + w) * a.Cout + co;
             if (a.residual) {  // out = conv + residual; with a block residual: + (x1 - residual) where a shortcut tile covers the pixel
@@ -453,6 +514,14 @@ __global__ __launch_bounds__(256, G::OCC) void conv_tile3_kernel(const Tile3Args
     conv_tile3_body<G, SRC, AFF, CAT, FULL, Y16>(a, blockIdx.x, smem);
 }
 
+// the phase convs' launch: blockIdx.y = the phase (a raw gather of one tensor into a full tensor, the only form they have)
+template <typename G>
+__global__ __launch_bounds__(256, G::OCC) void conv_tile3_phase_kernel(const Tile3Args a) {
+    kernarg_touch<sizeof(Tile3Args)>();
+    __shared__ __attribute__((aligned(16))) unsigned char smem[G::LDS_BYTES];
+    conv_tile3_body<G, T3_GATHER, false, false, true>(a, blockIdx.x, smem, blockIdx.y);
+}
+
 // the host side of a v3 launch (conv_tile3.hip): argument checks, Tile3Args, launch.  `c.packed_tile3` holds the weights; prec:
 // WIDE_F32 | WIDE_F16; block: 6 | 10, the window edge.  SIGE_HIP_EUNSUPPORTED: the caller falls back
 struct TileConvCall;  // (conv_call.hpp)
@@ -465,5 +534,8 @@ template <int TPW, int PREC = WIDE_F32>
 void launch_conv_tile3_gather(const Tile3Args &a, bool aff, bool cat, bool full, hipStream_t st);
 template <int TPW, int PREC = WIDE_F32>
 void launch_conv_tile3_sg(const Tile3Args &a, bool full, bool y16, hipStream_t st);
+
+template <int TPW, int PREC>
+void launch_conv_tile3_phase(const Tile3Args &a, hipStream_t st);  // (conv_tile3_phase.hip)
 
 }  // namespace sige

@@ -109,6 +109,12 @@ _SIGNATURES = {
     "sige_hip_tile_conv3_block_nhwc": (
         _c_int, [_c_int, _c_int, _c_vp, _c_vp, _c_int] + [_c_int] * 8 + [_c_vp, _c_int, _c_vp, _c_int, _c_int] + [_c_vp, _c_vp, _c_int, _c_int]
         + [_c_vp, _c_vp, _c_int] + [_c_int] * 5 + [_c_vp, _c_int] + [_c_vp, _c_vp] + [_c_int] * 5 + [_c_vp, _c_vp, _c_int] + [_c_vp] * 6 + [_c_vp, _c_vp]),
+    "sige_hip_upsample_phase_tile3_supported": (_c_int, [_c_int] * 2),
+    "sige_hip_upsample_phase_tile3_packed_size": (_c_sz, [_c_int] * 3),
+    "sige_hip_upsample_phase_tile3_pack": (_c_int, [_c_vp] + [_c_int] * 3 + [_c_vp, _c_vp]),
+    "sige_hip_upsample_phase_tile3_nhwc": (
+        _c_int, [_c_int, _c_vp] + [_c_int] * 4 + [_c_vp, _c_int, _c_vp, _c_vp] + [_c_int] * 3 + [_c_vp, _c_int, _c_int]
+        + [_c_vp, _c_vp, _c_int] + [_c_vp] * 6 + [_c_int, _c_vp, _c_vp]),
     "sige_hip_conv_ksplit_hint": (_c_int, [_c_int] * 7),
     "sige_hip_gather_nhwc_f32": (
         _c_int, [_c_vp] + [_c_int] * 6 + [_c_vp, _c_int] + [_c_vp, _c_int, _c_int] * 2 + [_c_int, _c_vp, _c_vp]),
@@ -1020,6 +1026,46 @@ def upsample_phase_pack(weight: torch.Tensor, kernels: Optional[torch.Tensor] = 
     return packed
 
 
+# The phase form on the tile conv v3 (csrc/conv_tile3.hpp: Tile3GeoP), behind Gather.PHASE_UPSAMPLE_TILE3 (off):
+# sige_hip_upsample_phase_tile3_nhwc runs a call whose grid -- ceil(tiles / 8) x (Cout / 64) x 4 phases -- has at least this many
+# workgroups and refuses smaller ones, which then take today's route.  The values are read off the launch-alone table of
+# profiles/upsample_phase_tile3_bench.json (each launch against the launch the same call takes today -- the phase form of
+# conv_mfma.hpp or the 9-tap tile conv v3 in fp32, the 9-tap fp16 tile convs in f16 -- same process, alternating, weights L2-warm):
+# exact fp32 wins at every measured grid from 448 workgroups on (1.2 - 2.0 x at 448 ... 5408) and loses at 320 (128 channels,
+# 318 tiles: 13.6 against 11.7 us) and at <= 128; fp16 operands win at every measured grid from 64 on (1.1 - 2.0 x) and tie at 32.
+# Whole forwards with these values, switch on against off: DESIGN.md 5.29 (every measured row gains).
+PHASE_TILE3_MIN_BLOCKS = 448
+PHASE_TILE3_MIN_BLOCKS_F16 = 64  # (compute "f16" passes the smaller of the two, so a test's PHASE_TILE3_MIN_BLOCKS = 1 holds for both)
+
+
+def upsample_phase_tile3_pack(weight: torch.Tensor, compute: str = "f32", kernels: Optional[torch.Tensor] = None,
+                              out: Optional[torch.Tensor] = None) -> Optional[torch.Tensor]:
+    """The `packed_phase3` operand of sige_hip_upsample_phase_tile3_nhwc for a [Cout,Cin,3,3] weight: `kernels` =
+    upsample_phase_kernels(weight) as four sub-packs in the tile conv v3's stream order, exact fp32 rows (compute "f32") or rounded
+    once more to fp16 (compute "f16").  None where the channel counts have no such kernel; `out`: an earlier pack of the same shape
+    and compute, rewritten in place."""
+    if weight.dim() != 4 or tuple(weight.shape[2:]) != (3, 3):
+        raise ValueError("upsample_phase_tile3_pack: a [Cout,Cin,3,3] weight")
+    if compute not in ("f32", "f16"):
+        raise ValueError("upsample_phase_tile3_pack: compute must be 'f32' or 'f16'")
+    w = _req(weight.detach(), torch.float32, "weight")
+    Cout, Cin = w.shape[:2]
+    if not lib().sige_hip_upsample_phase_tile3_supported(Cin, Cout):
+        return None
+    prec = _WIDE_PREC[compute]
+    n = int(lib().sige_hip_upsample_phase_tile3_packed_size(Cout, Cin, prec))
+    if out is not None and (out.numel() != n or out.device != w.device or getattr(out, "compute", None) != compute):
+        raise ValueError("upsample_phase_tile3_pack: `out` is not a pack of this shape and compute")
+    packed = torch.empty((n,), dtype=torch.float32, device=w.device).as_subclass(PackedWeights) if out is None else out
+    packed.compute = compute
+    wp = _req(upsample_phase_kernels(w) if kernels is None else kernels, torch.float32, "kernels", 5)
+    if tuple(wp.shape) != (4, Cout, Cin, 2, 2):
+        raise ValueError("upsample_phase_tile3_pack: `kernels` must be [4,Cout,Cin,2,2]")
+    _check(lib().sige_hip_upsample_phase_tile3_pack(wp.data_ptr(), Cout, Cin, prec, packed.data_ptr(), _stream(w)),
+           "upsample_phase_tile3_pack")
+    return packed
+
+
 # ---- dense layers on the fp16 matrix cores (csrc/conv_wide.hpp) ----
 COMPUTE_DTYPES = ("f32", "f16", "f16x3")
 
@@ -1817,12 +1863,17 @@ def tile_conv3_cl(source: int, x, x2, B, C1, C2, H, W, up, idx, smap, rx_sx, sca
 def gather_conv_cl(x, x2, block: Tuple[int, int], activeIndices, scale, shift, activationName: str,
                    packed, bias, Cout: int, kernel: Tuple[int, int], stride: Tuple[int, int],
                    full: Optional[dict] = None, out_affine: Optional[tuple] = None, upsample2x: bool = False,
-                   out: Optional[torch.Tensor] = None, twins=None, phase=None):
+                   out: Optional[torch.Tensor] = None, twins=None, phase=None, phase3=None):
     """Channels-last gather -> conv.  `full` = dict(offset=(oh, ow), out_res=(Ho, Wo), residual=tensor|None)
     writes the output tiles straight into a [B,Cout,Ho,Wo] tensor (dense layers).  `twins` (full only): up to two
     (buffer, scale, shift): buffer = SiLU(scale * result + shift), the activated input of a consumer's conv1, written by
     the same launch.  `phase` (with upsample2x and `full`): the conv's phase pack (upsample_phase_pack) -- the launch is tried in
     the phase form first (include/sige_hip.h: upsample2x = 2) and repeated in the 9-tap form where the library refuses it.
+    `phase3` (the same calls, no x2, no gather affine): the conv's upsample_phase_tile3_pack for this call's compute -- tried
+    before anything else on sige_hip_upsample_phase_tile3_nhwc, which refuses grids below the threshold handed to it; a refused call
+    goes on exactly as without it.  The threshold: PHASE_TILE3_MIN_BLOCKS for an exact-fp32 call; for compute "f16" the SMALLER of
+    PHASE_TILE3_MIN_BLOCKS and PHASE_TILE3_MIN_BLOCKS_F16 -- fp16 operands win from smaller grids on, and lowering
+    PHASE_TILE3_MIN_BLOCKS (tests and tools set it to 1) lowers both; to RAISE the f16 threshold raise both values.
     None if unsupported."""
     geo, usable = _geometry_of(block, kernel, stride, packed)
     if not usable:
@@ -1865,6 +1916,20 @@ def gather_conv_cl(x, x2, block: Tuple[int, int], activeIndices, scale, shift, a
         raise RuntimeError("gather_conv_cl: twins need a full-tensor destination")
     targs, twin_keep = _twin_args(twins if twins else None, out, Cout, "gather_conv_cl")
     compute = _compute_id(packed)
+    if (phase3 is not None and upsample2x and full is not None and x2 is None and scale is None and shift is None
+            and activationName == "identity" and geo is None and _compute_id(phase3) == compute
+            and (tuple(block), tuple(kernel), tuple(stride)) == ((6, 6), (3, 3), (1, 1))):
+        oargs3, o_keep3 = _out_affine_args(out_affine, Cout, "gather_conv_cl")
+        status = lib().sige_hip_upsample_phase_tile3_nhwc(
+            compute, x.data_ptr(), B, C1, H, W, idx.data_ptr(), N, phase3.data_ptr(), _p(bias_keep), Cout, full["offset"][0], full["offset"][1],
+            None if r is None else r.data_ptr(), Ho, Wo, *oargs3, *targs,
+            int(min(PHASE_TILE3_MIN_BLOCKS, PHASE_TILE3_MIN_BLOCKS_F16) if compute == 1 else PHASE_TILE3_MIN_BLOCKS), out.data_ptr(), _stream(x))
+        if status != UNSUPPORTED:
+            _check(status, "gather_conv_cl")
+            keep = getattr(_pair_state, "keep", None)
+            if keep is not None:  # (conv_pair(): a launch held before this call was flushed by it; its operands stay alive as ever)
+                keep.append((x, idx, phase3, bias_keep, out, out_affine, full, twin_keep))
+            return out
     t3 = _tile3_route(packed, B * N, C1, C2, Cout, kernel, stride, block)  # (TILE3 = True: the v3 kernel, forced)
     if getattr(_side_state, "armed", False):
         t3 = None  # (conv_side_begin() waits for THIS call: it stays on the kernels that can queue it)
@@ -1921,7 +1986,7 @@ def gather_conv_cl(x, x2, block: Tuple[int, int], activeIndices, scale, shift, a
         out = tag_tiles(out, idx, B)
     keep = getattr(_pair_state, "keep", None)
     if keep is not None:  # (conv_pair(): a held launch reads these after this call has returned)
-        keep.append((x, x2, idx, s_keep, t_keep, packed, phase, bias_keep, out, ws, out_affine, full, twin_keep))
+        keep.append((x, x2, idx, s_keep, t_keep, packed, phase, phase3, bias_keep, out, ws, out_affine, full, twin_keep))
     if getattr(_side_state, "armed", False):  # (conv_side_begin(): so do the hosts of a queued conv, until conv_side_flush())
         _side_state.armed = False
         _side_state.keep.append((x, x2, idx, s_keep, t_keep, packed, bias_keep, out, ws, out_affine, full, twin_keep))

@@ -134,6 +134,7 @@ class SIGEConv2d(nn.Conv2d, SIGEModule):
         SIGEModule.__init__(self, call_super=False)
         self._packed = {}
         self._phase = None  # [key, phase kernels, their pack | None]: see phase_kernels()
+        self._phase3 = None  # (key, the phase pack of the tile conv v3 | None): see phase_tile3_packed()
         self._tiles_runtime = self.load_runtime("conv2d_tiles", {})
         # "f32": exact fp32 products (v_mfma_f32_*_f32); "f16": fp16 operands, fp32 accumulation on the 16x faster fp16
         # matrix path (SIGEModel.set_compute_dtype; channels-last tiles only -- BASELINE.json configs[4])
@@ -196,17 +197,41 @@ class SIGEConv2d(nn.Conv2d, SIGEModule):
             self._phase[2] = hip.upsample_phase_pack(self.weight, wp)
         return self._phase[2]
 
+    def phase_tile3_packed(self):
+        """The phase kernels of this conv laid out for the tile conv v3 (sige_amd.hip.upsample_phase_tile3_pack) in
+        this conv's compute dtype, or None: anything but a plain 3x3 / stride-1 / padding-1 / groups-1 conv with channels in multiples
+        of 64 on a GPU, and compute "f16x3".  Derived state of its own (`_phase` and `phase_kernels()` keep their meaning): keyed
+        like them, dropped by `clear_cache()`, rewritten in place by `rebuild_derived_caches()`, never part of the state dict."""
+        if (tuple(self.kernel_size) != (3, 3) or tuple(self.stride) != (1, 1) or tuple(self.padding) != (1, 1) or self.groups != 1
+                or tuple(self.dilation) != (1, 1) or self.compute_dtype not in ("f32", "f16") or not self.weight.is_cuda
+                or self.in_channels % 64 or self.out_channels % 64):
+            return None
+        from .. import hip
+
+        key = self._phase_key()
+        if self._phase3 is None or self._phase3[0] != key:
+            self._phase3 = (key, hip.upsample_phase_tile3_pack(self.weight, self.compute_dtype))
+        return self._phase3[1]
+
     def clear_cache(self):
         self._phase = None
+        self._phase3 = None
 
     def rebuild_derived_caches(self):
-        """Derive the phase kernels again; their pack is rewritten IN PLACE where its size still fits (a captured graph keeps
+        """Derive the phase kernels again; their packs are rewritten IN PLACE where their size still fits (a captured graph keeps
         reading the same address)."""
         old, self._phase = self._phase, None
         if old is not None and old[2] is not None and self.phase_kernels() is not None and old[0][2:4] == self._phase[0][2:4]:
             from .. import hip
 
             self._phase[2] = hip.upsample_phase_pack(self.weight, self._phase[1], out=old[2])
+        old3, self._phase3 = self._phase3, None
+        if old3 is not None and old3[1] is not None:
+            from .. import hip
+
+            key = self._phase_key()
+            if key[2:] == old3[0][2:]:  # (same shape, device and compute dtype: the same size and layout)
+                self._phase3 = (key, hip.upsample_phase_tile3_pack(self.weight, self.compute_dtype, out=old3[1]))
 
     def _block_conv(self, x: torch.Tensor, out_affine=None) -> torch.Tensor:
         from .. import hip

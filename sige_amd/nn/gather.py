@@ -24,6 +24,9 @@ class Gather(SIGEModule):
     # channel pair instead of 9 on copied pixels (sige_amd.hip.upsample_phase_kernels).  Sparse mode, GPU,
     # channels-last, exact-fp32 convs, one edit; anything else, and False, gives the 9-tap launch and its bits.
     PHASE_UPSAMPLE = True
+    # The same four phase convs on the tile conv v3: launches whose grid reaches sige_amd.hip.PHASE_TILE3_MIN_BLOCKS
+    # -- large edits, stacked edits, the SD VAE decoder -- in exact fp32 and on fp16 operands, any edit batch.  Off: no new code runs.
+    PHASE_UPSAMPLE_TILE3 = False
 
     def __init__(
         self,
@@ -138,7 +141,8 @@ class Gather(SIGEModule):
                 return deferred.DeferredTiles(
                     (x.shape[0] * idx.shape[0], channels, bh, bw), x.dtype, x.device, run,
                     dict(kind="gather", x=x, x2=x2, block=(bh, bw), idx=idx, scale=scale, shift=shift, act=act, cl=cl,
-                         up=upsample2x, phase=bool(upsample2x and self.PHASE_UPSAMPLE)))
+                         up=upsample2x, phase=bool(upsample2x and self.PHASE_UPSAMPLE),
+                         phase3=bool(upsample2x and self.PHASE_UPSAMPLE_TILE3)))
             return run()
         if self.mode == "full":
             self.note_full_input(x.shape[2:])

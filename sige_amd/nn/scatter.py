@@ -292,10 +292,15 @@ def _fused_conv_into(conv, tiles, out, g: Gather, residual=None, x1=None, table1
         if (spec.get("phase") and spec.get("x2") is None and spec["scale"] is None and spec["shift"] is None and spec["act"] == "identity"
                 and getattr(packed, "compute", "f32") == "f32" and spec["x"].is_cuda and hip.get_edit_batch() == 1):
             phase = conv.phase_packed()  # (None: not a 3x3 / stride-1 conv)
+        more = {}
+        if (spec.get("phase3") and spec.get("x2") is None and spec["scale"] is None and spec["shift"] is None and spec["act"] == "identity"
+                and spec["x"].is_cuda and getattr(packed, "compute", "f32") == conv.compute_dtype):
+            # (Gather.PHASE_UPSAMPLE_TILE3: the keyword exists only on this path, so that off is today's call, argument for argument)
+            more["phase3"] = conv.phase_tile3_packed()  # (None: no such kernel for this conv)
         return hip.gather_conv_cl(spec["x"], spec.get("x2"), spec["block"], spec["idx"], spec["scale"], spec["shift"], spec["act"],
                                   packed, conv.bias, conv.out_channels, conv.kernel_size, conv.stride,
                                   full=dict(offset=g.offset, out_res=tuple(out.shape[2:]), residual=residual),
-                                  upsample2x=spec.get("up", False), out=out, twins=twins, phase=phase)
+                                  upsample2x=spec.get("up", False), out=out, twins=twins, phase=phase, **more)
     if tuple(conv.kernel_size) != (3, 3) or tuple(conv.stride) != (1, 1):
         return None
     return hip.scatter_gather_conv_scatter_cl(spec["x"], spec["y"], spec["block"], spec["idx"], spec["map"], spec["scale"],

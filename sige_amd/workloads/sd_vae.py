@@ -32,7 +32,8 @@ and full.  Every SIGEConv2d on tiles runs the fp16 tile kernels, the derived K |
 What has no fp16 form keeps its exact-fp32 kernel in that mode: `conv_in` / `conv_out` with the decoder's conv3x3_small_cout_cl
 head, the encoder's latent head (conv_latent_head.hip), the stride-2 Downsample conv (hip.conv_pack_weights packs that geometry for
 the exact-fp32 tile conv; the full pass runs it as the torch conv), the GroupNorm statistics, and the torch chain (`_chain`: CPU, NCHW, NATIVE_ATTENTION off,
-and the full-mode attention).  The Upsample conv runs as the 9-tap fp16 tile conv: SIGEConv2d.phase_kernels() is None outside f32.
+and the full-mode attention).  The Upsample conv runs as the 9-tap fp16 tile conv: SIGEConv2d.phase_kernels() is None outside f32
+(the four-phase form on fp16 operands exists behind Gather.PHASE_UPSAMPLE_TILE3, off by default: DESIGN.md 5.29).
 "f16x3" has no attention or tile form of its own: both run exact fp32.
 
 The encoder (SIGEEncoder, sige_model.py:177) is built from the same blocks: SparseVAEEncoder, at the end of the file."""
