@@ -1,10 +1,15 @@
-// Shared by the transposed-score attention kernels (attention_tokens.hip, attention_tokens_f16.hip, attention_wide.hip): the row
-// maximum -- lane (kq, j) holds scores of query j, the four lane rows kq of a query meet in two v_permlane*_swap -- and the weight
-// of a partial softmax state in a merge.
+// Shared by the transposed-score attention kernels (attention_tokens.hip, attention_tokens_f16.hip, attention_wide.hip,
+// attention_wide_f16.hip): the row maximum -- lane (kq, j) holds scores of query j, the four lane rows kq of a query meet in two
+// v_permlane*_swap --, the weight of a partial softmax state in a merge, the image of a query tile under stacked edits; for the two
+// token units also the workgroup -> (pair, query tile) mapping; on the host the
+// argument check of the batched entries and the geometry of the `_tiles_` entries.  (What only the wide pair shares:
+// attention_wide_image.hpp.)
 #pragma once
 #include "common.hpp"
 
 namespace sige {
+
+typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 // (v_permlane32_swap a, b: a's lanes 32..63 <-> b's lanes 0..31; with a == b == v both end up holding a half of v twice, max(a, b)
 //  is max(v[l], v[l ^ 32]) in every lane; v_permlane16_swap likewise for the odd / even rows of 16.  Inline asm: the clang builtin of
@@ -39,6 +44,52 @@ __device__ __forceinline__ int tile_image(const int32_t *__restrict__ tiles, int
     } else {
         return 0;
     }
+}
+
+// Token kernels: workgroup -> (batch * head pair, query tile).  The hardware deals consecutive workgroup ids round-robin to the 8 XCDs,
+// each with its own 4 MB L2: with `xcd_pairs` > 0 (the host sets it when B * heads is a multiple of 8) the pairs are dealt to the XCDs
+// -- pair = xcd * xcd_pairs + ... -- so that one L2 holds the K / V of ITS pairs (SD, 64 x 64 latent: 2 x 1.3 MB) instead of every
+// L2 streaming all of them (16 x 1.3 MB: each key block re-read from the Infinity Cache by every XCD)
+__device__ __forceinline__ void workgroup_pair_tile(int q_tiles, int xcd_pairs, int &pair, int &qtile) {
+    if (xcd_pairs > 0) {
+        const int id = blockIdx.x, xcd = id & 7, local = id >> 3;
+        pair = xcd * xcd_pairs + local / q_tiles;
+        qtile = local - (local / q_tiles) * q_tiles;
+    } else {
+        pair = blockIdx.x / q_tiles;
+        qtile = blockIdx.x - pair * q_tiles;
+    }
+}
+
+// ---- host ----
+
+// The argument check of the four batched entries (row strides: the smallest of them, C where rows are dense).  true: there is a
+// launch to make; false: *status is the entry's answer -- bad arguments, or no query and nothing to do.
+inline bool attention_batch_args(int B, int Nq, int Nk, int C, int heads, int ld_min, const void *q, const void *k, const void *v,
+                                 const void *out, int *status) {
+    *status = SIGE_HIP_EINVAL;
+    if (B < 0 || Nq < 0 || Nk <= 0 || C <= 0 || heads <= 0) return false;
+    if (ld_min < C) return false;
+    if ((long)B * Nq == 0) { *status = SIGE_HIP_OK; return false; }
+    return q && k && v && out;
+}
+
+// Stacked edits (sige_hip_set_edit_batch) as a `_tiles_` entry sees them: the queries are the tokens of T active 4x4 tiles of the
+// tall image [1,C,H,W] = `images` images of H / images rows, and tile t attends to the `Nk` keys of ITS image only -- one launch
+// for the tiles of all edits, the per-edit tile counts never on the host.  shift 0 = no edit batch: one image, the launch of the
+// batched entry, and `tiles` is nullptr -- the index list is not read.
+struct StackedKeys {
+    const int32_t *tiles;
+    int shift, images, Nk;
+};
+
+inline int stacked_keys(const int32_t *active_indices, int T, int H, int W, StackedKeys *g) {
+    const int s = stacked_shift(H);
+    if (s < 0) return SIGE_HIP_EUNSUPPORTED;  // (one image's height: a power of two >= 4)
+    const int E = s > 0 ? H >> s : 1;
+    if ((long)T * 16 > 0x7fffffffL || (long)(H / E) * W > 0x7fffffffL) return SIGE_HIP_EUNSUPPORTED;
+    *g = StackedKeys{s > 0 ? active_indices : nullptr, s, E, (H / E) * W};
+    return SIGE_HIP_OK;
 }
 
 }  // namespace sige

@@ -32,8 +32,6 @@
 
 namespace sige {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
 // TILES (stacked edits, sige_hip_attention_tokens_tiles_f32): B = 1, query tile t is the 4x4 tile with origin row tiles[2t] of the tall
 // image of `images` images of 2^img_shift rows, and k / v / Nk are those of ITS image.  false: the three arguments are not read and
 // the kernel is the one it was.
@@ -54,19 +52,8 @@ void attention_tokens_kernel(const float *__restrict__ q, const float *__restric
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int kq = lane >> 4, j = lane & 15;
-    // workgroup -> (batch * head pair, query tile).  The hardware deals consecutive workgroup ids round-robin to the 8 XCDs, each with
-    // its own 4 MB L2: with `xcd_pairs` > 0 (the host sets it when B * heads is a multiple of 8) the pairs are dealt to the XCDs --
-    // pair = xcd * xcd_pairs + ... -- so that one L2 holds the K / V of ITS pairs (SD, 64 x 64 latent: 2 x 1.3 MB) instead of every
-    // L2 streaming all of them (16 x 1.3 MB: each key block re-read from the Infinity Cache by every XCD)
-    int pair, qtile;
-    if (xcd_pairs > 0) {
-        const int id = blockIdx.x, xcd = id & 7, local = id >> 3;
-        pair = xcd * xcd_pairs + local / q_tiles;
-        qtile = local - (local / q_tiles) * q_tiles;
-    } else {
-        pair = blockIdx.x / q_tiles;
-        qtile = blockIdx.x - pair * q_tiles;
-    }
+    int pair, qtile;  // (workgroup -> XCD: attention_rows.hpp)
+    workgroup_pair_tile(q_tiles, xcd_pairs, pair, qtile);
     const int head = pair % heads, b = pair / heads;
     const int q0 = qtile * QR;
     const size_t hoff = (size_t)head * d;
@@ -256,15 +243,8 @@ void attention_tokens_t_kernel(const float *__restrict__ q, const float *__restr
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int kq = lane >> 4, j = lane & 15;
-    int pair, qtile;  // (workgroup -> XCD: as in attention_tokens_kernel)
-    if (xcd_pairs > 0) {
-        const int id = blockIdx.x, xcd = id & 7, local = id >> 3;
-        pair = xcd * xcd_pairs + local / q_tiles;
-        qtile = local - (local / q_tiles) * q_tiles;
-    } else {
-        pair = blockIdx.x / q_tiles;
-        qtile = blockIdx.x - pair * q_tiles;
-    }
+    int pair, qtile;  // (workgroup -> XCD: attention_rows.hpp)
+    workgroup_pair_tile(q_tiles, xcd_pairs, pair, qtile);
     const int head = pair % heads, b = pair / heads;
     const int q0 = qtile * 16;
     const size_t hoff = (size_t)head * d;
@@ -457,24 +437,19 @@ static int launch_attention_tokens(const float *q, const float *k, const float *
 extern "C" int sige_hip_attention_tokens_f32(const float *q, const float *k, const float *v, int B, int Nq, int Nk, int C,
                                              int heads, float scale, float *out, void *stream) {
     SIGE_PLAN_HOOK(sige_hip_attention_tokens_f32, q, k, v, B, Nq, Nk, C, heads, scale, out, stream);
-    if (B < 0 || Nq < 0 || Nk <= 0 || C <= 0 || heads <= 0) return SIGE_HIP_EINVAL;
-    if ((long)B * Nq == 0) return SIGE_HIP_OK;
-    if (!q || !k || !v || !out) return SIGE_HIP_EINVAL;
+    int status;
+    if (!attention_batch_args(B, Nq, Nk, C, heads, C, q, k, v, out, &status)) return status;
     return launch_attention_tokens(q, k, v, B, Nq, Nk, C, heads, scale, out, nullptr, 0, 1, stream);
 }
 
-// Stacked edits (sige_hip_set_edit_batch): the queries are the tokens of T active 4x4 tiles of the tall image [1,C,H,W] = E images
-// of H / E rows, and tile t attends to the (H / E) W keys of ITS image only -- one launch for the tiles of all E edits, the
-// per-edit tile counts never on the host.  E = 1 (shift 0): the launch of sige_hip_attention_tokens_f32, the list unread.
+// Stacked edits: tile t attends to the keys of ITS image only (attention_rows.hpp: stacked_keys)
 extern "C" int sige_hip_attention_tokens_tiles_f32(const float *q, const float *k, const float *v, const int32_t *active_indices,
                                                    int T, int H, int W, int C, int heads, float scale, float *out, void *stream) {
     SIGE_PLAN_HOOK(sige_hip_attention_tokens_tiles_f32, q, k, v, active_indices, T, H, W, C, heads, scale, out, stream);
     if (T < 0 || H <= 0 || W <= 0 || C <= 0 || heads <= 0) return SIGE_HIP_EINVAL;
     if (T == 0) return SIGE_HIP_OK;
     if (!q || !k || !v || !out || !active_indices) return SIGE_HIP_EINVAL;
-    const int s = stacked_shift(H);
-    if (s < 0) return SIGE_HIP_EUNSUPPORTED;  // (one image's height: a power of two >= 4)
-    const int E = s > 0 ? H >> s : 1;
-    if ((long)T * 16 > 0x7fffffffL || (long)(H / E) * W > 0x7fffffffL) return SIGE_HIP_EUNSUPPORTED;
-    return launch_attention_tokens(q, k, v, 1, 16 * T, (H / E) * W, C, heads, scale, out, s > 0 ? active_indices : nullptr, s, E, stream);
+    StackedKeys g;
+    if (const int status = stacked_keys(active_indices, T, H, W, &g)) return status;
+    return launch_attention_tokens(q, k, v, 1, 16 * T, g.Nk, C, heads, scale, out, g.tiles, g.shift, g.images, stream);
 }

@@ -39,7 +39,6 @@
 
 namespace sige {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
 typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 
@@ -86,15 +85,8 @@ void attention_tokens_f16_kernel(const float *__restrict__ q, const float *__res
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int kq = lane >> 4, j = lane & 15;
-    int pair, qtile;  // (workgroup -> XCD: as in attention_tokens_kernel)
-    if (xcd_pairs > 0) {
-        const int id = blockIdx.x, xcd = id & 7, local = id >> 3;
-        pair = xcd * xcd_pairs + local / q_tiles;
-        qtile = local - (local / q_tiles) * q_tiles;
-    } else {
-        pair = blockIdx.x / q_tiles;
-        qtile = blockIdx.x - pair * q_tiles;
-    }
+    int pair, qtile;  // (workgroup -> XCD: attention_rows.hpp)
+    workgroup_pair_tile(q_tiles, xcd_pairs, pair, qtile);
     const int head = pair % heads, b = pair / heads;
     const int q0 = qtile * 16;
     const size_t hoff = (size_t)head * d;
@@ -291,9 +283,8 @@ static int launch_attention_tokens_f16(const float *q, const float *k, const flo
 extern "C" int sige_hip_attention_tokens_f16c(const float *q, const float *k, const float *v, int B, int Nq, int Nk, int C,
                                               int heads, float scale, float *out, void *stream) {
     SIGE_PLAN_HOOK(sige_hip_attention_tokens_f16c, q, k, v, B, Nq, Nk, C, heads, scale, out, stream);
-    if (B < 0 || Nq < 0 || Nk <= 0 || C <= 0 || heads <= 0) return SIGE_HIP_EINVAL;
-    if ((long)B * Nq == 0) return SIGE_HIP_OK;
-    if (!q || !k || !v || !out) return SIGE_HIP_EINVAL;
+    int status;
+    if (!attention_batch_args(B, Nq, Nk, C, heads, C, q, k, v, out, &status)) return status;
     return launch_attention_tokens_f16(q, k, v, B, Nq, Nk, C, heads, scale, out, nullptr, 0, 1, stream);
 }
 
@@ -304,9 +295,7 @@ extern "C" int sige_hip_attention_tokens_tiles_f16c(const float *q, const float 
     if (T < 0 || H <= 0 || W <= 0 || C <= 0 || heads <= 0) return SIGE_HIP_EINVAL;
     if (T == 0) return SIGE_HIP_OK;
     if (!q || !k || !v || !out || !active_indices) return SIGE_HIP_EINVAL;
-    const int s = stacked_shift(H);
-    if (s < 0) return SIGE_HIP_EUNSUPPORTED;  // (one image's height: a power of two >= 4)
-    const int E = s > 0 ? H >> s : 1;
-    if ((long)T * 16 > 0x7fffffffL || (long)(H / E) * W > 0x7fffffffL) return SIGE_HIP_EUNSUPPORTED;
-    return launch_attention_tokens_f16(q, k, v, 1, 16 * T, (H / E) * W, C, heads, scale, out, s > 0 ? active_indices : nullptr, s, E, stream);
+    StackedKeys g;
+    if (const int status = stacked_keys(active_indices, T, H, W, &g)) return status;
+    return launch_attention_tokens_f16(q, k, v, 1, 16 * T, g.Nk, C, heads, scale, out, g.tiles, g.shift, g.images, stream);
 }

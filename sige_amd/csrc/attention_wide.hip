@@ -30,29 +30,9 @@
 // of an image), clamped, and both buffer descriptors start at image e's first key row and span ONE image's Nk keys.  Everything
 // else -- the split arithmetic, tail masking, clamped key rows, the range check -- is per image without knowing it.  Without an
 // index list e = 0: the batched entry's launch, bit for bit.
-#include <algorithm>
-
-#include "attention_rows.hpp"  // (max_over_rows, merge_weight: shared with attention_tokens.hip)
-#include "split_finish.hpp"
+#include "attention_wide_image.hpp"  // (everything behind the operand path: arguments, descriptors, wave merge, stores, split finish, launch plan)
 
 namespace sige {
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
-struct WideAttnArgs {
-    const float *q, *k, *v;
-    float *out;
-    float *ws;          // [units * ksplit][(4G + 1) * 64] float4: the splits' merged accumulator images (ksplit > 1)
-    int32_t *tickets;   // one per (pair, query tile), zero between launches
-    int ldq, ldk, ldv, ldo;
-    int Nq, Nk, C, heads, d;
-    int q_tiles, ksplit, split_blocks;  // split s takes key blocks [s * split_blocks, (s + 1) * split_blocks)
-    float scale_log2e;
-    // per-image keys (sige_hip_attention_wide_tiles_f32; stacked edits): query tile t is the 4x4 tile with origin row tiles[2t] of
-    // the tall image, its keys are the Nk rows of image tiles[2t] >> img_shift.  nullptr: every tile reads the keys of image 0.
-    const int32_t *tiles;
-    int img_shift, images;
-};
 
 // ring depth: the largest divisor of the 2G chunks of a key block that is <= 8 (slots stay compile-time across blocks)
 constexpr int wide_ring(int G) { return (2 * G) % 8 == 0 ? 8 : (2 * G) % 7 == 0 ? 7 : (2 * G) % 6 == 0 ? 6 : 5; }
@@ -62,7 +42,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1)))
 void attention_wide_kernel(WideAttnArgs a) {
     kernarg_touch<sizeof(WideAttnArgs)>();
     constexpr int QS = 64 * G + 4;             // padded row of the Q stage
-    constexpr int SLOTS = 4 * G + 1;           // float4 per lane of an accumulator image: o[g][.][r'] at 4g + r', then (m, l)
+    constexpr int SLOTS = wide_slots(G);       // float4 per lane of an accumulator image (the merge reuses the Q stage's LDS)
     constexpr int NB = wide_ring(G), CH = 2 * G;
     constexpr int LDS_FLOATS = 16 * QS > SLOTS * 256 ? 16 * QS : SLOTS * 256;
     __shared__ __attribute__((aligned(16))) float smem[LDS_FLOATS];
@@ -96,10 +76,10 @@ void attention_wide_kernel(WideAttnArgs a) {
 
     // the key blocks of this split: [kb0, kb1), dealt round-robin to the waves
     const int nkb = (a.Nk + 15) / 16;
-    const int kb0 = (int)split * a.split_blocks, kb1 = min(nkb, kb0 + a.split_blocks);  // (host: every split has a block)
+    const int kb0 = (int)split * a.split_len, kb1 = min(nkb, kb0 + a.split_len);  // (host: every split has a block)
 
     float m_run = -INFINITY, l_run = 0.f;  // of query j: the maximum over every key so far, the sum over THIS lane's keys
-    f32x4 o[G][4];                         // o[g][e][r'] = O[query j][channel 64g + 16kq + 4r' + e]
+    f32x4 o[G][4];                         // o[g][e][r'] = O[query j][channel 64g + 16kq + 4r' + e] (attention_wide_image.hpp)
 #pragma unroll
     for (int g = 0; g < G; ++g) {
 #pragma unroll
@@ -210,51 +190,9 @@ void attention_wide_kernel(WideAttnArgs a) {
     }
     __syncthreads();  // (every wave is done with the Q stage)
 
-    // ---- merge the four waves' (m, l, O) in registers through one LDS image: 3 -> 2, 1 -> 0, 2 -> 0 ----
-    float4 *img = reinterpret_cast<float4 *>(smem);
-    auto put = [&]() {
-#pragma unroll
-        for (int g = 0; g < G; ++g) {
-#pragma unroll
-            for (int r = 0; r < 4; ++r) img[(4 * g + r) * 64 + lane] = make_float4(o[g][0][r], o[g][1][r], o[g][2][r], o[g][3][r]);
-        }
-        img[(SLOTS - 1) * 64 + lane] = make_float4(m_run, l_run, 0.f, 0.f);
-    };
-    auto take = [&]() {
-        const float4 ml = img[(SLOTS - 1) * 64 + lane];
-        const float M = fmaxf(m_run, ml.x);
-        const float f1 = merge_weight(m_run, M), f2 = merge_weight(ml.x, M);  // (a wave without a key block: weight 0)
-        m_run = M;
-        l_run = f1 * l_run + f2 * ml.y;
-#pragma unroll
-        for (int g = 0; g < G; ++g) {
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const float4 t = img[(4 * g + r) * 64 + lane];
-                o[g][0][r] = f1 * o[g][0][r] + f2 * t.x;
-                o[g][1][r] = f1 * o[g][1][r] + f2 * t.y;
-                o[g][2][r] = f1 * o[g][2][r] + f2 * t.z;
-                o[g][3][r] = f1 * o[g][3][r] + f2 * t.w;
-            }
-        }
-    };
-    if (wave == 3) put();
-    __syncthreads();
-    if (wave == 2) take();
-    __syncthreads();
-    if (wave == 1) put();
-    __syncthreads();
-    if (wave == 0) take();
-    __syncthreads();
-    if (wave == 2) put();
-    __syncthreads();
-    if (wave == 0) {
-        take();
-        // the sum of query j over its four lane rows
-        l_run += __shfl_xor(l_run, 16);
-        l_run += __shfl_xor(l_run, 32);
-    }
-
+    // ---- the four waves merged; then the output rows from wave 0's registers, or -- key split -- this workgroup's image to its
+    // workspace slice, a ticket, and the last split of the tile adds the slices up ----
+    wide_merge_waves<G>(smem, wave, lane, o, m_run, l_run);
     float *const orow = a.out + ((size_t)b * a.Nq + q0 + j) * a.ldo + hoff + 16 * kq;
     if (a.ksplit <= 1) {
         if (wave == 0) {
@@ -271,19 +209,8 @@ void attention_wide_kernel(WideAttnArgs a) {
         }
         return;
     }
-
-    // ---- key split: this workgroup's image to its workspace slice, a ticket, the last split of the tile adds them up ----
     float4 *const ws = reinterpret_cast<float4 *>(a.ws) + (size_t)unit * a.ksplit * (SLOTS * 64);
-    if (wave == 0) {
-        float4 *mine = ws + (size_t)split * (SLOTS * 64);
-#pragma unroll
-        for (int g = 0; g < G; ++g) {
-#pragma unroll
-            for (int r = 0; r < 4; ++r)
-                coherent_store(reinterpret_cast<float *>(mine + (4 * g + r) * 64 + lane), make_float4(o[g][0][r], o[g][1][r], o[g][2][r], o[g][3][r]));
-        }
-        coherent_store(reinterpret_cast<float *>(mine + (SLOTS - 1) * 64 + lane), make_float4(m_run, l_run, 0.f, 0.f));
-    }
+    if (wave == 0) wide_publish<G>(ws + (size_t)split * (SLOTS * 64), lane, o, m_run, l_run);
     if (!split_arrive_last(a.tickets + unit, a.ksplit, &ticket_lds)) return;  // (the protocol: split_finish.hpp)
     // thread (wave, lane) -> slots wave, wave + 4, ... of lane `lane`: slot 4g + wave = channels 64g + 16kq + 4 wave .. +3 of query j.
     // The slices in split order with a running maximum, four slices' loads in flight at a time (a dependent round trip to the
@@ -336,46 +263,19 @@ extern "C" int sige_hip_attention_wide_supported(int Nq, int Nk, int C, int head
 
 namespace sige {
 
-// Both entry points: q [B,Nq,ldq] against k / v of Nk keys per batch -- or, with `tiles` (B = 1), per image of 2^img_shift rows.
+// Both entry points (wide_plan) on this unit's instances
 static int launch_attention_wide(const float *q, int ldq, const float *k, int ldk, const float *v, int ldv, int B, int Nq, int Nk, int C,
                                  int heads, float scale, float *out, int ldo, const int32_t *tiles, int img_shift, int images, void *stream) {
-    if (!sige_hip_attention_wide_supported(Nq, Nk, C, heads)) return SIGE_HIP_EUNSUPPORTED;
-    auto al = [](const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; };
-    if (!al(q) || !al(k) || !al(v) || !al(out) || ((ldq | ldk | ldv | ldo) & 3)) return SIGE_HIP_EUNSUPPORTED;
-    // (32-bit byte offsets into one batch's -- one image's -- K / V)
-    if ((size_t)Nk * ldk * sizeof(float) >= 0x7fffffffu || (size_t)Nk * ldv * sizeof(float) >= 0x7fffffffu) return SIGE_HIP_EUNSUPPORTED;
-    const int d = C / heads, G = (d + 63) / 64;
-    const long units = (long)B * heads * (Nq / 16);
-    if ((long)B * heads > 65535 || Nq / 16 > 65535) return SIGE_HIP_EUNSUPPORTED;  // (grid z / y)
-    hipStream_t st = as_stream(stream);
-
-    // key split: about one workgroup per CU in all, at least 4 key blocks (one per wave) per split, at most 16 slices to add up
-    const int nkb = (Nk + 15) / 16;
-    int ksplit = (int)std::min<long>(std::min<long>(256 / units, nkb / 4), 16);
-    WideAttnArgs a;
-    a.ws = nullptr; a.tickets = nullptr;
-    if (ksplit > 1) {
-        a.tickets = split_tickets(st, units);
-        if (a.tickets) a.ws = split_workspace(st, (size_t)units * ksplit * (4 * G + 1) * 256);
-        if (!a.tickets || !a.ws) ksplit = 1;
-    }
-    if (ksplit < 1) ksplit = 1;
-    a.split_blocks = (nkb + ksplit - 1) / ksplit;
-    ksplit = (nkb + a.split_blocks - 1) / a.split_blocks;  // (no empty split)
-    a.q = q; a.k = k; a.v = v; a.out = out;
-    a.ldq = ldq; a.ldk = ldk; a.ldv = ldv; a.ldo = ldo;
-    a.Nq = Nq; a.Nk = Nk; a.C = C; a.heads = heads; a.d = d;
-    a.q_tiles = Nq / 16; a.ksplit = ksplit;
-    a.scale_log2e = scale * 1.44269504088896341f;
-    a.tiles = tiles; a.img_shift = img_shift; a.images = images;
-    const dim3 grid((unsigned)ksplit, (unsigned)(Nq / 16), (unsigned)(B * heads));
-    switch (G) {
-        case 3: attention_wide_kernel<3><<<grid, 256, 0, st>>>(a); break;
-        case 4: attention_wide_kernel<4><<<grid, 256, 0, st>>>(a); break;
-        case 5: attention_wide_kernel<5><<<grid, 256, 0, st>>>(a); break;
-        case 6: attention_wide_kernel<6><<<grid, 256, 0, st>>>(a); break;
-        case 7: attention_wide_kernel<7><<<grid, 256, 0, st>>>(a); break;
-        case 8: attention_wide_kernel<8><<<grid, 256, 0, st>>>(a); break;
+    WidePlan p;
+    const int status = wide_plan(q, ldq, k, ldk, v, ldv, B, Nq, Nk, C, heads, scale, out, ldo, tiles, img_shift, images, stream, 16, &p);
+    if (status != SIGE_HIP_OK) return status;
+    switch (p.G) {
+        case 3: attention_wide_kernel<3><<<p.grid, 256, 0, p.st>>>(p.a); break;
+        case 4: attention_wide_kernel<4><<<p.grid, 256, 0, p.st>>>(p.a); break;
+        case 5: attention_wide_kernel<5><<<p.grid, 256, 0, p.st>>>(p.a); break;
+        case 6: attention_wide_kernel<6><<<p.grid, 256, 0, p.st>>>(p.a); break;
+        case 7: attention_wide_kernel<7><<<p.grid, 256, 0, p.st>>>(p.a); break;
+        case 8: attention_wide_kernel<8><<<p.grid, 256, 0, p.st>>>(p.a); break;
         default: return SIGE_HIP_EUNSUPPORTED;
     }
     return launch_status();
@@ -386,16 +286,12 @@ static int launch_attention_wide(const float *q, int ldq, const float *k, int ld
 extern "C" int sige_hip_attention_wide_f32(const float *q, int ldq, const float *k, int ldk, const float *v, int ldv,
                                            int B, int Nq, int Nk, int C, int heads, float scale, float *out, int ldo, void *stream) {
     SIGE_PLAN_HOOK(sige_hip_attention_wide_f32, q, ldq, k, ldk, v, ldv, B, Nq, Nk, C, heads, scale, out, ldo, stream);
-    if (B < 0 || Nq < 0 || Nk <= 0 || C <= 0 || heads <= 0) return SIGE_HIP_EINVAL;
-    if (ldq < C || ldk < C || ldv < C || ldo < C) return SIGE_HIP_EINVAL;
-    if ((long)B * Nq == 0) return SIGE_HIP_OK;
-    if (!q || !k || !v || !out) return SIGE_HIP_EINVAL;
+    int status;
+    if (!attention_batch_args(B, Nq, Nk, C, heads, std::min({ldq, ldk, ldv, ldo}), q, k, v, out, &status)) return status;
     return launch_attention_wide(q, ldq, k, ldk, v, ldv, B, Nq, Nk, C, heads, scale, out, ldo, nullptr, 0, 1, stream);
 }
 
-// Stacked edits (sige_hip_set_edit_batch): the queries are the tokens of T active 4x4 tiles of the tall image [1,C,H,W] = E images
-// of H / E rows, and tile t attends to the (H / E) W keys of ITS image only -- one launch for the tiles of all E edits, the
-// per-edit tile counts never on the host.
+// Stacked edits: tile t attends to the keys of ITS image only (attention_rows.hpp: stacked_keys)
 extern "C" int sige_hip_attention_wide_tiles_f32(const float *q, int ldq, const float *k, int ldk, const float *v, int ldv,
                                                  const int32_t *active_indices, int T, int H, int W, int C, int heads, float scale,
                                                  float *out, int ldo, void *stream) {
@@ -404,9 +300,7 @@ extern "C" int sige_hip_attention_wide_tiles_f32(const float *q, int ldq, const 
     if (ldq < C || ldk < C || ldv < C || ldo < C) return SIGE_HIP_EINVAL;
     if (T == 0) return SIGE_HIP_OK;
     if (!q || !k || !v || !out || !active_indices) return SIGE_HIP_EINVAL;
-    const int s = stacked_shift(H);
-    if (s < 0) return SIGE_HIP_EUNSUPPORTED;  // (one image's height: a power of two >= 4)
-    const int E = s > 0 ? H >> s : 1;         // (shift 0 = no edit batch: one image, base 0 -- the other entry's launch)
-    if ((long)T * 16 > 0x7fffffffL || (long)(H / E) * W > 0x7fffffffL) return SIGE_HIP_EUNSUPPORTED;
-    return launch_attention_wide(q, ldq, k, ldk, v, ldv, 1, 16 * T, (H / E) * W, C, heads, scale, out, ldo, active_indices, s, E, stream);
+    StackedKeys g;
+    if (const int status = stacked_keys(active_indices, T, H, W, &g)) return status;
+    return launch_attention_wide(q, ldq, k, ldk, v, ldv, 1, 16 * T, g.Nk, C, heads, scale, out, ldo, g.tiles, g.shift, g.images, stream);
 }

@@ -7,7 +7,8 @@
 // split_finish.hpp (fp32 workspace slices in the SAME accumulator image, a ticket, the last workgroup adds them up in split order),
 // K / V as branch-free clamped buffer loads through a register ring that runs across step boundaries, kernarg_touch, and -- under
 // the template flag TILES -- the per-image keys of stacked edits.  The accumulator layout o[g][e][r'] is the fp32 kernel's, so the
-// wave merge, the workspace image and the output stores are its code word for word.
+// arguments, the wave merge, the workspace image, the launch plan are ONE piece of code for both
+// forms: attention_wide_image.hpp.
 //
 // What differs is the operand path.  Step: 32 keys per wave (two 16-key tiles t = 0, 1), as in attention_tokens_f16.hip.
 //   * Q stage: fp16 in LDS (16.6 KB at d = 512 in place of 33 KB; the LDS allocation is still the 33 KB merge image), laid out in
@@ -26,36 +27,19 @@
 //   * the ring: wide_ring(G) chunks of 16 registers (the fp32 kernel's 4: fp16 products finish sooner, the loads do not), 4G chunks
 //     per step, fp32 as loaded and packed to halves at their use.
 //
-// Arithmetic: the contract of sige_hip_attention_tokens_f16c (include/sige_hip.h), word for word -- q, k, v rounded to nearest even to fp16
+// Arithmetic: the contract of sige_hip_attention_tokens_f16c (include/sige_hip.h) -- q, k, v rounded to nearest even to fp16
 // in registers (fptrunc; never v_cvt_pkrtz), fp32 scores scaled in fp32 in units of log2, fp32 (m, l, alpha), l from the unrounded
 // probabilities, P carried as exp2(s - m + 15) and rounded to nearest even to fp16 (attention_tokens_f16.hip says why 15), O, the wave
 // merge, the split merge and the division by l in fp32.  The factor 2^15 is in every wave's and every split's l and O alike.
 // Resource numbers and times: DESIGN.md 5.28.
-#include <algorithm>
-
-#include "attention_rows.hpp"
-#include "split_finish.hpp"
+#include "attention_wide_image.hpp"
 
 namespace sige {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
 typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 
 constexpr float WIDE_P_SHIFT = 15.f;
-
-struct WideF16Args {
-    const float *q, *k, *v;
-    float *out;
-    float *ws;          // [units * ksplit][(4G + 1) * 64] float4: the splits' merged accumulator images (ksplit > 1)
-    int32_t *tickets;   // one per (pair, query tile), zero between launches
-    int ldq, ldk, ldv, ldo;
-    int Nq, Nk, C, heads, d;
-    int q_tiles, ksplit, split_steps;  // split s takes the 32-key steps [s * split_steps, (s + 1) * split_steps)
-    float scale_log2e;
-    const int32_t *tiles;  // TILES: the Gather's index list (sige_hip_attention_wide_tiles_f16c)
-    int img_shift, images;
-};
 
 __device__ __forceinline__ f16x8 wide_pack8(f32x4 a, f32x4 b) {  // (fptrunc: round to nearest even)
     const f16x4 lo = __builtin_convertvector(a, f16x4);
@@ -68,10 +52,10 @@ constexpr int wide_f16_ring(int G) { return (2 * G) % 8 == 0 ? 8 : (2 * G) % 7 =
 
 template <int G, bool TILES>  // 64-channel groups covering the head dimension: 64 (G - 1) < d <= 64 G
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1)))
-void attention_wide_f16_kernel(WideF16Args a) {
-    kernarg_touch<sizeof(WideF16Args)>();
+void attention_wide_f16_kernel(WideAttnArgs a) {
+    kernarg_touch<sizeof(WideAttnArgs)>();
     constexpr int QSH = 64 * G + 8;            // padded row of the Q stage, in halves (16-byte rows)
-    constexpr int SLOTS = 4 * G + 1;           // float4 per lane of an accumulator image: o[g][.][r'] at 4g + r', then (m, l)
+    constexpr int SLOTS = wide_slots(G);       // float4 per lane of an accumulator image (the merge reuses the Q stage's LDS)
     constexpr int NB = wide_f16_ring(G), CH = 4 * G;
     static_assert(CH % NB == 0 && NB >= 3 && 16 * QSH / 2 <= SLOTS * 256, "ring / LDS");
     __shared__ __attribute__((aligned(16))) float smem[SLOTS * 256];
@@ -104,10 +88,10 @@ void attention_wide_f16_kernel(WideF16Args a) {
 
     // the 32-key steps of this split: [ks0, ks1), dealt round-robin to the waves
     const int nks = (a.Nk + 31) / 32;
-    const int ks0 = (int)split * a.split_steps, ks1 = min(nks, ks0 + a.split_steps);  // (host: every split has a step)
+    const int ks0 = (int)split * a.split_len, ks1 = min(nks, ks0 + a.split_len);  // (host: every split has a step)
 
     float m_run = -INFINITY, l_run = 0.f;  // of query j: the maximum over every key so far, the (scaled) sum over THIS lane's keys
-    f32x4 o[G][4];                         // o[g][e][r'] = 2^15 O[query j][channel 64g + 16kq + 4r' + e]
+    f32x4 o[G][4];                         // o[g][e][r'] = 2^15 O[query j][channel 64g + 16kq + 4r' + e] (attention_wide_image.hpp)
 #pragma unroll
     for (int g = 0; g < G; ++g) {
 #pragma unroll
@@ -235,51 +219,9 @@ void attention_wide_f16_kernel(WideF16Args a) {
     }
     __syncthreads();  // (every wave is done with the Q stage)
 
-    // ---- merge the four waves' (m, l, O) in registers through one LDS image: 3 -> 2, 1 -> 0, 2 -> 0 (attention_wide.hip) ----
-    float4 *img = reinterpret_cast<float4 *>(smem);
-    auto put = [&]() {
-#pragma unroll
-        for (int g = 0; g < G; ++g) {
-#pragma unroll
-            for (int r = 0; r < 4; ++r) img[(4 * g + r) * 64 + lane] = make_float4(o[g][0][r], o[g][1][r], o[g][2][r], o[g][3][r]);
-        }
-        img[(SLOTS - 1) * 64 + lane] = make_float4(m_run, l_run, 0.f, 0.f);
-    };
-    auto take = [&]() {
-        const float4 ml = img[(SLOTS - 1) * 64 + lane];
-        const float M = fmaxf(m_run, ml.x);
-        const float f1 = merge_weight(m_run, M), f2 = merge_weight(ml.x, M);  // (a wave without a key step: weight 0)
-        m_run = M;
-        l_run = f1 * l_run + f2 * ml.y;
-#pragma unroll
-        for (int g = 0; g < G; ++g) {
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const float4 t = img[(4 * g + r) * 64 + lane];
-                o[g][0][r] = f1 * o[g][0][r] + f2 * t.x;
-                o[g][1][r] = f1 * o[g][1][r] + f2 * t.y;
-                o[g][2][r] = f1 * o[g][2][r] + f2 * t.z;
-                o[g][3][r] = f1 * o[g][3][r] + f2 * t.w;
-            }
-        }
-    };
-    if (wave == 3) put();
-    __syncthreads();
-    if (wave == 2) take();
-    __syncthreads();
-    if (wave == 1) put();
-    __syncthreads();
-    if (wave == 0) take();
-    __syncthreads();
-    if (wave == 2) put();
-    __syncthreads();
-    if (wave == 0) {
-        take();
-        // the sum of query j over its four lane rows
-        l_run += __shfl_xor(l_run, 16);
-        l_run += __shfl_xor(l_run, 32);
-    }
-
+    // ---- the four waves merged; then the output rows from wave 0's registers, or -- key split -- this workgroup's image to its
+    // workspace slice, a ticket, and the last split of the tile adds the slices up ----
+    wide_merge_waves<G>(smem, wave, lane, o, m_run, l_run);
     float *const orow = a.out + ((size_t)b * a.Nq + q0 + j) * a.ldo + hoff + 16 * kq;
     if (a.ksplit <= 1) {
         if (wave == 0) {
@@ -296,19 +238,8 @@ void attention_wide_f16_kernel(WideF16Args a) {
         }
         return;
     }
-
-    // ---- key split: this workgroup's image to its workspace slice, a ticket, the last split of the tile adds them up ----
     float4 *const ws = reinterpret_cast<float4 *>(a.ws) + (size_t)unit * a.ksplit * (SLOTS * 64);
-    if (wave == 0) {
-        float4 *mine = ws + (size_t)split * (SLOTS * 64);
-#pragma unroll
-        for (int g = 0; g < G; ++g) {
-#pragma unroll
-            for (int r = 0; r < 4; ++r)
-                coherent_store(reinterpret_cast<float *>(mine + (4 * g + r) * 64 + lane), make_float4(o[g][0][r], o[g][1][r], o[g][2][r], o[g][3][r]));
-        }
-        coherent_store(reinterpret_cast<float *>(mine + (SLOTS - 1) * 64 + lane), make_float4(m_run, l_run, 0.f, 0.f));
-    }
+    if (wave == 0) wide_publish<G>(ws + (size_t)split * (SLOTS * 64), lane, o, m_run, l_run);
     if (!split_arrive_last(a.tickets + unit, a.ksplit, &ticket_lds)) return;  // (the protocol: split_finish.hpp)
     // thread (wave, lane) -> slots wave, wave + 4, ... of lane `lane`; the slices in split order with a running maximum, four slices'
     // loads in flight at a time (attention_wide.hip)
@@ -348,45 +279,18 @@ void attention_wide_f16_kernel(WideF16Args a) {
     }
 }
 
-// Both entry points (as launch_attention_wide of attention_wide.hip): Nk keys per batch, or with `tiles` (B = 1) per image.
+// Both entry points (wide_plan) on this unit's instances
 static int launch_attention_wide_f16(const float *q, int ldq, const float *k, int ldk, const float *v, int ldv, int B, int Nq, int Nk, int C,
                                      int heads, float scale, float *out, int ldo, const int32_t *tiles, int img_shift, int images, void *stream) {
-    if (!sige_hip_attention_wide_supported(Nq, Nk, C, heads)) return SIGE_HIP_EUNSUPPORTED;
-    auto al = [](const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; };
-    if (!al(q) || !al(k) || !al(v) || !al(out) || ((ldq | ldk | ldv | ldo) & 3)) return SIGE_HIP_EUNSUPPORTED;
-    // (32-bit byte offsets into one batch's -- one image's -- K / V)
-    if ((size_t)Nk * ldk * sizeof(float) >= 0x7fffffffu || (size_t)Nk * ldv * sizeof(float) >= 0x7fffffffu) return SIGE_HIP_EUNSUPPORTED;
-    const int d = C / heads, G = (d + 63) / 64;
-    const long units = (long)B * heads * (Nq / 16);
-    if ((long)B * heads > 65535 || Nq / 16 > 65535) return SIGE_HIP_EUNSUPPORTED;  // (grid z / y)
-    hipStream_t st = as_stream(stream);
-
-    // key split: about one workgroup per CU in all, at least 4 steps (one per wave) per split, at most 16 slices to add up
-    const int nks = (Nk + 31) / 32;
-    int ksplit = (int)std::min<long>(std::min<long>(256 / units, nks / 4), 16);
-    WideF16Args a;
-    a.ws = nullptr; a.tickets = nullptr;
-    if (ksplit > 1) {
-        a.tickets = split_tickets(st, units);
-        if (a.tickets) a.ws = split_workspace(st, (size_t)units * ksplit * (4 * G + 1) * 256);
-        if (!a.tickets || !a.ws) ksplit = 1;
-    }
-    if (ksplit < 1) ksplit = 1;
-    a.split_steps = (nks + ksplit - 1) / ksplit;
-    ksplit = (nks + a.split_steps - 1) / a.split_steps;  // (no empty split)
-    a.q = q; a.k = k; a.v = v; a.out = out;
-    a.ldq = ldq; a.ldk = ldk; a.ldv = ldv; a.ldo = ldo;
-    a.Nq = Nq; a.Nk = Nk; a.C = C; a.heads = heads; a.d = d;
-    a.q_tiles = Nq / 16; a.ksplit = ksplit;
-    a.scale_log2e = scale * 1.44269504088896341f;
-    a.tiles = tiles; a.img_shift = img_shift; a.images = images;
-    const dim3 grid((unsigned)ksplit, (unsigned)(Nq / 16), (unsigned)(B * heads));
+    WidePlan p;
+    const int status = wide_plan(q, ldq, k, ldk, v, ldv, B, Nq, Nk, C, heads, scale, out, ldo, tiles, img_shift, images, stream, 32, &p);
+    if (status != SIGE_HIP_OK) return status;
 #define SIGE_WIDE16_GO(GG)                                                                     \
     do {                                                                                       \
-        if (tiles) attention_wide_f16_kernel<GG, true><<<grid, 256, 0, st>>>(a);               \
-        else attention_wide_f16_kernel<GG, false><<<grid, 256, 0, st>>>(a);                    \
+        if (tiles) attention_wide_f16_kernel<GG, true><<<p.grid, 256, 0, p.st>>>(p.a);         \
+        else attention_wide_f16_kernel<GG, false><<<p.grid, 256, 0, p.st>>>(p.a);              \
     } while (0)
-    switch (G) {
+    switch (p.G) {
         case 3: SIGE_WIDE16_GO(3); break;
         case 4: SIGE_WIDE16_GO(4); break;
         case 5: SIGE_WIDE16_GO(5); break;
@@ -403,24 +307,17 @@ static int launch_attention_wide_f16(const float *q, int ldq, const float *k, in
 
 using namespace sige;
 
-// the key split of a launch whose pools have room (the formula of launch_attention_wide_f16; tests)
+// the key split of a launch whose pools have room (tests)
 extern "C" int sige_hip_attention_wide_f16c_splits(int B, int Nq, int Nk, int C, int heads) {
     if (B <= 0 || !sige_hip_attention_wide_supported(Nq, Nk, C, heads)) return 0;
-    const long units = (long)B * heads * (Nq / 16);
-    const int nks = (Nk + 31) / 32;
-    int ksplit = (int)std::min<long>(std::min<long>(256 / units, nks / 4), 16);
-    if (ksplit < 1) ksplit = 1;
-    const int steps = (nks + ksplit - 1) / ksplit;
-    return (nks + steps - 1) / steps;
+    return wide_key_split((long)B * heads * (Nq / 16), (Nk + 31) / 32);
 }
 
 extern "C" int sige_hip_attention_wide_f16c(const float *q, int ldq, const float *k, int ldk, const float *v, int ldv,
                                             int B, int Nq, int Nk, int C, int heads, float scale, float *out, int ldo, void *stream) {
     SIGE_PLAN_HOOK(sige_hip_attention_wide_f16c, q, ldq, k, ldk, v, ldv, B, Nq, Nk, C, heads, scale, out, ldo, stream);
-    if (B < 0 || Nq < 0 || Nk <= 0 || C <= 0 || heads <= 0) return SIGE_HIP_EINVAL;
-    if (ldq < C || ldk < C || ldv < C || ldo < C) return SIGE_HIP_EINVAL;
-    if ((long)B * Nq == 0) return SIGE_HIP_OK;
-    if (!q || !k || !v || !out) return SIGE_HIP_EINVAL;
+    int status;
+    if (!attention_batch_args(B, Nq, Nk, C, heads, std::min({ldq, ldk, ldv, ldo}), q, k, v, out, &status)) return status;
     return launch_attention_wide_f16(q, ldq, k, ldk, v, ldv, B, Nq, Nk, C, heads, scale, out, ldo, nullptr, 0, 1, stream);
 }
 
@@ -433,10 +330,7 @@ extern "C" int sige_hip_attention_wide_tiles_f16c(const float *q, int ldq, const
     if (ldq < C || ldk < C || ldv < C || ldo < C) return SIGE_HIP_EINVAL;
     if (T == 0) return SIGE_HIP_OK;
     if (!q || !k || !v || !out || !active_indices) return SIGE_HIP_EINVAL;
-    const int s = stacked_shift(H);
-    if (s < 0) return SIGE_HIP_EUNSUPPORTED;  // (one image's height: a power of two >= 4)
-    const int E = s > 0 ? H >> s : 1;         // (shift 0 = no edit batch: one image -- the other entry's launch)
-    if ((long)T * 16 > 0x7fffffffL || (long)(H / E) * W > 0x7fffffffL) return SIGE_HIP_EUNSUPPORTED;
-    return launch_attention_wide_f16(q, ldq, k, ldk, v, ldv, 1, 16 * T, (H / E) * W, C, heads, scale, out, ldo,
-                                     s > 0 ? active_indices : nullptr, s, E, stream);
+    StackedKeys g;
+    if (const int status = stacked_keys(active_indices, T, H, W, &g)) return status;
+    return launch_attention_wide_f16(q, ldq, k, ldk, v, ldv, 1, 16 * T, g.Nk, C, heads, scale, out, ldo, g.tiles, g.shift, g.images, stream);
 }

@@ -2750,30 +2750,33 @@ def attention_tokens(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, heads: i
         return None
     Nk = k.shape[1]
     if tiles is not None:
-        idx, H, W = tiles
-        if not (idx.is_cuda and idx.dtype == torch.int32 and idx.dim() == 2 and idx.shape[1] == 2 and idx.is_contiguous()):
-            raise ValueError("attention_tokens: tiles = (device int32 [T,2] index list, H, W)")
-        if B != 1 or Nq != 16 * idx.shape[0] or Nk != int(H) * int(W):
-            raise ValueError("attention_tokens: with tiles, q is [1,16T,C] and k / v are [1,H*W,C]")
-        q, k, v = (t if t.is_contiguous() else t.contiguous() for t in (q, k, v))
-        out = torch.empty((B, Nq, C), dtype=torch.float32, device=q.device)
-        entry = lib().sige_hip_attention_tokens_tiles_f16c if compute == "f16" else lib().sige_hip_attention_tokens_tiles_f32
-        status = entry(q.data_ptr(), k.data_ptr(), v.data_ptr(), idx.data_ptr(), Nq // 16, int(H), int(W), C, heads, float(scale),
-                       out.data_ptr(), _stream(q))
-        if status == UNSUPPORTED:
-            return None
-        _check(status, "attention_tokens")
-        return out
-    if not lib().sige_hip_attention_tokens_supported(Nq, Nk, C, heads):
+        idx, H, W = _attention_tiles(tiles, B, Nq, Nk, "attention_tokens")
+    elif not lib().sige_hip_attention_tokens_supported(Nq, Nk, C, heads):
         return None
     q, k, v = (t if t.is_contiguous() else t.contiguous() for t in (q, k, v))
     out = torch.empty((B, Nq, C), dtype=torch.float32, device=q.device)
-    entry = lib().sige_hip_attention_tokens_f16c if compute == "f16" else lib().sige_hip_attention_tokens_f32
-    status = entry(q.data_ptr(), k.data_ptr(), v.data_ptr(), B, Nq, Nk, C, heads, float(scale), out.data_ptr(), _stream(q))
+    if tiles is not None:
+        entry = lib().sige_hip_attention_tokens_tiles_f16c if compute == "f16" else lib().sige_hip_attention_tokens_tiles_f32
+        status = entry(q.data_ptr(), k.data_ptr(), v.data_ptr(), idx.data_ptr(), Nq // 16, H, W, C, heads, float(scale),
+                       out.data_ptr(), _stream(q))
+    else:
+        entry = lib().sige_hip_attention_tokens_f16c if compute == "f16" else lib().sige_hip_attention_tokens_f32
+        status = entry(q.data_ptr(), k.data_ptr(), v.data_ptr(), B, Nq, Nk, C, heads, float(scale), out.data_ptr(), _stream(q))
     if status == UNSUPPORTED:
         return None
     _check(status, "attention_tokens")
     return out
+
+
+def _attention_tiles(tiles, B: int, Nq: int, Nk: int, name: str):
+    """`tiles` = (active_indices, H, W) of attention_tokens / attention_wide, checked against q [B,Nq,C] and k / v [B,Nk,C] ->
+    (index list, int H, int W).  (With `tiles` the `_supported` predicate is not asked first: the entry answers UNSUPPORTED.)"""
+    idx, H, W = tiles
+    if not (idx.is_cuda and idx.dtype == torch.int32 and idx.dim() == 2 and idx.shape[1] == 2 and idx.is_contiguous()):
+        raise ValueError("%s: tiles = (device int32 [T,2] index list, H, W)" % name)
+    if B != 1 or Nq != 16 * idx.shape[0] or Nk != int(H) * int(W):
+        raise ValueError("%s: with tiles, q is [1,16T,C] and k / v are [1,H*W,C]" % name)
+    return idx, int(H), int(W)
 
 
 def _token_rows(t: torch.Tensor):
@@ -2809,11 +2812,7 @@ def attention_wide(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, heads: int
         return None
     Nk = k.shape[1]
     if tiles is not None:
-        idx, H, W = tiles
-        if not (idx.is_cuda and idx.dtype == torch.int32 and idx.dim() == 2 and idx.shape[1] == 2 and idx.is_contiguous()):
-            raise ValueError("attention_wide: tiles = (device int32 [T,2] index list, H, W)")
-        if B != 1 or Nq != 16 * idx.shape[0] or Nk != int(H) * int(W):
-            raise ValueError("attention_wide: with tiles, q is [1,16T,C] and k / v are [1,H*W,C]")
+        idx, H, W = _attention_tiles(tiles, B, Nq, Nk, "attention_wide")
     elif not lib().sige_hip_attention_wide_supported(Nq, Nk, C, heads):
         return None
     (q, ldq), (k, ldk), (v, ldv) = _token_rows(q), _token_rows(k), _token_rows(v)
@@ -2823,7 +2822,7 @@ def attention_wide(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, heads: int
         raise ValueError("attention_wide: `out` must be a [B,Nq,C] fp32 tensor with contiguous rows")
     if tiles is not None:
         entry = lib().sige_hip_attention_wide_tiles_f16c if compute == "f16" else lib().sige_hip_attention_wide_tiles_f32
-        status = entry(q.data_ptr(), ldq, k.data_ptr(), ldk, v.data_ptr(), ldv, idx.data_ptr(), Nq // 16, int(H), int(W), C, heads,
+        status = entry(q.data_ptr(), ldq, k.data_ptr(), ldk, v.data_ptr(), ldv, idx.data_ptr(), Nq // 16, H, W, C, heads,
                        float(scale), out.data_ptr(), max(out.stride(1), C), _stream(q))
     else:
         entry = lib().sige_hip_attention_wide_f16c if compute == "f16" else lib().sige_hip_attention_wide_f32

@@ -172,3 +172,10 @@ def test_the_host_split_formula(L):
     assert fn(1, 16, 4096, 512, 1) == 16 and fn(1, 16 * 20, 4096, 512, 1) == 12  # (11 steps each: 12 splits, none empty)
     assert fn(1, 16, 100, 192, 1) == 1 and fn(2, 32 * 65, 256, 512, 1) == 1
     assert fn(1, 16, 100, 160, 1) == 0
+    # the edges of the rule min(256 / units, steps / 4, 16), at least 1, re-divided so that no split is empty (4096 keys = 128 steps):
+    # 128 units -> 2; 256 units: the last quotient of 1; 257: the first of 0, clamped to 1
+    assert fn(1, 16 * 128, 4096, 512, 1) == 2 and fn(1, 16 * 256, 4096, 512, 1) == 1 and fn(1, 16 * 257, 4096, 512, 1) == 1
+    # one unit, 3 / 4 / 7 steps: under two splits of four steps -> 1; 8 steps -> 2
+    assert [fn(1, 16, 32 * n, 512, 1) for n in (3, 4, 7, 8)] == [1, 1, 1, 2]
+    # 784 keys = 25 steps (the last of 16 keys): 25 / 4 = 6 splits of ceil(25 / 6) = 5 steps -> ceil(25 / 5) = 5 splits, one dropped
+    assert fn(1, 16, 784, 192, 1) == 5
