@@ -695,6 +695,22 @@ int sige_hip_token_linear_f32(const float *x, int64_t M, int K, const float *ln_
                               const float *packed, const float *bias, int N, int geglu, const float *residual, int parts,
                               float *out0, float *out1, float *out2, void *stream);
 
+/* ... with fp16 OPERANDS (csrc/token_linear_f16.hip, v_mfma_f32_32x32x16_f16 / 16x16x32_f16): the token linear of the f16 compute mode.
+ * Same tensors (fp32 in memory), arguments, prologue, epilogues, status codes and alignment rules as the four entries above.
+ * Arithmetic contract: prologue(x) -- x, or the LayerNorm output computed in fp32 -- and W are each rounded to nearest even to fp16;
+ * the products of the rounded operands are exact in fp32 and summed in fp32 in a fixed order (no atomics: two calls return the same
+ * bits); everything after the sum (bias, GEGLU's erf form, residual, the outputs) is fp32.  |operand| > 65504 is outside the contract.
+ *   packed_size_f16  fp16 elements of the packed weights, 0 = unsupported (N % 16, K % 32; geglu as above).  Host only.
+ *   supported_f16c   as `supported`, on packed_size_f16's shape rules.  Host only.
+ *   pack_f16         fp32 W [N,K] in -> fp16 packed out (half the bytes of `pack`'s; NOT interchangeable with it).
+ *   token_linear_f16c  M == 0 returns OK without a launch.  All pointers 16-byte aligned. */
+size_t sige_hip_token_linear_packed_size_f16(int N, int K, int geglu);
+int sige_hip_token_linear_supported_f16c(int64_t M, int N, int K, int layer_norm, int geglu, int parts);
+int sige_hip_token_linear_pack_f16(const float *w, int N, int K, int geglu, void *packed, void *stream);
+int sige_hip_token_linear_f16c(const float *x, int64_t M, int K, const float *ln_gamma, const float *ln_beta, float ln_eps,
+                               const void *packed, const float *bias, int N, int geglu, const float *residual, int parts,
+                               float *out0, float *out1, float *out2, void *stream);
+
 /* ---- 3x3 / padding-1 conv with <= 4 output channels over a full channels-last tensor
  * (the U-Net's conv_out after norm_out + SiLU, sige_fused_unet.py:430-434, which the
  * reference runs densely in sparse mode too): out [B,H,W,Cout] = conv(act(scale*x + shift)),

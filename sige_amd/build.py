@@ -15,10 +15,13 @@ LIB_DIR = os.path.join(PKG, "lib")
 LIB = os.path.join(LIB_DIR, "libsige_hip.so")
 SOURCES = ["api.hip", "plan.hip", "gather.hip", "scatter.hip", "reduce_mask.hip", "mask_pipeline.hip", "block_conv.hip", "conv_k3s1.hip", "conv_k1.hip",
            "conv_k3s2.hip", "conv_k3s1_nhwc.hip", "conv_k1_nhwc.hip", "conv_k3s2_nhwc.hip", "conv_k3s1_nhwc_w8.hip", "conv_k1_nhwc_w8.hip", "conv_k3s1_nhwc_h.hip", "conv_k1_nhwc_h.hip", "conv_k3s1_nhwc_x.hip", "conv_k1_nhwc_x.hip", "conv_k3s1_nhwc_c16.hip", "conv_k3s1_nhwc_h_c16.hip", "conv_k3s1_nhwc_x_c16.hip", "conv_pair_nhwc_x_t4.hip", "conv_pair_nhwc_x_f4.hip",
-           "conv_pair_nhwc_t4.hip", "conv_pair_nhwc_t8.hip", "conv_pair_nhwc_f4.hip", "conv_pair_nhwc_f8.hip", "conv_pair_nhwc_h_t4.hip", "conv_pair_nhwc_h_f4.hip", "conv_wide.hip", "conv_wide_k3_p8.hip", "conv_wide_k3_f32.hip", "conv_wide_k1_p8.hip", "conv_wide_pair_f32.hip", "conv_wide_pair_x3.hip", "conv_wide_pair_f16.hip", "group_norm.hip", "attention.hip", "attention_fused.hip", "attention_tokens.hip", "nhwc_ops.hip", "conv_out.hip", "conv_in.hip", "spade_ops.hip", "conv_tile3.hip", "conv_tile3_f32.hip", "token_ops.hip", "conv_tile3_f16.hip", "token_linear.hip", "resample_tiles.hip", "attention_wide.hip", "conv_side_nhwc_f4.hip", "conv_latent_head.hip", "spade_separable.hip", "conv_up_phase_nhwc.hip", "conv_tile3_f32_b10.hip", "attention_tokens_f16.hip", "split_pool.hip", "commit_tiles.hip", "attention_wide_f16.hip", "conv_tile3_phase.hip"]
+           "conv_pair_nhwc_t4.hip", "conv_pair_nhwc_t8.hip", "conv_pair_nhwc_f4.hip", "conv_pair_nhwc_f8.hip", "conv_pair_nhwc_h_t4.hip", "conv_pair_nhwc_h_f4.hip", "conv_wide.hip", "conv_wide_k3_p8.hip", "conv_wide_k3_f32.hip", "conv_wide_k1_p8.hip", "conv_wide_pair_f32.hip", "conv_wide_pair_x3.hip", "conv_wide_pair_f16.hip", "group_norm.hip", "attention.hip", "attention_fused.hip", "attention_tokens.hip", "nhwc_ops.hip", "conv_out.hip", "conv_in.hip", "spade_ops.hip", "conv_tile3.hip", "conv_tile3_f32.hip", "token_ops.hip", "conv_tile3_f16.hip", "token_linear.hip", "resample_tiles.hip", "attention_wide.hip", "conv_side_nhwc_f4.hip", "conv_latent_head.hip", "spade_separable.hip", "conv_up_phase_nhwc.hip", "conv_tile3_f32_b10.hip", "attention_tokens_f16.hip", "split_pool.hip", "commit_tiles.hip", "attention_wide_f16.hip", "conv_tile3_phase.hip", "token_linear_f16.hip"]
 # -ffp-contract=off: the reference applies scale then shift as two separately
 # rounded fp32 ops (sige/cpu/gather.cpp:33-53); an fma would differ in the last bit.
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-Wno-unused-result"]
+# units compiled without the packed fp32 VALU forms (v_pk_add_f32 / v_pk_mul_f32 / v_pk_fma_f32): plain fp32 instructions only
+NO_PACKED_F32 = ("token_linear_f16.hip",)
+NO_PACKED_F32_FLAGS = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
 
 
 def source_hash() -> str:
@@ -26,7 +29,7 @@ def source_hash() -> str:
     committed profile was taken on (bench.py prints `roofline.traffic` only for a matching hash; the GPU box has no .git)."""
     import hashlib
 
-    h = hashlib.sha256(" ".join(FLAGS).encode())
+    h = hashlib.sha256(" ".join(FLAGS + list(NO_PACKED_F32) + NO_PACKED_F32_FLAGS).encode())
     for f in sorted(os.listdir(CSRC)):
         if f.endswith((".hip", ".hpp", ".h")):
             h.update(f.encode())
@@ -59,13 +62,14 @@ def _stale(obj: str, src: str, headers) -> bool:
 
 # translation units that read a dispatch knob (csrc/tuning.hpp): compiled a second time with -DSIGE_HIP_TUNING for the
 # measurement library lib/libsige_hip_tuning.so; every other object is shared with the product build
-TUNING_UNITS = ("api.hip", "block_conv.hip", "gather.hip", "conv_wide.hip", "attention_tokens.hip", "conv_out.hip", "conv_tile3.hip", "token_linear.hip", "split_pool.hip")
+TUNING_UNITS = ("api.hip", "block_conv.hip", "gather.hip", "conv_wide.hip", "attention_tokens.hip", "conv_out.hip", "conv_tile3.hip", "token_linear.hip", "split_pool.hip", "token_linear_f16.hip")
 TUNING_LIB = os.path.join(LIB_DIR, "libsige_hip_tuning.so")
 
 
 def _compile_cmd(src: str, obj: str, defs=()):
     # -DSIGE_TU_ID: the unit's anchor kernel (csrc/common.hpp) that sige_hip_preload() loads the unit's code object through
-    return [_hipcc(), *FLAGS, "-DSIGE_TU_ID=%d" % SOURCES.index(src), *defs, "-I" + os.path.join(REPO, "include"), "-I" + CSRC, "-c",
+    extra = NO_PACKED_F32_FLAGS if src in NO_PACKED_F32 else []
+    return [_hipcc(), *FLAGS, *extra, "-DSIGE_TU_ID=%d" % SOURCES.index(src), *defs, "-I" + os.path.join(REPO, "include"), "-I" + CSRC, "-c",
             os.path.join(CSRC, src), "-o", obj]
 
 

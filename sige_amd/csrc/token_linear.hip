@@ -18,28 +18,10 @@
 // the 32x32x2 form's lane order, zero padded to 64 columns and 64 channels; the 16-token form reads the same tensor through a permuted
 // lane address.  GEGLU: a workgroup's 64 packed columns are 32 value columns and THEIR 32 gate columns.
 // Row tails and dead channel slices: the buffer descriptor's range check (offset kOOB reads 0); column tails: the zero padding.
-#include "conv_mfma.hpp"
+#include "token_linear.hpp"
 
 namespace sige {
 namespace {
-
-constexpr int kTokMaxLnK = 2048;      // token_ops.hip's limit (kMaxPerLane * 64)
-constexpr int kTokSlots = 512;        // 64-token workgroups the chip holds at once: 256 CUs x 2 (LDS and registers)
-
-struct TokArgs {
-    const float *x, *gamma, *beta, *packed, *bias, *residual;
-    float *out0, *out1, *out2;
-    float eps;
-    int M, K, N;            // N: columns of the product (2 D for GEGLU)
-    int No;                 // columns (= row stride) of one output: N / parts, D for GEGLU
-    int ntn, nchunks, tpp;  // 64-column blocks, 64-channel chunks, column blocks per part
-    int x_bytes, w_bytes;   // ranges of the two buffer descriptors
-};
-
-__device__ __forceinline__ f32x4 buf4(rsrc_t r, unsigned byte_off) {
-    return __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(r, (int)byte_off, 0, 0));
-}
-__device__ __forceinline__ float gelu_erf(float z) { return 0.5f * z * (1.0f + erff(z * 0.70710678118654752440f)); }
 
 // BM: token rows per workgroup (64 | 16).
 template <int BM, bool LN, bool GEGLU>
@@ -49,14 +31,14 @@ __global__ __launch_bounds__(256) void token_linear_kernel(const TokArgs a) {
     constexpr int MT = BIG ? 2 : 1;   // M tiles per wave
     constexpr int NT = BIG ? 2 : 4;   // N tiles per wave
     constexpr int AP = BIG ? 2 : 1;   // 16-byte A pieces per lane, tile and chunk
-    constexpr int RP = 68;
+    constexpr int RP = kTokRP;
     __shared__ __attribute__((aligned(16))) float smem[4 * BM * RP];
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int ntile = blockIdx.x % a.ntn, mtile = blockIdx.x / a.ntn;
     const int row0 = mtile * BM;
     const rsrc_t rx = __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(a.x), 0, a.x_bytes, 0x00020000);
-    const rsrc_t rw = __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(a.packed), 0, a.w_bytes, 0x00020000);
+    const rsrc_t rw = __builtin_amdgcn_make_buffer_rsrc(const_cast<void *>(a.packed), 0, a.w_bytes, 0x00020000);
     // this lane's rows and channel group: 32x32x2 -- row lane & 31 of each M tile, channels 8 kq .. 8 kq + 7 of the wave's 16 (MFMA step
     // s contracts channels s and 8 + s); 16x16x4 -- row lane & 15, channels 4 kg .. 4 kg + 3 (step s: channels s, 4 + s, 8 + s, 12 + s)
     const int rl = BIG ? (lane & 31) : (lane & 15), kg = BIG ? (lane >> 5) : (lane >> 4);
@@ -67,72 +49,7 @@ __global__ __launch_bounds__(256) void token_linear_kernel(const TokArgs a) {
 #pragma unroll
     for (int mt = 0; mt < MT; ++mt) mean[mt] = 0.f, rstd[mt] = 1.f;
     if constexpr (LN) {
-        constexpr int TPR = 256 / BM;
-        const int r = tid / TPR, sub = tid % TPR;
-        const unsigned rb = row0 + r < a.M ? (unsigned)((row0 + r) * a.K) * 4u : kOOB;
-        const int iters = (a.K / 4 + TPR - 1) / TPR;
-        // (U requests in flight per round trip; a row share of up to U float4 -- K <= 64 U at 16 lanes per row -- stays in registers
-        //  for the second pass)
-        constexpr int U = 8;
-        auto load8 = [&](int i0, f32x4 (&v)[U], bool (&in)[U]) {
-#pragma unroll
-            for (int u = 0; u < U; ++u) {
-                const int k = (sub + TPR * (i0 + u)) * 4;
-                in[u] = k < a.K;
-                v[u] = buf4(rx, in[u] ? rb + (unsigned)k * 4u : kOOB);
-            }
-        };
-        auto sum8 = [&](const f32x4 (&v)[U]) {
-            float t = 0.f;
-#pragma unroll
-            for (int u = 0; u < U; ++u) t += (v[u][0] + v[u][1]) + (v[u][2] + v[u][3]);  // (absent pieces read 0)
-            return t;
-        };
-        auto sq8 = [&](const f32x4 (&v)[U], const bool (&in)[U], float mu) {
-            float t = 0.f;
-#pragma unroll
-            for (int u = 0; u < U; ++u) {
-                const float d0 = v[u][0] - mu, d1 = v[u][1] - mu, d2 = v[u][2] - mu, d3 = v[u][3] - mu;
-                t += in[u] ? (d0 * d0 + d1 * d1) + (d2 * d2 + d3 * d3) : 0.f;
-            }
-            return t;
-        };
-        auto row_sum = [&](float t) {
-#pragma unroll
-            for (int d = TPR / 2; d >= 1; d >>= 1) t += __shfl_xor(t, d);
-            return t;
-        };
-        f32x4 v[U];
-        bool in[U];
-        float mu, q = 0.f;
-        if (iters <= U) {  // (uniform)
-            load8(0, v, in);
-            mu = row_sum(sum8(v)) / (float)a.K;
-            q = sq8(v, in, mu);
-        } else {
-            float s = 0.f;
-            for (int i0 = 0; i0 < iters; i0 += U) {
-                load8(i0, v, in);
-                s += sum8(v);
-            }
-            mu = row_sum(s) / (float)a.K;
-            for (int i0 = 0; i0 < iters; i0 += U) {
-                load8(i0, v, in);
-                q += sq8(v, in, mu);
-            }
-        }
-        q = row_sum(q);
-        const float rs = 1.0f / sqrtf(q / (float)a.K + a.eps);
-        if (sub == 0) {
-            smem[2 * r] = mu;
-            smem[2 * r + 1] = rs;
-        }
-        __syncthreads();
-#pragma unroll
-        for (int mt = 0; mt < MT; ++mt) {
-            mean[mt] = smem[2 * (mt * 32 + rl)];
-            rstd[mt] = smem[2 * (mt * 32 + rl) + 1];
-        }
+        tok_row_stats<BM>(a, rx, smem, tid, row0, rl, mean, rstd);
     }
 
     // ---- K loop: the registers of chunk c + 1 are requested before the MFMAs of chunk c ----
@@ -216,74 +133,7 @@ __global__ __launch_bounds__(256) void token_linear_kernel(const TokArgs a) {
         cur = nxt;
     }
 
-    // ---- epilogue units of this lane: one float4 = 4 consecutive output columns of one row per step.  Bias and residual are
-    //      requested here, ahead of the reduction's barriers (clamped addresses: every lane loads, `ok` decides the store) ----
-    constexpr int EU = GEGLU ? (BM * 8 + 255) / 256 : BM * 16 / 256;
-    constexpr int CW = GEGLU ? 8 : 16;  // float4 units per row
-    const int part = GEGLU ? 0 : ntile / a.tpp;
-    float *const outp = part == 0 ? a.out0 : (part == 1 ? a.out1 : a.out2);
-    bool ok[EU];
-    unsigned addr[EU];
-    float4 bv[EU], bg[EU], rv[EU];
-#pragma unroll
-    for (int k = 0; k < EU; ++k) {
-        const int o = tid + 256 * k;
-        const int n4 = o & (CW - 1), m = (o / CW) & (BM - 1);
-        const int row = row0 + m;
-        // (GEGLU: D % 32 == 0, every column of the block is real)
-        const int co = GEGLU ? ntile * 32 + 4 * n4 : ntile * 64 + 4 * n4;
-        ok[k] = o < BM * CW && row < a.M && (GEGLU || co < a.N);
-        addr[k] = ok[k] ? (unsigned)(row * a.No + (co - part * a.No)) : 0u;
-        bv[k] = bg[k] = rv[k] = make_float4(0.f, 0.f, 0.f, 0.f);
-        if (a.bias) {
-            bv[k] = *reinterpret_cast<const float4 *>(a.bias + (GEGLU ? co : min(co, a.N - 4)));
-            if constexpr (GEGLU) bg[k] = *reinterpret_cast<const float4 *>(a.bias + a.No + co);
-        }
-        if (a.residual) rv[k] = *reinterpret_cast<const float4 *>(a.residual + addr[k]);
-    }
-
-    // ---- the four waves' K shares meet in LDS ----
-    __syncthreads();  // (every lane has read its rows' statistics)
-    {
-        float *r = smem + wave * BM * RP;
-#pragma unroll
-        for (int mt = 0; mt < MT; ++mt)
-#pragma unroll
-            for (int nt = 0; nt < NT; ++nt)
-#pragma unroll
-                for (int q = 0; q < (BIG ? 16 : 4); ++q) {
-                    // C / D maps: 32x32 -- column lane & 31, row (q & 3) + 8 (q >> 2) + 4 (lane >> 5); 16x16 -- column lane & 15, row 4 (lane >> 4) + q
-                    const int m = BIG ? mt * 32 + (q & 3) + 8 * (q >> 2) + 4 * kg : 4 * kg + q;
-                    r[m * RP + nt * (BIG ? 32 : 16) + rl] = acc[mt][nt][q];
-                }
-    }
-    __syncthreads();
-
-    auto sum4 = [&](int m, int c) -> float4 {  // the four waves' shares, in wave order
-        const float *r0 = smem + m * RP + c;
-        float4 s = *reinterpret_cast<const float4 *>(r0);
-#pragma unroll
-        for (int w = 1; w < 4; ++w) {
-            const float4 v = *reinterpret_cast<const float4 *>(r0 + w * BM * RP);
-            s.x += v.x; s.y += v.y; s.z += v.z; s.w += v.w;
-        }
-        return s;
-    };
-    auto add4 = [](float4 p, float4 q) { return make_float4(p.x + q.x, p.y + q.y, p.z + q.z, p.w + q.w); };
-#pragma unroll
-    for (int k = 0; k < EU; ++k) {
-        const int o = tid + 256 * k;
-        const int n4 = o & (CW - 1), m = (o / CW) & (BM - 1);
-        float4 s = sum4(m, 4 * n4);
-        if (a.bias) s = add4(s, bv[k]);
-        if constexpr (GEGLU) {
-            float4 g = sum4(m, 32 + 4 * n4);
-            if (a.bias) g = add4(g, bg[k]);
-            s = make_float4(s.x * gelu_erf(g.x), s.y * gelu_erf(g.y), s.z * gelu_erf(g.z), s.w * gelu_erf(g.w));
-        }
-        if (a.residual) s = add4(rv[k], s);
-        if (ok[k]) store_out4(outp + addr[k], s);
-    }
+    tok_finish<BM, GEGLU>(a, smem, acc, tid, wave, ntile, row0, rl, kg);
 }
 
 // packed[((ntile * nchunks + chunk) * 4 + wave) * 1024 + ((nt * 2 + piece) * 64 + lane) * 4 + j] =
@@ -303,8 +153,6 @@ __global__ __launch_bounds__(256) void token_linear_pack_kernel(const float *__r
     const float4 v = *reinterpret_cast<const float4 *>(w + (ok ? (size_t)n * K + k : 0));
     *reinterpret_cast<float4 *>(packed + (size_t)u * 4) = ok ? v : make_float4(0.f, 0.f, 0.f, 0.f);
 }
-
-inline bool al16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
 // 64-column blocks of the packed tensor; 0 = the shape is not supported
 inline int tok_ntn(int N, int K, int geglu) {
@@ -348,7 +196,7 @@ extern "C" int sige_hip_token_linear_pack(const float *w, int N, int K, int gegl
     if (N <= 0 || K <= 0) return SIGE_HIP_EINVAL;
     if (!w || !packed) return SIGE_HIP_EINVAL;
     const size_t floats = sige_hip_token_linear_packed_size(N, K, geglu);
-    if (!floats || !al16(w) || !al16(packed)) return SIGE_HIP_EUNSUPPORTED;
+    if (!floats || !tok_al16(w) || !tok_al16(packed)) return SIGE_HIP_EUNSUPPORTED;
     token_linear_pack_kernel<<<(unsigned)(floats / 1024), 256, 0, as_stream(stream)>>>(w, N, K, geglu ? N / 2 : 0, tok_nchunks(K), packed);
     return launch_status();
 }
@@ -362,24 +210,18 @@ extern "C" int sige_hip_token_linear_f32(const float *x, int64_t M, int K, const
     if (!x || !packed || !out0 || (parts > 1 && !out1) || (parts > 2 && !out2) || (ln_gamma && !ln_beta)) return SIGE_HIP_EINVAL;
     if (!sige_hip_token_linear_supported(M, N, K, ln_gamma != nullptr, geglu, parts)) return SIGE_HIP_EUNSUPPORTED;
     if (parts > 1 && residual) return SIGE_HIP_EUNSUPPORTED;
-    if (!al16(x) || !al16(packed) || !al16(out0) || !al16(out1) || !al16(out2) || !al16(bias) || !al16(residual) || !al16(ln_gamma) || !al16(ln_beta))
+    if (!tok_al16(x) || !tok_al16(packed) || !tok_al16(out0) || !tok_al16(out1) || !tok_al16(out2) || !tok_al16(bias) || !tok_al16(residual) || !tok_al16(ln_gamma) || !tok_al16(ln_beta))
         return SIGE_HIP_EUNSUPPORTED;
-    TokArgs a;
-    a.x = x; a.gamma = ln_gamma; a.beta = ln_beta; a.packed = packed; a.bias = bias; a.residual = residual;
-    a.out0 = out0; a.out1 = parts > 1 ? out1 : out0; a.out2 = parts > 2 ? out2 : out0;
-    a.eps = ln_eps;
-    a.M = (int)M; a.K = K; a.N = N;
-    a.No = geglu ? N / 2 : N / parts;
+    TokArgs a = tok_args(x, M, K, ln_gamma, ln_beta, ln_eps, bias, N, geglu, residual, parts, out0, out1, out2);
+    a.packed = packed;
     a.ntn = tok_ntn(N, K, geglu);
     a.nchunks = tok_nchunks(K);
     a.tpp = parts > 1 ? a.No / 64 : a.ntn;
-    a.x_bytes = (int)(M * K * 4);
     a.w_bytes = (int)(sige_hip_token_linear_packed_size(N, K, geglu) * 4);
     // grid fill (as plan_conv chooses its tile): the 64-token form reads every weight byte for four times the rows, but its grid comes
     // in rounds of kTokSlots workgroups and in whole 64-row blocks; it runs where real rows fill at least 0.8 of the rounds' slots
     // (measured per shape: DESIGN.md 5.12), the 16-token form's four times finer grid everywhere else
-    const long b64 = ((M + 63) / 64) * a.ntn, rounds = (b64 + kTokSlots - 1) / kTokSlots;
-    const double fill = (double)M * a.ntn / (64.0 * (double)(rounds * kTokSlots));
+    const double fill = tok_fill64(M, a.ntn, kTokSlots);
     const int knob = tuning(SIGE_HIP_TUNE_TOKEN_LINEAR_FORM);
     const bool big = knob ? knob == 2 : fill >= 0.8;
     hipStream_t st = as_stream(stream);

@@ -205,6 +205,11 @@ _SIGNATURES = {
     "sige_hip_token_linear_pack": (_c_int, [_c_vp, _c_int, _c_int, _c_int, _c_vp, _c_vp]),
     "sige_hip_token_linear_f32": (_c_int, [_c_vp, ctypes.c_int64, _c_int, _c_vp, _c_vp, ctypes.c_float, _c_vp, _c_vp, _c_int, _c_int, _c_vp, _c_int]
                                   + [_c_vp] * 4),
+    "sige_hip_token_linear_packed_size_f16": (_c_sz, [_c_int] * 3),
+    "sige_hip_token_linear_supported_f16c": (_c_int, [ctypes.c_int64] + [_c_int] * 5),
+    "sige_hip_token_linear_pack_f16": (_c_int, [_c_vp, _c_int, _c_int, _c_int, _c_vp, _c_vp]),
+    "sige_hip_token_linear_f16c": (_c_int, [_c_vp, ctypes.c_int64, _c_int, _c_vp, _c_vp, ctypes.c_float, _c_vp, _c_vp, _c_int, _c_int, _c_vp, _c_int]
+                                   + [_c_vp] * 4),
     "sige_hip_set_edit_batch": (_c_int, [_c_int]),
     "sige_hip_get_edit_batch": (_c_int, []),
     # launch plans (csrc/plan.hip; host side: sige_amd/plan.py)
@@ -2240,21 +2245,36 @@ def add_bias_tokens(x, delta, bias):
 
 
 # ---- token linear of the SD transformer blocks (csrc/token_linear.hip) --------------------------------------------------------------
-def token_linear_pack(weight, geglu: bool = False) -> Optional[torch.Tensor]:
+def _token_linear_entries(compute: str):
+    """(packed_size, supported, pack, launch, dtype of the pack) of the token linear's compute: "f32" exact fp32 products
+    (csrc/token_linear.hip), "f16" fp16 operands with fp32 accumulation (csrc/token_linear_f16.hip)."""
+    L = lib()
+    if compute == "f32":
+        return L.sige_hip_token_linear_packed_size, L.sige_hip_token_linear_supported, L.sige_hip_token_linear_pack, L.sige_hip_token_linear_f32, torch.float32
+    if compute == "f16":
+        return (L.sige_hip_token_linear_packed_size_f16, L.sige_hip_token_linear_supported_f16c, L.sige_hip_token_linear_pack_f16,
+                L.sige_hip_token_linear_f16c, torch.float16)
+    raise ValueError("sige_amd.hip.token_linear: compute is 'f32' or 'f16', not %r" % (compute,))
+
+
+def token_linear_pack(weight, geglu: bool = False, compute: str = "f32") -> Optional[torch.Tensor]:
     """nn.Linear.weight [N,K] (or a list of them, stacked along N: q | k | v) in the token linear's packed order; None if the shape
-    is unsupported (include/sige_hip.h: sige_hip_token_linear_packed_size).  `geglu`: the rows are [value D | gate D]."""
+    is unsupported (include/sige_hip.h: sige_hip_token_linear_packed_size / _f16).  `geglu`: the rows are [value D | gate D].
+    `compute`: "f32" -> a float32 pack for exact fp32 products, "f16" -> a float16 pack (the weights rounded to nearest even) for
+    token_linear(compute="f16"); a pack serves the compute it was made for only."""
+    size_of, _, pack, _, dtype = _token_linear_entries(compute)
     ws = list(weight) if isinstance(weight, (list, tuple)) else [weight]
     ws = [w.detach() for w in ws]
     w = ws[0] if len(ws) == 1 else torch.cat(ws, dim=0)
     if not (w.is_cuda and w.dtype == torch.float32 and w.dim() == 2):
         return None
     N, K = w.shape
-    size = lib().sige_hip_token_linear_packed_size(N, K, int(geglu))
+    size = size_of(N, K, int(geglu))
     if not size:
         return None
     w = w if w.is_contiguous() else w.contiguous()
-    packed = torch.empty(size, dtype=torch.float32, device=w.device)
-    status = lib().sige_hip_token_linear_pack(w.data_ptr(), N, K, int(geglu), packed.data_ptr(), _stream(w))
+    packed = torch.empty(size, dtype=dtype, device=w.device)
+    status = pack(w.data_ptr(), N, K, int(geglu), packed.data_ptr(), _stream(w))
     if status == UNSUPPORTED:
         return None
     _check(status, "token_linear_pack")
@@ -2262,18 +2282,22 @@ def token_linear_pack(weight, geglu: bool = False) -> Optional[torch.Tensor]:
 
 
 def token_linear(x: torch.Tensor, packed: torch.Tensor, N: int, bias=None, norm: Optional[torch.nn.LayerNorm] = None, residual=None,
-                 geglu: bool = False, parts: int = 1):
+                 geglu: bool = False, parts: int = 1, compute: str = "f32"):
     """epilogue(LayerNorm?(x) @ W^T) in ONE launch for tokens x [..., K] and W [N,K] packed by token_linear_pack: `norm` = the
     LayerNorm applied to x on the way in; `bias` [N]; `geglu`: value * gelu(gate) -> [..., N/2]; `residual` (shaped like the output) is
-    added; `parts` > 1: a tuple of that many [..., N/parts] tensors (q, k, v).  None if unsupported (the caller runs its other path)."""
+    added; `parts` > 1: a tuple of that many [..., N/parts] tensors (q, k, v).  `compute`: "f32" exact fp32 products | "f16" the
+    LayerNorm output and W rounded to fp16, fp32 accumulation, everything else fp32 (include/sige_hip.h has the contract); `packed`
+    must have been made with the same `compute`.  None if unsupported (the caller runs its other path)."""
+    size_of, supported, _, launch, dtype = _token_linear_entries(compute)
     if not (x.is_cuda and x.dtype == torch.float32 and x.dim() >= 2 and packed is not None):
         return None
     K = x.shape[-1]
     M = x.numel() // K if K else 0
-    if not lib().sige_hip_token_linear_supported(M, N, K, int(norm is not None), int(geglu), parts) or (parts > 1 and residual is not None):
+    if not supported(M, N, K, int(norm is not None), int(geglu), parts) or (parts > 1 and residual is not None):
         return None
-    if packed.numel() != lib().sige_hip_token_linear_packed_size(N, K, int(geglu)):
-        raise RuntimeError("sige_amd.hip.token_linear: `packed` does not belong to a [%d, %d] weight" % (N, K))
+    if packed.dtype != dtype or packed.numel() != size_of(N, K, int(geglu)):
+        raise RuntimeError("sige_amd.hip.token_linear: `packed` (%s, %d elements) is not the compute=%r pack of a [%d, %d] weight"
+                           % (packed.dtype, packed.numel(), compute, N, K))
     x = x if x.is_contiguous() else x.contiguous()
     No = N // 2 if geglu else N // parts
     outs = [torch.empty((*x.shape[:-1], No), dtype=torch.float32, device=x.device) for _ in range(parts)]
@@ -2287,10 +2311,10 @@ def token_linear(x: torch.Tensor, packed: torch.Tensor, N: int, bias=None, norm:
     g = e = None
     if norm is not None:
         g, e = norm.weight.detach(), norm.bias.detach()
-    status = lib().sige_hip_token_linear_f32(x.data_ptr(), M, K, _p(g), _p(e), float(norm.eps) if norm is not None else 0.0,
-                                             packed.data_ptr(), _p(bias), N, int(geglu), _p(residual), parts,
-                                             outs[0].data_ptr(), _p(outs[1] if parts > 1 else None), _p(outs[2] if parts > 2 else None),
-                                             _stream(x))
+    status = launch(x.data_ptr(), M, K, _p(g), _p(e), float(norm.eps) if norm is not None else 0.0,
+                    packed.data_ptr(), _p(bias), N, int(geglu), _p(residual), parts,
+                    outs[0].data_ptr(), _p(outs[1] if parts > 1 else None), _p(outs[2] if parts > 2 else None),
+                    _stream(x))
     if status == UNSUPPORTED:
         return None
     _check(status, "token_linear")

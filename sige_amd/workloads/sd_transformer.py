@@ -25,6 +25,7 @@ the keys of ITS image only, found inside the launch from the Gather's index list
 has no per-image form (the switches listed at `_refuse_stacked`) raises a RuntimeError that names stacked edits; nothing falls
 back to a chain that would softmax over the keys of all E images.
 """
+import functools
 from typing import Optional
 
 import torch
@@ -59,12 +60,20 @@ from ..nn import Gather, Scatter, SIGEConv2d, SIGEModule
 #                     operands with fp32 accumulation on the same fp32 tensors (sige_hip_attention_tokens_f16c: the attention of the
 #                     f16 compute mode) -- in full and in sparse mode, like the convs' compute dtype.  This one CHANGES values, within
 #                     the f16 criterion (sige_amd/tolerance.py).  "f32" by default: DESIGN.md 5.21 has the measurements.
+#   TOKEN_LINEAR_COMPUTE  the operands of TOKEN_LINEAR's six launches: "f32" exact fp32 products (sige_hip_token_linear_f32), "f16" the
+#                     LayerNorm output and the weights rounded to fp16, fp32 accumulation, bias / GEGLU / residual and every tensor
+#                     fp32 (sige_hip_token_linear_f16c: the token linear of the f16 compute mode; the packs are re-made as fp16).
+#                     Sparse mode only, like TOKEN_LINEAR itself: full mode, the untiled middle transformer and the cross-attention's
+#                     cached K / V stay on torch's fp32 linears -- so the cached K / V of the original image are fp32-computed and the
+#                     rows a sparse pass refreshes are f16-computed.  CHANGES values, within the f16 criterion.  "f32" by default:
+#                     DESIGN.md 5.30 has the measurements.
 NATIVE_ATTENTION = True
 ATTENTION_COMPUTE = "f32"
 NATIVE_LINEAR = False
 BATCHED_QKV = True
 FUSED_TOKENS = True
 TOKEN_LINEAR = False
+TOKEN_LINEAR_COMPUTE = "f32"
 
 
 def linear(lin: nn.Linear, x: torch.Tensor) -> torch.Tensor:
@@ -212,8 +221,9 @@ class TransformerBlock(SIGEModule):
                 and x.shape[2] % 4 == 0 and x.shape[2] <= 2048 and x.is_contiguous())
 
     def _token_linear_packs(self, x):
-        """The packed weights of the block's six token linears (csrc/token_linear.hip), cached on the modules as plain attributes
-        under the key linear() uses -- an in-place weight update re-packs --; None if the library refuses one of the six shapes (or
+        """The packed weights of the block's six token linears (csrc/token_linear.hip, token_linear_f16.hip), cached on the modules as
+        plain attributes under the key linear() uses plus TOKEN_LINEAR_COMPUTE -- an in-place weight update re-packs, and so does
+        flipping the compute --; None if the library refuses one of the six shapes (or
         the cross-attention has no cached K / V): the block then takes the other path as a whole."""
         from .. import hip
 
@@ -221,7 +231,8 @@ class TransformerBlock(SIGEModule):
         if a2.cached_k is None or a2.cached_v is None or a1.to_k.in_features != a1.to_q.in_features:
             return None
         m, c = x.shape[0] * x.shape[1], x.shape[2]
-        L = hip.lib()
+        compute = TOKEN_LINEAR_COMPUTE
+        supported = hip._token_linear_entries(compute)[1]
         # (owner, weights, LayerNorm, GEGLU, parts)
         spec = ((a1, (a1.to_q, a1.to_k, a1.to_v), True, False, 3), (a1.to_out[0], (a1.to_out[0],), False, False, 1),
                 (a2.to_q, (a2.to_q,), True, False, 1), (a2.to_out[0], (a2.to_out[0],), False, False, 1),
@@ -229,11 +240,11 @@ class TransformerBlock(SIGEModule):
         packs = []
         for owner, lins, ln, geglu, parts in spec:
             n, k = sum(l.out_features for l in lins), lins[0].in_features
-            if not L.sige_hip_token_linear_supported(m, n, k, int(ln), int(geglu), parts):
+            if not supported(m, n, k, int(ln), int(geglu), parts):
                 return None
-            key = tuple((l.weight.data_ptr(), l.weight._version, tuple(l.weight.shape), l.weight.device) for l in lins)
+            key = (compute, *((l.weight.data_ptr(), l.weight._version, tuple(l.weight.shape), l.weight.device) for l in lins))
             if getattr(owner, "_sige_tl_key", None) != key:
-                owner._sige_tl_packed = hip.token_linear_pack([l.weight for l in lins], geglu)
+                owner._sige_tl_packed = hip.token_linear_pack([l.weight for l in lins], geglu, compute=compute)
                 owner._sige_tl_key = key
             if owner._sige_tl_packed is None:
                 return None
@@ -252,25 +263,26 @@ class TransformerBlock(SIGEModule):
         tiles = _kv_tiles(kv_scatter)
         as_tiles = lambda t: t.reshape(-1, 4, 4, t.shape[2]).permute(0, 3, 1, 2)  # noqa: E731
         as_tokens = lambda t: t.permute(0, 2, 3, 1).reshape(t.shape[0], hh * ww, t.shape[1])  # noqa: E731
+        tl = functools.partial(hip.token_linear, compute=TOKEN_LINEAR_COMPUTE)  # (the packs were made for it: _token_linear_packs)
 
         def need(t, what):  # (the shapes were accepted by sige_hip_token_linear_supported: a refusal here is an error, not a detour)
             if t is None:
                 raise RuntimeError("TOKEN_LINEAR: the library refused %s" % what)
             return t
 
-        q_t, k_t, v_t = need(hip.token_linear(x, p_qkv, n_qkv, norm=self.norm1, parts=3), "the q | k | v projection")
+        q_t, k_t, v_t = need(tl(x, p_qkv, n_qkv, norm=self.norm1, parts=3), "the q | k | v projection")
         k = sk(as_tiles(k_t))
         v = sv(as_tiles(v_t))
         o = hip.attention_tokens(q_t, as_tokens(k), as_tokens(v), a1.heads, a1.scale, compute=ATTENTION_COMPUTE, tiles=tiles)
         if o is None and tiles is not None:
             _refuse_stacked("the library refused the self-attention (K / V %d x %d for the whole edit batch)" % (hh, ww))
         need(o, "the self-attention")
-        x1 = need(hip.token_linear(o, p_o1, n_o1, bias=a1.to_out[0].bias, residual=x), "attn1.to_out")
-        q2 = need(hip.token_linear(x1, p_q2, n_q2, norm=self.norm2), "attn2.to_q")
+        x1 = need(tl(o, p_o1, n_o1, bias=a1.to_out[0].bias, residual=x), "attn1.to_out")
+        q2 = need(tl(x1, p_q2, n_q2, norm=self.norm2), "attn2.to_q")
         o = need(hip.attention_tokens(q2, a2.cached_k, a2.cached_v, a2.heads, a2.scale, compute=ATTENTION_COMPUTE), "the cross-attention")
-        x2 = need(hip.token_linear(o, p_o2, n_o2, bias=a2.to_out[0].bias, residual=x1), "attn2.to_out")
-        h = need(hip.token_linear(x2, p_f0, n_f0, bias=ff.net[0].proj.bias, norm=self.norm3, geglu=True), "the GEGLU projection")
-        return need(hip.token_linear(h, p_f2, n_f2, bias=ff.net[2].bias, residual=x2), "ff.net.2")
+        x2 = need(tl(o, p_o2, n_o2, bias=a2.to_out[0].bias, residual=x1), "attn2.to_out")
+        h = need(tl(x2, p_f0, n_f0, bias=ff.net[0].proj.bias, norm=self.norm3, geglu=True), "the GEGLU projection")
+        return need(tl(h, p_f2, n_f2, bias=ff.net[2].bias, residual=x2), "ff.net.2")
 
     def _forward_fused(self, x, full_x, context, kv_scatter):
         """The sparse-mode block with the token helpers of csrc/token_ops.hip: per block LayerNorm, [q | k | v GEMM, K / V scatter,

@@ -6,6 +6,14 @@ unless --tuned is given (a process-wide PyTorch setting).
 
     python tools/sd_token_linear_ab.py --out out/sd_token_linear.json
     python tools/sd_token_linear_ab.py --tuned --out out/sd_token_linear_tuned.json
+
+`--compute f16`: the model in the f16 compute mode (SIGEModel.set_compute_dtype("f16"), as bench.py --workload sd --dtype f16), the
+switch-on settings with the token linear on fp16 operands (sd_transformer.TOKEN_LINEAR_COMPUTE = "f16"); every row carries the f16
+criterion (sige_amd.tolerance.f16_check) of its output against the all-fp32 model's.  The two TunableOp sessions go into ONE file, under
+"sessions": the second run adds its session to the file the first one wrote.
+
+    python tools/sd_token_linear_ab.py --compute f16 --out profiles/sd_token_linear_f16_ab.json
+    python tools/sd_token_linear_ab.py --compute f16 --tuned --out profiles/sd_token_linear_f16_ab.json
 """
 import argparse
 import json
@@ -28,9 +36,11 @@ def main():
     ap.add_argument("--masks", default="bench,other")
     ap.add_argument("--replays", type=int, default=20)
     ap.add_argument("--tuned", action="store_true", help="TunableOp on with the shipped table (sige_amd/workloads/gemm_tuning.py)")
+    ap.add_argument("--compute", default="f32", choices=("f32", "f16"), help="the model's compute mode and the token linear's operands")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     from sige_amd import hip
+    from sige_amd.tolerance import f16_check
     from sige_amd.utils import downsample_mask
     from sige_amd.workloads import gemm_tuning, sd_transformer
     from sige_amd.workloads.sd_unet import SDConfig, SDUNet
@@ -50,19 +60,32 @@ def main():
     ts = torch.full((2,), 500.0, device=dev)
     run = lambda x: model(x, ts, context=ctx)  # noqa: E731
     res = {"workload": "bench.py --workload sd (SD v1 U-Net, latent [2,4,64,64]), hipGraph replay", "tunableop_table": tuned, "masks": {}}
-    keep = sd_transformer.TOKEN_LINEAR
+    keep = sd_transformer.TOKEN_LINEAR, sd_transformer.TOKEN_LINEAR_COMPUTE
+    sd_transformer.TOKEN_LINEAR_COMPUTE = args.compute
+    res["compute"] = args.compute
     try:
         with torch.no_grad():
             for name in args.masks.split(","):
-                model.set_mode("full")  # (the caches of the original image, fresh for every mask)
-                run(x0)
                 r0, r1, c0, c1 = MASKS[name]
                 mask512 = torch.zeros(512, 512, dtype=torch.bool, device=dev)
                 mask512[r0:r1, c0:c1] = True
                 masks = downsample_mask(mask512, min_res=8, dilation=1)
                 x1 = cl(x0 + noise * masks[(64, 64)])
-                model.set_masks(masks)
-                model.set_mode("sparse")
+
+                def prepare():  # (the caches of the original image, fresh for every mask and compute mode)
+                    model.set_mode("full")
+                    run(x0)
+                    model.set_masks(masks)
+                    model.set_mode("sparse")
+
+                fp32_out = None
+                if args.compute == "f16":  # the all-fp32 model's output: what the f16 criterion is taken against
+                    sd_transformer.TOKEN_LINEAR = False
+                    model.set_compute_dtype("f32")
+                    prepare()
+                    fp32_out = run(x1).float().clone()
+                    model.set_compute_dtype("f16")
+                prepare()
                 rows, ref = [], None
                 for st in args.settings.split(","):
                     sd_transformer.TOKEN_LINEAR = bool(int(st))
@@ -77,14 +100,20 @@ def main():
                         ref = o
                     rows.append({"mask": name, "token_linear": bool(int(st)), "forward_ms": round(ms, 3), "library_launches": launches,
                                  "max_abs_vs_first_setting": round(float((o - ref).abs().max()), 8)})
+                    if fp32_out is not None:
+                        rows[-1]["f16_check_vs_fp32_model"] = f16_check(o, fp32_out)
                     print(json.dumps(rows[-1]), flush=True)
                 res["masks"][name] = {"box": MASKS[name], "edit_ratio": round(float(mask512.float().mean()), 4), "rows": rows}
     finally:
-        sd_transformer.TOKEN_LINEAR = keep
+        sd_transformer.TOKEN_LINEAR, sd_transformer.TOKEN_LINEAR_COMPUTE = keep
         if tuned:
             gemm_tuning.disable_tuned_gemms()
     if args.out:
         os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        if args.compute == "f16":
+            both = json.load(open(args.out)) if os.path.isfile(args.out) else {}
+            both.setdefault("sessions", {})["tunableop_on" if tuned else "tunableop_off"] = res
+            res = both
         json.dump(res, open(args.out, "w"), indent=1)
 
 

@@ -14,8 +14,12 @@ smaller of two timings), the GEMM
 side once on the libraries' default solutions and once with the shipped TunableOp table on (sige_amd/workloads/gemm_tuning.py).
 `--forms`: also both row-block forms of the token linear (measurement build, SIGE_HIP_TUNE_TOKEN_LINEAR_FORM), not only the one the
 library picks.  Two masks: the benchmarked one and one whose token counts the TunableOp table does not hold.
+`--compute f16`: the library columns are the token linear on fp16 operands (csrc/token_linear_f16.hip), the exact-fp32 form of the same
+run is the column `f32_library_us`, and `max_abs_vs_fp64` is max |out - fp64| of the launch's outputs (the formula evaluated in fp64 on
+the same inputs).
 
     python tools/token_linear_bench.py --out out/token_linear_bench.json
+    python tools/token_linear_bench.py --compute f16 --forms --out profiles/token_linear_f16_bench.json
 """
 import argparse
 import collections
@@ -83,7 +87,7 @@ def block_shapes(mask_box, dev):
     return shapes
 
 
-def rows_of(M, C, dev, hip, forms, reps):
+def rows_of(M, C, dev, hip, forms, reps, compute="f32"):
     """The six launches of one block at (M, C): library us, GEMM-library us on the default and on the tuned solutions."""
     from sige_amd.workloads import gemm_tuning
 
@@ -95,33 +99,51 @@ def rows_of(M, C, dev, hip, forms, reps):
     wq, wk, wv, wo, w0, w2 = w(C, C), w(C, C), w(C, C), w(C, C), w(8 * C, C), w(C, 4 * C)
     bo, b0, b2 = rn(C), rn(8 * C), rn(C)
     qkv_w = torch.stack([t.t() for t in (wq, wk, wv)]).contiguous()
-    p_qkv, p_o, p_q = hip.token_linear_pack([wq, wk, wv]), hip.token_linear_pack(wo), hip.token_linear_pack(wq)
-    p_0, p_2 = hip.token_linear_pack(w0, geglu=True), hip.token_linear_pack(w2)
+    packs = {c: (hip.token_linear_pack([wq, wk, wv], compute=c), hip.token_linear_pack(wo, compute=c), hip.token_linear_pack(wq, compute=c),
+                 hip.token_linear_pack(w0, geglu=True, compute=c), hip.token_linear_pack(w2, compute=c)) for c in {"f32", compute}}
+    f64 = lambda t: t.double()  # noqa: E731
+    ln64 = lambda t: F.layer_norm(f64(t), (C,), f64(norm.weight), f64(norm.bias), norm.eps)  # noqa: E731
+
+    def geglu64(t):
+        v, gate = t.chunk(2, dim=-1)
+        return v * F.gelu(gate)
+
+    # (name, N, K, form, launches per block, the library launch for a compute, what it replaces, the same formula in fp64)
     spec = [
         ("qkv", 3 * C, C, "ln+parts3", 1,
-         lambda: hip.token_linear(x, p_qkv, 3 * C, norm=norm, parts=3),
-         lambda: torch.matmul(hip.add_layer_norm_tokens(x, None, None, norm)[1].reshape(1, M, C), qkv_w)),
+         lambda c: hip.token_linear(x, packs[c][0], 3 * C, norm=norm, parts=3, compute=c),
+         lambda: torch.matmul(hip.add_layer_norm_tokens(x, None, None, norm)[1].reshape(1, M, C), qkv_w),
+         lambda: ln64(x) @ f64(torch.cat([wq, wk, wv])).t()),
         ("to_out", C, C, "bias+residual", 2,
-         lambda: hip.token_linear(o, p_o, C, bias=bo, residual=x),
-         lambda: F.linear(o, wo)),
+         lambda c: hip.token_linear(o, packs[c][1], C, bias=bo, residual=x, compute=c),
+         lambda: F.linear(o, wo),
+         lambda: f64(x) + F.linear(f64(o), f64(wo), f64(bo))),
         ("attn2.q", C, C, "ln", 1,
-         lambda: hip.token_linear(x, p_q, C, norm=norm),
-         lambda: F.linear(hip.add_layer_norm_tokens(x, d, bo, norm)[1], wq)),
+         lambda c: hip.token_linear(x, packs[c][2], C, norm=norm, compute=c),
+         lambda: F.linear(hip.add_layer_norm_tokens(x, d, bo, norm)[1], wq),
+         lambda: ln64(x) @ f64(wq).t()),
         ("ff.proj", 8 * C, C, "ln+geglu", 1,
-         lambda: hip.token_linear(x, p_0, 8 * C, bias=b0, norm=norm, geglu=True),
-         lambda: hip.geglu_tokens(F.linear(hip.add_layer_norm_tokens(x, d, bo, norm)[1], w0, b0))),
+         lambda c: hip.token_linear(x, packs[c][3], 8 * C, bias=b0, norm=norm, geglu=True, compute=c),
+         lambda: hip.geglu_tokens(F.linear(hip.add_layer_norm_tokens(x, d, bo, norm)[1], w0, b0)),
+         lambda: geglu64(F.linear(ln64(x), f64(w0), f64(b0)))),
         ("ff.out", C, 4 * C, "bias+residual", 1,
-         lambda: hip.token_linear(h, p_2, C, bias=b2, residual=x),
-         lambda: hip.add_bias_tokens(x, F.linear(h, w2), b2)),
+         lambda c: hip.token_linear(h, packs[c][4], C, bias=b2, residual=x, compute=c),
+         lambda: hip.add_bias_tokens(x, F.linear(h, w2), b2),
+         lambda: f64(x) + F.linear(f64(h), f64(w2), f64(b2))),
     ]
     out = []
     # (every figure the smaller of two timings: the first graph after host-side set-up runs while the clock still ramps)
     timed = lambda fn: min(time_graph_of(fn, reps) for _ in range(2))  # noqa: E731
     with torch.no_grad():
-        for name, N, K, form, per_block, lib_fn, base_fn in spec:
-            assert lib_fn() is not None, (name, M, N, K)
-            row = {"launch": name, "M": M, "N": N, "K": K, "form": form, "per_block": per_block, "gflop": 2e-9 * M * N * K}
+        for name, N, K, form, per_block, lib_c, base_fn, ref_fn in spec:
+            lib_fn = lambda lib_c=lib_c: lib_c(compute)  # noqa: E731
+            got = lib_fn()
+            assert got is not None, (name, M, N, K)
+            row = {"launch": name, "M": M, "N": N, "K": K, "form": form, "per_block": per_block, "gflop": 2e-9 * M * N * K, "compute": compute}
+            row["max_abs_vs_fp64"] = float((torch.cat(got, dim=-1) if isinstance(got, tuple) else got).double().sub(ref_fn()).abs().max())
             row["library_us"] = timed(lib_fn)
+            if compute != "f32":
+                row["f32_library_us"] = timed(lambda: lib_c("f32"))
             if forms:
                 for key, knob in (("library_16tok_us", 1), ("library_64tok_us", 2)):
                     with hip.tuning_build():
@@ -136,7 +158,7 @@ def rows_of(M, C, dev, hip, forms, reps):
                     gemm_tuning.disable_tuned_gemms()
             row["library_tflops"] = row["gflop"] * 1e-3 / (row["library_us"] * 1e-6)
             row["library_frac_of_f32_mfma_peak"] = row["library_tflops"] / PEAK_F32_MFMA_TFS
-            out.append({k: (round(v, 4) if isinstance(v, float) else v) for k, v in row.items()})
+            out.append({k: (float("%.4g" % v) if isinstance(v, float) else v) for k, v in row.items()})
             print(json.dumps(out[-1]), flush=True)
     return out
 
@@ -146,6 +168,7 @@ def main():
     ap.add_argument("--masks", default="bench,other")
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--forms", action="store_true", help="also time both row-block forms (needs the measurement build)")
+    ap.add_argument("--compute", default="f32", choices=("f32", "f16"), help="the operands of the library columns")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     from sige_amd import hip
@@ -155,13 +178,13 @@ def main():
     in_table = table_token_counts()
     shapes = block_shapes({m: MASKS[m] for m in args.masks.split(",")}, dev)
     res = {"workload": "bench.py --workload sd (SD v1 U-Net, latent [2,4,64,64]); us per call from a hipGraph of %d back-to-back calls" % args.reps,
-           "f32_mfma_peak_tflops": PEAK_F32_MFMA_TFS, "masks": {}}
+           "f32_mfma_peak_tflops": PEAK_F32_MFMA_TFS, "library_compute": args.compute, "masks": {}}
     done = {}
     for mask, sh in shapes.items():
         entry = {"box": MASKS[mask], "levels": []}
         for (M, C, on_path), blocks in sorted(sh.items(), key=lambda kv: -kv[0][0]):
             if (M, C) not in done:
-                done[(M, C)] = rows_of(M, C, dev, hip, args.forms, args.reps)
+                done[(M, C)] = rows_of(M, C, dev, hip, args.forms, args.reps, args.compute)
             rows = done[(M, C)]
             tot = lambda key: (None if any(r[key] is None for r in rows) else round(sum(r[key] * r["per_block"] for r in rows), 2))  # noqa: E731
             entry["levels"].append({"M": M, "C": C, "blocks_per_forward": blocks, "on_switch_path": on_path, "M_in_tunableop_table": M in in_table,
