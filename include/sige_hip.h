@@ -666,6 +666,37 @@ int sige_hip_upsample_phase_tile3_nhwc(
         float *twin1, const float *twin1_scale, const float *twin1_shift,
         int min_blocks, float *out, void *stream);
 
+/* ---- the 3x3 / stride-2 Downsample conv ON THE TILE CONV V3, fp16 operands (csrc/conv_tile3.hpp: Tile3GeoS2): what
+ * sige_hip_gather_conv_nhwc computes for 5x5 windows, kernel 3x3, stride 2 and a full destination, with the operands rounded to fp16.
+ * A workgroup is 8 tiles x 64 output channels; the grid is ceil(B N / 8) * (Cout / 64).
+ *   n = sige_hip_down_tile3_packed_size(Cout, Cin)      floats (0: no such kernel for these channels)
+ *   sige_hip_down_tile3_pack(w, Cout, Cin, packed)      w [Cout,Cin,3,3] fp32 -> the v3 fp16 stream
+ *       [ntile][wave][chunk][tap = 3 kh + kw][nt][lane = (kq, j)][e], channel 64 chunk + 16 wave + 8 kq + e, output channel
+ *       64 ntile + 32 nt + j, rounded to fp16 (RNE, saturated), followed by the stream's padding of zero steps
+ * sige_hip_down_tile3_nhwc: x [B,H,W,C] raw (no affine, one tensor); the 5x5 window of a tile starts AT its origin (zero fill outside
+ * the image is the conv's padding: origins 4i with padding (0,1,0,1), 4i - 1 with padding 1); its 2x2 outputs go straight into
+ * out [B,Ho,Wo,Cout] at ((offset + origin) / 2 + (y, x)), clipped, with bias, fp32 `residual`, out-affine and both twins as
+ * sige_hip_upsample_phase_tile3_nhwc; cells outside the list are untouched.  Activations are rounded to fp16 (RNE, saturated) in the
+ * staging path, accumulation is fp32, tensors are fp32 in memory.  Stacked edits: a tile reads the rows of its own image.
+ * The call runs when its grid has at least `min_blocks` > 0 workgroups.  SIGE_HIP_EUNSUPPORTED -- nothing touched, never a wrong
+ * answer -- for a smaller grid, min_blocks <= 0, compute other than 1, C or Cout not a multiple of 64, tensors beyond 32-bit byte
+ * offsets, a pointer off 16 bytes, a stacked height that does not stack, a call sige_hip_conv_side_begin waits for, and while a launch
+ * plan records (no plan hook).  A shortcut held by sige_hip_conv_pair_begin is launched first; queued side convs are flushed on a
+ * hazard.  N = 0 or B = 0: SIGE_HIP_OK, no launch.
+ * PRECONDITION the library cannot check (the index list lives on the device): offset + origin is EVEN in both coordinates for every
+ * tile -- the lists of a stride-2 conv, origins 4i - offset -- so that a tile's 2x2 output block starts at a whole output pixel;
+ * (offset + origin) / 2 truncates, as in sige_hip_gather_conv_nhwc. */
+int sige_hip_down_tile3_supported(int C, int Cout);
+size_t sige_hip_down_tile3_packed_size(int Cout, int Cin);
+int sige_hip_down_tile3_pack(const float *w, int Cout, int Cin, float *packed, void *stream);
+int sige_hip_down_tile3_nhwc(
+        int compute, const float *x, int B, int C, int H, int W, const int32_t *active_indices, int N,
+        const float *packed_down3, const float *bias, int Cout, int offsetH, int offsetW, const float *residual, int Ho, int Wo,
+        const float *out_scale, const float *out_shift, int out_activation,
+        float *twin0, const float *twin0_scale, const float *twin0_shift,
+        float *twin1, const float *twin1_scale, const float *twin1_shift,
+        int min_blocks, float *out, void *stream);
+
 /* ---- token-matrix helpers of Stable Diffusion's spatial transformer (csrc/token_ops.hip; sige_attention.py:86-185): tokens [T,C]
  * row-major fp32.  add_layer_norm: y = x (+ delta + bias[c] when delta != NULL; bias may be NULL); sum_out = y when not NULL;
  * out = LayerNorm(y) * gamma + beta (eps as nn.LayerNorm's).  geglu: out[t,d] = x[t,d] * gelu(x[t,D+d]), x [T,2D] (F.gelu's erf

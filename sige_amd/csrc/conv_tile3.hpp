@@ -127,6 +127,38 @@ struct Tile3GeoP {
     static constexpr long sub_bytes(int ntn, int nchunks) { return (long)ntn * 4 * nchunks * STEPS * STEPB + (long)kWidePadSteps * STEPB; }
 };
 
+// The same kernel over the 5x5 windows of a 3x3 / STRIDE-2 conv (the models' Downsample), fp16 operands only: a tile's
+// output is 2x2, pixel (y, x) at ((offH + h0) / 2 + y, (offW + w0) / 2 + x) of the full destination, and tap (kh, kw) of it reads staged
+// pixel (2y + kh) * 5 + (2x + kw) -- the stride enters the staging coordinates only.  A 32-pixel M tile is 8 tiles x 4 pixels, as in
+// the phase form.  TPW = 8: 200 staged pixels x 4 float4 units = 13 staging slots per lane (the last one half padding), stage rows
+// of 48 B: 4 waves x 2 stages x 9 984 B = 79 872 B of LDS -> two workgroups per CU, which leaves a lane 256 registers: the 52 of the
+// slots' loads in flight fit beside 32 accumulators and the three-step ring without scratch (the shared-stage kernels of conv_mfma.hpp
+// hold the same 13 slots against a 128-register budget).  Zero fill outside the image (or the tile's own image, stacked) IS the conv's
+// padding.  A raw gather of one tensor into a full tensor is the only form.
+template <int TPW_, int PREC_ = WIDE_F16>
+struct Tile3GeoS2 {
+    static constexpr int TPW = TPW_, PREC = PREC_;
+    static constexpr bool F32 = false;
+    static_assert(PREC_ == WIDE_F16, "stride-2 tile conv v3: fp16 operands only (an fp32 stage of this geometry is 128 KB)");
+    static_assert(TPW_ % 8 == 0, "a 32-pixel M tile is 8 tiles x 4 pixels");
+    static constexpr int KK = 9;
+    static constexpr bool PHASE = false;
+    static constexpr int EDGE = 5, OSH = 1, OE = 2, WPX = 25, OPX = 4, MT_STRIDE = 200;
+    static constexpr int MTN = TPW_ / 8, BM = 4 * TPW_;
+    static constexpr int NP = 1, CW = 16, CC = 64, STEPS = 9;
+    // (the stage is padded to whole slots -- 208 rows for the 200 pixels of 8 windows -- so that the last slot stores like the others:
+    //  a lane-guarded store draws its load into the guarded block, a dependent round trip per chunk; the pad rows hold zeros, unread)
+    static constexpr int QP = CW / 4, NPX = (WPX * TPW_ + 64 / QP - 1) / (64 / QP) * (64 / QP), UNITS = NPX * QP, NS = UNITS / 64;
+    static constexpr int KSB = 32, KQB = 16, PLB = 32, ROWB = KSB + 16, ABUF = NPX * ROWB, STEPB = 2048;
+    static constexpr int RB = 3, OCC = 2;
+    static constexpr int LDS_BYTES = cmax(4 * 2 * ABUF, 4 * BM * 68 * 4);
+    static_assert((2 * STEPS) % RB == 0, "the ring position of a step must not depend on the chunk");
+    static_assert(RB <= kWidePadSteps, "the read-ahead stays inside the pack's padding");
+    static_assert(TPW_ != 8 || (NS == 13 && LDS_BYTES == 79872), "8 windows of 5x5: 13 staging slots, two workgroups per CU by LDS");
+};
+template <typename G> struct tile3_is_s2 : std::false_type {};
+template <int TPW_, int PREC_> struct tile3_is_s2<Tile3GeoS2<TPW_, PREC_>> : std::true_type {};
+
 struct Tile3Args {
     const float *x, *x2;        // GATHER: [B,Hs,Ws,C1] (+ [B,Hs,Ws,C2]: channels of x2 follow x) | SCATTER_GATHER: conv tiles [B*N,Rx,Sx,Cin], cached y [B,H,W,Cin]
     const int32_t *idx;         // [N,2] tile origins
@@ -156,6 +188,8 @@ __device__ __forceinline__ void conv_tile3_body(const Tile3Args &a, const int bx
     constexpr bool SG = SRC == T3_SCATTER_GATHER;
     constexpr bool F32 = G::F32;
     constexpr bool PH = G::PHASE;
+    constexpr bool S2 = tile3_is_s2<G>::value;
+    static_assert(!S2 || (SRC == T3_GATHER && !AFF && !CAT && FULL), "stride-2 convs: a raw gather of one tensor into a full tensor");
     static_assert(!Y16 || SG, "fp16-stored cache: the scatter_gather source");
     static_assert(!PH || (SRC == T3_GATHER && !AFF && !CAT && FULL), "phase convs: a raw gather of one tensor into a full tensor");
     const int ph_a = ph >> 1, ph_b = ph & 1;
@@ -173,11 +207,47 @@ __device__ __forceinline__ void conv_tile3_body(const Tile3Args &a, const int bx
     unsigned livemask = 0;
     int z_h[NS], z_w[NS], z_b[NS];
     bool z_ok[NS];
+    // stride 2: the workgroup's TPW tile origins, images and row ranges are the same for every lane -- fetched ONCE, as uniform values,
+    // before any slot is looked at (13 slots that each fetched their own origin would be 13 dependent round trips in front of the
+    // first activation load); a slot's 16 staged pixels lie in at most two tiles, known at compile time, so a slot selects
+    constexpr int NT = S2 ? G::TPW : 1;
+    int t_x[NT], t_y[NT], t_b[NT], t_lo[NT], t_hi[NT], t_ok[NT];
+    if constexpr (S2) {
+        int2 o[NT];
+        int tb[NT];
+        static_for<0, NT>([&](auto k_tag) {
+            constexpr int k = decltype(k_tag)::value;
+            const int t = mtile * G::TPW + k;
+            const int tt = min(t, a.T - 1);
+            tb[k] = tt / a.N;
+            o[k] = *reinterpret_cast<const int2 *>(a.idx + 2 * (tt - tb[k] * a.N));
+            t_ok[k] = t < a.T ? 1 : 0;
+        });
+        const int sh = a.hp_shift;  // (stacked edits: rows beyond the tile's own image are padding; its window's third row is inside it)
+        static_for<0, NT>([&](auto k_tag) {
+            constexpr int k = decltype(k_tag)::value;
+            t_x[k] = o[k].x; t_y[k] = o[k].y; t_b[k] = tb[k];
+            t_lo[k] = sh ? ((o[k].x + 2) >> sh) << sh : 0;
+            t_hi[k] = sh ? t_lo[k] + (1 << sh) : a.H;
+        });
+    }
     static_for<0, NS>([&](auto i_tag) {  // (1) tile origins: all loads issued before the first one is used
         constexpr int i = decltype(i_tag)::value;
         const int v = lane + 64 * i;
         const int p = v / G::QP;
         const int tl = p / G::WPX, q = p - tl * G::WPX;
+        if constexpr (S2) {
+            constexpr int PPS = 64 / G::QP;  // staged pixels per slot
+            constexpr int k0 = (PPS * i) / G::WPX, k1 = (PPS * i + PPS - 1) / G::WPX < NT ? (PPS * i + PPS - 1) / G::WPX : NT - 1;
+            const bool up = tl != k0;
+            z_b[i] = up ? t_b[k1] : t_b[k0];
+            z_h[i] = (up ? t_x[k1] : t_x[k0]) + q / G::EDGE;
+            z_w[i] = (up ? t_y[k1] : t_y[k0]) + q % G::EDGE;
+            const int hlo = up ? t_lo[k1] : t_lo[k0], hhi = up ? t_hi[k1] : t_hi[k0], live = up ? t_ok[k1] : t_ok[k0];
+            z_ok[i] = (int)(p < G::WPX * G::TPW) & live & (int)(z_h[i] >= hlo) & (int)(z_h[i] < hhi) & (int)(z_w[i] >= 0) & (int)(z_w[i] < a.W);
+            ldsw[i] = p * G::ROWB + (v % G::QP) * 8;
+            return;
+        }
         const int t = mtile * G::TPW + tl;
         z_ok[i] = v < G::UNITS && t < a.T;
         const int tt = min(t, a.T - 1);
@@ -327,7 +397,9 @@ __device__ __forceinline__ void conv_tile3_body(const Tile3Args &a, const int bx
     const int i32 = lane & 31, kq = lane >> 5;
     // (10x10 windows: pixel i32 of M tile mt = output row 4 mt + (i32 >> 3), column i32 & 7 of the workgroup's window)
     // (phase convs: pixel i32 = tile i32 >> 2 of the M tile's eight, output (y, x) = ((i32 >> 1) & 1, i32 & 1) of its 2x2 block)
-    const int abase = (PH ? (i32 >> 2) * 9 + ((i32 >> 1) & 1) * 3 + (i32 & 1)
+    // (stride 2: the same eight tiles x 2x2 outputs, output (y, x) two staged pixels apart in its 5x5 window)
+    const int abase = (S2 ? (i32 >> 2) * 25 + ((i32 >> 1) & 1) * 10 + (i32 & 1) * 2
+                       : PH ? (i32 >> 2) * 9 + ((i32 >> 1) & 1) * 3 + (i32 & 1)
                           : G::EDGE == 6 ? (i32 >> 4) * 36 + ((i32 & 15) >> 2) * 6 + (i32 & 3) : (i32 >> 3) * G::EDGE + (i32 & 7)) * G::ROWB +
                       kq * G::KQB;  // + mt * MT_STRIDE * ROWB
     struct AHalf { f16x8 v[MTN]; };
@@ -467,16 +539,32 @@ __device__ __forceinline__ void conv_tile3_body(const Tile3Args &a, const int bx
         }
         size_t addr;
         if constexpr (FULL) {
-            const int b = t / a.N, n = t - b * a.N;
-            const int2 og = *reinterpret_cast<const int2 *>(a.idx + 2 * n);
+            int b;
+            int2 og;
+            if constexpr (S2) {  // (the prologue's uniform copies: no second fetch, no division)
+                b = t_b[0]; og = make_int2(t_x[0], t_y[0]);
+                static_for<1, NT>([&](auto k_tag) {
+                    constexpr int kk = decltype(k_tag)::value;
+                    b = tl == kk ? t_b[kk] : b; og.x = tl == kk ? t_x[kk] : og.x; og.y = tl == kk ? t_y[kk] : og.y;
+                });
+            } else {
+                b = t / a.N;
+                og = *reinterpret_cast<const int2 *>(a.idx + 2 * (t - b * a.N));
+            }
             constexpr int PS = PH ? 2 : 1;  // (phase convs: the 2x2 block's pixels are two hi-res pixels apart, from (a, b))
-            const int h = a.offH + og.x + PS * (pix >> G::OSH) + ph_a, w = a.offW + og.y + PS * (pix & (G::OE - 1)) + ph_b;
+            int h = a.offH + og.x + PS * (pix >> G::OSH) + ph_a, w = a.offW + og.y + PS * (pix & (G::OE - 1)) + ph_b;
+            if constexpr (S2) {  // (the destination is the half-resolution tensor)
+                h = (a.offH + og.x) / 2 + (pix >> 1);
+                w = (a.offW + og.y) / 2 + (pix & 1);
+            }
             if (h < 0 || h >= a.Ho || w < 0 || w >= a.Wo) continue;
             addr = (((size_t)b * a.Ho + h) * a.Wo + w) * a.Cout + co;
             if (a.residual) {  // out = conv + residual; with a block residual: + (x1 - residual) where a shortcut tile covers the pixel
-                const float4 rr = ld_f32x4_or_h4(a.residual, addr, a.res_f16 != 0);
+                float4 rr;
+                if constexpr (S2) rr = *reinterpret_cast<const float4 *>(a.residual + addr);  // (fp32 residuals only, no block residual)
+                else rr = ld_f32x4_or_h4(a.residual, addr, a.res_f16 != 0);
                 s.x += rr.x; s.y += rr.y; s.z += rr.z; s.w += rr.w;
-                if (a.x1) {
+                if (!S2 && a.x1) {
                     const int t1 = a.table1[(h / a.R1) * a.gW1 + w / a.S1];
                     if (t1 >= 0) {
                         const float4 xv = *reinterpret_cast<const float4 *>(a.x1 + ((((size_t)b * a.N1 + t1) * a.R1 + h % a.R1) * a.S1 + w % a.S1) * a.Cout + co);

@@ -115,6 +115,12 @@ _SIGNATURES = {
     "sige_hip_upsample_phase_tile3_nhwc": (
         _c_int, [_c_int, _c_vp] + [_c_int] * 4 + [_c_vp, _c_int, _c_vp, _c_vp] + [_c_int] * 3 + [_c_vp, _c_int, _c_int]
         + [_c_vp, _c_vp, _c_int] + [_c_vp] * 6 + [_c_int, _c_vp, _c_vp]),
+    "sige_hip_down_tile3_supported": (_c_int, [_c_int] * 2),
+    "sige_hip_down_tile3_packed_size": (_c_sz, [_c_int] * 2),
+    "sige_hip_down_tile3_pack": (_c_int, [_c_vp] + [_c_int] * 2 + [_c_vp, _c_vp]),
+    "sige_hip_down_tile3_nhwc": (
+        _c_int, [_c_int, _c_vp] + [_c_int] * 4 + [_c_vp, _c_int, _c_vp, _c_vp] + [_c_int] * 3 + [_c_vp, _c_int, _c_int]
+        + [_c_vp, _c_vp, _c_int] + [_c_vp] * 6 + [_c_int, _c_vp, _c_vp]),
     "sige_hip_conv_ksplit_hint": (_c_int, [_c_int] * 7),
     "sige_hip_gather_nhwc_f32": (
         _c_int, [_c_vp] + [_c_int] * 6 + [_c_vp, _c_int] + [_c_vp, _c_int, _c_int] * 2 + [_c_int, _c_vp, _c_vp]),
@@ -1071,6 +1077,36 @@ def upsample_phase_tile3_pack(weight: torch.Tensor, compute: str = "f32", kernel
     return packed
 
 
+# The stride-2 Downsample conv on the tile conv v3, fp16 operands (csrc/conv_tile3.hpp: Tile3GeoS2), behind
+# Gather.DOWNSAMPLE_TILE3 (off): sige_hip_down_tile3_nhwc runs a call whose grid -- ceil(tiles / 8) x (Cout / 64) -- has at least
+# this many workgroups and refuses smaller ones, which then take today's route (the exact-fp32 launch of conv_mfma.hpp).  Read off
+# the launch-alone table of profiles/down_tile3_bench.json (SD VAE encoder and SD U-Net shapes, 1.2 / 5 / 15 % and E = 8 stacked, the
+# two launches alternating in one process, weights L2-warm; the VAE shapes also with lists cut to 40 / 48 / 56 / 64 workgroups): the new
+# launch wins beyond the run-to-run range at every measured grid from 48 workgroups on (1.3 - 2.8 x); below, it wins or ties everywhere
+# but at 1280 channels from 16^2, where 4 and 9 tiles (20 and 40 workgroups) leave the 32-pixel M tile an eighth full: 1.11 and 1.44 x
+# slower -- so 40 is the largest grid with a measured loss.  Whole forwards: DESIGN.md 5.31.
+DOWN_TILE3_MIN_BLOCKS_F16 = 48
+
+
+def down_tile3_pack(weight: torch.Tensor, out: Optional[torch.Tensor] = None) -> Optional[torch.Tensor]:
+    """The `packed_down3` operand of sige_hip_down_tile3_nhwc for a [Cout,Cin,3,3] weight: the tile conv v3's fp16 stream (rounded
+    RNE, saturated).  None where the channel counts have no such kernel; `out`: an earlier pack of the same shape, rewritten in
+    place."""
+    if weight.dim() != 4 or tuple(weight.shape[2:]) != (3, 3):
+        raise ValueError("down_tile3_pack: a [Cout,Cin,3,3] weight")
+    w = _req(weight.detach(), torch.float32, "weight")
+    Cout, Cin = w.shape[:2]
+    n = int(lib().sige_hip_down_tile3_packed_size(Cout, Cin))
+    if n == 0:
+        return None
+    if out is not None and (out.numel() != n or out.device != w.device or getattr(out, "compute", None) != "f16"):
+        raise ValueError("down_tile3_pack: `out` is not a pack of this shape")
+    packed = torch.empty((n,), dtype=torch.float32, device=w.device).as_subclass(PackedWeights) if out is None else out
+    packed.compute = "f16"
+    _check(lib().sige_hip_down_tile3_pack(w.data_ptr(), Cout, Cin, packed.data_ptr(), _stream(w)), "down_tile3_pack")
+    return packed
+
+
 # ---- dense layers on the fp16 matrix cores (csrc/conv_wide.hpp) ----
 COMPUTE_DTYPES = ("f32", "f16", "f16x3")
 
@@ -1868,7 +1904,7 @@ def tile_conv3_cl(source: int, x, x2, B, C1, C2, H, W, up, idx, smap, rx_sx, sca
 def gather_conv_cl(x, x2, block: Tuple[int, int], activeIndices, scale, shift, activationName: str,
                    packed, bias, Cout: int, kernel: Tuple[int, int], stride: Tuple[int, int],
                    full: Optional[dict] = None, out_affine: Optional[tuple] = None, upsample2x: bool = False,
-                   out: Optional[torch.Tensor] = None, twins=None, phase=None, phase3=None):
+                   out: Optional[torch.Tensor] = None, twins=None, phase=None, phase3=None, down3=None):
     """Channels-last gather -> conv.  `full` = dict(offset=(oh, ow), out_res=(Ho, Wo), residual=tensor|None)
     writes the output tiles straight into a [B,Cout,Ho,Wo] tensor (dense layers).  `twins` (full only): up to two
     (buffer, scale, shift): buffer = SiLU(scale * result + shift), the activated input of a consumer's conv1, written by
@@ -1879,6 +1915,9 @@ def gather_conv_cl(x, x2, block: Tuple[int, int], activeIndices, scale, shift, a
     goes on exactly as without it.  The threshold: PHASE_TILE3_MIN_BLOCKS for an exact-fp32 call; for compute "f16" the SMALLER of
     PHASE_TILE3_MIN_BLOCKS and PHASE_TILE3_MIN_BLOCKS_F16 -- fp16 operands win from smaller grids on, and lowering
     PHASE_TILE3_MIN_BLOCKS (tests and tools set it to 1) lowers both; to RAISE the f16 threshold raise both values.
+    `down3` (3x3 / stride 2 on 5x5 windows with `full`, no x2, no gather affine): the conv's down_tile3_pack -- the call is tried
+    first on sige_hip_down_tile3_nhwc, ON FP16 OPERANDS whatever `packed` holds (in f16 mode this geometry's `packed` is the exact-fp32
+    layout), with the threshold DOWN_TILE3_MIN_BLOCKS_F16; a refused call goes on exactly as without it.
     None if unsupported."""
     geo, usable = _geometry_of(block, kernel, stride, packed)
     if not usable:
@@ -1934,6 +1973,19 @@ def gather_conv_cl(x, x2, block: Tuple[int, int], activeIndices, scale, shift, a
             keep = getattr(_pair_state, "keep", None)
             if keep is not None:  # (conv_pair(): a launch held before this call was flushed by it; its operands stay alive as ever)
                 keep.append((x, idx, phase3, bias_keep, out, out_affine, full, twin_keep))
+            return out
+    if (down3 is not None and not upsample2x and full is not None and x2 is None and scale is None and shift is None
+            and activationName == "identity" and geo is None and getattr(down3, "compute", None) == "f16"
+            and (tuple(block), tuple(kernel), tuple(stride)) == ((5, 5), (3, 3), (2, 2))):
+        oargs3, o_keep3 = _out_affine_args(out_affine, Cout, "gather_conv_cl")
+        status = lib().sige_hip_down_tile3_nhwc(
+            1, x.data_ptr(), B, C1, H, W, idx.data_ptr(), N, down3.data_ptr(), _p(bias_keep), Cout, full["offset"][0], full["offset"][1],
+            None if r is None else r.data_ptr(), Ho, Wo, *oargs3, *targs, int(DOWN_TILE3_MIN_BLOCKS_F16), out.data_ptr(), _stream(x))
+        if status != UNSUPPORTED:
+            _check(status, "gather_conv_cl")
+            keep = getattr(_pair_state, "keep", None)
+            if keep is not None:  # (conv_pair(): a launch held before this call was flushed by it; its operands stay alive as ever)
+                keep.append((x, idx, down3, bias_keep, out, out_affine, full, twin_keep))
             return out
     t3 = _tile3_route(packed, B * N, C1, C2, Cout, kernel, stride, block)  # (TILE3 = True: the v3 kernel, forced)
     if getattr(_side_state, "armed", False):

@@ -135,6 +135,7 @@ class SIGEConv2d(nn.Conv2d, SIGEModule):
         self._packed = {}
         self._phase = None  # [key, phase kernels, their pack | None]: see phase_kernels()
         self._phase3 = None  # (key, the phase pack of the tile conv v3 | None): see phase_tile3_packed()
+        self._down3 = None  # (key, the stride-2 pack of the tile conv v3 | None): see down_tile3_packed()
         self._tiles_runtime = self.load_runtime("conv2d_tiles", {})
         # "f32": exact fp32 products (v_mfma_f32_*_f32); "f16": fp16 operands, fp32 accumulation on the 16x faster fp16
         # matrix path (SIGEModel.set_compute_dtype; channels-last tiles only -- BASELINE.json configs[4])
@@ -213,9 +214,26 @@ class SIGEConv2d(nn.Conv2d, SIGEModule):
             self._phase3 = (key, hip.upsample_phase_tile3_pack(self.weight, self.compute_dtype))
         return self._phase3[1]
 
+    def down_tile3_packed(self):
+        """This conv's weight laid out for the stride-2 tile conv v3 on fp16 operands (sige_amd.hip.down_tile3_pack), or
+        None: anything but a 3x3 / stride-2 / groups-1 conv with channels in multiples of 64 on a GPU whose compute dtype is "f16"
+        (the padding may be the model's own: zero fill outside the image is the conv's padding either way).  Derived state like
+        `phase_tile3_packed()`: keyed on the weight and the compute dtype, dropped by `clear_cache()`, rewritten in place by
+        `rebuild_derived_caches()`, never part of the state dict."""
+        if (tuple(self.kernel_size) != (3, 3) or tuple(self.stride) != (2, 2) or self.groups != 1 or tuple(self.dilation) != (1, 1)
+                or self.compute_dtype != "f16" or not self.weight.is_cuda or self.in_channels % 64 or self.out_channels % 64):
+            return None
+        from .. import hip
+
+        key = self._phase_key()
+        if self._down3 is None or self._down3[0] != key:
+            self._down3 = (key, hip.down_tile3_pack(self.weight))
+        return self._down3[1]
+
     def clear_cache(self):
         self._phase = None
         self._phase3 = None
+        self._down3 = None
 
     def rebuild_derived_caches(self):
         """Derive the phase kernels again; their packs are rewritten IN PLACE where their size still fits (a captured graph keeps
@@ -232,6 +250,13 @@ class SIGEConv2d(nn.Conv2d, SIGEModule):
             key = self._phase_key()
             if key[2:] == old3[0][2:]:  # (same shape, device and compute dtype: the same size and layout)
                 self._phase3 = (key, hip.upsample_phase_tile3_pack(self.weight, self.compute_dtype, out=old3[1]))
+        oldd, self._down3 = self._down3, None
+        if oldd is not None and oldd[1] is not None:
+            from .. import hip
+
+            key = self._phase_key()
+            if key[2:] == oldd[0][2:]:
+                self._down3 = (key, hip.down_tile3_pack(self.weight, out=oldd[1]))
 
     def _block_conv(self, x: torch.Tensor, out_affine=None) -> torch.Tensor:
         from .. import hip

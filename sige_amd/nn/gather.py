@@ -27,6 +27,9 @@ class Gather(SIGEModule):
     # The same four phase convs on the tile conv v3: launches whose grid reaches sige_amd.hip.PHASE_TILE3_MIN_BLOCKS
     # -- large edits, stacked edits, the SD VAE decoder -- in exact fp32 and on fp16 operands, any edit batch.  Off: no new code runs.
     PHASE_UPSAMPLE_TILE3 = False
+    # The 3x3 / stride-2 Downsample conv on the tile conv v3, fp16 operands: convs whose compute policy is "f16", on
+    # launches whose grid reaches sige_amd.hip.DOWN_TILE3_MIN_BLOCKS_F16; every other call, and off, is today's exact-fp32 launch.
+    DOWNSAMPLE_TILE3 = False
 
     def __init__(
         self,
@@ -142,7 +145,8 @@ class Gather(SIGEModule):
                     (x.shape[0] * idx.shape[0], channels, bh, bw), x.dtype, x.device, run,
                     dict(kind="gather", x=x, x2=x2, block=(bh, bw), idx=idx, scale=scale, shift=shift, act=act, cl=cl,
                          up=upsample2x, phase=bool(upsample2x and self.PHASE_UPSAMPLE),
-                         phase3=bool(upsample2x and self.PHASE_UPSAMPLE_TILE3)))
+                         phase3=bool(upsample2x and self.PHASE_UPSAMPLE_TILE3),
+                         down3=bool(self.DOWNSAMPLE_TILE3 and not upsample2x and tuple(self.model_stride) == (2, 2))))
             return run()
         if self.mode == "full":
             self.note_full_input(x.shape[2:])

@@ -297,6 +297,10 @@ def _fused_conv_into(conv, tiles, out, g: Gather, residual=None, x1=None, table1
                 and spec["x"].is_cuda and getattr(packed, "compute", "f32") == conv.compute_dtype):
             # (Gather.PHASE_UPSAMPLE_TILE3: the keyword exists only on this path, so that off is today's call, argument for argument)
             more["phase3"] = conv.phase_tile3_packed()  # (None: no such kernel for this conv)
+        if (spec.get("down3") and spec.get("x2") is None and spec["scale"] is None and spec["shift"] is None and spec["act"] == "identity"
+                and spec["x"].is_cuda and conv.compute_dtype == "f16" and tuple(conv.stride) == (2, 2)):
+            # (Gather.DOWNSAMPLE_TILE3: as above, the keyword exists only on this path; "f16x3" levels stay where they are)
+            more["down3"] = conv.down_tile3_packed()  # (None: no such kernel for this conv)
         return hip.gather_conv_cl(spec["x"], spec.get("x2"), spec["block"], spec["idx"], spec["scale"], spec["shift"], spec["act"],
                                   packed, conv.bias, conv.out_channels, conv.kernel_size, conv.stride,
                                   full=dict(offset=g.offset, out_res=tuple(out.shape[2:]), residual=residual),

@@ -23,7 +23,9 @@ from sige_amd import build  # noqa: E402
 
 def asm_of(src, tmp):
     out = os.path.join(tmp, os.path.basename(src) + ".s")
-    cmd = [build._hipcc(), "--offload-arch=gfx950", "-O3", "-std=c++17", "-I" + os.path.join(REPO, "include"),
+    # (a unit build.py compiles without the packed fp32 VALU forms is scanned as it ships: with build.py's flags)
+    own = [*build.FLAGS, *build.NO_PACKED_F32_FLAGS] if os.path.basename(src) in build.NO_PACKED_F32 else ["--offload-arch=gfx950", "-O3", "-std=c++17"]
+    cmd = [build._hipcc(), *own, "-I" + os.path.join(REPO, "include"),
            "-I" + os.path.join(REPO, "sige_amd", "csrc"), "-S", "--cuda-device-only", src, "-o", out]
     subprocess.run(cmd, check=True, stderr=subprocess.DEVNULL)
     return open(out).read().split("\n")

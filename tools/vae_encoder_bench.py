@@ -153,8 +153,14 @@ def child_f16(a):
         tiles = int(models["f16"][0].mid.attn_1.gather.active_indices.shape[0])
         row["attention_tiles"] = tiles
         graphs, outs = {}, {}
-        for name, dtype, attention in (("a_f16", "f16", "f16"), ("b_f32", "f32", "f32"), ("c_f16_attention_f32", "f16", "f32")):
+        from sige_amd.nn import Gather
+
+        forms = [("a_f16", "f16", "f16"), ("b_f32", "f32", "f32"), ("c_f16_attention_f32", "f16", "f32")]
+        if a.down_tile3:  # (d): (a) with Gather.DOWNSAMPLE_TILE3 on -- the stride-2 convs on fp16 operands
+            forms.append(("d_f16_down_tile3", "f16", "f16"))
+        for name, dtype, attention in forms:
             sd_vae.ATTENTION_COMPUTE = attention
+            Gather.DOWNSAMPLE_TILE3 = name == "d_f16_down_tile3"
             m, quant = models[dtype]
             m.moments(x1, quant)
             n0 = hip.launch_count()
@@ -162,11 +168,12 @@ def child_f16(a):
             row[name + "_library_launches"] = hip.launch_count() - n0
             graphs[name], outs[name] = capture_fn(lambda m=m, quant=quant: m.moments(x1, quant))
         sd_vae.ATTENTION_COMPUTE = None
+        Gather.DOWNSAMPLE_TILE3 = False
         ms = {k: [] for k in graphs}
         names = list(graphs)
         for batch in range(a.batches):
             x1.copy_(edits[batch % len(edits)])
-            for name in names[batch % 3:] + names[:batch % 3]:
+            for name in names[batch % len(names):] + names[:batch % len(names)]:
                 ms[name].append(events_ms(graphs[name], a.steps, 5))
         row["a_minus_b_max_abs"] = float((outs["a_f16"] - outs["b_f32"]).abs().max())
         row["a_minus_c_max_abs"] = float((outs["a_f16"] - outs["c_f16_attention_f32"]).abs().max())
@@ -174,6 +181,10 @@ def child_f16(a):
             row[name + "_ms"] = round(statistics.median(v), 4)
             row[name + "_ms_min_max"] = [round(min(v), 4), round(max(v), 4)]
         row["f16_over_f32"] = round(row["a_f16_ms"] / row["b_f32_ms"], 3)
+        if a.down_tile3:
+            row["d_minus_a_us"] = round((row["d_f16_down_tile3_ms"] - row["a_f16_ms"]) * 1e3, 2)
+            row["d_minus_a_max_abs"] = float((outs["d_f16_down_tile3"] - outs["a_f16"]).abs().max())
+            row["down_tile3_min_blocks"] = int(hip.DOWN_TILE3_MIN_BLOCKS_F16)
         del graphs
         row["attention_alone"] = attention_forms_alone(tiles, 4, a.steps)
     print("VAE_ENC_BENCH_ROW " + json.dumps(row), flush=True)
@@ -254,6 +265,8 @@ def main():
     ap.add_argument("--limit", type=int, default=240, help="seconds per child")
     ap.add_argument("--out", default=None, help="default: profiles/sd_vae_encoder_bench.json; --dtype f16: profiles/sd_vae_f16_bench.json")
     ap.add_argument("--dtype", choices=("f32", "f16"), default="f32", help="f16: the f16 compute mode beside f32, child_f16()")
+    ap.add_argument("--down-tile3", action="store_true",
+                    help="(--dtype f16) a fourth graph: f16 mode with Gather.DOWNSAMPLE_TILE3 on; default --out profiles/down_tile3_forward_ab.json")
     vae_stacked.add_arguments(ap)
     a = ap.parse_args()
     if a.stacked:
@@ -263,7 +276,8 @@ def main():
     if a.ratio is not None:
         return child_f16(a) if a.dtype == "f16" else child(a)
     if a.out is None:
-        a.out = os.path.join(REPO, "profiles", "sd_vae_f16_bench.json" if a.dtype == "f16" else "sd_vae_encoder_bench.json")
+        a.out = os.path.join(REPO, "profiles", "down_tile3_forward_ab.json" if a.down_tile3 else
+                             "sd_vae_f16_bench.json" if a.dtype == "f16" else "sd_vae_encoder_bench.json")
     from sige_amd import build
 
     res = {"workload": "SD VAE encoder (configs/sige.yaml ddconfig), image [1,3,512,512] -> moments [1,8,64,64] through quant_conv, "
@@ -272,7 +286,8 @@ def main():
     common = ["--steps", str(a.steps), "--batches", str(a.batches), "--reps", str(a.reps)]
     jobs = [("head", ["--head"])] + [(r, ["--ratio", r]) for r in a.ratios.split(",")]
     if a.dtype == "f16":
-        jobs = [(r, ["--ratio", r, "--dtype", "f16"]) for r in a.ratios.split(",")]  # (the latent head has no fp16 form: not measured again)
+        more = ["--down-tile3"] if a.down_tile3 else []
+        jobs = [(r, ["--ratio", r, "--dtype", "f16", *more]) for r in a.ratios.split(",")]  # (the latent head has no fp16 form: not measured again)
     for tag, extra in jobs:
         cmd = ["timeout", "-k", "10", str(a.limit), sys.executable, os.path.abspath(__file__), *extra, *common]
         p = subprocess.run(cmd, cwd=REPO, capture_output=True, text=True)
