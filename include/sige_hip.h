@@ -742,6 +742,26 @@ int sige_hip_token_linear_f16c(const float *x, int64_t M, int K, const float *ln
                                const void *packed, const float *bias, int N, int geglu, const float *residual, int parts,
                                float *out0, float *out1, float *out2, void *stream);
 
+/* ... with the reduction over K split over workgroups INSIDE the launch: the few-row launches (M of a few hundred rows or less, deep K)
+ * whose 16-token grid leaves most of the chip idle.  `ksplit` workgroups share one 16 x 64 output block, each walks its own run of
+ * channel chunks (64 channels fp32 | 128 f16; LayerNorm statistics still over the whole row), writes its partial block to a workspace
+ * slice, and the workgroup that arrives last adds the slices in split order 0 .. ksplit - 1 and runs the one epilogue: one launch, no
+ * float atomics, the same call gives the same bits.  The sums differ from the unsplit launch's in the order of fp32 additions only.
+ *   ksplit       the split the library's rule picks for the shape (f16: 0 = the fp32 unit's rule, 1 = the f16 unit's): 1 where it does
+ *                not split or the 64-token form runs, 0 for an unsupported shape.  Host only.
+ *   split_f32 / split_f16c   the arguments of token_linear_f32 / _f16c plus `ksplit`: 0 = the rule (where it does not split, and when
+ *                the split's tickets or workspace cannot be had -- first use inside a stream capture, regions exhausted --, the launch
+ *                of token_linear_f32 / _f16c, same bits); 1 = the unsplit 16-token form;
+ *                2 .. 16 = forced, on the 16-token form whatever the fill -- UNSUPPORTED if ksplit exceeds the chunk count or 16 or
+ *                the tickets / workspace cannot be had (a forced split never degrades).  Negative: EINVAL. */
+int sige_hip_token_linear_ksplit(int64_t M, int N, int K, int layer_norm, int geglu, int parts, int f16);
+int sige_hip_token_linear_split_f32(const float *x, int64_t M, int K, const float *ln_gamma, const float *ln_beta, float ln_eps,
+                                    const float *packed, const float *bias, int N, int geglu, const float *residual, int parts,
+                                    float *out0, float *out1, float *out2, int ksplit, void *stream);
+int sige_hip_token_linear_split_f16c(const float *x, int64_t M, int K, const float *ln_gamma, const float *ln_beta, float ln_eps,
+                                     const void *packed, const float *bias, int N, int geglu, const float *residual, int parts,
+                                     float *out0, float *out1, float *out2, int ksplit, void *stream);
+
 /* ---- 3x3 / padding-1 conv with <= 4 output channels over a full channels-last tensor
  * (the U-Net's conv_out after norm_out + SiLU, sige_fused_unet.py:430-434, which the
  * reference runs densely in sparse mode too): out [B,H,W,Cout] = conv(act(scale*x + shift)),

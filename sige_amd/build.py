@@ -80,6 +80,8 @@ def _headers():
 
 
 def _headers_of(src: str, headers):
+    if not src.startswith("token_linear"):  # (token_linear.hpp: the two token linear units only)
+        headers = [h for h in headers if not h.endswith("token_linear.hpp")]
     return (headers if src.startswith("conv_wide") else [h for h in headers if not h.endswith("conv_wide.hpp")] if src.startswith(("conv_k", "conv_pair", "conv_side", "conv_tile3", "block_conv", "token_linear"))
             else [h for h in headers if not h.endswith(("conv_mfma.hpp", "conv_wide.hpp", "conv_tile3.hpp"))])
 

@@ -29,10 +29,13 @@ __device__ __forceinline__ f16x8 tok_pack8(f32x4 a, f32x4 b) {  // (fptrunc: rou
     return __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
 }
 
-// BM: token rows per workgroup (64 | 16).
-template <int BM, bool LN, bool GEGLU>
-__global__ __launch_bounds__(256) void token_linear_f16_kernel(const TokArgs a) {
-    kernarg_touch<sizeof(TokArgs)>();
+// BM: token rows per workgroup (64 | 16).  SPLIT (16-token form): blockIdx.y of gridDim.y = a.ksplit workgroups that share the output
+// block blockIdx.x -- the split is the slow grid dimension, so the workgroups of one block are dispatched a whole grid row apart, to
+// different CUs / XCDs --, each on its own run of chunks; they finish inside the launch (token_linear.hpp: tok_finish_split).
+template <int BM, bool LN, bool GEGLU, bool SPLIT = false>
+__global__ __launch_bounds__(256) void token_linear_f16_kernel(const typename std::conditional<SPLIT, TokSplitArgs, TokArgs>::type a) {
+    static_assert(!SPLIT || BM == 16, "the K split is a variant of the 16-token form");
+    kernarg_touch<sizeof(a)>();
     constexpr bool BIG = BM == 64;
     constexpr int MT = BIG ? 2 : 1;   // M tiles per wave
     constexpr int NT = BIG ? 2 : 4;   // N tiles per wave
@@ -99,10 +102,16 @@ __global__ __launch_bounds__(256) void token_linear_f16_kernel(const TokArgs a) 
 #pragma unroll
             for (int r = 0; r < (BIG ? 16 : 4); ++r) acc[mt][nt][r] = 0.0f;
 
+    // this workgroup's chunks [c0, c1): all of them, or its split's run (never empty: host side)
+    int c0 = 0, c1 = a.nchunks;
+    if constexpr (SPLIT) {
+        c0 = (int)blockIdx.y * a.cps;
+        c1 = min(c0 + a.cps, a.nchunks);
+    }
     Frag cur, nxt;
-    load(0, cur);
-    for (int c = 0; c < a.nchunks; ++c) {
-        load(min(c + 1, a.nchunks - 1), nxt);
+    load(c0, cur);
+    for (int c = c0; c < c1; ++c) {
+        load(min(c + 1, c1 - 1), nxt);
         __builtin_amdgcn_sched_barrier(0);  // (the scheduler otherwise sinks the prefetch down to its first use)
         if constexpr (LN) {
             const bool live = c * 128 + wave * 32 < a.K;
@@ -134,7 +143,8 @@ __global__ __launch_bounds__(256) void token_linear_f16_kernel(const TokArgs a) 
         cur = nxt;
     }
 
-    tok_finish<BM, GEGLU>(a, smem, acc, tid, wave, ntile, row0, rl, kg);
+    if constexpr (SPLIT) tok_finish_split<GEGLU>(a, smem, acc, tid, wave, ntile, row0, rl, kg, (int)blockIdx.x, (int)blockIdx.y);
+    else tok_finish<BM, GEGLU>(a, smem, acc, tid, wave, ntile, row0, rl, kg);
 }
 
 // packed (halves)[((ntile * nchunks + chunk) * 4 + wave) * 2048 + ((nt * 2 + step) * 64 + lane) * 8 + j] =
@@ -172,6 +182,8 @@ inline int tokh_nchunks(int K) { return (K + 127) / 128; }
 // shapes where this form wins by 7 - 10 % to the 16-token form.)
 constexpr int kTokRoundF16 = 256;
 constexpr double kTokFillF16 = 0.7;
+// every split of the K split keeps at least this many 128-channel chunks (the rule's other constants: token_linear.hpp)
+constexpr int kTokSplitMinChunksF16 = 10;
 
 template <int BM>
 void launch_tokh(const TokArgs &a, bool ln, bool geglu, unsigned grid, hipStream_t st) {
@@ -179,6 +191,15 @@ void launch_tokh(const TokArgs &a, bool ln, bool geglu, unsigned grid, hipStream
     else if (ln) token_linear_f16_kernel<BM, true, false><<<grid, 256, 0, st>>>(a);
     else if (geglu) token_linear_f16_kernel<BM, false, true><<<grid, 256, 0, st>>>(a);
     else token_linear_f16_kernel<BM, false, false><<<grid, 256, 0, st>>>(a);
+}
+
+// grid (output blocks, splits)
+void launch_tokh_split(const TokSplitArgs &a, bool ln, bool geglu, unsigned blocks, hipStream_t st) {
+    const dim3 grid(blocks, (unsigned)a.ksplit);
+    if (ln && geglu) token_linear_f16_kernel<16, true, true, true><<<grid, 256, 0, st>>>(a);
+    else if (ln) token_linear_f16_kernel<16, true, false, true><<<grid, 256, 0, st>>>(a);
+    else if (geglu) token_linear_f16_kernel<16, false, true, true><<<grid, 256, 0, st>>>(a);
+    else token_linear_f16_kernel<16, false, false, true><<<grid, 256, 0, st>>>(a);
 }
 
 }  // namespace
@@ -213,27 +234,65 @@ extern "C" int sige_hip_token_linear_pack_f16(const float *w, int N, int K, int 
     return launch_status();
 }
 
-extern "C" int sige_hip_token_linear_f16c(const float *x, int64_t M, int K, const float *ln_gamma, const float *ln_beta, float ln_eps,
-                                          const void *packed, const float *bias, int N, int geglu, const float *residual, int parts,
-                                          float *out0, float *out1, float *out2, void *stream) {
-    SIGE_PLAN_HOOK(sige_hip_token_linear_f16c, x, M, K, ln_gamma, ln_beta, ln_eps, packed, bias, N, geglu, residual, parts, out0, out1, out2, stream);
-    if (M < 0 || K <= 0 || N <= 0 || parts < 1 || parts > 3) return SIGE_HIP_EINVAL;
+namespace sige {
+
+static bool tokh_big(int64_t M, int ntn) {
+    const int knob = tuning(SIGE_HIP_TUNE_TOKEN_LINEAR_FORM);
+    return knob ? knob == 2 : tok_fill64(M, ntn, kTokRoundF16) >= kTokFillF16;
+}
+
+int token_linear_ksplit_f16(int64_t M, int N, int K, int layer_norm, int geglu, int parts) {
+    if (!sige_hip_token_linear_supported_f16c(M, N, K, layer_norm, geglu, parts)) return 0;
+    const int ntn = tokh_ntn(N, K, geglu);
+    if (M == 0 || tokh_big(M, ntn)) return 1;
+    return tok_split_rule(M, ntn, tokh_nchunks(K), kTokSplitMinChunksF16);
+}
+
+// Both launching entry points.  ksplit: -1 = sige_hip_token_linear_f16c (form by fill, no split) | sige_hip_token_linear_split_f16c's
+static int token_linear_f16c(const float *x, int64_t M, int K, const float *ln_gamma, const float *ln_beta, float ln_eps, const void *packed,
+                             const float *bias, int N, int geglu, const float *residual, int parts, float *out0, float *out1, float *out2,
+                             int ksplit, void *stream) {
+    if (M < 0 || K <= 0 || N <= 0 || parts < 1 || parts > 3 || ksplit < -1) return SIGE_HIP_EINVAL;
     if (M == 0) return SIGE_HIP_OK;
     if (!x || !packed || !out0 || (parts > 1 && !out1) || (parts > 2 && !out2) || (ln_gamma && !ln_beta)) return SIGE_HIP_EINVAL;
     if (!sige_hip_token_linear_supported_f16c(M, N, K, ln_gamma != nullptr, geglu, parts)) return SIGE_HIP_EUNSUPPORTED;
     if (parts > 1 && residual) return SIGE_HIP_EUNSUPPORTED;
     if (!tok_al16(x) || !tok_al16(packed) || !tok_al16(out0) || !tok_al16(out1) || !tok_al16(out2) || !tok_al16(bias) || !tok_al16(residual) || !tok_al16(ln_gamma) || !tok_al16(ln_beta))
         return SIGE_HIP_EUNSUPPORTED;
-    TokArgs a = tok_args(x, M, K, ln_gamma, ln_beta, ln_eps, bias, N, geglu, residual, parts, out0, out1, out2);
+    TokSplitArgs a;
+    static_cast<TokArgs &>(a) = tok_args(x, M, K, ln_gamma, ln_beta, ln_eps, bias, N, geglu, residual, parts, out0, out1, out2);
     a.packed = packed;
     a.ntn = tokh_ntn(N, K, geglu);
     a.nchunks = tokh_nchunks(K);
     a.tpp = parts > 1 ? a.No / 64 : a.ntn;
     a.w_bytes = (int)(sige_hip_token_linear_packed_size_f16(N, K, geglu) * 2);
-    const int knob = tuning(SIGE_HIP_TUNE_TOKEN_LINEAR_FORM);
-    const bool big = knob ? knob == 2 : tok_fill64(M, a.ntn, kTokRoundF16) >= kTokFillF16;
     hipStream_t st = as_stream(stream);
-    if (big) launch_tokh<64>(a, ln_gamma != nullptr, geglu != 0, (unsigned)(((M + 63) / 64) * a.ntn), st);
-    else launch_tokh<16>(a, ln_gamma != nullptr, geglu != 0, (unsigned)(((M + 15) / 16) * a.ntn), st);
+    const bool ln = ln_gamma != nullptr;
+    const unsigned blocks16 = (unsigned)(((M + 15) / 16) * a.ntn);
+    int ks = 1;
+    if (ksplit >= 0) {
+        ks = tok_plan_split(a, M, ksplit, token_linear_ksplit_f16(M, N, K, ln, geglu, parts), st);
+        if (!ks) return SIGE_HIP_EUNSUPPORTED;
+    }
+    if (ks > 1) launch_tokh_split(a, ln, geglu != 0, blocks16, st);
+    else if (ksplit <= 0 && tokh_big(M, a.ntn)) launch_tokh<64>(a, ln, geglu != 0, (unsigned)(((M + 63) / 64) * a.ntn), st);
+    else launch_tokh<16>(a, ln, geglu != 0, blocks16, st);
     return launch_status();
+}
+
+}  // namespace sige
+
+extern "C" int sige_hip_token_linear_f16c(const float *x, int64_t M, int K, const float *ln_gamma, const float *ln_beta, float ln_eps,
+                                          const void *packed, const float *bias, int N, int geglu, const float *residual, int parts,
+                                          float *out0, float *out1, float *out2, void *stream) {
+    SIGE_PLAN_HOOK(sige_hip_token_linear_f16c, x, M, K, ln_gamma, ln_beta, ln_eps, packed, bias, N, geglu, residual, parts, out0, out1, out2, stream);
+    return token_linear_f16c(x, M, K, ln_gamma, ln_beta, ln_eps, packed, bias, N, geglu, residual, parts, out0, out1, out2, -1, stream);
+}
+
+extern "C" int sige_hip_token_linear_split_f16c(const float *x, int64_t M, int K, const float *ln_gamma, const float *ln_beta, float ln_eps,
+                                                const void *packed, const float *bias, int N, int geglu, const float *residual, int parts,
+                                                float *out0, float *out1, float *out2, int ksplit, void *stream) {
+    SIGE_PLAN_HOOK(sige_hip_token_linear_split_f16c, x, M, K, ln_gamma, ln_beta, ln_eps, packed, bias, N, geglu, residual, parts, out0, out1, out2, ksplit, stream);
+    if (ksplit < 0) return SIGE_HIP_EINVAL;
+    return token_linear_f16c(x, M, K, ln_gamma, ln_beta, ln_eps, packed, bias, N, geglu, residual, parts, out0, out1, out2, ksplit, stream);
 }

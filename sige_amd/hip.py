@@ -216,6 +216,11 @@ _SIGNATURES = {
     "sige_hip_token_linear_pack_f16": (_c_int, [_c_vp, _c_int, _c_int, _c_int, _c_vp, _c_vp]),
     "sige_hip_token_linear_f16c": (_c_int, [_c_vp, ctypes.c_int64, _c_int, _c_vp, _c_vp, ctypes.c_float, _c_vp, _c_vp, _c_int, _c_int, _c_vp, _c_int]
                                    + [_c_vp] * 4),
+    "sige_hip_token_linear_ksplit": (_c_int, [ctypes.c_int64] + [_c_int] * 6),
+    "sige_hip_token_linear_split_f32": (_c_int, [_c_vp, ctypes.c_int64, _c_int, _c_vp, _c_vp, ctypes.c_float, _c_vp, _c_vp, _c_int, _c_int, _c_vp, _c_int]
+                                        + [_c_vp] * 3 + [_c_int, _c_vp]),
+    "sige_hip_token_linear_split_f16c": (_c_int, [_c_vp, ctypes.c_int64, _c_int, _c_vp, _c_vp, ctypes.c_float, _c_vp, _c_vp, _c_int, _c_int, _c_vp, _c_int]
+                                         + [_c_vp] * 3 + [_c_int, _c_vp]),
     "sige_hip_set_edit_batch": (_c_int, [_c_int]),
     "sige_hip_get_edit_batch": (_c_int, []),
     # launch plans (csrc/plan.hip; host side: sige_amd/plan.py)
@@ -2334,12 +2339,14 @@ def token_linear_pack(weight, geglu: bool = False, compute: str = "f32") -> Opti
 
 
 def token_linear(x: torch.Tensor, packed: torch.Tensor, N: int, bias=None, norm: Optional[torch.nn.LayerNorm] = None, residual=None,
-                 geglu: bool = False, parts: int = 1, compute: str = "f32"):
+                 geglu: bool = False, parts: int = 1, compute: str = "f32", ksplit: Optional[int] = None):
     """epilogue(LayerNorm?(x) @ W^T) in ONE launch for tokens x [..., K] and W [N,K] packed by token_linear_pack: `norm` = the
     LayerNorm applied to x on the way in; `bias` [N]; `geglu`: value * gelu(gate) -> [..., N/2]; `residual` (shaped like the output) is
     added; `parts` > 1: a tuple of that many [..., N/parts] tensors (q, k, v).  `compute`: "f32" exact fp32 products | "f16" the
     LayerNorm output and W rounded to fp16, fp32 accumulation, everything else fp32 (include/sige_hip.h has the contract); `packed`
-    must have been made with the same `compute`.  None if unsupported (the caller runs its other path)."""
+    must have been made with the same `compute`.  `ksplit`: None -> sige_hip_token_linear_f32 / _f16c; an int -> the K split inside
+    the launch (sige_hip_token_linear_split_f32 / _f16c): 0 the library's rule (token_linear_ksplit), 1 the unsplit 16-token form,
+    2 .. 16 forced -- refused, never degraded, when it cannot run.  None if unsupported (the caller runs its other path)."""
     size_of, supported, _, launch, dtype = _token_linear_entries(compute)
     if not (x.is_cuda and x.dtype == torch.float32 and x.dim() >= 2 and packed is not None):
         return None
@@ -2363,14 +2370,23 @@ def token_linear(x: torch.Tensor, packed: torch.Tensor, N: int, bias=None, norm:
     g = e = None
     if norm is not None:
         g, e = norm.weight.detach(), norm.bias.detach()
+    if ksplit is not None:
+        launch = lib().sige_hip_token_linear_split_f32 if compute == "f32" else lib().sige_hip_token_linear_split_f16c
     status = launch(x.data_ptr(), M, K, _p(g), _p(e), float(norm.eps) if norm is not None else 0.0,
                     packed.data_ptr(), _p(bias), N, int(geglu), _p(residual), parts,
                     outs[0].data_ptr(), _p(outs[1] if parts > 1 else None), _p(outs[2] if parts > 2 else None),
-                    _stream(x))
+                    *(() if ksplit is None else (int(ksplit),)), _stream(x))
     if status == UNSUPPORTED:
         return None
     _check(status, "token_linear")
     return outs[0] if parts == 1 else tuple(outs)
+
+
+def token_linear_ksplit(M: int, N: int, K: int, norm: bool = False, geglu: bool = False, parts: int = 1, compute: str = "f32") -> int:
+    """The K split token_linear(..., ksplit=0) runs at this shape (sige_hip_token_linear_ksplit; host arithmetic): 1 = none, also where
+    the 64-token form runs; 0 = the shape is unsupported."""
+    _token_linear_entries(compute)
+    return lib().sige_hip_token_linear_ksplit(M, N, K, int(bool(norm)), int(geglu), parts, int(compute == "f16"))
 
 
 # ---- GauGAN helpers (csrc/spade_ops.hip): the sparse forward of the SPADE generator without a torch kernel ----------------------

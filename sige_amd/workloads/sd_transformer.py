@@ -67,6 +67,11 @@ from ..nn import Gather, Scatter, SIGEConv2d, SIGEModule
 #                     cached K / V stay on torch's fp32 linears -- so the cached K / V of the original image are fp32-computed and the
 #                     rows a sparse pass refreshes are f16-computed.  CHANGES values, within the f16 criterion.  "f32" by default:
 #                     DESIGN.md 5.30 has the measurements.
+#   TOKEN_LINEAR_KSPLIT  TOKEN_LINEAR's six launches through the entry that may split K inside the launch (hip.token_linear(ksplit=0):
+#                     sige_hip_token_linear_split_f32 / _f16c) -- at the few-row levels, where the 16-token grid leaves most of the
+#                     chip idle, the library's rule shares an output block among 2 .. 8 workgroups that finish in the launch; the same
+#                     launch count, the same products in another fixed summation order.  Off: no new code runs.  Off by default:
+#                     DESIGN.md 5.32 has the rule and the measurements.
 NATIVE_ATTENTION = True
 ATTENTION_COMPUTE = "f32"
 NATIVE_LINEAR = False
@@ -74,6 +79,7 @@ BATCHED_QKV = True
 FUSED_TOKENS = True
 TOKEN_LINEAR = False
 TOKEN_LINEAR_COMPUTE = "f32"
+TOKEN_LINEAR_KSPLIT = False
 
 
 def linear(lin: nn.Linear, x: torch.Tensor) -> torch.Tensor:
@@ -263,7 +269,8 @@ class TransformerBlock(SIGEModule):
         tiles = _kv_tiles(kv_scatter)
         as_tiles = lambda t: t.reshape(-1, 4, 4, t.shape[2]).permute(0, 3, 1, 2)  # noqa: E731
         as_tokens = lambda t: t.permute(0, 2, 3, 1).reshape(t.shape[0], hh * ww, t.shape[1])  # noqa: E731
-        tl = functools.partial(hip.token_linear, compute=TOKEN_LINEAR_COMPUTE)  # (the packs were made for it: _token_linear_packs)
+        tl = functools.partial(hip.token_linear, compute=TOKEN_LINEAR_COMPUTE,  # (the packs were made for it: _token_linear_packs)
+                               ksplit=0 if TOKEN_LINEAR_KSPLIT else None)
 
         def need(t, what):  # (the shapes were accepted by sige_hip_token_linear_supported: a refusal here is an error, not a detour)
             if t is None:

@@ -14,6 +14,12 @@ criterion (sige_amd.tolerance.f16_check) of its output against the all-fp32 mode
 
     python tools/sd_token_linear_ab.py --compute f16 --out profiles/sd_token_linear_f16_ab.json
     python tools/sd_token_linear_ab.py --compute f16 --tuned --out profiles/sd_token_linear_f16_ab.json
+
+`--ksplit`: TOKEN_LINEAR stays on and the settings alternate sd_transformer.TOKEN_LINEAR_KSPLIT (the K split inside the few-row
+launches) instead; with --compute f16 the session goes into the same file under "f16".
+
+    python tools/sd_token_linear_ab.py --ksplit --out profiles/sd_token_linear_ksplit_ab.json
+    python tools/sd_token_linear_ab.py --ksplit --compute f16 --out profiles/sd_token_linear_ksplit_ab.json
 """
 import argparse
 import json
@@ -37,6 +43,7 @@ def main():
     ap.add_argument("--replays", type=int, default=20)
     ap.add_argument("--tuned", action="store_true", help="TunableOp on with the shipped table (sige_amd/workloads/gemm_tuning.py)")
     ap.add_argument("--compute", default="f32", choices=("f32", "f16"), help="the model's compute mode and the token linear's operands")
+    ap.add_argument("--ksplit", action="store_true", help="alternate TOKEN_LINEAR_KSPLIT with TOKEN_LINEAR on")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     from sige_amd import hip
@@ -61,6 +68,8 @@ def main():
     run = lambda x: model(x, ts, context=ctx)  # noqa: E731
     res = {"workload": "bench.py --workload sd (SD v1 U-Net, latent [2,4,64,64]), hipGraph replay", "tunableop_table": tuned, "masks": {}}
     keep = sd_transformer.TOKEN_LINEAR, sd_transformer.TOKEN_LINEAR_COMPUTE
+    keep_split = sd_transformer.TOKEN_LINEAR_KSPLIT
+    res["alternates"] = "TOKEN_LINEAR_KSPLIT (TOKEN_LINEAR on)" if args.ksplit else "TOKEN_LINEAR"
     sd_transformer.TOKEN_LINEAR_COMPUTE = args.compute
     res["compute"] = args.compute
     try:
@@ -88,7 +97,10 @@ def main():
                 prepare()
                 rows, ref = [], None
                 for st in args.settings.split(","):
-                    sd_transformer.TOKEN_LINEAR = bool(int(st))
+                    if args.ksplit:
+                        sd_transformer.TOKEN_LINEAR, sd_transformer.TOKEN_LINEAR_KSPLIT = True, bool(int(st))
+                    else:
+                        sd_transformer.TOKEN_LINEAR = bool(int(st))
                     run(x1)
                     n0 = hip.launch_count()
                     run(x1)
@@ -96,9 +108,10 @@ def main():
                     ms, out, g = _replay_ms(lambda: run(x1), k=args.replays, warm=3)
                     o = out.float().clone()
                     del g
+                    hip.release_graph_tickets()  # (the graph is gone: the slices of its split launches start over)
                     if ref is None:
                         ref = o
-                    rows.append({"mask": name, "token_linear": bool(int(st)), "forward_ms": round(ms, 3), "library_launches": launches,
+                    rows.append({"mask": name, "token_linear_ksplit" if args.ksplit else "token_linear": bool(int(st)), "forward_ms": round(ms, 3), "library_launches": launches,
                                  "max_abs_vs_first_setting": round(float((o - ref).abs().max()), 8)})
                     if fp32_out is not None:
                         rows[-1]["f16_check_vs_fp32_model"] = f16_check(o, fp32_out)
@@ -106,11 +119,16 @@ def main():
                 res["masks"][name] = {"box": MASKS[name], "edit_ratio": round(float(mask512.float().mean()), 4), "rows": rows}
     finally:
         sd_transformer.TOKEN_LINEAR, sd_transformer.TOKEN_LINEAR_COMPUTE = keep
+        sd_transformer.TOKEN_LINEAR_KSPLIT = keep_split
         if tuned:
             gemm_tuning.disable_tuned_gemms()
     if args.out:
         os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-        if args.compute == "f16":
+        if args.ksplit:
+            both = json.load(open(args.out)) if os.path.isfile(args.out) else {}
+            both.setdefault("sessions", {})[args.compute] = res
+            res = both
+        elif args.compute == "f16":
             both = json.load(open(args.out)) if os.path.isfile(args.out) else {}
             both.setdefault("sessions", {})["tunableop_on" if tuned else "tunableop_off"] = res
             res = both

@@ -20,6 +20,14 @@ the same inputs).
 
     python tools/token_linear_bench.py --out out/token_linear_bench.json
     python tools/token_linear_bench.py --compute f16 --forms --out profiles/token_linear_f16_bench.json
+
+`--ksplit`: instead of the columns above, the K split inside the launch (hip.token_linear(ksplit=...)) at the same shapes, in both
+computes: the launch at ksplit 1 -- the unsplit 16-token instance -- and forced at 2 / 4 / 8 in the same run, `library_us` (the entry
+without a split argument: the form the library picks) next to them, each figure [smallest, largest] of three timings, and the split the
+library's rule picks.  A captured split launch keeps its workspace slice for the life of its graph, so a graph holds as many
+back-to-back calls (at most --reps) as the pool's graph region has slices for: `reps` of the row.
+
+    python tools/token_linear_bench.py --ksplit --out profiles/token_linear_ksplit_bench.json
 """
 import argparse
 import collections
@@ -163,18 +171,79 @@ def rows_of(M, C, dev, hip, forms, reps, compute="f32"):
     return out
 
 
+def ksplit_rows_of(M, C, dev, hip, reps):
+    """The five launches of one block at (M, C), both computes: us at ksplit 1 | 2 | 4 | 8 (None: refused), [smallest, largest] of three."""
+    g = torch.Generator().manual_seed(M * 7 + C)
+    rn = lambda *s: torch.randn(*s, generator=g).to(dev)  # noqa: E731
+    x, o, h = rn(1, M, C), rn(1, M, C), rn(1, M, 4 * C)
+    norm = torch.nn.LayerNorm(C).to(dev)
+    w = lambda n, k: (rn(n, k) * k ** -0.5)  # noqa: E731
+    wq, wk, wv, wo, w0, w2 = w(C, C), w(C, C), w(C, C), w(C, C), w(8 * C, C), w(C, 4 * C)
+    bo, b0, b2 = rn(C), rn(8 * C), rn(C)
+    out = []
+    for c in ("f32", "f16"):
+        pk = (hip.token_linear_pack([wq, wk, wv], compute=c), hip.token_linear_pack(wo, compute=c), hip.token_linear_pack(wq, compute=c),
+              hip.token_linear_pack(w0, geglu=True, compute=c), hip.token_linear_pack(w2, compute=c))
+        # (name, N, K, LayerNorm, GEGLU, parts, the launch at a ksplit)
+        spec = [("qkv", 3 * C, C, True, False, 3, lambda ks: hip.token_linear(x, pk[0], 3 * C, norm=norm, parts=3, compute=c, ksplit=ks)),
+                ("to_out", C, C, False, False, 1, lambda ks: hip.token_linear(o, pk[1], C, bias=bo, residual=x, compute=c, ksplit=ks)),
+                ("attn2.q", C, C, True, False, 1, lambda ks: hip.token_linear(x, pk[2], C, norm=norm, compute=c, ksplit=ks)),
+                ("ff.proj", 8 * C, C, True, True, 1, lambda ks: hip.token_linear(x, pk[3], 8 * C, bias=b0, norm=norm, geglu=True, compute=c, ksplit=ks)),
+                ("ff.out", C, 4 * C, False, False, 1, lambda ks: hip.token_linear(h, pk[4], C, bias=b2, residual=x, compute=c, ksplit=ks))]
+        with torch.no_grad():
+            for name, N, K, ln, geglu, parts, fn in spec:
+                units = -(-M // 16) * -(-N // 64)
+                row = {"launch": name, "compute": c, "M": M, "N": N, "K": K, "grid16": units, "chunks": -(-K // (64 if c == "f32" else 128)),
+                       "rule_ksplit": hip.token_linear_ksplit(M, N, K, ln, geglu, parts, compute=c), "us": {}, "reps": {}}
+                for key, ks in (("library", None), ("1", 1), ("2", 2), ("4", 4), ("8", 8)):
+                    if ks is not None and fn(ks) is None:  # (more splits than chunks)
+                        row["us"][key] = None
+                        continue
+                    # the graph region of the workspace pool: 24 Mi floats, units * ks * 1024 per captured launch (and its warm-up)
+                    n = reps if ks in (None, 1) else max(1, min(reps, (24 << 20) // (units * ks * 1024) - 1))
+                    ts = []
+                    for _ in range(3):
+                        ts.append(time_graph_of(lambda: fn(ks), n))
+                        hip.release_graph_tickets()  # (the graph is gone: its slices start over)
+                    row["us"][key], row["reps"][key] = [float("%.4g" % min(ts)), float("%.4g" % max(ts))], n
+                out.append(row)
+                print(json.dumps(row), flush=True)
+    return out
+
+
+def main_ksplit(args, hip, dev):
+    shapes = block_shapes({m: MASKS[m] for m in args.masks.split(",")}, dev)
+    res = {"workload": "bench.py --workload sd (SD v1 U-Net, latent [2,4,64,64]); us per call from a hipGraph of `reps` back-to-back calls, "
+                       "[smallest, largest] of three graphs; ksplit 1 = the unsplit 16-token instance, library = the entry without a split",
+           "masks": {}}
+    done = {}
+    for mask, sh in shapes.items():
+        levels = []
+        for (M, C, on_path), blocks in sorted(sh.items(), key=lambda kv: -kv[0][0]):
+            if (M, C) not in done:
+                done[(M, C)] = ksplit_rows_of(M, C, dev, hip, args.reps)
+            levels.append({"M": M, "C": C, "blocks_per_forward": blocks, "on_switch_path": on_path, "rows": done[(M, C)]})
+        res["masks"][mask] = {"box": MASKS[mask], "levels": levels}
+    if args.out:
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        json.dump(res, open(args.out, "w"), indent=1)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--masks", default="bench,other")
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--forms", action="store_true", help="also time both row-block forms (needs the measurement build)")
     ap.add_argument("--compute", default="f32", choices=("f32", "f16"), help="the operands of the library columns")
+    ap.add_argument("--ksplit", action="store_true", help="time the K split inside the launch at ksplit 1 / 2 / 4 / 8, both computes")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     from sige_amd import hip
 
     dev = torch.device("cuda:0")
     hip.lib()
+    if args.ksplit:
+        return main_ksplit(args, hip, dev)
     in_table = table_token_counts()
     shapes = block_shapes({m: MASKS[m] for m in args.masks.split(",")}, dev)
     res = {"workload": "bench.py --workload sd (SD v1 U-Net, latent [2,4,64,64]); us per call from a hipGraph of %d back-to-back calls" % args.reps,
