@@ -1065,6 +1065,32 @@ int sige_hip_attention_tokens_tiles_f32(const float *q, const float *k, const fl
 int sige_hip_attention_tokens_tiles_f16c(const float *q, const float *k, const float *v, const int32_t *active_indices,
                                          int T, int H, int W, int C, int heads, float scale, float *out, void *stream);
 
+/* ---- ... on K / V that are STORED as fp16 ---------------------------------------------------------------------
+ * sige_hip_attention_tokens_f16c / _tiles_f16c with k16, v16 fp16 (_Float16) token matrices [B,Nk,C] / [H W, C], row-major, heads as
+ * strides; q and out stay fp32.  The arithmetic contract is the one stated at sige_hip_attention_tokens_f16c with "k, v rounded to
+ * nearest even to fp16" ALREADY DONE in memory: on k16 = half(k), v16 = half(v) the two entries compute the same products (another
+ * channel order inside a score, the same roundings of q and of the probabilities).  Infinities or NaNs in a NEIGHBOURING head's
+ * channels never reach a head's result: the lanes that would read them load exact zeros from out of the descriptor's range.
+ * Shapes: sige_hip_attention_tokens_supported and d % 8 == 0 (a lane's 16-byte load is 8 channels of one head).  Status rules of the
+ * f16c entries, argument for argument: SIGE_HIP_EINVAL for bad dims and for null pointers with work to do, SIGE_HIP_EUNSUPPORTED
+ * for a refused shape, a pointer that is not 16-byte aligned, one batch's (image's) K or V >= 2 GiB.                              */
+int sige_hip_attention_tokens_f16kv_supported(int Nq, int Nk, int C, int heads);
+int sige_hip_attention_tokens_f16kv(const float *q, const void *k16, const void *v16, int B, int Nq, int Nk, int C,
+                                    int heads, float scale, float *out, void *stream);
+int sige_hip_attention_tokens_tiles_f16kv(const float *q, const void *k16, const void *v16, const int32_t *active_indices,
+                                          int T, int H, int W, int C, int heads, float scale, float *out, void *stream);
+
+/* ---- ... and their producer in a sparse pass: the refreshed K and V rows, rounded once, in ONE launch ---------------------------
+ * k_rows, v_rows: fp32 [B * tiles_per_image * 16, C], row 16 t + 4 i + j = cell (i, j) of the 4x4 tile t (batch-major: tile t is
+ * entry t % tiles_per_image of the list, in image t / tiles_per_image) -- what the q | k | v token linear leaves.  Each row is
+ * rounded to nearest even to fp16 and stored as row (y0 + i) W + x0 + j of k16 / v16, fp16 [B, H W, C], (y0, x0) =
+ * active_indices[2 n], [2 n + 1]; a cell off the image is skipped, every other row of k16 / v16 is left as it is (the in-place
+ * channels-last Scatter with offset 0 and stride 1, both tensors at once).  Under stacked edits B = 1 and H is the tall image's.
+ * SIGE_HIP_EINVAL: negative counts, non-positive H / W / C, null pointers with work to do.  B * tiles_per_image == 0: SIGE_HIP_OK,
+ * nothing launched.  SIGE_HIP_EUNSUPPORTED: C % 8, a pointer that is not 16-byte aligned.                                          */
+int sige_hip_kv_rows_store_f16(const float *k_rows, const float *v_rows, void *k16, void *v16, const int32_t *active_indices,
+                               int tiles_per_image, int B, int H, int W, int C, void *stream);
+
 /* ---- the same attention for WIDE heads: 160 < d <= 512, d % 16 == 0 (the SD VAE decoder's single 512-channel head) -----
  * q [B,Nq,ldq], k [B,Nk,ldk], v [B,Nk,ldv], out [B,Nq,ldo]: every operand comes with its ROW STRIDE in elements (>= C, a
  * multiple of 4; batch stride = rows * row stride), so k and v may be the two halves of one [B,Nk,2C] tensor and q / out

@@ -172,6 +172,10 @@ _SIGNATURES = {
     "sige_hip_attention_tokens_f16c": (_c_int, [_c_vp] * 3 + [_c_int] * 5 + [ctypes.c_float, _c_vp, _c_vp]),
     "sige_hip_attention_tokens_tiles_f32": (_c_int, [_c_vp] * 4 + [_c_int] * 5 + [ctypes.c_float, _c_vp, _c_vp]),
     "sige_hip_attention_tokens_tiles_f16c": (_c_int, [_c_vp] * 4 + [_c_int] * 5 + [ctypes.c_float, _c_vp, _c_vp]),
+    "sige_hip_attention_tokens_f16kv_supported": (_c_int, [_c_int] * 4),
+    "sige_hip_attention_tokens_f16kv": (_c_int, [_c_vp] * 3 + [_c_int] * 5 + [ctypes.c_float, _c_vp, _c_vp]),
+    "sige_hip_attention_tokens_tiles_f16kv": (_c_int, [_c_vp] * 4 + [_c_int] * 5 + [ctypes.c_float, _c_vp, _c_vp]),
+    "sige_hip_kv_rows_store_f16": (_c_int, [_c_vp] * 5 + [_c_int] * 5 + [_c_vp]),
     "sige_hip_attention_wide_supported": (_c_int, [_c_int] * 4),
     "sige_hip_attention_wide_f32": (_c_int, [_c_vp, _c_int] * 3 + [_c_int] * 5 + [ctypes.c_float, _c_vp, _c_int, _c_vp]),
     "sige_hip_attention_wide_tiles_f32": (_c_int, [_c_vp, _c_int] * 3 + [_c_vp] + [_c_int] * 5 + [ctypes.c_float, _c_vp, _c_int, _c_vp]),
@@ -2858,6 +2862,62 @@ def attention_tokens(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, heads: i
         return None
     _check(status, "attention_tokens")
     return out
+
+
+def attention_tokens_kv16(q: torch.Tensor, k16: torch.Tensor, v16: torch.Tensor, heads: int, scale: float,
+                          tiles=None) -> Optional[torch.Tensor]:
+    """attention_tokens(..., compute="f16") on K / V that are STORED as fp16: q [B,Nq,C] fp32, k16 / v16 [B,Nk,C] fp16 -> [B,Nq,C]
+    fp32 (sige_hip_attention_tokens_f16kv / _tiles_f16kv: the f16c contract with the rounding of k, v already done in memory).
+    None if unsupported (CPU tensors, a shape sige_hip_attention_tokens_f16kv_supported refuses: d % 8 != 0 among them).  A wrong
+    dtype or a malformed `tiles` (the argument of attention_tokens) raises ValueError: no tensor is converted here."""
+    if q.dtype != torch.float32 or k16.dtype != torch.float16 or v16.dtype != torch.float16:
+        raise ValueError("attention_tokens_kv16: q must be fp32 and k16 / v16 fp16, got %s / %s / %s" % (q.dtype, k16.dtype, v16.dtype))
+    if not (q.is_cuda and q.dim() == k16.dim() == v16.dim() == 3):
+        return None
+    B, Nq, C = q.shape
+    if tuple(k16.shape) != tuple(v16.shape) or k16.shape[0] != B or k16.shape[2] != C:
+        return None
+    Nk = k16.shape[1]
+    if tiles is not None:
+        idx, H, W = _attention_tiles(tiles, B, Nq, Nk, "attention_tokens_kv16")
+    elif not lib().sige_hip_attention_tokens_f16kv_supported(Nq, Nk, C, heads):
+        return None
+    q, k16, v16 = (t if t.is_contiguous() else t.contiguous() for t in (q, k16, v16))
+    out = torch.empty((B, Nq, C), dtype=torch.float32, device=q.device)
+    if tiles is not None:
+        status = lib().sige_hip_attention_tokens_tiles_f16kv(q.data_ptr(), k16.data_ptr(), v16.data_ptr(), idx.data_ptr(), Nq // 16, H, W,
+                                                             C, heads, float(scale), out.data_ptr(), _stream(q))
+    else:
+        status = lib().sige_hip_attention_tokens_f16kv(q.data_ptr(), k16.data_ptr(), v16.data_ptr(), B, Nq, Nk, C, heads, float(scale),
+                                                       out.data_ptr(), _stream(q))
+    if status == UNSUPPORTED:
+        return None
+    _check(status, "attention_tokens_kv16")
+    return out
+
+
+def kv_rows_store_f16(k_rows: torch.Tensor, v_rows: torch.Tensor, k16: torch.Tensor, v16: torch.Tensor, indices: torch.Tensor,
+                      H: int, W: int) -> None:
+    """The refreshed K / V rows of a sparse pass into the fp16-stored K / V, rounded to nearest even, both tensors in ONE launch
+    (sige_hip_kv_rows_store_f16): k_rows / v_rows fp32 [B,16T,C] (or [B*16T,C]) -- the tokens of the T active 4x4 tiles per image,
+    tile-major --, k16 / v16 contiguous fp16 [B,H*W,C] written IN PLACE at the tiles of `indices` (the Gather's device int32 [T,2]
+    list); cells off the image are skipped.  T = 0: nothing is launched.  Malformed arguments raise ValueError."""
+    if k_rows.dtype != torch.float32 or v_rows.dtype != torch.float32 or k16.dtype != torch.float16 or v16.dtype != torch.float16:
+        raise ValueError("kv_rows_store_f16: k_rows / v_rows must be fp32 and k16 / v16 fp16")
+    if not (indices.dtype == torch.int32 and indices.dim() == 2 and indices.shape[1] == 2 and indices.is_contiguous()):
+        raise ValueError("kv_rows_store_f16: indices = the int32 [T,2] index list")
+    if k16.dim() != 3 or tuple(k16.shape) != tuple(v16.shape) or k16.shape[1] != int(H) * int(W):
+        raise ValueError("kv_rows_store_f16: k16 / v16 are [B,H*W,C]")
+    B, _, C = k16.shape
+    T = indices.shape[0]
+    if k_rows.numel() != B * T * 16 * C or v_rows.numel() != B * T * 16 * C or k_rows.shape[-1] != C or v_rows.shape[-1] != C:
+        raise ValueError("kv_rows_store_f16: k_rows / v_rows are the [B,16T,C] tokens of the T tiles of the list")
+    if not (k_rows.is_contiguous() and v_rows.is_contiguous() and k16.is_contiguous() and v16.is_contiguous()):
+        raise ValueError("kv_rows_store_f16: contiguous tensors (k16 / v16 are written in place)")
+    if not (k_rows.is_cuda and v_rows.is_cuda and k16.is_cuda and v16.is_cuda and indices.is_cuda):
+        raise ValueError("kv_rows_store_f16: device tensors")
+    _check(lib().sige_hip_kv_rows_store_f16(k_rows.data_ptr(), v_rows.data_ptr(), k16.data_ptr(), v16.data_ptr(), indices.data_ptr(),
+                                            T, B, int(H), int(W), C, _stream(k16)), "kv_rows_store_f16")
 
 
 def _attention_tiles(tiles, B: int, Nq: int, Nk: int, name: str):

@@ -2,6 +2,7 @@
 (15 % edit of a 64 x 64 latent, batch 2: self-attention over all HW keys from the active tiles' queries, cross-attention over 77 text
 tokens), a graph of 8 back-to-back launches per shape and form; checked against softmax(q k^T) v in fp64.  Both forms are timed at
 every shape, in one process, one row each (`--compute` restricts the run to one of them).  SIGE_HIP_LIB selects the build.
+`--kv16`: the f16c launch beside `sige_hip_attention_tokens_f16kv` on k.half(), v.half() (rows "f16" and "f16kv").
 
     python tools/attention_tokens_bench.py [--tag name] [--compute f32|f16] >> profiles/attention_tokens_f16.jsonl
 """
@@ -25,7 +26,12 @@ def time_one(bench, hip, name, q, k, v, heads, scale, compute, want):
     """One shape, one form: a graph of 8 back-to-back launches, 3 warm replays, 20 timed -> a row."""
     B, Nq, C = q.shape
     Nk, d = k.shape[1], C // heads
-    g, out = bench.capture_fn(lambda: [hip.attention_tokens(q, k, v, heads, scale, compute=compute) for _ in range(8)][-1], warm=2)
+    if compute == "f16kv":
+        k16, v16 = k.half(), v.half()
+        launch = lambda: hip.attention_tokens_kv16(q, k16, v16, heads, scale)  # noqa: E731
+    else:
+        launch = lambda: hip.attention_tokens(q, k, v, heads, scale, compute=compute)  # noqa: E731
+    g, out = bench.capture_fn(lambda: [launch() for _ in range(8)][-1], warm=2)
     for _ in range(3):
         g.replay()
     torch.cuda.synchronize()
@@ -49,6 +55,7 @@ def main():
     ap.add_argument("--eager", type=int, default=0, help="N eager launches per shape and form and nothing else (for rocprofv3 --pmc)")
     ap.add_argument("--only", default="", help="comma-separated shape names")
     ap.add_argument("--compute", choices=("f32", "f16"), default=None, help="this form only (default: both, f32 first)")
+    ap.add_argument("--kv16", action="store_true", help="the f16c launch and the launch on fp16-stored K / V, side by side")
     ap.add_argument("--form", type=int, default=None, help="attention_form knob (needs SIGE_HIP_LIB=.../libsige_hip_tuning.so)")
     args = ap.parse_args()
     import bench
@@ -58,7 +65,7 @@ def main():
     if args.form is not None:
         hip.tuning_set("attention_form", args.form)
     torch.manual_seed(0)
-    computes = (args.compute,) if args.compute else ("f32", "f16")
+    computes = ("f16", "f16kv") if args.kv16 else (args.compute,) if args.compute else ("f32", "f16")
     rows = []
     for name, B, Nq, Nk, C, heads in SHAPES:
         q, k, v = (torch.randn(B, n, C, device=dev) for n in (Nq, Nk, Nk))
@@ -68,6 +75,9 @@ def main():
         if args.eager:
             for compute in computes:
                 for _ in range(args.eager):
+                    if compute == "f16kv":
+                        hip.attention_tokens_kv16(q, k.half(), v.half(), heads, scale)
+                        continue
                     hip.attention_tokens(q, k, v, heads, scale, compute=compute)
             torch.cuda.synchronize()
             continue
