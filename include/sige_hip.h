@@ -340,6 +340,11 @@ int64_t sige_hip_conv_side_workgroups(int flushed);
  * finish (still correct, one more launch).  A long-running host that re-captures per mask calls this once every hipGraph
  * captured so far on the CURRENT device has been destroyed: the region is handed out again from the start. */
 int sige_hip_release_graph_tickets(void);
+/* How much of the CURRENT device's graph regions captured launches hold (a measurement aid: a tool that captures several graphs
+ * checks that every split launch it recorded got its slices -- a launch that finds the region exhausted runs unsplit).
+ * which = 0: tickets (of 3 M), 1: workspace floats (of 24 M: the splits of attention_wide, conv_latent_head).  Negative: an error
+ * code (no device; SIGE_HIP_EINVAL for another `which`).                                                                          */
+int sige_hip_split_graph_used(int which);
 
 /* ---- fused gather -> conv and scatter_gather -> conv ------------------------
  * The same MFMA conv with the producer of its input tiles fused into the
@@ -1135,6 +1140,32 @@ int sige_hip_attention_wide_f16c(const float *q, int ldq, const float *k, int ld
 int sige_hip_attention_wide_tiles_f16c(const float *q, int ldq, const float *k, int ldk, const float *v, int ldv,
                                        const int32_t *active_indices, int T, int H, int W, int C, int heads, float scale,
                                        float *out, int ldo, void *stream);
+
+/* ---- ... and both on K / V that are STORED as fp16 --------------------------------------------------------------
+ * sige_hip_attention_wide_f16c / _tiles_f16c with k16, v16 fp16 (_Float16) token matrices; ldk, ldv are row strides in HALVES (>= C),
+ * so k16 and v16 may be the two column halves of one fp16 [B,Nk,2C] tensor; q, out and their strides stay fp32.  The arithmetic
+ * contract is the one stated at sige_hip_attention_tokens_f16c with "k, v rounded to nearest even to fp16" ALREADY DONE in memory
+ * (another channel order inside a score, the same roundings of q and of the probabilities).  Whatever lies behind a head's d
+ * channels in a row -- the next head, the other half of a K | V row, Inf or NaN -- never reaches the head's result: the lanes that
+ * would read it load exact zeros from out of the descriptor's range.  Shape predicate: sige_hip_attention_wide_supported; the key
+ * split is the f16c launch's (sige_hip_attention_wide_f16c_splits).  Status rules of the f16c entries, argument for argument, and
+ * SIGE_HIP_EUNSUPPORTED as well for k16 / v16 not 16-byte aligned, ldk or ldv not a multiple of 8 halves, and Nk * ldk or
+ * Nk * ldv >= 2^29 halves per batch (image).                                                                                     */
+int sige_hip_attention_wide_f16kv_supported(int Nq, int Nk, int C, int heads);
+int sige_hip_attention_wide_f16kv(const float *q, int ldq, const void *k16, int ldk, const void *v16, int ldv,
+                                  int B, int Nq, int Nk, int C, int heads, float scale, float *out, int ldo, void *stream);
+int sige_hip_attention_wide_tiles_f16kv(const float *q, int ldq, const void *k16, int ldk, const void *v16, int ldv,
+                                        const int32_t *active_indices, int T, int H, int W, int C, int heads, float scale,
+                                        float *out, int ldo, void *stream);
+
+/* ---- ... and their producer where K | V lives in a channels-last IMAGE (the SD VAE attention block) ----------------------------
+ * src: fp32 channels-last [1,C,H,W] (memory [H W, C]; C = all channels of the image, K | V together); dst16: an fp16 image of the
+ * same shape and layout.  The cells of the T 4x4 tiles of active_indices (device int32 [T,2], row origin first) are rounded to
+ * nearest even and stored into the same cells of dst16; a cell off the image is skipped, every other cell of dst16 is left as it
+ * is.  Under stacked edits H is the tall image's.  SIGE_HIP_EINVAL: T < 0, non-positive H / W / C, null pointers with work to do.
+ * T == 0: SIGE_HIP_OK, nothing launched.  SIGE_HIP_EUNSUPPORTED: C % 8, a pointer that is not 16-byte aligned.                     */
+int sige_hip_kv_tiles_store_f16(const float *src, void *dst16, const int32_t *active_indices, int T, int H, int W, int C,
+                                void *stream);
 
 /* ---- fp16-STORED caches: the "_f16" forms of SURVEY.md 8b's export list (8f row 4: fp16 cache) ---------------------
  * The reference is fp32-only (sige/nn/base.py:15,55-63).  Here the CACHED tensors of a SIGE model -- Scatter /

@@ -19,6 +19,9 @@
 
 namespace sige {
 
+// (k, v, ldk, ldv: fp32 pointers and strides in floats for the two units named above.  attention_wide_f16kv.hip passes fp16
+// tensors through these same fields -- the pointers cast, the strides in HALVES -- and its kernel casts them back; nothing in this
+// header dereferences k or v, and wide_plan's 2 GiB test then counts a half as four bytes: stricter than needed, never laxer.)
 struct WideAttnArgs {
     const float *q, *k, *v;
     float *out;

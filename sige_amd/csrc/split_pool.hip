@@ -43,6 +43,11 @@ struct DevicePools {
         std::lock_guard<std::mutex> lock(mu);
         dev[d].pool.release_graph();
     }
+
+    size_t graph_used(int d) {
+        std::lock_guard<std::mutex> lock(mu);
+        return dev[d].pool.graph_pos;
+    }
 };
 
 // Tickets: one int per unit of a split launch, zero whenever no such launch is running (zeroed once, put back by the last
@@ -70,4 +75,11 @@ extern "C" int sige_hip_release_graph_tickets(void) {
     sige::g_workspace.release_graph(dev);
     sige::g_tickets.release_graph(dev);
     return SIGE_HIP_OK;
+}
+
+// elements of the current device's graph region that captured launches hold (which = 0: tickets, 1: workspace floats)
+extern "C" int sige_hip_split_graph_used(int which) {
+    int dev = -1;
+    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 32 || which < 0 || which > 1) return SIGE_HIP_EINVAL;
+    return (int)(which == 0 ? sige::g_tickets.graph_used(dev) : sige::g_workspace.graph_used(dev));
 }

@@ -163,6 +163,7 @@ _SIGNATURES = {
         _c_int, [_c_vp, _c_vp] + [_c_int] * 6 + [_c_vp, _c_vp, _c_int, _c_int] + [_c_vp, _c_int, _c_int, _c_vp, _c_int, _c_int, _c_int]
         + [_c_vp, _c_vp, _c_vp, _c_int] + [_c_vp] * 6 + [_c_vp, _c_sz, _c_vp, _c_vp, _c_vp]),
     "sige_hip_release_graph_tickets": (_c_int, []),
+    "sige_hip_split_graph_used": (_c_int, [_c_int]),
     "sige_hip_channel_stats_tiles": (_c_int, [_c_int, _c_int]),
     "sige_hip_channel_stats_nhwc_f32": (_c_int, [_c_vp] + [_c_int] * 4 + [_c_vp, _c_vp]),
     "sige_hip_group_norm_affine_from_stats_f32": (
@@ -182,6 +183,10 @@ _SIGNATURES = {
     "sige_hip_attention_wide_f16c_splits": (_c_int, [_c_int] * 5),
     "sige_hip_attention_wide_f16c": (_c_int, [_c_vp, _c_int] * 3 + [_c_int] * 5 + [ctypes.c_float, _c_vp, _c_int, _c_vp]),
     "sige_hip_attention_wide_tiles_f16c": (_c_int, [_c_vp, _c_int] * 3 + [_c_vp] + [_c_int] * 5 + [ctypes.c_float, _c_vp, _c_int, _c_vp]),
+    "sige_hip_attention_wide_f16kv_supported": (_c_int, [_c_int] * 4),
+    "sige_hip_attention_wide_f16kv": (_c_int, [_c_vp, _c_int] * 3 + [_c_int] * 5 + [ctypes.c_float, _c_vp, _c_int, _c_vp]),
+    "sige_hip_attention_wide_tiles_f16kv": (_c_int, [_c_vp, _c_int] * 3 + [_c_vp] + [_c_int] * 5 + [ctypes.c_float, _c_vp, _c_int, _c_vp]),
+    "sige_hip_kv_tiles_store_f16": (_c_int, [_c_vp] * 3 + [_c_int] * 4 + [_c_vp]),
     # fp16-stored caches
     "sige_hip_gather_nhwc_f16": (
         _c_int, [_c_vp] + [_c_int] * 6 + [_c_vp, _c_int] + [_c_vp, _c_int, _c_int] * 2 + [_c_int, _c_vp, _c_vp]),
@@ -1428,6 +1433,16 @@ def release_graph_tickets():
     """Every hipGraph captured so far on the current device has been destroyed: hand the K-split tickets of captured launches
     out again from the start (include/sige_hip.h: sige_hip_release_graph_tickets)."""
     _check(lib().sige_hip_release_graph_tickets(), "release_graph_tickets")
+
+
+def split_graph_used(which: int = 1) -> int:
+    """Elements of the current device's graph region that captured split launches hold: 0 tickets, 1 workspace floats
+    (sige_hip_split_graph_used).  A tool that captures several graphs reads it around each capture: a split launch that found
+    the region exhausted took nothing and runs unsplit."""
+    used = lib().sige_hip_split_graph_used(int(which))
+    if used < 0:
+        _check(used, "split_graph_used")
+    return used
 
 
 def conv_force_ksplit_pass(second_pass: bool = False):
@@ -2920,6 +2935,26 @@ def kv_rows_store_f16(k_rows: torch.Tensor, v_rows: torch.Tensor, k16: torch.Ten
                                             T, B, int(H), int(W), C, _stream(k16)), "kv_rows_store_f16")
 
 
+def kv_tiles_store_f16(src: torch.Tensor, dst16: torch.Tensor, indices: torch.Tensor) -> None:
+    """The 4x4 tiles of `indices` (the Gather's device int32 [T,2] list) of the channels-last fp32 image `src` [1,C,H,W] rounded to
+    nearest even into the same cells of `dst16`, a channels-last fp16 image of the same shape, written IN PLACE
+    (sige_hip_kv_tiles_store_f16: the producer of attention_wide(compute="f16kv") where K | V is an image); cells off the image
+    are skipped, every other cell of dst16 stays.  T = 0: nothing is launched.  Malformed arguments raise ValueError."""
+    if src.dtype != torch.float32 or dst16.dtype != torch.float16:
+        raise ValueError("kv_tiles_store_f16: src must be fp32 and dst16 fp16")
+    if not (indices.dtype == torch.int32 and indices.dim() == 2 and indices.shape[1] == 2 and indices.is_contiguous()):
+        raise ValueError("kv_tiles_store_f16: indices = the int32 [T,2] index list")
+    if src.dim() != 4 or src.shape[0] != 1 or tuple(src.shape) != tuple(dst16.shape):
+        raise ValueError("kv_tiles_store_f16: src / dst16 are two [1,C,H,W] images of one shape")
+    if not (src.is_contiguous(memory_format=CL) and dst16.is_contiguous(memory_format=CL)):
+        raise ValueError("kv_tiles_store_f16: channels-last images (dst16 is written in place)")
+    if not (src.is_cuda and dst16.is_cuda and indices.is_cuda):
+        raise ValueError("kv_tiles_store_f16: device tensors")
+    _, C, H, W = src.shape
+    _check(lib().sige_hip_kv_tiles_store_f16(src.data_ptr(), dst16.data_ptr(), indices.data_ptr(), indices.shape[0], H, W, C,
+                                             _stream(dst16)), "kv_tiles_store_f16")
+
+
 def _attention_tiles(tiles, B: int, Nq: int, Nk: int, name: str):
     """`tiles` = (active_indices, H, W) of attention_tokens / attention_wide, checked against q [B,Nq,C] and k / v [B,Nk,C] ->
     (index list, int H, int W).  (With `tiles` the `_supported` predicate is not asked first: the entry answers UNSUPPORTED.)"""
@@ -2941,6 +2976,16 @@ def _token_rows(t: torch.Tensor):
     return t, t.stride(1)
 
 
+def _token_rows16(t: torch.Tensor):
+    """_token_rows for an fp16 operand (attention_wide, compute="f16kv"): a lane's 16-byte load is 8 halves, so the row stride is a
+    multiple of 8; anything else is copied (fp16 to fp16: nothing is converted)."""
+    B, N, C = t.shape
+    if not (t.stride(2) == 1 and t.stride(1) >= C and t.stride(1) % 8 == 0 and (B == 1 or t.stride(0) == N * t.stride(1))
+            and t.data_ptr() % 16 == 0):
+        t = t.contiguous()
+    return t, t.stride(1)
+
+
 def attention_wide(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, heads: int, scale: float,
                    out: Optional[torch.Tensor] = None, tiles=None, compute: str = "f32") -> Optional[torch.Tensor]:
     """attention_tokens for WIDE heads (160 < d <= 512, d % 16 == 0; include/sige_hip.h: sige_hip_attention_wide_f32): ONE launch.
@@ -2954,10 +2999,17 @@ def attention_wide(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, heads: int
     origin_row // (H/E).  T = 0: `out` without a launch.
 
     `compute`: "f32" exact fp32 products; "f16" fp16 operands with fp32 accumulation on the same fp32 tensors
-    (sige_hip_attention_wide_f16c / _tiles_f16c: the contract stated at sige_hip_attention_tokens_f16c)."""
-    if compute not in ("f32", "f16"):
-        raise ValueError("attention_wide: compute must be 'f32' or 'f16', got %r" % (compute,))
-    if not (q.is_cuda and q.dtype == k.dtype == v.dtype == torch.float32 and q.dim() == k.dim() == v.dim() == 3):
+    (sige_hip_attention_wide_f16c / _tiles_f16c: the contract stated at sige_hip_attention_tokens_f16c); "f16kv" the same
+    arithmetic on k / v that are STORED as fp16 (sige_hip_attention_wide_f16kv / _tiles_f16kv; q and `out` stay fp32): they are
+    read in place like the fp32 operands (row stride a multiple of 8 halves), and k / v of another dtype raise ValueError --
+    nothing is converted here (the producers: kv_tiles_store_f16, or one .half() of the whole tensor)."""
+    if compute not in ("f32", "f16", "f16kv"):
+        raise ValueError("attention_wide: compute must be 'f32', 'f16' or 'f16kv', got %r" % (compute,))
+    kv16 = compute == "f16kv"
+    if kv16 and not (q.dtype == torch.float32 and k.dtype == v.dtype == torch.float16):
+        raise ValueError("attention_wide: compute='f16kv' takes q fp32 and k / v fp16, got %s / %s / %s" % (q.dtype, k.dtype, v.dtype))
+    if not (q.is_cuda and q.dtype == torch.float32 and k.dtype == v.dtype == (torch.float16 if kv16 else torch.float32)
+            and q.dim() == k.dim() == v.dim() == 3):
         return None
     B, Nq, C = q.shape
     if tuple(k.shape) != tuple(v.shape) or k.shape[0] != B or k.shape[2] != C:
@@ -2967,17 +3019,20 @@ def attention_wide(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, heads: int
         idx, H, W = _attention_tiles(tiles, B, Nq, Nk, "attention_wide")
     elif not lib().sige_hip_attention_wide_supported(Nq, Nk, C, heads):
         return None
-    (q, ldq), (k, ldk), (v, ldv) = _token_rows(q), _token_rows(k), _token_rows(v)
+    rows_kv = _token_rows16 if kv16 else _token_rows
+    (q, ldq), (k, ldk), (v, ldv) = _token_rows(q), rows_kv(k), rows_kv(v)
     if out is None:
         out = torch.empty((B, Nq, C), dtype=torch.float32, device=q.device)
     elif tuple(out.shape) != (B, Nq, C) or out.dtype != torch.float32 or _token_rows(out)[0] is not out:
         raise ValueError("attention_wide: `out` must be a [B,Nq,C] fp32 tensor with contiguous rows")
     if tiles is not None:
-        entry = lib().sige_hip_attention_wide_tiles_f16c if compute == "f16" else lib().sige_hip_attention_wide_tiles_f32
+        entry = {"f32": lib().sige_hip_attention_wide_tiles_f32, "f16": lib().sige_hip_attention_wide_tiles_f16c,
+                 "f16kv": lib().sige_hip_attention_wide_tiles_f16kv}[compute]
         status = entry(q.data_ptr(), ldq, k.data_ptr(), ldk, v.data_ptr(), ldv, idx.data_ptr(), Nq // 16, H, W, C, heads,
                        float(scale), out.data_ptr(), max(out.stride(1), C), _stream(q))
     else:
-        entry = lib().sige_hip_attention_wide_f16c if compute == "f16" else lib().sige_hip_attention_wide_f32
+        entry = {"f32": lib().sige_hip_attention_wide_f32, "f16": lib().sige_hip_attention_wide_f16c,
+                 "f16kv": lib().sige_hip_attention_wide_f16kv}[compute]
         status = entry(q.data_ptr(), ldq, k.data_ptr(), ldk, v.data_ptr(), ldv, B, Nq, Nk, C, heads, float(scale), out.data_ptr(),
                        out.stride(1), _stream(q))
     if status == UNSUPPORTED:

@@ -101,6 +101,13 @@ class _OutputBuffers:
             self.bufs[cache_id] = entry
         return entry[1]
 
+    def state(self, cache_id):
+        """(key, buffer) of `cache_id`'s persistent output as it stands, or None: the key -- mask stamp, cache generation, shape,
+        strides -- changes whenever the buffer is rebuilt or restored, so whoever derives something from the buffer (sd_vae's fp16
+        twin) remembers it and knows a stale derivative by it."""
+        entry = self.bufs.get(cache_id)
+        return None if entry is None else (entry[0], entry[1])
+
     def invalidate(self, cache_id=None):
         """The cached tensor of `cache_id` (None: of every id) was replaced or rewritten."""
         for k in ([cache_id] if cache_id is not None else set(self.bufs) | set(self.gen)):

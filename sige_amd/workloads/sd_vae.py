@@ -58,6 +58,10 @@ NATIVE_HEAD = True
 # The arithmetic of the attention launch: "f32" exact fp32 products, "f16" fp16 operands with fp32 accumulation on the same fp32
 # tensors (sige_hip_attention_wide_f16c / sige_hip_attention_tokens_f16c), None: the model's compute policy -- "f16" where the block's
 # `q` conv has compute dtype "f16" (set_compute_dtype("f16") without a `keep` prefix naming it), "f32" otherwise ("f16x3" included).
+# "f16kv" (opt-in; None never resolves to it): the "f16" arithmetic on an fp16 TWIN of the persistent K | V that a block
+# with more than 160 channels keeps beside the fp32 tensor (hip.attention_wide, compute="f16kv": sige_hip_attention_wide_f16kv) -- a
+# faster launch, not a memory saving: the twin is one more tensor of half the fp32 tensor's bytes per cache id.  Blocks with <= 160
+# channels, sparse_update and a block without a twin run the "f16" launch.
 ATTENTION_COMPUTE = None
 # precision order of the compute dtypes: the derived K | V conv takes the higher one of `k` and `v`
 _PRECISION = {"f16": 0, "f16x3": 1, "f32": 2}
@@ -151,12 +155,14 @@ class VAEAttnBlock(SIGEModule):
         self.kv_scatter = Scatter(self.gather)
         self.affine = {}      # cache_id -> (scale, shift) as [1,C,1,1]
         self._attn_out = None  # [1, 16 * active tiles, C]: the attention launch's output rows (alloc_buffers)
+        self._kv16 = {}        # cache_id -> (key of the persistent K | V, that tensor, its fp16 twin): ATTENTION_COMPUTE = "f16kv"
         self.plain = False
         self.edit_batch = 1    # stacked edits (sige_amd/stacked.py: `with stacked.edit_batch(model, E)`)
 
     def clear_cache(self):
         self.affine = {}
         self._attn_out = None
+        self._kv16 = {}
         self.__dict__.pop("_kv_conv", None)
 
     # ---- derived: the C -> 2C conv (k | v) ------------------------------------------------------------------------------------
@@ -203,20 +209,64 @@ class VAEAttnBlock(SIGEModule):
         if kv is None or g.active_indices is None:
             return
         if self.kv_scatter.inplace:
-            self.kv_scatter._out_bufs.get(self.cache_id, kv, g.timestamp)
+            self._refresh_kv16(self.kv_scatter._out_bufs.get(self.cache_id, kv, g.timestamp))
         self.folded_kv()
         rows = 16 * int(g.active_indices.shape[0]) * kv.shape[0]
         buf = self._attn_out
         if buf is None or buf.shape[1] != rows or buf.device != kv.device:
             self._attn_out = torch.empty((1, rows, self.ch), dtype=torch.float32, device=kv.device)
 
+    # ---- the fp16 twin of the persistent K | V (ATTENTION_COMPUTE = "f16kv") -----------------------------------------------------------
+    def _refresh_kv16(self, kv: torch.Tensor):
+        """`kv`: the persistent fp32 K | V of the current cache id as alloc_buffers() has just restored it (the original's values
+        everywhere).  The twin is its whole-tensor copy rounded to nearest even to fp16 -- one library launch, so a launch plan
+        records it behind the restore --, made here and nowhere else: outside any forward, under the switch only, and remembered
+        with the key the Scatter module keeps for `kv` (mask stamp and cache generation: explicit counters, never a tensor's
+        address or version).  A forward then rewrites the active tiles of both (kv_scatter.forward_fused, hip.kv_tiles_store_f16).
+        The twin sits BESIDE the fp32 tensor (+8 MB per cache id at 512 channels, 64 x 64): a faster launch, no memory saving."""
+        cid = self.cache_id
+        if ATTENTION_COMPUTE != "f16kv" or self.ch <= 160 or self.sparse_update or kv.numel() % 4:
+            self._kv16.pop(cid, None)
+            return
+        from .. import hip
+
+        old = self._kv16.get(cid)
+        twin = old[2] if old is not None and old[2].shape == kv.shape and old[2].device == kv.device else \
+            torch.empty_like(kv, dtype=torch.float16, memory_format=torch.preserve_format)
+        hip.copy_dense_(twin, kv)
+        self._kv16[cid] = (self.kv_scatter._out_bufs.state(cid)[0], kv, twin)
+
+    def _kv16_twin(self, cid=None):
+        """The twin of cache id `cid`'s (default: the current one's) persistent K | V, or None: none was made (the switch came on
+        after set_masks() / set_mode(), a block driven module by module) or it was made for another state of that tensor (the
+        Scatter module rebuilt or restored its output since: _OutputBuffers.state)."""
+        cid = self.cache_id if cid is None else cid
+        entry, cur = self._kv16.get(cid), self.kv_scatter._out_bufs.state(cid)
+        if entry is None or cur is None or cur[1] is not entry[1] or cur[0] != entry[0]:
+            return None
+        return entry[2]
+
+    def rebuild_derived_caches(self):
+        """(sige_amd.parallel.refresh_derived) the caches were rewritten in place and every persistent Scatter output re-copied
+        under its old key: the twins follow, in place -- without this hook a cache broadcast would leave them stale."""
+        from .. import hip
+
+        for cid in list(self._kv16):
+            twin = self._kv16_twin(cid)
+            if twin is None:
+                self._kv16.pop(cid)
+            else:
+                hip.copy_dense_(twin, self._kv16[cid][1])
+
     def persistent_buffers(self):
         """(tests) [(name, tensor, rewritten)]: `rewritten` = the forward writes every element it later reads -- K | V is rewritten
-        on the active tiles only; everywhere else it carries the original's values (a cache)."""
+        on the active tiles only; everywhere else it carries the original's values (a cache), and so does its fp16 twin."""
         out = []
         entry = self.kv_scatter._out_bufs.bufs.get(self.cache_id)
         if entry is not None:
             out.append(("kv", entry[1], False))
+        if self._kv16_twin() is not None:
+            out.append(("kv16", self._kv16_twin(), False))
         if self._attn_out is not None:
             out.append(("attn_out", self._attn_out, True))
         return out
@@ -289,12 +339,12 @@ class VAEAttnBlock(SIGEModule):
                            "keys --, which only hip.attention_wide(tiles=...) does: %s (this block has %d channels)" % (needs, self.ch))
 
     def attention_compute(self) -> str:
-        """ "f32" | "f16": `ATTENTION_COMPUTE`, or under None the compute policy as it reached `q`."""
+        """ "f32" | "f16" | "f16kv": `ATTENTION_COMPUTE`, or under None the compute policy as it reached `q` (never "f16kv")."""
         compute = ATTENTION_COMPUTE
         if compute is None:
             compute = "f16" if getattr(self.q, "compute_dtype", "f32") == "f16" else "f32"
-        if compute not in ("f32", "f16"):
-            raise ValueError("sd_vae.ATTENTION_COMPUTE must be None, 'f32' or 'f16', got %r" % (compute,))
+        if compute not in ("f32", "f16", "f16kv"):
+            raise ValueError("sd_vae.ATTENTION_COMPUTE must be None, 'f32', 'f16' or 'f16kv', got %r" % (compute,))
         return compute
 
     def _sparse_fused(self, x, s, t, stacked=False):
@@ -325,6 +375,11 @@ class VAEAttnBlock(SIGEModule):
         tok = kv.permute(0, 2, 3, 1).reshape(1, H * W, 2 * C)
         scale = int(C) ** (-0.5)
         compute = self.attention_compute()
+        kv16 = self._kv16_twin() if compute == "f16kv" and C > 160 else None
+        if kv16 is not None and self._kv16[self.cache_id][1] is not kv:
+            kv16 = None  # (the launch above wrote another tensor than the one the twin was made for)
+        if compute == "f16kv":
+            compute = "f16"  # (the launch on the fp32 tensor: <= 160 channels, no twin, a refusal of the f16kv entry)
         if C <= 160:
             o = hip.attention_tokens(qt, tok[:, :, :C], tok[:, :, C:], 1, scale, compute=compute)
         else:
@@ -333,8 +388,15 @@ class VAEAttnBlock(SIGEModule):
                 # (not reached after set_masks() / set_mode(): only a block driven module by module allocates here)
                 buf = self._attn_out = torch.empty((1, 16 * T, C), dtype=torch.float32, device=x.device)
             # stacked edits: kv is the tall image; tile t's keys are the rows of the image its origin row lies in, found inside the launch
-            o = hip.attention_wide(qt, tok[:, :, :C], tok[:, :, C:], 1, scale, out=buf,
-                                   tiles=(g.active_indices, H, W) if stacked else None, compute=compute)
+            tiles = (g.active_indices, H, W) if stacked else None
+            o = None
+            if kv16 is not None:
+                # the tiles the launch above has just written, rounded into the twin; then K and V read as they are stored
+                hip.kv_tiles_store_f16(kv, kv16, g.indices_on(kv.device))
+                tok16 = kv16.permute(0, 2, 3, 1).reshape(1, H * W, 2 * C)
+                o = hip.attention_wide(qt, tok16[:, :, :C], tok16[:, :, C:], 1, scale, out=buf, tiles=tiles, compute="f16kv")
+            if o is None:
+                o = hip.attention_wide(qt, tok[:, :, :C], tok[:, :, C:], 1, scale, out=buf, tiles=tiles, compute=compute)
         if o is None and stacked:
             self._refuse_stacked("a shape sige_hip_attention_wide_tiles_f32 / _f16c takes (one image's height a power of two >= 4; K | V is "
                                  "%d x %d for the whole edit batch)" % (H, W))

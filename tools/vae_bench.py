@@ -89,26 +89,40 @@ def attention_alone(tiles, reps, steps):
 
 
 def attention_forms_alone(tiles, reps, steps):
-    """hip.attention_wide in both arithmetic forms and the torch chain at the decoder's shape for `tiles` active 4x4 tiles: three graphs
-    of `reps` launches, rotated, medians of 7."""
+    """hip.attention_wide in its arithmetic forms -- "f32", "f16", and "f16kv" on the fp16 copy of the same K | V -- and the torch chain at
+    the decoder's shape for `tiles` active 4x4 tiles: four graphs of at most `reps` launches, rotated, medians of 7.
+
+    Every captured split launch keeps its workspace slices for the life of its graph, out of a bounded region (hip.split_graph_used);
+    one that finds the region exhausted runs UNSPLIT -- another launch altogether at these few query tiles.  So the caller has
+    released the region, `reps` is lowered until the three forms' launches fit, and after each capture the region must have grown by
+    exactly the launches' slices: every timed launch has the split the decoder's launch has."""
     import torch
 
     from benchlib.common import capture_fn
     from sige_amd import hip
 
     Nq, Nk, d = 16 * tiles, LATENT * LATENT, 512
+    splits = getattr(hip.lib().sige_hip_attention_wide_f16c_splits, "fn", hip.lib().sige_hip_attention_wide_f16c_splits)
+    ksplit = splits(1, Nq, Nk, d, 1)
+    need = tiles * ksplit * (4 * (d // 64) + 1) * 256 if ksplit > 1 else 0  # floats per launch: attention_wide_image.hpp, wide_plan
+    room = (24 << 20) - hip.split_graph_used(1)
+    if need:
+        reps = min(reps, room // (3 * need))
+    assert reps >= 1, "the graph region has no room for one launch of each form (%d floats each, %d left)" % (need, room)
     g = torch.Generator().manual_seed(tiles)
     q = (torch.randn(1, Nq, d, generator=g) * 2.0).cuda()
     kv = torch.randn(1, Nk, 2 * d, generator=g).cuda()
     k, v = kv[:, :, :d], kv[:, :, d:]
     kc, vc = k.contiguous(), v.contiguous()
     scale = d ** -0.5
-    outs = {c: torch.empty(1, Nq, d, device="cuda") for c in ("f32", "f16")}
+    kv16 = kv.half()
+    operands = {"f32": (k, v), "f16": (k, v), "f16kv": (kv16[:, :, :d], kv16[:, :, d:])}
+    outs = {c: torch.empty(1, Nq, d, device="cuda") for c in operands}
 
     def native(compute):
         def run():
             for _ in range(reps):
-                hip.attention_wide(q, k, v, 1, scale, out=outs[compute], compute=compute)
+                hip.attention_wide(q, *operands[compute], 1, scale, out=outs[compute], compute=compute)
             return outs[compute]
         return run
 
@@ -117,27 +131,39 @@ def attention_forms_alone(tiles, reps, steps):
             o = torch.bmm(torch.softmax(torch.bmm(q, kc.transpose(1, 2)) * scale, dim=2), vc)
         return o
 
-    graphs = {"f32": capture_fn(native("f32")), "f16": capture_fn(native("f16")), "torch_chain": capture_fn(chain)}
+    graphs = {}
+    for compute in operands:
+        native(compute)()  # (eager once: the first use of the pools is not inside a capture)
+        used = hip.split_graph_used(1)
+        graphs[compute] = capture_fn(native(compute))
+        took = hip.split_graph_used(1) - used
+        assert took == reps * need, "%s: %d captured launches took %d workspace floats, %d with their split of %d" % (
+            compute, reps, took, reps * need, ksplit)
+    graphs["torch_chain"] = capture_fn(chain)
     names = list(graphs)
     us = {n: [] for n in names}
     for i in range(7):
-        for n in names[i % 3:] + names[:i % 3]:
+        for n in names[i % 4:] + names[:i % 4]:
             us[n].append(events_ms(graphs[n][0], steps, 3) * 1e3 / reps)
     flop = 4.0 * Nq * Nk * d
-    row = {"tiles": tiles, "Nq": Nq, "Nk": Nk, "d": d, "flop": flop}
+    row = {"tiles": tiles, "Nq": Nq, "Nk": Nk, "d": d, "flop": flop, "launches_per_graph": reps, "key_split_of_every_launch": ksplit,
+           "split_workspace_floats_per_launch": need}
     for n in names:
         row[n + "_us"] = round(statistics.median(us[n]), 2)
         row[n + "_us_min_max"] = [round(min(us[n]), 2), round(max(us[n]), 2)]
     row["f16_not_slower_than_f32"] = bool(row["f16_us"] <= row["f32_us"])
     row["f16_tflops"] = round(flop / (row["f16_us"] * 1e-6) / 1e12, 2)
     row["max_abs_f16_minus_f32"] = float((graphs["f16"][1] - graphs["f32"][1]).abs().max())
+    row["f16kv_over_f16"] = round(row["f16kv_us"] / row["f16_us"], 3)
+    row["max_abs_f16kv_minus_f16"] = float((graphs["f16kv"][1] - graphs["f16"][1]).abs().max())
     return row
 
 
 def child_f16(a):
     """--dtype f16, one ratio: the sparse forward in f16 mode (a), in f32 mode (b: a second model with its own caches), in f16 mode
-    with sd_vae.ATTENTION_COMPUTE = "f32" (c), as graphs that alternate batch by batch; the library launches of each; the attention
-    launch alone in both forms beside the torch chain."""
+    with sd_vae.ATTENTION_COMPUTE = "f32" (c) and = "f16kv" (d: the attention on the block's fp16 twin of K | V, the producer launch
+    included), as graphs that alternate batch by batch; the library launches of each; the attention launch alone in its forms beside
+    the torch chain."""
     import torch
 
     from benchlib.common import capture_fn
@@ -166,8 +192,10 @@ def child_f16(a):
             m.set_mode("full")
             m(cl(z0))
             masks = downsample_mask(dilate_mask(mask.to(dev), 2), LATENT)
+            sd_vae.ATTENTION_COMPUTE = "f16kv"  # (the twin is made where the buffers are: by set_masks() / set_mode())
             m.set_masks(masks)
             m.set_mode("sparse")
+            sd_vae.ATTENTION_COMPUTE = None
             models[dtype] = m
         m64 = masks[(LATENT, LATENT)].cpu()
         edits = [cl(z0 + n * m64) for n in noises]
@@ -175,28 +203,39 @@ def child_f16(a):
         tiles = int(models["f16"].mid.attn_1.gather.active_indices.shape[0])
         row["attention_tiles"] = tiles
         graphs, outs = {}, {}
-        for name, dtype, attention in (("a_f16", "f16", "f16"), ("b_f32", "f32", "f32"), ("c_f16_attention_f32", "f16", "f32")):
+        for name, dtype, attention in (("a_f16", "f16", "f16"), ("b_f32", "f32", "f32"), ("c_f16_attention_f32", "f16", "f32"),
+                                       ("d_f16_attention_f16kv", "f16", "f16kv")):
             sd_vae.ATTENTION_COMPUTE = attention
             m = models[dtype]
             m(z1)
             n0 = hip.launch_count()
             m(z1)
             row[name + "_library_launches"] = hip.launch_count() - n0
+            used = hip.split_graph_used(1)
             graphs[name], outs[name] = capture_fn(lambda m=m: m(z1))
+            # (the workspace slices the captured attention launch holds: 0 would be a launch that found the region exhausted and
+            #  runs unsplit -- attention_forms_alone)
+            row[name + "_split_workspace_floats"] = hip.split_graph_used(1) - used
         sd_vae.ATTENTION_COMPUTE = None
+        took = [row[n + "_split_workspace_floats"] for n in graphs]
+        assert min(took) == max(took) > 0, "the captured attention launches do not have the same key split: %s" % (took,)
         ms = {k: [] for k in graphs}
         names = list(graphs)
         for batch in range(a.batches):
             z1.copy_(edits[batch % len(edits)])
-            for name in names[batch % 3:] + names[:batch % 3]:
+            for name in names[batch % 4:] + names[:batch % 4]:
                 ms[name].append(events_ms(graphs[name], a.steps, 5))
+        row["a_minus_d_max_abs"] = float((outs["a_f16"] - outs["d_f16_attention_f16kv"]).abs().max())
         row["a_minus_b_max_abs"] = float((outs["a_f16"] - outs["b_f32"]).abs().max())
         row["a_minus_c_max_abs"] = float((outs["a_f16"] - outs["c_f16_attention_f32"]).abs().max())
         for name, v in ms.items():
             row[name + "_ms"] = round(statistics.median(v), 4)
             row[name + "_ms_min_max"] = [round(min(v), 4), round(max(v), 4)]
         row["f16_over_f32"] = round(row["a_f16_ms"] / row["b_f32_ms"], 3)
+        row["f16kv_over_f16"] = round(row["d_f16_attention_f16kv_ms"] / row["a_f16_ms"], 3)
         del graphs
+        torch.cuda.synchronize()
+        hip.release_graph_tickets()  # (the forward graphs are gone: their slices start over)
         row["attention_alone"] = attention_forms_alone(tiles, a.reps, a.steps)
     print("VAE_BENCH_ROW " + json.dumps(row), flush=True)
 
