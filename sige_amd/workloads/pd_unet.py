@@ -22,7 +22,8 @@ On the CPU, in NCHW and on any backend without the fused channels-last path ever
 (affine -> swish -> avg_pool2d / interpolate -> gather).
 
 Stacked edits (sige_amd/stacked.py): under `stacked.edit_batch(model, E)` the model takes [E,3,H,W] in sparse mode.
-conv_in (image by image, see forward), norm_out and conv_out are whole-image ops on [E,C,H,W]; in between every tensor is the tall image [1,C,E*H,W] and every block runs its fused
+conv_in (ONE launch at batch E), norm_out and conv_out are whole-image ops on [E,C,H,W]; in between every tensor is the tall image
+[1,C,E*H,W] and every block runs its fused
 launches on it (hip.resample_tiles with the tiles of all E images; attention over the same bytes seen as [E, tokens, 3c], one launch).
 There is no chain to fall back to: NCHW, the CPU, FUSED_RESAMPLE = False, a block without a fused form and a shape the attention entry
 does not take raise a RuntimeError that names stacked edits."""
@@ -546,13 +547,7 @@ class PDSparseUNet(SIGEModel):
     def forward(self, x: torch.Tensor, logsnr: torch.Tensor) -> torch.Tensor:
         assert x.shape[2] == x.shape[3] == self.resolution
         temb = self._temb(logsnr)
-        if self.mode == "sparse" and self.edit_batch > 1 and x.shape[0] > 1 and x.is_cuda:
-            # stacked edits: the first conv image by image.  ONE launch of the library's first conv at batch 8 (64 output channels,
-            # 128 x 128) returned wrong pixels in some images, differently from run to run, while its launches on one image each
-            # are right (found with tools/pd_bench.py --stacked, cause not found)
-            h0 = torch.cat([input_conv2d(self.conv_in, x[e:e + 1]) for e in range(x.shape[0])])
-        else:
-            h0 = input_conv2d(self.conv_in, x) if self.mode == "sparse" else self.conv_in(x)
+        h0 = input_conv2d(self.conv_in, x) if self.mode == "sparse" else self.conv_in(x)
         if x.is_contiguous(memory_format=torch.channels_last) and not x.is_contiguous():
             h0 = h0.contiguous(memory_format=torch.channels_last)  # (MIOpen may hand back NCHW for 3 input channels)
         E = self.edit_batch

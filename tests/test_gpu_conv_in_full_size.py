@@ -1,6 +1,7 @@
 """The first-layer conv (csrc/conv_in.hip) at the size the networks run it, 1 x 3 x 256 x 256, for every supported width against
 torch's conv: the 32- and 64-channel forms gave wrong pixels there, intermittently (profiles/conv_in_narrow_probe.txt), and the
-smaller shapes of tests/test_gpu_channels_last.py never showed it.  Four launches per width: the fault was not in every launch."""
+smaller shapes of tests/test_gpu_channels_last.py never showed it.  Four launches per width: the fault was not in every launch.
+Batch > 1 on up to 2048 workgroups, ragged, NCHW and batch-strided inputs and the tile-list form: tests/test_gpu_conv_in_batch.py."""
 import pytest
 import torch
 

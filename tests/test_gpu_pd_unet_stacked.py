@@ -270,6 +270,7 @@ def test_stacked_edits_vs_cpu_oracle_and_single_edits_over_poisoned_shortcut_buf
 
         print("pd_unet small: %d library launches stacked (E=%d), %d single" % (launches, E, single_launches))
         _record_launches("small configuration", E, launches, single_launches)
+        assert launches == single_launches  # (the first conv is ONE launch at batch E: no launch more than a single edit's forward)
         tiled = [r for r in log if r[0].startswith("resample") and r[1]]
         assert [r[0] for r in tiled] == ["resample down", "resample down", "resample up"], log
         assert all(n == 1 and b == 1 for _, _, b, n, _ in tiled), log  # ONE launch per tiled resampling block
@@ -398,6 +399,7 @@ def test_pd128_two_stacked_edits():
     util.assert_finite(got, "pd128 stacked output")
     print("pd_unet pd128: %d library launches stacked (E=2), %d single" % (launches, single_launches))
     _record_launches("pd128", 2, launches, single_launches)
+    assert launches == single_launches
     check_pd128(full, got[0:1], util.CONV_ATOL, lambda what, value, tol: util.record_margin(TEST + " pd128 E=2 edit 0", what, value, tol))
     own = float((got[1] - single[0]).abs().max())
     print("pd_unet pd128 E=2 edit 1: vs single %.3e" % own)
