@@ -1,15 +1,39 @@
-// Shared by the transposed-score attention kernels (attention_tokens.hip, attention_tokens_f16.hip, attention_wide.hip,
-// attention_wide_f16.hip): the row maximum -- lane (kq, j) holds scores of query j, the four lane rows kq of a query meet in two
-// v_permlane*_swap --, the weight of a partial softmax state in a merge, the image of a query tile under stacked edits; for the two
-// token units also the workgroup -> (pair, query tile) mapping; on the host the
-// argument check of the batched entries and the geometry of the `_tiles_` entries.  (What only the wide pair shares:
-// attention_wide_image.hpp.)
+// Shared by the six transposed-score attention units (attention_tokens.hip, attention_tokens_f16.hip, attention_tokens_f16kv.hip,
+// attention_wide.hip, attention_wide_f16.hip, attention_wide_f16kv.hip): the row maximum -- lane (kq, j) holds scores of query j, the
+// four lane rows kq of a query meet in two v_permlane*_swap --, the weight of a partial softmax state in a merge, the image of a query
+// tile under stacked edits; for the four fp16-operand units the vector types, the rounding pack, the shift P is carried with and the
+// buffer offset that loads zeros; for the three token units also the workgroup -> (pair, query tile) mapping; on the host the
+// argument checks of the batched and of the `_tiles_` entries (_f32 / _f16c / _f16kv alike) and the geometry of the latter.
+// (What only the token trio shares: attention_tokens_image.hpp; only the wide trio: attention_wide_image.hpp.)
 #pragma once
 #include "common.hpp"
 
 namespace sige {
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
+typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
+typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
+typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
+typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
+
+// The fp16-operand kernels carry P as exp2(s - m + P_SHIFT), at most 2^15 (attention_tokens_f16.hip says why); the factor is in
+// every wave's and every split's l and O alike and cancels in O / l.
+constexpr float P_SHIFT = 15.f;
+// A buffer offset past every descriptor of the f16kv kernels (one image's K or V < 2 GiB): the load returns zeros.
+constexpr unsigned OUT_OF_RANGE = 0x80000000u;
+
+__device__ __forceinline__ f16x8 pack8(f32x4 a, f32x4 b) {  // (fptrunc: round to nearest even)
+    const f16x4 lo = __builtin_convertvector(a, f16x4);
+    const f16x4 hi = __builtin_convertvector(b, f16x4);
+    return __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
+}
+// (the token kernels hold their fragments as float4: as f32x4 from the load on, every instance compiled to other code)
+// (written out, not a call of the form above: through the call the Q pack of two f16kv instances was scheduled differently)
+__device__ __forceinline__ f16x8 pack8(float4 a, float4 b) {
+    const f16x4 lo = __builtin_convertvector(f32x4{a.x, a.y, a.z, a.w}, f16x4);
+    const f16x4 hi = __builtin_convertvector(f32x4{b.x, b.y, b.z, b.w}, f16x4);
+    return __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
+}
 
 // (v_permlane32_swap a, b: a's lanes 32..63 <-> b's lanes 0..31; with a == b == v both end up holding a half of v twice, max(a, b)
 //  is max(v[l], v[l ^ 32]) in every lane; v_permlane16_swap likewise for the odd / even rows of 16.  Inline asm: the clang builtin of
@@ -31,7 +55,7 @@ __device__ __forceinline__ float max_over_rows(float v) {
 // key (m = -inf, where M may be -inf too) weighs nothing.
 __device__ __forceinline__ float merge_weight(float m, float M) { return m == -INFINITY ? 0.f : __builtin_amdgcn_exp2f(m - M); }
 
-// Stacked edits in the token kernels (sige_hip_attention_tokens_tiles_f32 / _f16c): the image of query tile `qtile` -- its origin row
+// Stacked edits in the token kernels (sige_hip_attention_tokens_tiles_f32 / _f16c / _f16kv): the image of query tile `qtile` -- its origin row
 // tiles[2 qtile] of the tall image >> log2 of one image's height, clamped into [0, images - 1] so that no index list can move the
 // K / V descriptors outside k / v (the rule of attention_wide.hip).  The index is the same in every lane and made uniform: ONE
 // scalar load per workgroup, a shift and two scalar min / max in front of the pointer arithmetic -- no branch, no division.
@@ -63,7 +87,7 @@ __device__ __forceinline__ void workgroup_pair_tile(int q_tiles, int xcd_pairs, 
 
 // ---- host ----
 
-// The argument check of the four batched entries (row strides: the smallest of them, C where rows are dense).  true: there is a
+// The argument check of the six batched entries (row strides: the smallest of them, C where rows are dense).  true: there is a
 // launch to make; false: *status is the entry's answer -- bad arguments, or no query and nothing to do.
 inline bool attention_batch_args(int B, int Nq, int Nk, int C, int heads, int ld_min, const void *q, const void *k, const void *v,
                                  const void *out, int *status) {
@@ -72,6 +96,17 @@ inline bool attention_batch_args(int B, int Nq, int Nk, int C, int heads, int ld
     if (ld_min < C) return false;
     if ((long)B * Nq == 0) { *status = SIGE_HIP_OK; return false; }
     return q && k && v && out;
+}
+
+// The argument check of the six `_tiles_` entries in front of stacked_keys, in the order include/sige_hip.h states: sizes, row strides
+// (as above), the empty list, null pointers -- the index list among them.  true: go on; false: *status is the entry's answer.
+inline bool attention_tiles_args(int T, int H, int W, int C, int heads, int ld_min, const void *q, const void *k, const void *v,
+                                 const void *out, const int32_t *active_indices, int *status) {
+    *status = SIGE_HIP_EINVAL;
+    if (T < 0 || H <= 0 || W <= 0 || C <= 0 || heads <= 0) return false;
+    if (ld_min < C) return false;
+    if (T == 0) { *status = SIGE_HIP_OK; return false; }
+    return q && k && v && out && active_indices;
 }
 
 // Stacked edits (sige_hip_set_edit_batch) as a `_tiles_` entry sees them: the queries are the tokens of T active 4x4 tiles of the

@@ -28,7 +28,7 @@
 //
 // q [B,Nq,C], k / v [B,Nk,C], out [B,Nq,C], C = heads * d, all row-major fp32 (a channels-last [B,C,H,W] tensor IS [B,HW,C];
 // channels-last tiles [T,C,4,4] ARE [T*16, C]: no copy on either side).  Nq % 16 == 0; Nk arbitrary (tail keys masked).
-#include "attention_rows.hpp"
+#include "attention_tokens_image.hpp"  // (attention_tokens_t_kernel's place, merge image and launcher: shared with the two fp16 forms)
 
 namespace sige {
 
@@ -237,20 +237,14 @@ void attention_tokens_t_kernel(const float *__restrict__ q, const float *__restr
                                float *__restrict__ out, int Nq, int Nk, int C, int heads, int d, float scale_log2e,
                                int q_tiles, int xcd_pairs, const int32_t *__restrict__ tiles, int img_shift, int images) {
     constexpr int DT = UNITS;           // 16-channel tiles of O
-    constexpr int OS = UNITS * 16 + 4;  // padded row of the merge buffer (a multiple of 4 floats: 16-byte rows)
+    constexpr int OS = tokens_image_row(DT);
     __shared__ float m_lds[4][16], l_lds[4][4][16];
     extern __shared__ __attribute__((aligned(16))) float o_lds[];  // [4 waves][16 queries][OS]
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int kq = lane >> 4, j = lane & 15;
-    int pair, qtile;  // (workgroup -> XCD: attention_rows.hpp)
-    workgroup_pair_tile(q_tiles, xcd_pairs, pair, qtile);
-    const int head = pair % heads, b = pair / heads;
-    const int q0 = qtile * 16;
-    const size_t hoff = (size_t)head * d;
-    const size_t kv0 = ((size_t)b + tile_image<TILES>(tiles, qtile, img_shift, images)) * Nk * C + hoff;
-    const float *kb = k + kv0;
-    const float *vb = v + kv0;
+    const TokensPlace p = tokens_place<TILES>(Nk, C, heads, d, q_tiles, xcd_pairs, tiles, img_shift, images);
+    const int tid = p.tid, wave = p.wave, kq = p.kq, j = p.j, b = p.b, q0 = p.q0;
+    const size_t hoff = p.hoff;
+    const float *kb = k + p.kv0;
+    const float *vb = v + p.kv0;
 
     // Q of this lane = the B operand: query j, channels 16u + 4kq .. +3 of every unit (zeros beyond d)
     float4 qr[UNITS];
@@ -385,51 +379,33 @@ namespace sige {
 // Both entry points: q [B,Nq,C] against k / v of Nk keys per batch -- or, with `tiles` (B = 1), per image of 2^img_shift rows.
 static int launch_attention_tokens(const float *q, const float *k, const float *v, int B, int Nq, int Nk, int C, int heads, float scale,
                                    float *out, const int32_t *tiles, int img_shift, int images, void *stream) {
-    if (!sige_hip_attention_tokens_supported(Nq, Nk, C, heads)) return SIGE_HIP_EUNSUPPORTED;
-    auto al = [](const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; };
-    // (32-bit byte offsets into one batch's -- one image's -- K / V)
-    if (!al(q) || !al(k) || !al(v) || !al(out) || (size_t)Nk * C * sizeof(float) >= 0x7fffffffu) return SIGE_HIP_EUNSUPPORTED;
-    const int d = C / heads;
-    const int units = (d + 15) / 16;
-    const float sl = scale * 1.44269504088896341f;
-    hipStream_t st = as_stream(stream);
     // forms: 0 (automatic) = the transposed-score kernel (round 6); 1 = round 4's 16 queries per workgroup with P through LDS;
     // 2 = 32 queries per workgroup (two query tiles share every K / V fragment a wave loads; d <= 96) -- measured equal to form 1
     // at SD's shapes (profiles/r4i_bench_sd.json).  1 and 2 are kept for the A/B in the measurement build.  With `tiles` the two
     // tiles of form 2 may belong to two images: knob 2 is form 1 there.
     const int knob = tuning(SIGE_HIP_TUNE_ATTENTION_FORM);
-    const int form = tiles ? (knob == 1 || knob == 2 ? 1 : 0) : (knob == 2 && units <= 6) ? 2 : (knob == 1 ? 1 : 0);
-    const int pairs = B * heads, t16 = Nq / 16, t32 = (Nq + 31) / 32;
-    if ((long)pairs * t16 > 0x7fffffffL) return SIGE_HIP_EUNSUPPORTED;
+    return launch_tokens(std::integer_sequence<int, 1, 2, 3, 4, 5, 6, 8, 10>(), sizeof(float), sige_hip_attention_tokens_supported, q, k, v,
+                         out, B, Nq, Nk, C, heads, scale, tiles, stream, [&](auto UNITS, auto TILES, const TokensLaunch &l) -> void {
+        constexpr int U = decltype(UNITS)::value;
+        constexpr size_t lds = tokens_image_bytes(U);
+        const int t16 = l.t16, t32 = (Nq + 31) / 32;
 #ifdef SIGE_ATTENTION_PLAIN_ORDER
-    const int xp = 0;
+        const int xp = 0;
 #else
-    const int xp = pairs % 8 == 0 ? pairs / 8 : 0;
+        const int xp = l.xcd_pairs;
 #endif
-#define SIGE_ATT_ARGS(QT) q, k, v, out, Nq, Nk, C, heads, d, sl, QT, xp, tiles, img_shift, images
-#define SIGE_ATT_GO(U)                                                                                             \
-    do {                                                                                                           \
-        const size_t lds = (size_t)4 * 16 * (U * 16 + 4) * sizeof(float);                                          \
-        if (tiles && form == 0) attention_tokens_t_kernel<U, true><<<dim3(t16 * pairs), 256, lds, st>>>(SIGE_ATT_ARGS(t16)); \
-        else if (tiles) attention_tokens_kernel<U, 1, true><<<dim3(t16 * pairs), 256, lds, st>>>(SIGE_ATT_ARGS(t16)); \
-        else if (form == 0) attention_tokens_t_kernel<U><<<dim3(t16 * pairs), 256, lds, st>>>(SIGE_ATT_ARGS(t16)); \
-        else if (form == 2) attention_tokens_kernel<(U <= 6 ? U : 1), 2><<<dim3(t32 * pairs), 256, 2 * lds, st>>>(SIGE_ATT_ARGS(t32)); \
-        else attention_tokens_kernel<U, 1><<<dim3(t16 * pairs), 256, lds, st>>>(SIGE_ATT_ARGS(t16));               \
-    } while (0)
-    switch (units) {
-        case 1: SIGE_ATT_GO(1); break;
-        case 2: SIGE_ATT_GO(2); break;
-        case 3: SIGE_ATT_GO(3); break;
-        case 4: SIGE_ATT_GO(4); break;
-        case 5: SIGE_ATT_GO(5); break;
-        case 6: SIGE_ATT_GO(6); break;
-        case 8: SIGE_ATT_GO(8); break;
-        case 10: SIGE_ATT_GO(10); break;
-        default: return SIGE_HIP_EUNSUPPORTED;
-    }
-#undef SIGE_ATT_GO
+#define SIGE_ATT_ARGS(QT) q, k, v, out, Nq, Nk, C, heads, l.d, l.scale_log2e, QT, xp, tiles, img_shift, images
+        if constexpr (decltype(TILES)::value) {
+            if (knob != 1 && knob != 2) attention_tokens_t_kernel<U, true><<<dim3(t16 * l.pairs), 256, lds, l.st>>>(SIGE_ATT_ARGS(t16));
+            else attention_tokens_kernel<U, 1, true><<<dim3(t16 * l.pairs), 256, lds, l.st>>>(SIGE_ATT_ARGS(t16));
+        } else {
+            const int form = (knob == 2 && U <= 6) ? 2 : (knob == 1 ? 1 : 0);
+            if (form == 0) attention_tokens_t_kernel<U><<<dim3(t16 * l.pairs), 256, lds, l.st>>>(SIGE_ATT_ARGS(t16));
+            else if (form == 2) attention_tokens_kernel<(U <= 6 ? U : 1), 2><<<dim3(t32 * l.pairs), 256, 2 * lds, l.st>>>(SIGE_ATT_ARGS(t32));
+            else attention_tokens_kernel<U, 1><<<dim3(t16 * l.pairs), 256, lds, l.st>>>(SIGE_ATT_ARGS(t16));
+        }
 #undef SIGE_ATT_ARGS
-    return launch_status();
+    });
 }
 
 }  // namespace sige
@@ -446,10 +422,9 @@ extern "C" int sige_hip_attention_tokens_f32(const float *q, const float *k, con
 extern "C" int sige_hip_attention_tokens_tiles_f32(const float *q, const float *k, const float *v, const int32_t *active_indices,
                                                    int T, int H, int W, int C, int heads, float scale, float *out, void *stream) {
     SIGE_PLAN_HOOK(sige_hip_attention_tokens_tiles_f32, q, k, v, active_indices, T, H, W, C, heads, scale, out, stream);
-    if (T < 0 || H <= 0 || W <= 0 || C <= 0 || heads <= 0) return SIGE_HIP_EINVAL;
-    if (T == 0) return SIGE_HIP_OK;
-    if (!q || !k || !v || !out || !active_indices) return SIGE_HIP_EINVAL;
+    int status;
+    if (!attention_tiles_args(T, H, W, C, heads, C, q, k, v, out, active_indices, &status)) return status;
     StackedKeys g;
-    if (const int status = stacked_keys(active_indices, T, H, W, &g)) return status;
+    if ((status = stacked_keys(active_indices, T, H, W, &g))) return status;
     return launch_attention_tokens(q, k, v, 1, 16 * T, g.Nk, C, heads, scale, out, g.tiles, g.shift, g.images, stream);
 }

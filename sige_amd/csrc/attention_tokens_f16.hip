@@ -35,20 +35,9 @@
 // scaling is not needed for them to count; it is kept because it costs one subtraction per step and everything down to 2^-29 then
 // rounds with fp16's full 11 bits (`dust` of tests/attention_f16.py: error 1.3e-4 against the unscaled emulation's 1.3e-3).  l is summed
 // from the same scaled, unrounded values: the factor 2^15 cancels in O / l, in the rescale and in the merge (every wave carries it).
-#include "attention_rows.hpp"
+#include "attention_tokens_image.hpp"
 
 namespace sige {
-
-typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-
-constexpr float P_SHIFT = 15.f;
-
-__device__ __forceinline__ f16x8 pack8(float4 a, float4 b) {  // (fptrunc: round to nearest even)
-    const f16x4 lo = __builtin_convertvector(f32x4{a.x, a.y, a.z, a.w}, f16x4);
-    const f16x4 hi = __builtin_convertvector(f32x4{b.x, b.y, b.z, b.w}, f16x4);
-    return __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
-}
 
 // N consecutive floats of a buffer in one load (dword-aligned offsets).  The result goes through ONE __builtin_bit_cast to a float
 // vector: indexing the builtin's own return value -- x[1] of a b64 / b128 load -- compiles to a buffer_load_dword and undefined upper
@@ -74,30 +63,23 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(DT <= 3 ? 4
 void attention_tokens_f16_kernel(const float *__restrict__ q, const float *__restrict__ k, const float *__restrict__ v,
                                  float *__restrict__ out, int Nq, int Nk, int C, int heads, int d, float scale_log2e,
                                  int q_tiles, int xcd_pairs, const int32_t *__restrict__ tiles, int img_shift, int images) {
-    constexpr int OS = DT * 16 + 4;  // padded row of the merge buffer (a multiple of 4 floats: 16-byte rows)
     // V: a lane loads VC consecutive channels of a key in ONE load, so row i of O^T's tile n = VC g + c is channel 16 VC g + VC i + c
     // (the rows of an MFMA's A operand may be any channels; the merge puts them back)
     // (three channels per 12-byte load at DT = 3 -- eight loads per step at d = 40 in place of 24 -- need 3-register tuples: tried,
     //  28 bytes of scratch under the 128 VGPRs of 4 waves / SIMD)
     constexpr int VC = DT % 4 == 0 ? 4 : DT % 2 == 0 ? 2 : 1, VG = DT / VC;
+    constexpr int OS = tokens_image_row(DT);
     __shared__ float m_lds[4][16], l_lds[4][4][16];
     extern __shared__ __attribute__((aligned(16))) float o_lds[];  // [4 waves][16 queries][OS]
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int kq = lane >> 4, j = lane & 15;
-    int pair, qtile;  // (workgroup -> XCD: attention_rows.hpp)
-    workgroup_pair_tile(q_tiles, xcd_pairs, pair, qtile);
-    const int head = pair % heads, b = pair / heads;
-    const int q0 = qtile * 16;
-    const size_t hoff = (size_t)head * d;
-    const size_t kv0 = ((size_t)b + tile_image<TILES>(tiles, qtile, img_shift, images)) * Nk * C + hoff;
-    const float *kb = k + kv0;
-    const float *vb = v + kv0;
+    const TokensPlace p = tokens_place<TILES>(Nk, C, heads, d, q_tiles, xcd_pairs, tiles, img_shift, images);
+    const int wave = p.wave, kq = p.kq, j = p.j;
+    const float *kb = k + p.kv0;
+    const float *vb = v + p.kv0;
 
     // Q of this lane = the B operand of the scores: query j, slot e of unit u = channel 16 (2u + (e >> 2)) + 4kq + (e & 3) (zeros beyond d)
     f16x8 qh[U32];
     {
-        const float *qb = q + ((size_t)b * Nq + q0 + j) * C + hoff;
+        const float *qb = q + ((size_t)p.b * Nq + p.q0 + j) * C + p.hoff;
 #pragma unroll
         for (int u = 0; u < U32; ++u) {
             float4 t[2];
@@ -120,10 +102,10 @@ void attention_tokens_f16_kernel(const float *__restrict__ q, const float *__res
     // row's, or the zeros a buffer load returns past the end of this batch's [Nk, C] matrix; a lane whose key lies past Nk the last
     // key's.  What it reads is a finite fp16 value (the contract) that meets a ZERO on the other side of the product or lands in a
     // padded column of O that is never stored.
-    // TILES: kb / vb and kv_bytes are those of the tile's IMAGE (Nk = one image's keys), so the tail mask, the clamps and the
+    // TILES: the descriptors are those of the tile's IMAGE (Nk = one image's keys), so the tail mask, the clamps and the
     // out-of-range zeros are per image; past the last head of the last row of image e < E - 1 lie image e + 1's first channels, which
-    // are past THIS descriptor's kv_bytes: zeros, as at the end of the tensor (attention_tokens.hip has the argument in full).
-    const unsigned kv_bytes = (unsigned)(((size_t)Nk * C - hoff) * sizeof(float));
+    // are past THIS descriptor's range: zeros, as at the end of the tensor (attention_tokens.hip has the argument in full).
+    const unsigned kv_bytes = (unsigned)(((size_t)Nk * C - p.hoff) * sizeof(float));
     const __amdgpu_buffer_rsrc_t r_k = __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(kb), 0, kv_bytes, 0x00020000);
     const __amdgpu_buffer_rsrc_t r_v = __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(vb), 0, kv_bytes, 0x00020000);
     const unsigned row_bytes = (unsigned)C * (unsigned)sizeof(float);
@@ -219,7 +201,7 @@ void attention_tokens_f16_kernel(const float *__restrict__ q, const float *__res
     __syncthreads();
     // thread -> (query row, 4 consecutive channels)
     const int units_per_row = d / 4;
-    for (int e = tid; e < 16 * units_per_row; e += 256) {
+    for (int e = p.tid; e < 16 * units_per_row; e += 256) {
         const int row = e / units_per_row, c = (e - row * units_per_row) * 4;
         const float M = fmaxf(fmaxf(m_lds[0][row], m_lds[1][row]), fmaxf(m_lds[2][row], m_lds[3][row]));
         float L = 0.f;
@@ -233,52 +215,25 @@ void attention_tokens_f16_kernel(const float *__restrict__ q, const float *__res
             acc.x += f * ov.x; acc.y += f * ov.y; acc.z += f * ov.z; acc.w += f * ov.w;
         }
         const float inv = 1.0f / L;
-        *reinterpret_cast<float4 *>(out + ((size_t)b * Nq + q0 + row) * C + hoff + c) =
+        *reinterpret_cast<float4 *>(out + ((size_t)p.b * Nq + p.q0 + row) * C + p.hoff + c) =
             make_float4(acc.x * inv, acc.y * inv, acc.z * inv, acc.w * inv);
     }
+}
+
+// Both entry points: Nk keys per batch, or with `tiles` (B = 1) per image -- the head sizes the fp32 entry takes.
+static int launch_attention_tokens_f16(const float *q, const float *k, const float *v, int B, int Nq, int Nk, int C, int heads,
+                                       float scale, float *out, const int32_t *tiles, int img_shift, int images, void *stream) {
+    return launch_tokens(std::integer_sequence<int, 1, 2, 3, 4, 5, 6, 8, 10>(), sizeof(float), sige_hip_attention_tokens_supported, q, k, v,
+                         out, B, Nq, Nk, C, heads, scale, tiles, stream, [&](auto U, auto TILES, const TokensLaunch &l) -> void {
+        constexpr int DT = decltype(U)::value;
+        attention_tokens_f16_kernel<(DT + 1) / 2, DT, decltype(TILES)::value><<<dim3(l.t16 * l.pairs), 256, tokens_image_bytes(DT), l.st>>>(
+            q, k, v, out, Nq, Nk, C, heads, l.d, l.scale_log2e, l.t16, l.xcd_pairs, tiles, img_shift, images);
+    });
 }
 
 }  // namespace sige
 
 using namespace sige;
-
-namespace sige {
-
-// Both entry points (as launch_attention_tokens of attention_tokens.hip): Nk keys per batch, or with `tiles` (B = 1) per image.
-static int launch_attention_tokens_f16(const float *q, const float *k, const float *v, int B, int Nq, int Nk, int C, int heads,
-                                       float scale, float *out, const int32_t *tiles, int img_shift, int images, void *stream) {
-    if (!sige_hip_attention_tokens_supported(Nq, Nk, C, heads)) return SIGE_HIP_EUNSUPPORTED;
-    auto al = [](const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; };
-    if (!al(q) || !al(k) || !al(v) || !al(out) || (size_t)Nk * C * sizeof(float) >= 0x7fffffffu) return SIGE_HIP_EUNSUPPORTED;
-    const int d = C / heads;
-    const int units = (d + 15) / 16;
-    const float sl = scale * 1.44269504088896341f;
-    hipStream_t st = as_stream(stream);
-    const int pairs = B * heads, t16 = Nq / 16;
-    if ((long)pairs * t16 > 0x7fffffffL) return SIGE_HIP_EUNSUPPORTED;
-    const int xp = pairs % 8 == 0 ? pairs / 8 : 0;
-#define SIGE_ATT16_GO(U)                                                                                                        \
-    do {                                                                                                                        \
-        const size_t lds = (size_t)4 * 16 * (U * 16 + 4) * sizeof(float);                                                       \
-        if (tiles) attention_tokens_f16_kernel<(U + 1) / 2, U, true><<<dim3(t16 * pairs), 256, lds, st>>>(q, k, v, out, Nq, Nk, C, heads, d, sl, t16, xp, tiles, img_shift, images); \
-        else attention_tokens_f16_kernel<(U + 1) / 2, U><<<dim3(t16 * pairs), 256, lds, st>>>(q, k, v, out, Nq, Nk, C, heads, d, sl, t16, xp, tiles, img_shift, images); \
-    } while (0)
-    switch (units) {  // (the head sizes the fp32 entry takes)
-        case 1: SIGE_ATT16_GO(1); break;
-        case 2: SIGE_ATT16_GO(2); break;
-        case 3: SIGE_ATT16_GO(3); break;
-        case 4: SIGE_ATT16_GO(4); break;
-        case 5: SIGE_ATT16_GO(5); break;
-        case 6: SIGE_ATT16_GO(6); break;
-        case 8: SIGE_ATT16_GO(8); break;
-        case 10: SIGE_ATT16_GO(10); break;
-        default: return SIGE_HIP_EUNSUPPORTED;
-    }
-#undef SIGE_ATT16_GO
-    return launch_status();
-}
-
-}  // namespace sige
 
 extern "C" int sige_hip_attention_tokens_f16c(const float *q, const float *k, const float *v, int B, int Nq, int Nk, int C,
                                               int heads, float scale, float *out, void *stream) {
@@ -292,10 +247,9 @@ extern "C" int sige_hip_attention_tokens_f16c(const float *q, const float *k, co
 extern "C" int sige_hip_attention_tokens_tiles_f16c(const float *q, const float *k, const float *v, const int32_t *active_indices,
                                                     int T, int H, int W, int C, int heads, float scale, float *out, void *stream) {
     SIGE_PLAN_HOOK(sige_hip_attention_tokens_tiles_f16c, q, k, v, active_indices, T, H, W, C, heads, scale, out, stream);
-    if (T < 0 || H <= 0 || W <= 0 || C <= 0 || heads <= 0) return SIGE_HIP_EINVAL;
-    if (T == 0) return SIGE_HIP_OK;
-    if (!q || !k || !v || !out || !active_indices) return SIGE_HIP_EINVAL;
+    int status;
+    if (!attention_tiles_args(T, H, W, C, heads, C, q, k, v, out, active_indices, &status)) return status;
     StackedKeys g;
-    if (const int status = stacked_keys(active_indices, T, H, W, &g)) return status;
+    if ((status = stacked_keys(active_indices, T, H, W, &g))) return status;
     return launch_attention_tokens_f16(q, k, v, 1, 16 * T, g.Nk, C, heads, scale, out, g.tiles, g.shift, g.images, stream);
 }

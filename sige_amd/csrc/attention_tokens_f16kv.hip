@@ -1,12 +1,9 @@
 // attention_tokens_f16 (attention_tokens_f16.hip: the transposed-score kernel on v_mfma_f32_16x16x32_f16) for K and V that are STORED
 // as fp16: k, v are _Float16 [B,Nk,C] token matrices (heads as strides), q and out stay fp32.  The f16c kernel rounds every K / V
 // element to fp16 each time it loads it; here the producer (kv_rows_f16.hip, or one .half() of the full pass) rounded it once, so
-// this kernel reads half the bytes, converts nothing and takes its operands as they lie in memory.  Same launch shape -- one workgroup
-// per 16 queries of one (batch, head), four waves round-robin over 32-key steps, each with its own running (m, l, O), merged through
-// LDS; the (batch, head) pairs dealt to the XCDs; the row maximum over two v_permlane*_swap (attention_rows.hpp) -- and the same
-// arithmetic (include/sige_hip.h: the contract of sige_hip_attention_tokens_f16c with "k, v rounded to fp16" already done): Q and P
-// rounded to nearest even (fptrunc, never v_cvt_pkrtz), fp32 scores / (m, l, alpha) / O / merge, P carried as exp2(s - m + 15).
-// What is its own is the load path:
+// this kernel reads half the bytes, converts nothing and takes its operands as they lie in memory.  Launch shape, state and launcher:
+// attention_tokens_image.hpp; arithmetic: the contract of sige_hip_attention_tokens_f16c (include/sige_hip.h) with "k, v rounded to
+// fp16" already done.  What is its own is the load path:
 //
 //   * scores S^T = K Q^T.  Slot e of lane (kq, j) in 32-channel unit u is channel 32u + 8kq + e of key j (A) and of query j (B): the
 //     A fragment IS one 16-byte buffer load, used as the MFMA operand as it arrives; Q is permuted identically as it is packed.  (The
@@ -33,23 +30,9 @@
 //
 // Branch-free buffer loads throughout; end of keys and end of batch as in the f16c kernel: a key past Nk is the last key (its scores
 // are masked to -inf), the descriptor spans one batch's (TILES: one image's) [Nk, C] halves from this head's first channel on.
-#include "attention_rows.hpp"
+#include "attention_tokens_image.hpp"  // (the workgroup's place, the merge image, the launcher; attention_rows.hpp: pack8, P_SHIFT, OUT_OF_RANGE)
 
 namespace sige {
-
-typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-
-constexpr float P_SHIFT16 = 15.f;
-constexpr unsigned OUT_OF_RANGE = 0x80000000u;  // a buffer offset past every descriptor here (one image's K or V < 2 GiB): loads zeros
-
-__device__ __forceinline__ f16x8 pack8_rne(float4 a, float4 b) {  // (fptrunc: round to nearest even)
-    const f16x4 lo = __builtin_convertvector(f32x4{a.x, a.y, a.z, a.w}, f16x4);
-    const f16x4 hi = __builtin_convertvector(f32x4{b.x, b.y, b.z, b.w}, f16x4);
-    return __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
-}
 
 // The greedy cut of DT tiles into groups of 4, 2, 1: group g's tile count, first tile, and the number of groups; the dwords a lane
 // holds per key slot over all groups (a 2-byte load fills one)
@@ -72,7 +55,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(DT <= 3 ? 4
 void attention_tokens_f16kv_kernel(const float *__restrict__ q, const _Float16 *__restrict__ k, const _Float16 *__restrict__ v,
                                    float *__restrict__ out, int Nq, int Nk, int C, int heads, int d, float scale_log2e,
                                    int q_tiles, int xcd_pairs, const int32_t *__restrict__ tiles, int img_shift, int images) {
-    constexpr int OS = DT * 16 + 4;  // padded row of the merge buffer (a multiple of 4 floats: 16-byte rows)
+    constexpr int OS = tokens_image_row(DT);
     constexpr int G = kv16_groups(DT);
     __shared__ float m_lds[4][16], l_lds[4][4][16];
     extern __shared__ __attribute__((aligned(16))) float o_lds[];  // [4 waves][16 queries][OS]
@@ -96,7 +79,7 @@ void attention_tokens_f16kv_kernel(const float *__restrict__ q, const _Float16 *
             const float *p = qb + min(c, d - 8);
             const float4 x = *reinterpret_cast<const float4 *>(p), y = *reinterpret_cast<const float4 *>(p + 4);
             const float4 z = make_float4(0.f, 0.f, 0.f, 0.f);
-            qh[u] = pack8_rne(c < d ? x : z, c < d ? y : z);
+            qh[u] = pack8(c < d ? x : z, c < d ? y : z);
         }
     }
     float m_run = -INFINITY, l_run = 0.f;  // of query j: the maximum over every key so far, the (scaled) sum over THIS lane's keys
@@ -185,14 +168,14 @@ void attention_tokens_f16kv_kernel(const float *__restrict__ q, const _Float16 *
 #pragma unroll
             for (int n = 0; n < DT; ++n) { o[n][0] *= alpha; o[n][1] *= alpha; o[n][2] *= alpha; o[n][3] *= alpha; }
         }
-        const float m_off = m_run - P_SHIFT16;
+        const float m_off = m_run - P_SHIFT;
         float4 pr[2];
 #pragma unroll
         for (int t = 0; t < 2; ++t)
             pr[t] = make_float4(__builtin_amdgcn_exp2f(sv[t][0] - m_off), __builtin_amdgcn_exp2f(sv[t][1] - m_off),
                                 __builtin_amdgcn_exp2f(sv[t][2] - m_off), __builtin_amdgcn_exp2f(sv[t][3] - m_off));
         l_run += ((pr[0].x + pr[0].y) + (pr[0].z + pr[0].w)) + ((pr[1].x + pr[1].y) + (pr[1].z + pr[1].w));
-        const f16x8 ph = pack8_rne(pr[0], pr[1]);
+        const f16x8 ph = pack8(pr[0], pr[1]);
         // ---- V's fragments: dword p of tile n = (slot 2p, slot 2p + 1) of the tile's channel, from the dwords (one key, VC channels) ----
         u32x4 vh[DT];
 #pragma unroll
@@ -258,37 +241,13 @@ void attention_tokens_f16kv_kernel(const float *__restrict__ q, const _Float16 *
 // Both entry points (as launch_attention_tokens_f16 of attention_tokens_f16.hip): Nk keys per batch, or with `tiles` (B = 1) per image.
 static int launch_attention_tokens_f16kv(const float *q, const _Float16 *k, const _Float16 *v, int B, int Nq, int Nk, int C, int heads,
                                          float scale, float *out, const int32_t *tiles, int img_shift, int images, void *stream) {
-    if (!sige_hip_attention_tokens_f16kv_supported(Nq, Nk, C, heads)) return SIGE_HIP_EUNSUPPORTED;
-    auto al = [](const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; };
-    if (!al(q) || !al(k) || !al(v) || !al(out) || (size_t)Nk * C * sizeof(_Float16) >= 0x7fffffffu) return SIGE_HIP_EUNSUPPORTED;
-    const int d = C / heads;
-    const int units = (d + 15) / 16;
-    const float sl = scale * 1.44269504088896341f;
-    hipStream_t st = as_stream(stream);
-    const int pairs = B * heads, t16 = Nq / 16;
-    if ((long)pairs * t16 > 0x7fffffffL) return SIGE_HIP_EUNSUPPORTED;
-    const int xp = pairs % 8 == 0 ? pairs / 8 : 0;
-#define SIGE_ATT16KV_GO(U)                                                                                                      \
-    do {                                                                                                                        \
-        const size_t lds = (size_t)4 * 16 * (U * 16 + 4) * sizeof(float);                                                       \
-        if (tiles) attention_tokens_f16kv_kernel<(U + 1) / 2, U, true><<<dim3(t16 * pairs), 256, lds, st>>>(q, k, v, out, Nq, Nk, C, heads, d, sl, t16, xp, tiles, img_shift, images); \
-        else attention_tokens_f16kv_kernel<(U + 1) / 2, U><<<dim3(t16 * pairs), 256, lds, st>>>(q, k, v, out, Nq, Nk, C, heads, d, sl, t16, xp, tiles, img_shift, images); \
-    } while (0)
-    switch (units) {  // (d % 8 == 0: the tile counts of d = 8 .. 160)
-        case 1: SIGE_ATT16KV_GO(1); break;
-        case 2: SIGE_ATT16KV_GO(2); break;
-        case 3: SIGE_ATT16KV_GO(3); break;
-        case 4: SIGE_ATT16KV_GO(4); break;
-        case 5: SIGE_ATT16KV_GO(5); break;
-        case 6: SIGE_ATT16KV_GO(6); break;
-        case 7: SIGE_ATT16KV_GO(7); break;
-        case 8: SIGE_ATT16KV_GO(8); break;
-        case 9: SIGE_ATT16KV_GO(9); break;
-        case 10: SIGE_ATT16KV_GO(10); break;
-        default: return SIGE_HIP_EUNSUPPORTED;
-    }
-#undef SIGE_ATT16KV_GO
-    return launch_status();
+    // (d % 8 == 0: the tile counts of d = 8 .. 160)
+    return launch_tokens(std::integer_sequence<int, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10>(), sizeof(_Float16), sige_hip_attention_tokens_f16kv_supported,
+                         q, k, v, out, B, Nq, Nk, C, heads, scale, tiles, stream, [&](auto U, auto TILES, const TokensLaunch &l) -> void {
+        constexpr int DT = decltype(U)::value;
+        attention_tokens_f16kv_kernel<(DT + 1) / 2, DT, decltype(TILES)::value><<<dim3(l.t16 * l.pairs), 256, tokens_image_bytes(DT), l.st>>>(
+            q, k, v, out, Nq, Nk, C, heads, l.d, l.scale_log2e, l.t16, l.xcd_pairs, tiles, img_shift, images);
+    });
 }
 
 }  // namespace sige
@@ -312,11 +271,10 @@ extern "C" int sige_hip_attention_tokens_f16kv(const float *q, const void *k16, 
 extern "C" int sige_hip_attention_tokens_tiles_f16kv(const float *q, const void *k16, const void *v16, const int32_t *active_indices,
                                                      int T, int H, int W, int C, int heads, float scale, float *out, void *stream) {
     SIGE_PLAN_HOOK(sige_hip_attention_tokens_tiles_f16kv, q, k16, v16, active_indices, T, H, W, C, heads, scale, out, stream);
-    if (T < 0 || H <= 0 || W <= 0 || C <= 0 || heads <= 0) return SIGE_HIP_EINVAL;
-    if (T == 0) return SIGE_HIP_OK;
-    if (!q || !k16 || !v16 || !out || !active_indices) return SIGE_HIP_EINVAL;
+    int status;
+    if (!attention_tiles_args(T, H, W, C, heads, C, q, k16, v16, out, active_indices, &status)) return status;
     StackedKeys g;
-    if (const int status = stacked_keys(active_indices, T, H, W, &g)) return status;
+    if ((status = stacked_keys(active_indices, T, H, W, &g))) return status;
     return launch_attention_tokens_f16kv(q, static_cast<const _Float16 *>(k16), static_cast<const _Float16 *>(v16), 1, 16 * T, g.Nk, C,
                                          heads, scale, out, g.tiles, g.shift, g.images, stream);
 }

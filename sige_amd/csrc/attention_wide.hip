@@ -296,11 +296,9 @@ extern "C" int sige_hip_attention_wide_tiles_f32(const float *q, int ldq, const 
                                                  const int32_t *active_indices, int T, int H, int W, int C, int heads, float scale,
                                                  float *out, int ldo, void *stream) {
     SIGE_PLAN_HOOK(sige_hip_attention_wide_tiles_f32, q, ldq, k, ldk, v, ldv, active_indices, T, H, W, C, heads, scale, out, ldo, stream);
-    if (T < 0 || H <= 0 || W <= 0 || C <= 0 || heads <= 0) return SIGE_HIP_EINVAL;
-    if (ldq < C || ldk < C || ldv < C || ldo < C) return SIGE_HIP_EINVAL;
-    if (T == 0) return SIGE_HIP_OK;
-    if (!q || !k || !v || !out || !active_indices) return SIGE_HIP_EINVAL;
+    int status;
+    if (!attention_tiles_args(T, H, W, C, heads, std::min({ldq, ldk, ldv, ldo}), q, k, v, out, active_indices, &status)) return status;
     StackedKeys g;
-    if (const int status = stacked_keys(active_indices, T, H, W, &g)) return status;
+    if ((status = stacked_keys(active_indices, T, H, W, &g))) return status;
     return launch_attention_wide(q, ldq, k, ldk, v, ldv, 1, 16 * T, g.Nk, C, heads, scale, out, ldo, g.tiles, g.shift, g.images, stream);
 }

@@ -36,16 +36,7 @@
 
 namespace sige {
 
-typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-
-constexpr float WIDE_P_SHIFT = 15.f;
-
-__device__ __forceinline__ f16x8 wide_pack8(f32x4 a, f32x4 b) {  // (fptrunc: round to nearest even)
-    const f16x4 lo = __builtin_convertvector(a, f16x4);
-    const f16x4 hi = __builtin_convertvector(b, f16x4);
-    return __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
-}
+// (f16x8, pack8, P_SHIFT: attention_rows.hpp)
 
 // ring depth: the largest divisor of the 4G chunks of a step that is <= 8 (slots stay compile-time across steps)
 constexpr int wide_f16_ring(int G) { return (2 * G) % 8 == 0 ? 8 : (2 * G) % 7 == 0 ? 7 : (2 * G) % 6 == 0 ? 6 : 5; }
@@ -160,7 +151,7 @@ void attention_wide_f16_kernel(WideAttnArgs a) {
                         f32x4 hi = cur[2 * u + 1];
                         if (gc == G - 1 && 32 * U + 16 >= d) hi = f32x4{0.f, 0.f, 0.f, 0.f};
                         const f16x8 qv = *reinterpret_cast<const f16x8 *>(qrow + 32 * U);
-                        s[t] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wide_pack8(cur[2 * u], hi), qv, s[t], 0, 0, 0);
+                        s[t] = __builtin_amdgcn_mfma_f32_16x16x32_f16(pack8(cur[2 * u], hi), qv, s[t], 0, 0, 0);
                     }
                 }
                 fetch_ahead(c);
@@ -192,14 +183,14 @@ void attention_wide_f16_kernel(WideAttnArgs a) {
                     for (int e = 0; e < 4; ++e) { o[g][e][0] *= alpha; o[g][e][1] *= alpha; o[g][e][2] *= alpha; o[g][e][3] *= alpha; }
                 }
             }
-            const float m_off = m_run - WIDE_P_SHIFT;
+            const float m_off = m_run - P_SHIFT;
             f32x4 pr[2];
 #pragma unroll
             for (int tt = 0; tt < 2; ++tt)
                 pr[tt] = f32x4{__builtin_amdgcn_exp2f(sv[tt][0] - m_off), __builtin_amdgcn_exp2f(sv[tt][1] - m_off),
                                __builtin_amdgcn_exp2f(sv[tt][2] - m_off), __builtin_amdgcn_exp2f(sv[tt][3] - m_off)};
             l_run += ((pr[0][0] + pr[0][1]) + (pr[0][2] + pr[0][3])) + ((pr[1][0] + pr[1][1]) + (pr[1][2] + pr[1][3]));
-            const f16x8 ph = wide_pack8(pr[0], pr[1]);
+            const f16x8 ph = pack8(pr[0], pr[1]);
 #pragma unroll
             for (int c = 2 * G; c < CH; ++c) {
                 f32x4 (&cur)[4] = ring[c % NB];
@@ -210,7 +201,7 @@ void attention_wide_f16_kernel(WideAttnArgs a) {
 #pragma unroll
                     for (int e = 0; e < 4; ++e)
                         o[g][e] = __builtin_amdgcn_mfma_f32_16x16x32_f16(
-                            wide_pack8(f32x4{lo[0][e], lo[1][e], lo[2][e], lo[3][e]}, f32x4{cur[0][e], cur[1][e], cur[2][e], cur[3][e]}),
+                            pack8(f32x4{lo[0][e], lo[1][e], lo[2][e], lo[3][e]}, f32x4{cur[0][e], cur[1][e], cur[2][e], cur[3][e]}),
                             ph, o[g][e], 0, 0, 0);
                 }
                 fetch_ahead(c);
@@ -326,11 +317,9 @@ extern "C" int sige_hip_attention_wide_tiles_f16c(const float *q, int ldq, const
                                                   const int32_t *active_indices, int T, int H, int W, int C, int heads, float scale,
                                                   float *out, int ldo, void *stream) {
     SIGE_PLAN_HOOK(sige_hip_attention_wide_tiles_f16c, q, ldq, k, ldk, v, ldv, active_indices, T, H, W, C, heads, scale, out, ldo, stream);
-    if (T < 0 || H <= 0 || W <= 0 || C <= 0 || heads <= 0) return SIGE_HIP_EINVAL;
-    if (ldq < C || ldk < C || ldv < C || ldo < C) return SIGE_HIP_EINVAL;
-    if (T == 0) return SIGE_HIP_OK;
-    if (!q || !k || !v || !out || !active_indices) return SIGE_HIP_EINVAL;
+    int status;
+    if (!attention_tiles_args(T, H, W, C, heads, std::min({ldq, ldk, ldv, ldo}), q, k, v, out, active_indices, &status)) return status;
     StackedKeys g;
-    if (const int status = stacked_keys(active_indices, T, H, W, &g)) return status;
+    if ((status = stacked_keys(active_indices, T, H, W, &g))) return status;
     return launch_attention_wide_f16(q, ldq, k, ldk, v, ldv, 1, 16 * T, g.Nk, C, heads, scale, out, ldo, g.tiles, g.shift, g.images, stream);
 }

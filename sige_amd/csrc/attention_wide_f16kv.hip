@@ -14,7 +14,7 @@
 //   * Q stage: fp16 in LDS in NATURAL channel order, zeros beyond d (a padded row of 64 G + 8 halves): slot e of lane (kq, j) in
 //     32-channel unit U is channel 32U + 8kq + e of query j -- 16 contiguous bytes, one ds_read_b128 per MFMA B operand.
 //   * scores S^T = K Q^T: the A fragment of unit U is ONE 16-byte buffer load of the 8 consecutive halves 32U + 8kq .. + 7 of key j,
-//     used as it arrives (the f16c kernel: two fp32 loads 64 bytes apart and a wide_pack8).  A lane whose 8 channels lie past the
+//     used as it arrives (the f16c kernel: two fp32 loads 64 bytes apart and a pack8).  A lane whose 8 channels lie past the
 //     head (d % 32 == 16: the last live unit's kq >= 2; d % 64 <= 32: the whole last unit) loads from an offset past the descriptor:
 //     the hardware returns exact zeros, no branch, and nothing that lies behind the head -- the next head's channels, the V half of
 //     a K | V row, Inf or NaN for all this head knows -- reaches the product.  Only the last group's two units can be dead, so two
@@ -39,19 +39,7 @@
 
 namespace sige {
 
-typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-
-constexpr float WIDE_KV16_P_SHIFT = 15.f;
-constexpr unsigned WIDE_OUT_OF_RANGE = 0x80000000u;  // a buffer offset past every descriptor here (one image's K or V < 2 GiB): loads zeros
-
-__device__ __forceinline__ f16x8 wide_kv16_pack8(f32x4 a, f32x4 b) {  // (fptrunc: round to nearest even)
-    const f16x4 lo = __builtin_convertvector(a, f16x4);
-    const f16x4 hi = __builtin_convertvector(b, f16x4);
-    return __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
-}
+// (f16x8 / u32x4, pack8, P_SHIFT, OUT_OF_RANGE: attention_rows.hpp)
 
 // ring depth: the largest divisor of the 4G chunks of a step that is <= 16 (slots stay compile-time across steps)
 constexpr int wide_kv16_ring(int G) { return 4 * G <= 16 ? 4 * G : 2 * G; }
@@ -111,15 +99,15 @@ void attention_wide_f16kv_kernel(WideAttnArgs a) {
     const __amdgpu_buffer_rsrc_t r_k = __builtin_amdgcn_make_buffer_rsrc(const_cast<_Float16 *>(k16 + krow0 * a.ldk + hoff), 0, k_bytes, 0x00020000);
     const __amdgpu_buffer_rsrc_t r_v = __builtin_amdgcn_make_buffer_rsrc(const_cast<_Float16 *>(v16 + krow0 * a.ldv + hoff), 0, v_bytes, 0x00020000);
     const unsigned k_row = (unsigned)a.ldk * (unsigned)sizeof(_Float16), v_row = (unsigned)a.ldv * (unsigned)sizeof(_Float16);
-    // the column part of a lane's offsets in the LAST group, bytes into a key's row, or WIDE_OUT_OF_RANGE where the lane's channels
+    // the column part of a lane's offsets in the LAST group, bytes into a key's row, or OUT_OF_RANGE where the lane's channels
     // lie past the head (row part < 2^31: the sum neither wraps nor comes back into range); below the last group every channel is live
     unsigned k_last[2];
 #pragma unroll
     for (int u = 0; u < 2; ++u) {
         const int c = 32 * (2 * G - 2 + u) + 8 * kq;
-        k_last[u] = c < d ? 2u * c : WIDE_OUT_OF_RANGE;
+        k_last[u] = c < d ? 2u * c : OUT_OF_RANGE;
     }
-    const unsigned v_last = 64 * (G - 1) + 4 * j < d ? 2u * (64 * (G - 1) + 4 * j) : WIDE_OUT_OF_RANGE;
+    const unsigned v_last = 64 * (G - 1) + 4 * j < d ? 2u * (64 * (G - 1) + 4 * j) : OUT_OF_RANGE;
 
     unsigned ring[NB][8];
     // chunk cc of step `step`: cc < 2G: K[key 16t + j][32 (2c + u) + 8kq .. +7], c = cc >> 1, t = cc & 1, u = 0, 1 -> dwords 4u .. 4u + 3;
@@ -207,14 +195,14 @@ void attention_wide_f16kv_kernel(WideAttnArgs a) {
                     for (int e = 0; e < 4; ++e) { o[g][e][0] *= alpha; o[g][e][1] *= alpha; o[g][e][2] *= alpha; o[g][e][3] *= alpha; }
                 }
             }
-            const float m_off = m_run - WIDE_KV16_P_SHIFT;
+            const float m_off = m_run - P_SHIFT;
             f32x4 pr[2];
 #pragma unroll
             for (int tt = 0; tt < 2; ++tt)
                 pr[tt] = f32x4{__builtin_amdgcn_exp2f(sv[tt][0] - m_off), __builtin_amdgcn_exp2f(sv[tt][1] - m_off),
                                __builtin_amdgcn_exp2f(sv[tt][2] - m_off), __builtin_amdgcn_exp2f(sv[tt][3] - m_off)};
             l_run += ((pr[0][0] + pr[0][1]) + (pr[0][2] + pr[0][3])) + ((pr[1][0] + pr[1][1]) + (pr[1][2] + pr[1][3]));
-            const f16x8 ph = wide_kv16_pack8(pr[0], pr[1]);
+            const f16x8 ph = pack8(pr[0], pr[1]);
 #pragma unroll
             for (int c = 2 * G; c < CH; ++c) {
                 if (c & 1) {
@@ -349,11 +337,9 @@ extern "C" int sige_hip_attention_wide_tiles_f16kv(const float *q, int ldq, cons
                                                    const int32_t *active_indices, int T, int H, int W, int C, int heads, float scale,
                                                    float *out, int ldo, void *stream) {
     SIGE_PLAN_HOOK(sige_hip_attention_wide_tiles_f16kv, q, ldq, k16, ldk, v16, ldv, active_indices, T, H, W, C, heads, scale, out, ldo, stream);
-    if (T < 0 || H <= 0 || W <= 0 || C <= 0 || heads <= 0) return SIGE_HIP_EINVAL;
-    if (ldq < C || ldk < C || ldv < C || ldo < C) return SIGE_HIP_EINVAL;
-    if (T == 0) return SIGE_HIP_OK;
-    if (!q || !k16 || !v16 || !out || !active_indices) return SIGE_HIP_EINVAL;
+    int status;
+    if (!attention_tiles_args(T, H, W, C, heads, std::min({ldq, ldk, ldv, ldo}), q, k16, v16, out, active_indices, &status)) return status;
     StackedKeys g;
-    if (const int status = stacked_keys(active_indices, T, H, W, &g)) return status;
+    if ((status = stacked_keys(active_indices, T, H, W, &g))) return status;
     return launch_attention_wide_f16kv(q, ldq, k16, ldk, v16, ldv, 1, 16 * T, g.Nk, C, heads, scale, out, ldo, g.tiles, g.shift, g.images, stream);
 }
